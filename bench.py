@@ -13,6 +13,9 @@ the kernel runs on; `cpu_baseline` is the CPU oracle on a time-bounded sample; `
 PCIe-inclusive legs (pinned host memory in and out, JPEG in and out) -- reported, never `value`.
 
 --mixed N runs BASELINE config 5 instead (mixed 480p-8K sizes, pull scheduling).
+
+--dump-outputs DIR writes what the last timed step computed (rank 0) as float32 .npy files, one per output (resize.npy,
+thumbnail.npy, watermark.npy), so that two builds can be compared output for output: see dump_outputs().
 """
 import argparse
 import json
@@ -47,7 +50,38 @@ def parse():
     ap.add_argument("--mixed", type=int, default=0, metavar="N",
                     help="BASELINE config 5 instead: N frames per GPU of mixed sizes (480p-8K, seed 0x51), full "
                          "pipeline, pull scheduling over a shared largest-first queue (work stealing across ranks)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last step to DIR/<output>.npy (float32, a fixed seeded "
+                         "sample of the batch, at most 64 MB in all)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.mixed:
+        ap.error("--dump-outputs covers the default path, not --mixed")
+    return args
+
+
+def dump_outputs(dirname, F, outputs, seed=0xD0, max_slots=8, max_pixels=1 << 17):
+    """outputs: [(name, device buffer, frame stride in bytes, (h, w, 4))] of the last timed step -> dirname/<name>.npy, float32.
+
+    A fixed seeded sample, the same for the same arguments: slots 0 and F - 1 and up to max_slots - 2 others (all F when F <=
+    max_slots); of each frame, every pixel when it has at most max_pixels, else the same max_pixels positions (row-major order) in
+    every slot.  Arrays are slots x h x w x 4 (whole frames) or slots x max_pixels x 4 (sampled); at most 50.3 MB in all."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    if F <= max_slots:
+        slots = np.arange(F)
+    else:
+        slots = np.sort(np.concatenate(([0, F - 1], rng.choice(np.arange(1, F - 1), max_slots - 2, replace=False))))
+    os.makedirs(dirname, exist_ok=True)
+    for name, buf, stride, shape in outputs:
+        npx = shape[0] * shape[1]
+        pick = None if npx <= max_pixels else np.sort(rng.choice(npx, max_pixels, replace=False))
+        frames = []
+        for slot in slots:
+            f = buf.download(shape, offset=int(slot) * stride)
+            frames.append(f if pick is None else f.reshape(npx, 4)[pick])
+        np.save(os.path.join(dirname, name + ".npy"), np.stack(frames).astype(np.float32))
 
 
 def copy_ceiling(ctx, gib=4, pairs=3, reps=4):
@@ -503,6 +537,10 @@ def main():
                 if buf and not np.array_equal(buf.download(shape, offset=slot * stride), want[key]):
                     raise SystemExit("bench.py: %s of slot %d differs from the oracle" % (key, slot))
         checked = True
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, F, [(key, buf, stride, shape) for key, buf, stride, shape in (
+                ("resize", r_, rstride, (info.resize_h, info.resize_w, 4)), ("thumbnail", t_, tstride, (info.thumb_h, info.thumb_w, 4)),
+                ("watermark", w_, info.wm_bytes, (sh, sw, 4))) if buf])
 
     if rank == 0 and os.environ.get("IPX_BENCH_TRACE"):
         print("launch_ms:", " ".join("%.3f" % m for m in launch_ms), file=sys.stderr)

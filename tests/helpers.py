@@ -1,5 +1,10 @@
 """Shared synthetic inputs for the tests (seeded, shape-realistic, no reference data)."""
+import os
+
 import numpy as np
+
+# the glyphs of DejaVu Sans the font tests draw (tests/golden/make_font_subset.py)
+DEJAVU = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "DejaVuSans-subset.ttf")
 
 
 def rgba_frames(n, w, h, seed=0x1F00D, opaque=True, premul=True):

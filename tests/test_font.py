@@ -9,18 +9,14 @@ face are not in the image); pinned here by
   * FreeType itself (Pillow), within a tolerance, since Pillow hints and this path does not.
 """
 import io
-import os
 
 import numpy as np
 import pytest
 
 import imageprocessor_amd as ipx
 from imageprocessor_amd.operations import TrueTypeFont
+from helpers import DEJAVU
 
-DEJAVU = next((p for p in ("/usr/share/fonts/truetype/dejavu/DejaVuSans.ttf",
-                           "/usr/local/lib/python3.10/dist-packages/matplotlib/mpl-data/fonts/ttf/DejaVuSans.ttf")
-               if os.path.exists(p)), None)
-needs_dejavu = pytest.mark.skipif(DEJAVU is None, reason="DejaVuSans.ttf not in this image")
 DEFAULT_TEXT = "© ImageProcessor"   # domain.DefaultWatermarkText
 
 
@@ -171,7 +167,6 @@ def test_quadratic_contour_area():
     f.close()
 
 
-@needs_dejavu
 def test_tables_against_fonttools():
     from fontTools.ttLib import TTFont
     tt = TTFont(DEJAVU)
@@ -205,7 +200,6 @@ def test_tables_against_fonttools():
     f.close()
 
 
-@needs_dejavu
 @pytest.mark.parametrize("size", [36, 12, 17.3, 96])
 def test_masks_match_python_model(size):
     """csrc/ipx_font.cpp against oracle/ft_model.py on real outlines (simple, compound, transformed-compound
@@ -226,7 +220,6 @@ def test_masks_match_python_model(size):
     f.close()
 
 
-@needs_dejavu
 def test_clipped_text_matches_model():
     from oracle import ft_model
     model = ft_model.Font(DEJAVU)
@@ -240,7 +233,6 @@ def test_clipped_text_matches_model():
     f.close()
 
 
-@needs_dejavu
 def test_close_to_freetype_via_pillow():
     """FreeType (through Pillow) hints and snaps advances to whole pixels, so only glyph-level agreement is
     asked for: per-glyph ink within 6 % and bounding boxes within one pixel."""

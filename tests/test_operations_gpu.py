@@ -145,11 +145,8 @@ def test_watermarker_with_the_library_font(ctx, ops, ipx):
     """NewWatermarker's font slot filled by the library's own truetype / freetype restatement (ipx_font_*):
     text -> glyph masks on the host -> composite on the GPU, against the Python model of the glyph producer
     plus the oracle's composite."""
-    import os
     from oracle import ft_model
-    path = "/usr/share/fonts/truetype/dejavu/DejaVuSans.ttf"
-    if not os.path.exists(path):
-        pytest.skip("DejaVuSans.ttf not in this image")
+    from helpers import DEJAVU as path
     f = ops.TrueTypeFont.from_file(path)
     model = ft_model.Font(path)
     w = ops.Watermarker(f)

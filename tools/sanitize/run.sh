@@ -4,8 +4,9 @@
 # it restates does; defined in C++20, and neither gcc nor clang treats it otherwise).  usage: tools/sanitize/run.sh [cases per seed file]
 set -e
 cd "$(dirname "$0")/../.."
-out=/tmp/ipx_sanitize
-mkdir -p $out
+# a directory of its own per run: a fixed path under /tmp may belong to another user, or to a run going on beside this one
+out=$(mktemp -d "${TMPDIR:-/tmp}/ipx_sanitize.XXXXXX")
+trap 'rm -rf "$out"' EXIT
 python3 - $out <<'PY'
 import io, sys
 import numpy as np
@@ -19,5 +20,5 @@ Image.fromarray(img[..., 0]).save(out + "/g.jpg", "JPEG", quality=80)
 PY
 CXX="g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-sanitize=shift-base -fno-omit-frame-pointer -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include"
 $CXX -o $out/fuzz_parsers tools/sanitize/fuzz_parsers.cpp imageprocessor_amd/csrc/ipx_font.cpp imageprocessor_amd/csrc/ipx_jpeg_dec_host.cpp imageprocessor_amd/csrc/ipx_jpeg_dec_prog.cpp
-fonts=$(ls /usr/share/fonts/truetype/dejavu/DejaVuSans.ttf /usr/share/fonts/truetype/dejavu/DejaVuSerif-Bold.ttf 2>/dev/null || true)
+fonts="tests/golden/DejaVuSans-subset.ttf $(ls /usr/share/fonts/truetype/dejavu/DejaVuSans.ttf /usr/share/fonts/truetype/dejavu/DejaVuSerif-Bold.ttf 2>/dev/null || true)"
 ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $out/fuzz_parsers ${1:-3000} $out/*.jpg $fonts
