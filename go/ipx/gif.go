@@ -1,0 +1,62 @@
+package ipx
+
+/*
+#include "ipx.h"
+*/
+import "C"
+
+import "unsafe"
+
+// RunHostPalettedGIF: the GIF task's whole GPU leg.  Decoded GIF frames in (RunHostPaletted's arguments), operators on the GPU, then
+// gif.Encode(buf, img, nil) of the resize and thumbnail outputs (resize.go:78-91, thumbnail.go:68-81) and jpeg.Encode(q) of the
+// watermark output (watermark.go:66-79: a GIF watermark becomes a JPEG), all on the GPU; only the finished streams cross the link.
+// Release the Streams once they are written out.
+func (p *Plan) RunHostPalettedGIF(n int, index, palettes []byte, quality int) (*Streams, error) {
+	s := &Streams{x: p.x, resize: make([]C.ipx_bytes, n), thumb: make([]C.ipx_bytes, n), watermark: make([]C.ipx_bytes, n)}
+	err := call(func() C.int {
+		return C.ipx_plan_run_host_paletted_gif(p.x.c, p.c, C.int(n), ptr(index), C.int(p.w), C.size_t(p.w*p.h), ptr(palettes),
+			C.int(quality), &s.resize[0], &s.thumb[0], &s.watermark[0], &s.res)
+	})
+	if err != nil {
+		return nil, err
+	}
+	return s, nil
+}
+
+// GIFBatch holds the streams of EncodeGIFBatchDev: views into one pinned block owned by the library, valid until Release.
+type GIFBatch struct {
+	x       *Context
+	blob    *C.uint8_t
+	Streams [][]byte
+}
+
+func (b *GIFBatch) Release() {
+	if b.blob != nil {
+		C.ipx_host_free(b.x.c, unsafe.Pointer(b.blob))
+		b.blob = nil
+		b.Streams = nil
+	}
+}
+
+// EncodeGIFBatchDev: gif.Encode of n w x h RGBA frames resident in HBM (src, frameStride bytes apart, rows stride bytes apart), the
+// Plan 9 / Floyd-Steinberg dither and LZW on the GPU.
+func (x *Context) EncodeGIFBatchDev(src unsafe.Pointer, w, h, stride, frameStride, n int) (*GIFBatch, error) {
+	b := &GIFBatch{x: x}
+	if n <= 0 {
+		return b, nil
+	}
+	offs := make([]C.size_t, n)
+	lens := make([]C.size_t, n)
+	err := call(func() C.int {
+		return C.ipx_gif_encode_batch_dev(x.c, (*C.uint8_t)(src), C.int(w), C.int(h), C.int(stride), C.size_t(frameStride), C.int(n),
+			&b.blob, &offs[0], &lens[0])
+	})
+	if err != nil {
+		return nil, err
+	}
+	b.Streams = make([][]byte, n)
+	for i := range b.Streams {
+		b.Streams[i] = unsafe.Slice((*byte)(unsafe.Add(unsafe.Pointer(b.blob), int(offs[i]))), int(lens[i]))
+	}
+	return b, nil
+}

@@ -278,6 +278,25 @@ class Plan:
         lib().ipx_jpeg_result_free(self.ctx.handle, res)
         return out
 
+    def run_host_paletted_gif(self, index, palettes, quality=85, want=("resize", "thumbnail", "watermark"), copy=True):
+        """Decoded GIF frames (index: n x H x W uint8, palettes: n x 256 x 4 uint8, host) -> {operator: [bytes] * n}: operators,
+        gif.Encode of resize / thumbnail and jpeg.Encode (at `quality`) of the watermark on the GPU; only the streams come back."""
+        index = np.ascontiguousarray(index, dtype=np.uint8)
+        palettes = np.ascontiguousarray(palettes, dtype=np.uint8)
+        n, i = index.shape[0], self.info
+        assert index.shape[1:] == (self._sh, self._sw) and palettes.shape == (n, 256, 4)
+        arrs = {}
+        for k, present in (("resize", i.resize_bytes), ("thumbnail", i.thumb_bytes), ("watermark", i.wm_bytes)):
+            if k in want and present:
+                arrs[k] = (_lib.Bytes * n)()
+        res = C.c_void_p()
+        _check(lib().ipx_plan_run_host_paletted_gif(self.ctx.handle, self.handle, n, index.ctypes.data, self._sw, self._sw * self._sh,
+                                                    palettes.ctypes.data, int(quality), arrs.get("resize"), arrs.get("thumbnail"),
+                                                    arrs.get("watermark"), C.byref(res)))
+        out = {k: [C.string_at(a[j].data, a[j].len) if copy else a[j].len for j in range(n)] for k, a in arrs.items()}
+        lib().ipx_jpeg_result_free(self.ctx.handle, res)
+        return out
+
     def run_host_ycbcr_jpeg(self, y, cb, cr, ratio, quality=85, want=("resize", "thumbnail", "watermark"), copy=True):
         """Decoded JPEG planes (host) -> {operator: [jpeg bytes] * n}; see run_host_jpeg."""
         y, cb, cr = (np.ascontiguousarray(a, dtype=np.uint8) for a in (y, cb, cr))
@@ -582,6 +601,37 @@ class Context:
         _check(lib().ipx_jpeg_encode_batch_dev(self.handle, src_ptr, w, h, stride or w * 4,
                                                frame_stride if frame_stride is not None else w * h * 4, n, int(quality),
                                                C.byref(blob), offs, lens))
+        if not copy:
+            total = offs[n - 1] + lens[n - 1]
+            buf = (C.c_uint8 * total).from_address(blob.value)
+            mv = memoryview(buf)
+            return [mv[offs[i]:offs[i] + lens[i]] for i in range(n)], (lambda: lib().ipx_host_free(self.handle, blob))
+        res = [C.string_at(blob.value + offs[i], lens[i]) for i in range(n)]
+        lib().ipx_host_free(self.handle, blob)
+        return res
+
+    def gif_encode(self, frame):
+        """gif.Encode(w, *image.RGBA, nil) of one host frame (H x W x 4 uint8, premultiplied) -> bytes"""
+        frame = np.ascontiguousarray(frame, dtype=np.uint8)
+        h, w = frame.shape[:2]
+        out, n = C.c_void_p(), C.c_size_t()
+        _check(lib().ipx_gif_encode_rgba8(self.handle, frame.ctypes.data, w, h, w * 4, C.byref(out), C.byref(n)))
+        data = C.string_at(out, n.value)
+        lib().ipx_buffer_free(out)
+        return data
+
+    def gif_dither_dev(self, src_ptr, w, h, n, index_ptr, stride=None, frame_stride=None, stream=None):
+        """Plan 9 + Floyd-Steinberg of n frames in HBM -> n dense w x h index frames at index_ptr (HBM).  Asynchronous."""
+        _check(lib().ipx_dev_gif_dither_rgba8(self.handle, stream, src_ptr, w, h, stride or w * 4,
+                                              frame_stride if frame_stride is not None else w * h * 4, n, index_ptr))
+
+    def gif_encode_batch_dev(self, src_ptr, w, h, n, stride=None, frame_stride=None, copy=True):
+        """n frames in HBM -> n GIF streams.  copy=False returns (memoryviews into the pinned block, release()) instead of bytes."""
+        blob, offs, lens = C.c_void_p(), (C.c_size_t * max(n, 1))(), (C.c_size_t * max(n, 1))()
+        _check(lib().ipx_gif_encode_batch_dev(self.handle, src_ptr, w, h, stride or w * 4,
+                                              frame_stride if frame_stride is not None else w * h * 4, n, C.byref(blob), offs, lens))
+        if n == 0:
+            return ([], (lambda: None)) if not copy else []
         if not copy:
             total = offs[n - 1] + lens[n - 1]
             buf = (C.c_uint8 * total).from_address(blob.value)

@@ -204,6 +204,11 @@ SIGNATURES = {
     "ipx_jpeg_result_free": (None, [_P, _P]),
     "ipx_plan_run_host_ycbcr_jpeg": (_I, [_P, _P, _I, C.POINTER(YCbCrBatch), _I, C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(Bytes),
                                           C.POINTER(_P)]),
+    "ipx_gif_encode_rgba8": (_I, [_P, _P, _I, _I, _I, C.POINTER(_P), C.POINTER(_Z)]),
+    "ipx_gif_encode_batch_dev": (_I, [_P, _P, _I, _I, _I, _Z, _I, C.POINTER(_P), C.POINTER(_Z), C.POINTER(_Z)]),
+    "ipx_dev_gif_dither_rgba8": (_I, [_P, _P, _P, _I, _I, _I, _Z, _I, _P]),
+    "ipx_plan_run_host_paletted_gif": (_I, [_P, _P, _I, _P, _I, _Z, _P, _I, C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(Bytes),
+                                            C.POINTER(_P)]),
     "ipx_font_create": (_I, [_P, _Z, C.POINTER(_P)]),
     "ipx_font_destroy": (None, [_P]),
     "ipx_font_glyph_index": (_I, [_P, C.c_uint32]),

@@ -1,0 +1,60 @@
+// ipx_gif.h -- gif.Encode(w, *image.RGBA, nil) on the GPU: what the kernels (ipx_gif.hip) and the host half (ipx_gif_host.cpp) share.
+// Not part of the ABI.  The restatement of Go's writer is in DESIGN.md section 4.7; tests/gif_model.py is the model it is held to.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+namespace ipx {
+
+// palette.Plan9 (image/color/palette/gen.go), generated the way gen.go does: for r, v, g, b in 0..3 (nested in that order), i advancing
+// 16 per v and j = v - r + 4g + b, den = max(r, g, b); grey 0x11 * v when den == 0, else (r, g, b) * num / den with num = 17 * (4 den + v),
+// stored at i + (j & 15).  Every entry is opaque.
+struct Plan9 {
+    uint8_t rgb[256][3];
+    constexpr Plan9() : rgb{}
+    {
+        int i = 0;
+        for (int r = 0; r < 4; r++)
+            for (int v = 0; v < 4; v++, i += 16) {
+                int j = v - r;
+                for (int g = 0; g < 4; g++)
+                    for (int b = 0; b < 4; b++, j++) {
+                        int den = r > g ? r : g;
+                        den = den > b ? den : b;
+                        uint8_t *c = rgb[i + (j & 15)];
+                        if (den == 0) {
+                            c[0] = c[1] = c[2] = (uint8_t)(0x11 * v);
+                        } else {
+                            const int num = 17 * (4 * den + v);
+                            c[0] = (uint8_t)(r * num / den);
+                            c[1] = (uint8_t)(g * num / den);
+                            c[2] = (uint8_t)(b * num / den);
+                        }
+                    }
+            }
+    }
+};
+
+// GIF89a, logical screen w x h with the 256-entry global table (flags 0x87, background 0, aspect 0), the Plan 9 table, the image
+// descriptor (0x2C, at 0,0, w x h, flags 0: the frame uses the global table) and the LZW minimum code size 8
+constexpr int kGifHeaderBytes = 13 + 768 + 10 + 1;
+void gif_write_header(int w, int h, uint8_t out[kGifHeaderBytes]);
+// an upper bound of a whole stream's length for a w x h frame (header, sub-blocks of LZW data at <= 12 bits per code, trailer)
+size_t gif_stream_bound(int w, int h);
+
+// ---- kernel launchers (ipx_gif.hip) ----
+// rows_in_flight: a multiple of 64 up to 1024 (one wave per 64 rows); carry: n * w int4 of scratch (the last error row of a band)
+hipError_t launch_gif_dither(const uint8_t *src, int w, int h, int stride, size_t frame_stride, int n, uint8_t *index, int4 *carry,
+                             int rows_in_flight, hipStream_t s);
+// index: n frames of npix bytes; header: kGifHeaderBytes in HBM; region bytes of out per frame; lens[i] = the stream's length, or
+// 0xffffffff if the region was too small (cannot happen with gif_stream_bound; the kernel never writes past the region)
+hipError_t launch_gif_lzw(const uint8_t *index, size_t npix, int n, const uint8_t *header, uint8_t *out, size_t region, uint32_t *lens,
+                          hipStream_t s);
+// stream i (lens[i] bytes at out + i * region) to dst + obase[i]; obase 16-byte aligned, region a multiple of 16
+hipError_t launch_gif_pack(const uint8_t *out, size_t region, const uint32_t *lens, const unsigned long long *obase, int n, size_t max_len,
+                           uint8_t *dst, hipStream_t s);
+
+}  // namespace ipx

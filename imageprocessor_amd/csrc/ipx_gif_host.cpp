@@ -1,0 +1,42 @@
+// ipx_gif_host.cpp -- the host half of gif.Encode: the header bytes image/gif's writeHeader / writeImageBlock put before the LZW data of
+// a single-frame *image.Paletted with the Plan 9 palette, and the size bound the device regions are cut by.  Kernels: ipx_gif.hip.
+#include <cstring>
+
+#include "ipx_gif.h"
+
+namespace ipx {
+
+void gif_write_header(int w, int h, uint8_t out[kGifHeaderBytes])
+{
+    static constexpr Plan9 pal;
+    uint8_t *p = out;
+    memcpy(p, "GIF89a", 6);
+    p += 6;
+    auto u16 = [&](int v) { *p++ = (uint8_t)(v & 0xff); *p++ = (uint8_t)((v >> 8) & 0xff); };
+    u16(w);
+    u16(h);
+    *p++ = 0x80 | 7;   // fColorTable | log2(256) - 1
+    *p++ = 0;          // background index
+    *p++ = 0;          // pixel aspect ratio
+    memcpy(p, pal.rgb, 768);
+    p += 768;
+    // no NETSCAPE2.0 block (one frame) and no graphic control extension (delay 0, disposal 0, Plan 9 has no transparent entry)
+    *p++ = 0x2C;
+    u16(0);
+    u16(0);
+    u16(w);
+    u16(h);
+    *p++ = 0;          // the global table serves: no local one
+    *p++ = 8;          // LZW minimum code size: log2(256) - 1 + 1
+}
+
+size_t gif_stream_bound(int w, int h)
+{
+    const size_t npix = (size_t)w * (size_t)h;
+    // a code per pixel at most, plus the first clear code, the code Close writes, EOF, and a clear code per 3838 codes (hi runs 257 .. 4095)
+    const size_t codes = npix + 3 + npix / 3838 + 1;
+    const size_t data = (codes * 12 + 7) / 8;
+    return kGifHeaderBytes + data + (data + 254) / 255 + 1 + 1;   // length bytes, terminator, trailer
+}
+
+}  // namespace ipx

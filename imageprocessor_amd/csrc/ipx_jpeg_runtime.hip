@@ -120,8 +120,7 @@ IPX_CATCH_STATUS
 // jpeg.Encode of up to three sets of n frames (the three operators' outputs of one batch) with THREE waits for the device in all: every
 // set's transform + symbol sizing, one read-back of the sizes; every set's bit packing + 0xff count, one read-back; every set's byte
 // stuffing into one block, one download.  (One set after the other, as rounds 1 and 2 ran it, is nine waits: 5.5 ms for a batch of 8.)
-struct JpegEncSet { int16_t *dcoefs; const uint8_t *src; int w, h, stride; size_t frame_stride; size_t *offs, *lens; };   // offs / lens: [n], into *blob
-static int jpeg_encode_sets(ipx_ctx *ctx, hipStream_t s, const JpegEncSet *sets, int K, int n, int quality, uint8_t **blob)
+int jpeg_encode_sets(ipx_ctx *ctx, hipStream_t s, const JpegEncSet *sets, int K, int n, int quality, uint8_t **blob)
 {
     *blob = nullptr;
     if (K <= 0 || K > 3 || n <= 0) return IPX_OK;
@@ -257,7 +256,6 @@ static int jpeg_encode_core(ipx_ctx *ctx, hipStream_t s, int16_t *dcoefs, const 
 }
 
 // ---- host frames in, JPEG streams out: the worker's whole GPU leg ----------------------------------------
-struct ipx_jpeg_result { std::vector<uint8_t *> blobs; };
 
 extern "C" {
 

@@ -279,3 +279,11 @@ struct AsyncFree {
         return e;
     }
 };
+
+// jpeg.Encode of up to three sets of n frames in HBM into one pinned block *blob (ipx_jpeg_runtime.hip); dcoefs: n * ipx_jpeg_coef_count
+// int16 of scratch per set.  Also the watermark leg of ipx_plan_run_host_paletted_gif (ipx_gif.hip).
+struct JpegEncSet { int16_t *dcoefs; const uint8_t *src; int w, h, stride; size_t frame_stride; size_t *offs, *lens; };   // offs / lens: [n], into *blob
+int jpeg_encode_sets(ipx_ctx *ctx, hipStream_t s, const JpegEncSet *sets, int K, int n, int quality, uint8_t **blob);
+
+// the pinned blocks the streams of the *_jpeg / *_gif batch entries live in (ipx_jpeg_result_free)
+struct ipx_jpeg_result { std::vector<uint8_t *> blobs; };

@@ -460,6 +460,31 @@ int ipx_plan_run_host_ycbcr_jpeg(ipx_ctx *ctx, const ipx_plan *plan, int n, cons
                                  ipx_jpeg_result **result);
 void ipx_jpeg_result_free(ipx_ctx *ctx, ipx_jpeg_result *result);
 
+/* ---- gif.Encode (GIF half) ---------------------------------------------------------
+ * resize.go:78-91 and thumbnail.go:68-81 end a GIF task in gif.Encode(buf, img, nil) on the operator's *image.RGBA: no palette to
+ * reuse, so image/gif draws the frame onto palette.Plan9 with draw.FloydSteinberg (image/draw drawPaletted) and LZW-codes the indices
+ * (compress/lzw, LSB, literal width 8) into one image block.  Both run on the GPU: the dither as a wavefront of rows in flight, LZW one
+ * wave per frame with the dictionary in LDS, and only finished streams cross the link.  The bytes are the ones Go's writer produces for a
+ * single frame (GIF89a, global Plan 9 table, no extensions, LZW minimum code size 8, trailer 0x3B).  Frames 65536 pixels or more in
+ * either dimension are refused (IPX_ERR_INVALID), as gif.Encode refuses them.  DESIGN.md section 4.7. */
+/* one frame in host memory -> *out, malloc'd (ipx_buffer_free) */
+int ipx_gif_encode_rgba8(ipx_ctx *ctx, const uint8_t *pix, int w, int h, int stride, uint8_t **out, size_t *len);
+/* n frames resident in HBM -> n streams in ONE pinned block, the ownership rules of ipx_jpeg_encode_batch_dev: *blob is freed with
+ * ipx_host_free; stream i is blob[offs[i] .. offs[i] + lens[i]). */
+int ipx_gif_encode_batch_dev(ipx_ctx *ctx, const uint8_t *src, int w, int h, int stride, size_t frame_stride, int n, uint8_t **blob,
+                             size_t *offs, size_t *lens);
+/* the dither alone: n frames in HBM -> n dense w x h index frames (Plan 9 indices) at index + i * w * h, in HBM.  Asynchronous on
+ * `stream` (NULL: the context's stream). */
+int ipx_dev_gif_dither_rgba8(ipx_ctx *ctx, void *stream, const uint8_t *src, int w, int h, int stride, size_t frame_stride, int n,
+                             uint8_t *index);
+/* The GIF task's whole GPU leg for a batch of decoded GIF frames in host memory (the arguments of ipx_plan_run_host_paletted):
+ * upload, every requested operator, then gif.Encode of the resize and thumbnail outputs and jpeg.Encode at `quality` of the watermark
+ * output (watermark.go:66-79: a GIF watermark becomes a JPEG).  The streams land in pinned blocks owned by *result, released with
+ * ipx_jpeg_result_free as for ipx_plan_run_host_jpeg. */
+int ipx_plan_run_host_paletted_gif(ipx_ctx *ctx, const ipx_plan *plan, int n, const uint8_t *index, int stride, size_t frame_stride,
+                                   const uint8_t *palettes, int quality, ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out,
+                                   ipx_jpeg_result **result);
+
 /* ---- image.Decode for JPEGs (decoder side) -------------------------------------------
  * image_processor.go:47 decodes every upload; for JPEG files that is Go's image/jpeg.  A batch of
  * files of one size and one kind (three components at 4:4:4 / 4:2:2 / 4:2:0 / 4:4:0, or one component) is decoded here.  Baseline files:
