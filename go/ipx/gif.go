@@ -60,3 +60,38 @@ func (x *Context) EncodeGIFBatchDev(src unsafe.Pointer, w, h, stride, frameStrid
 	}
 	return b, nil
 }
+
+// RunGIFGIF: the GIF task compressed in, compressed out -- the objects as fileRepo.GetOriginal returned them, image.Decode
+// (image_processor.go:47: gif.Decode, the first image), every operator, gif.Encode of the resize and thumbnail outputs and jpeg.Encode(q)
+// of the watermark output, all on the GPU.  files must stay valid for the duration of the call (they are pinned here); Status[i] != OK
+// marks the files Go has to decode itself (Unsupported) or that Go's decoder rejects too (Invalid); their outputs are nil.
+func (p *Plan) RunGIFGIF(files [][]byte, quality int) (*Streams, error) {
+	n := len(files)
+	s := &Streams{x: p.x, resize: make([]C.ipx_bytes, n), thumb: make([]C.ipx_bytes, n), watermark: make([]C.ipx_bytes, n),
+		Status: make([]Status, n)}
+	if n == 0 {
+		return s, nil
+	}
+	cf := (*[1 << 24]C.ipx_bytes)(C.malloc(C.size_t(n) * C.size_t(unsafe.Sizeof(C.ipx_bytes{}))))
+	defer C.free(unsafe.Pointer(cf))
+	var pin runtimePinner
+	defer pin.Unpin()
+	for i, f := range files {
+		cf[i] = C.ipx_bytes{}
+		if len(f) > 0 {
+			pin.Pin(&f[0])
+			cf[i] = C.ipx_bytes{data: (*C.uint8_t)(unsafe.Pointer(&f[0])), len: C.size_t(len(f))}
+		}
+	}
+	st := make([]C.int, n)
+	err := call(func() C.int {
+		return C.ipx_plan_run_gif_gif(p.x.c, p.c, C.int(n), &cf[0], C.int(quality), &s.resize[0], &s.thumb[0], &s.watermark[0], &st[0], &s.res)
+	})
+	if err != nil {
+		return nil, err
+	}
+	for i := range st {
+		s.Status[i] = Status(st[i])
+	}
+	return s, nil
+}

@@ -337,6 +337,29 @@ class Plan:
             lib().ipx_jpeg_result_free(self.ctx.handle, res)
         return out, list(status)
 
+    def run_gif_gif(self, files, quality=85, want=("resize", "thumbnail", "watermark"), copy=True):
+        """GIF byte strings in -> ({operator: [bytes | None] * n}, status list): gif.Decode, operators, gif.Encode of resize / thumbnail
+        and jpeg.Encode (at `quality`) of the watermark on the GPU."""
+        n = len(files)
+        keep = [bytes(f) for f in files]
+        arr = (_lib.Bytes * max(n, 1))()
+        for j, f in enumerate(keep):
+            arr[j].data = C.cast(C.c_char_p(f), C.c_void_p)
+            arr[j].len = len(f)
+        i = self.info
+        outs = {}
+        for k, present in (("resize", i.resize_bytes), ("thumbnail", i.thumb_bytes), ("watermark", i.wm_bytes)):
+            if k in want and present:
+                outs[k] = (_lib.Bytes * max(n, 1))()
+        status = (C.c_int * max(n, 1))()
+        res = C.c_void_p()
+        _check(lib().ipx_plan_run_gif_gif(self.ctx.handle, self.handle, n, arr, int(quality), outs.get("resize"), outs.get("thumbnail"),
+                                          outs.get("watermark"), status, C.byref(res)))
+        out = {k: [(C.string_at(a[j].data, a[j].len) if copy else a[j].len) if a[j].data else None for j in range(n)] for k, a in outs.items()}
+        if res:
+            lib().ipx_jpeg_result_free(self.ctx.handle, res)
+        return out, list(status)[:n]
+
     def run_dev_nrgba(self, n, src_ptr, resize_ptr=None, thumb_ptr=None, wm_ptr=None, stream=None):
         """*image.NRGBA frames (tightly packed) resident in HBM (ipx_plan_run_dev_nrgba)"""
         i = self.info
@@ -674,6 +697,37 @@ class Context:
             lib().ipx_jpeg_planes_free(self.handle, owner)
         else:
             info.update(batch=b, free=lambda: lib().ipx_jpeg_planes_free(self.handle, owner))
+        return info, st
+
+    def gif_decode_batch(self, files, w=0, h=0, download=True):
+        """image.Decode of a batch of GIF byte strings on the GPU (the first image of each).  -> (info, status list); info = dict(w, h,
+        stride, index, palettes) with index as n x h x w and palettes as n x 256 x 4 uint8 arrays (download=True), or the device
+        batch (PalettedBatch) + `free()`; None when no file was decodable."""
+        n = len(files)
+        keep = [bytes(f) for f in files]
+        arr = (_lib.Bytes * max(n, 1))()
+        for i, f in enumerate(keep):
+            arr[i].data = C.cast(C.c_char_p(f), C.c_void_p)
+            arr[i].len = len(f)
+        cw, chh = C.c_int(w), C.c_int(h)
+        b = _lib.PalettedBatch()
+        status = (C.c_int * max(n, 1))()
+        owner = C.c_void_p()
+        _check(lib().ipx_gif_decode_batch(self.handle, None, arr, n, C.byref(cw), C.byref(chh), C.byref(b), status, C.byref(owner)))
+        st = list(status)[:n]
+        if not b.index:
+            return None, st
+        info = {"w": cw.value, "h": chh.value, "stride": b.stride}
+        if download:
+            fr = np.empty((n, b.frame_stride), np.uint8)
+            _check(lib().ipx_memcpy_d2h(self.handle, fr.ctypes.data, b.index, fr.nbytes))
+            pal = np.empty((n, 256, 4), np.uint8)
+            _check(lib().ipx_memcpy_d2h(self.handle, pal.ctypes.data, b.palettes, pal.nbytes))
+            info["index"] = fr[:, :cw.value * chh.value].reshape(n, chh.value, cw.value)
+            info["palettes"] = pal
+            lib().ipx_gif_frames_free(self.handle, owner)
+        else:
+            info.update(batch=b, free=lambda: lib().ipx_gif_frames_free(self.handle, owner))
         return info, st
 
     def composite_glyphs(self, dst, glyphs, col):

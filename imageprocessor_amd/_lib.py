@@ -48,6 +48,10 @@ class YCbCrBatch(C.Structure):
                 ("ratio", C.c_int32)]
 
 
+class PalettedBatch(C.Structure):
+    _fields_ = [("index", C.c_void_p), ("stride", C.c_int32), ("frame_stride", C.c_size_t), ("palettes", C.c_void_p)]
+
+
 class Param(C.Structure):
     _fields_ = [("key", C.c_char_p), ("type", C.c_int32), ("f64", C.c_double), ("i64", C.c_int64),
                 ("str", C.c_char_p)]
@@ -209,6 +213,11 @@ SIGNATURES = {
     "ipx_dev_gif_dither_rgba8": (_I, [_P, _P, _P, _I, _I, _I, _Z, _I, _P]),
     "ipx_plan_run_host_paletted_gif": (_I, [_P, _P, _I, _P, _I, _Z, _P, _I, C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(Bytes),
                                             C.POINTER(_P)]),
+    "ipx_gif_decode_batch": (_I, [_P, _P, C.POINTER(Bytes), _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(PalettedBatch), C.POINTER(_I),
+                                  C.POINTER(_P)]),
+    "ipx_gif_frames_free": (None, [_P, _P]),
+    "ipx_plan_run_gif_gif": (_I, [_P, _P, _I, C.POINTER(Bytes), _I, C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(_I),
+                                  C.POINTER(_P)]),
     "ipx_font_create": (_I, [_P, _Z, C.POINTER(_P)]),
     "ipx_font_destroy": (None, [_P]),
     "ipx_font_glyph_index": (_I, [_P, C.c_uint32]),

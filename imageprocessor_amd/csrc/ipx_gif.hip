@@ -258,7 +258,7 @@ static int gif_dither(hipStream_t s, const uint8_t *src, int w, int h, int strid
 }
 
 // n frames in HBM -> streams in one pinned block (ipx_host_alloc), everything on stream s; returns once the block is filled
-static int gif_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w, int h, int stride, size_t frame_stride, int n,
+int gif_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w, int h, int stride, size_t frame_stride, int n,
                            uint8_t **blob, size_t *offs, size_t *lens)
 {
     *blob = nullptr;

@@ -1,0 +1,64 @@
+// ipx_gif_dec.h -- gif.Decode (the first image of a file) on the GPU: what the kernels (ipx_gif_dec.hip) and the host half
+// (ipx_gif_dec_host.cpp) share.  Not part of the ABI.  The restatement of Go's reader is in DESIGN.md section 4.8;
+// tests/gif_decode_model.py is the model it is held to.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+namespace ipx {
+
+// ---- host parse ----------------------------------------------------------------------------------------------------------------
+// What the host reads of one file: the container up to the first image's LZW minimum code size, then the sub-block framing of its
+// image data.  status: IPX_OK (the image data still has to be decoded), IPX_ERR_INVALID (Go's reader fails before the image data:
+// header, tables, extensions, descriptor, code size) or IPX_ERR_UNSUPPORTED (a geometry the GPU path does not take: a non-zero
+// origin, an empty frame, a frame beyond the span the kernels address, a file of 2 GiB or more).
+struct GifFileInfo {
+    int status = 0;
+    int left = 0, top = 0, w = 0, h = 0;
+    int lit = 0;
+    bool interlaced = false;
+    bool terminated = false;     // the sub-blocks end in a block terminator (else the file ends first: Go fails once it reads there)
+    bool last_is_one = false;    // the last sub-block holds one byte
+    size_t data_pos = 0;         // offset in the file of the first sub-block's length byte
+    uint32_t data_len = 0;       // bytes of LZW data in the complete sub-blocks
+    uint32_t last_start = 0;     // offset in that data of the last sub-block's first byte
+    uint32_t pal_len = 0;        // len(m.Palette) (the transparent index may lengthen it past the table)
+    uint8_t pal[1024];           // 256 x (R, G, B, A): opaque entries A = 255, the transparent entry and unused entries zero
+};
+int gif_parse(const uint8_t *p, size_t n, GifFileInfo *info);
+// the LZW bytes of the complete sub-blocks, framing stripped, to dst (info.data_len bytes)
+void gif_gather(const uint8_t *p, size_t n, const GifFileInfo &info, uint8_t *dst);
+// entries of code scratch a file needs: one per code that outputs bytes (at most one per 3 bits of data and at most one per pixel:
+// the walk stops at the first byte past the frame) plus the closing offset
+uint32_t gif_code_cap(const GifFileInfo &info);
+
+// ---- device side ---------------------------------------------------------------------------------------------------------------
+enum : uint8_t { kGifTerminated = 1, kGifLastIsOne = 2, kGifInterlaced = 4 };
+struct GifDecDesc {              // one file of a launch
+    uint64_t data_off;           // its LZW bytes at blob + data_off
+    uint64_t code_off;           // its code scratch: code_cap entries at codes + code_off
+    uint32_t data_len, last_start, code_cap;
+    uint32_t w, h;
+    uint32_t pal_len;            // 256 or more: no index is out of range
+    uint32_t slot;               // its frame: frames + slot * frame_stride
+    uint16_t lit;
+    uint8_t flags, pad;
+};
+// One record per code that outputs bytes, written by the code walk: its string goes to [off, next record's off) of the frame's
+// (interlaced) pixel order.  segb: the record index of its segment's first code (since the last clear code); the code at ordinal
+// t >= 1 of a segment defines the entry eof + t = (the string of the code before it) + (the first byte of its own string).
+// packed: value (12 bits) | the previous code's value in the segment (12 bits) << 12 | the first byte of its string << 24.
+struct GifCode { uint32_t off, segb, packed; };
+// per file, after the walk: [0] status (0: decoded, 1: Go's reader fails on the image data, 2: the code scratch was too small --
+// cannot happen with gif_code_cap), [1] records written
+constexpr int kGifStateWords = 2;
+
+hipError_t launch_gif_walk(const uint8_t *blob, const GifDecDesc *desc, int n, GifCode *codes, uint32_t *state, hipStream_t s);
+// blocks_per_file: workgroups of 256 lanes striding over a file's records
+hipError_t launch_gif_expand(const GifDecDesc *desc, int n, const GifCode *codes, const uint32_t *state, uint8_t *frames,
+                             size_t frame_stride, int blocks_per_file, hipStream_t s);
+
+}  // namespace ipx

@@ -1,0 +1,455 @@
+// ipx_gif_dec.hip -- gif.Decode (image/gif reader.go, compress/lzw reader.go) of the first image of a batch of files on the GPU, and
+// the ABI entries built on it.  Kernels: the code walk (one lane per file reads the codes, keeps the live dictionary's lengths and
+// first bytes in LDS and checks every rule of the reader, O(1) work per code) and the expansion (every lane of a grid takes one code and
+// writes its string backwards along the entry -> code-ordinal map of its segment, straight into the de-interlaced row).  Host half:
+// ipx_gif_dec_host.cpp.  DESIGN.md section 4.8 has the restatement and the numbers.
+#include <memory>
+#include <vector>
+
+#include "ipx_gif_dec.h"
+#include "ipx_runtime_internal.h"
+#include "ipx_threads.h"
+
+namespace ipx {
+
+// ---- code walk -----------------------------------------------------------------------------------------------------------------
+// One wave per file; the wave stages the LZW bytes in LDS 4 KiB at a time, lane 0 reads the codes.  Per code that outputs bytes it
+// writes a GifCode record (its output offset, its segment, its value, the previous code's value, its first byte).  It stops at the EOF
+// code, at the end of the data, or at the first rule broken: an invalid code, a byte past the frame, a literal >= len(palette) (every
+// pixel is a copy of some literal code's value, and every literal code's own byte lands in the frame, so the set of pixel values is the
+// set of literal codes read: Go's per-pixel "invalid pixel value" check and this per-code one fail on the same files).  At the EOF code,
+// blockReader.close's rule: the code's last byte lies in the last sub-block, or the data ended exactly on a sub-block boundary and one
+// sub-block of one byte follows; either way a block terminator comes next.  Records are bounded by the host's code_cap.
+constexpr int kWalkChunk = 4096;
+
+__global__ __launch_bounds__(64) void gif_walk_kernel(const uint8_t *__restrict__ blob, const GifDecDesc *__restrict__ desc,
+                                                      GifCode *__restrict__ codes, uint32_t *__restrict__ state)
+{
+    __shared__ uint16_t s_len[4096];
+    __shared__ uint8_t s_first[4096];
+    __shared__ uint8_t s_buf[kWalkChunk + 4];
+    __shared__ uint32_t s_base;
+    __shared__ int s_done;
+    const int lane = threadIdx.x;
+    const GifDecDesc d = desc[blockIdx.x];
+    const uint8_t *src = blob + d.data_off;
+    GifCode *rec = codes + d.code_off;
+    const uint32_t clear = 1u << d.lit, eof = clear + 1, npix = d.w * d.h;
+    const uint64_t nbits = 8ull * d.data_len;
+    // the reader (meaningful in lane 0)
+    uint64_t bit = 0;
+    uint32_t width = d.lit + 1, hi = eof, overflow = 1u << width;
+    bool have_last = false;
+    uint32_t last = 0, last_len = 0, last_first = 0, count = 0, k = 0, segb = 0, st = 0;
+    if (lane == 0) { s_base = 0; s_done = 0; }
+    __syncthreads();
+    for (;;) {
+        const uint32_t base = s_base;
+        for (int i = lane; i < kWalkChunk + 4; i += 64) s_buf[i] = base + (uint32_t)i < d.data_len ? src[base + i] : 0;
+        __syncthreads();
+        if (lane == 0) {
+            bool done = false;
+            while ((uint32_t)(bit >> 3) - base < (uint32_t)kWalkChunk) {
+                if (bit + width > nbits) {        // the data end without an EOF code: accepted once the frame is complete
+                    st = (d.flags & kGifTerminated) && count == npix ? 0 : 1;
+                    done = true;
+                    break;
+                }
+                const uint32_t o = (uint32_t)(bit >> 3) - base;
+                const uint32_t raw = s_buf[o] | (uint32_t)s_buf[o + 1] << 8 | (uint32_t)s_buf[o + 2] << 16;
+                const uint32_t v = (raw >> (bit & 7)) & ((1u << width) - 1);
+                bit += width;
+                if (v == clear) {
+                    width = d.lit + 1; hi = eof; overflow = 1u << width; have_last = false; segb = k;
+                    continue;
+                }
+                if (v == eof) {
+                    const uint64_t used = (bit + 7) >> 3;
+                    const bool close_ok = (d.flags & kGifTerminated) &&
+                                          (used > d.last_start || (used == d.last_start && (d.flags & kGifLastIsOne)));
+                    st = count == npix && close_ok ? 0 : 1;
+                    done = true;
+                    break;
+                }
+                uint32_t L, f;
+                if (v < clear) {
+                    if (v >= d.pal_len) { st = 1; done = true; break; }     // invalid pixel value
+                    L = 1; f = v;
+                } else if (v < hi || (v == hi && !have_last)) {             // (the second: a full table, entry 4095)
+                    L = s_len[v]; f = s_first[v];
+                } else if (v == hi) {                                       // KwKwK
+                    L = last_len + 1; f = last_first;
+                } else {                                                    // invalid code
+                    st = 1; done = true; break;
+                }
+                if (L > npix - count) { st = 1; done = true; break; }       // too much image data
+                if (k + 1 >= d.code_cap) { st = 2; done = true; break; }
+                rec[k] = GifCode{count, segb, v | (have_last ? last : 0u) << 12 | f << 24};
+                if (have_last) { s_len[hi] = (uint16_t)(last_len + 1); s_first[hi] = (uint8_t)last_first; }
+                count += L;
+                k++;
+                have_last = true; last = v; last_len = L; last_first = f;
+                if (++hi >= overflow) {
+                    if (width == 12) { have_last = false; hi--; }           // no entry is added until a clear code
+                    else { width++; overflow <<= 1; }
+                }
+            }
+            if (done) s_done = 1;
+            else s_base = (uint32_t)(bit >> 3);
+        }
+        __syncthreads();
+        if (s_done) break;
+    }
+    if (lane == 0) {
+        rec[k].off = count;                     // the closing offset (k < code_cap)
+        state[kGifStateWords * d.slot] = st;
+        state[kGifStateWords * d.slot + 1] = k;
+    }
+}
+
+hipError_t launch_gif_walk(const uint8_t *blob, const GifDecDesc *desc, int n, GifCode *codes, uint32_t *state, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(gif_walk_kernel, dim3(n), dim3(64), 0, s, blob, desc, codes, state);
+    return hipGetLastError();
+}
+
+// ---- expansion -----------------------------------------------------------------------------------------------------------------
+// Lane per record.  The entry E > eof of a code in segment b was defined by record j = b + (E - eof): E's last byte is j's first byte
+// and the rest is the string of the code before j, whose value j carries.  Each step moves to a record strictly before the last, so a
+// string of L bytes costs L steps and nothing is shared between lanes.  Writes stay inside [off, next off) of the frame's own pixels
+// (checked against the frame size, whatever the records say); files whose walk failed are skipped.
+__global__ __launch_bounds__(256) void gif_expand_kernel(const GifDecDesc *__restrict__ desc, const GifCode *__restrict__ codes,
+                                                         const uint32_t *__restrict__ state, uint8_t *__restrict__ frames,
+                                                         size_t frame_stride)
+{
+    const GifDecDesc d = desc[blockIdx.y];
+    if (state[kGifStateWords * d.slot] != 0) return;
+    const uint32_t nrec = min(state[kGifStateWords * d.slot + 1], d.code_cap - 1);
+    const GifCode *rec = codes + d.code_off;
+    uint8_t *out = frames + (size_t)d.slot * frame_stride;
+    const uint32_t w = d.w, h = d.h, npix = w * h, clear = 1u << d.lit, eof = clear + 1;
+    const bool il = (d.flags & kGifInterlaced) != 0;
+    const uint32_t n0 = (h + 7) / 8, n1 = (h + 3) / 8, n2 = (h + 1) / 4;
+    auto row = [&](uint32_t r) -> uint32_t {      // the interlaced passes (8, 0), (8, 4), (4, 2), (2, 1)
+        if (!il) return r;
+        if (r < n0) return 8 * r;
+        r -= n0;
+        if (r < n1) return 8 * r + 4;
+        r -= n1;
+        if (r < n2) return 4 * r + 2;
+        return 2 * (r - n2) + 1;
+    };
+    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < nrec; k += gridDim.x * blockDim.x) {
+        const GifCode me = rec[k];
+        const uint32_t end = rec[k + 1].off;
+        if (end > npix || end <= me.off) continue;
+        uint32_t pos = end - 1, r = pos / w, x = pos - r * w, y = row(r);
+        uint32_t v = me.packed & 4095, lim = k;
+        for (;;) {
+            uint32_t byte, next = 0;
+            const bool lit = v < clear;
+            if (lit) {
+                byte = v;
+            } else {
+                const uint32_t j = me.segb + (v - eof);
+                if (v <= eof || j > lim) break;
+                const uint32_t p = rec[j].packed;
+                byte = p >> 24;
+                next = (p >> 12) & 4095;
+                lim = j - 1;
+            }
+            out[(size_t)y * w + x] = (uint8_t)byte;
+            if (lit || pos == me.off) break;
+            pos--;
+            if (x == 0) { x = w - 1; r--; y = row(r); }
+            else x--;
+            v = next;
+        }
+    }
+}
+
+hipError_t launch_gif_expand(const GifDecDesc *desc, int n, const GifCode *codes, const uint32_t *state, uint8_t *frames,
+                             size_t frame_stride, int blocks_per_file, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(gif_expand_kernel, dim3(blocks_per_file, n), dim3(256), 0, s, desc, codes, state, frames, frame_stride);
+    return hipGetLastError();
+}
+
+}  // namespace ipx
+
+// ---- the decode core -------------------------------------------------------------------------------------------------------------
+
+// parse n files (a thread per eight of them); status[i] from the container, then the batch's size: *w x *h, or the first parsed
+// file's when *w == 0 (files of another size: IPX_ERR_UNSUPPORTED)
+static int gif_parse_batch(const ipx_bytes *files, int n, int *w, int *h, std::vector<GifFileInfo> &info, int *status)
+{
+    std::atomic<int> failed{IPX_OK};
+    HostPool::instance().parallel_for(n, std::max(1, std::min(n / 8, 16)), [&](int i) {
+        const int rc = guarded_status([&] { status[i] = gif_parse(files[i].data, files[i].data ? files[i].len : 0, &info[i]); }, nullptr);
+        if (rc) failed = rc;
+    });
+    if (failed) { set_error("gif decode: host parse failed"); return failed; }
+    for (int i = 0; i < n; i++) {
+        if (status[i] != IPX_OK) continue;
+        if (*w <= 0) { *w = info[i].w; *h = info[i].h; }
+        if (info[i].w != *w || info[i].h != *h) status[i] = IPX_ERR_UNSUPPORTED;
+    }
+    return IPX_OK;
+}
+
+// Decodes the files with status IPX_OK into frames + i * frame_stride (w x h, rows w bytes apart) and their palettes into
+// palettes + i * 1024 (every slot's palette is written; zero for the others), all on stream s; the walk's verdict lands in status[].
+// The code scratch is cut into groups of at most ~4 GiB (IPX_GIF_DEC_SCRATCH_MB); one read-back of the per-file words at the end.
+static int gif_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files, int n, const std::vector<GifFileInfo> &info,
+                            uint8_t *frames, size_t frame_stride, uint8_t *palettes, int *status)
+{
+    std::vector<uint8_t *> pinned;
+    struct Release {    // the pinned blocks go back once the stream is past the copies that read them
+        ipx_ctx *ctx; hipStream_t s; std::vector<uint8_t *> &p;
+        ~Release() { (void)hipStreamSynchronize(s); for (uint8_t *q : p) (void)ipx_host_free(ctx, q); }
+    } release{ctx, s, pinned};
+    AsyncFree mem{s, {}};
+    uint32_t *dstate;
+    IPX_HIP(mem.get(&dstate, (size_t)n * kGifStateWords * 4));
+    // palettes: one upload of every slot
+    uint8_t *hpal = (uint8_t *)ipx_host_alloc(ctx, (size_t)n * 1024);
+    if (!hpal) return IPX_ERR_NOMEM;
+    pinned.push_back(hpal);
+    for (int i = 0; i < n; i++) {
+        if (status[i] == IPX_OK) memcpy(hpal + (size_t)i * 1024, info[i].pal, 1024);
+        else memset(hpal + (size_t)i * 1024, 0, 1024);
+    }
+    IPX_HIP(hipMemcpyAsync(palettes, hpal, (size_t)n * 1024, hipMemcpyHostToDevice, s));
+    const size_t budget = (size_t)env_int("IPX_GIF_DEC_SCRATCH_MB", 4096) << 20;
+    std::vector<int> group;
+    auto run_group = [&]() -> int {
+        const int m = (int)group.size();
+        if (m == 0) return IPX_OK;
+        size_t data_bytes = 0, codes = 0;
+        uint32_t max_cap = 0;
+        std::vector<GifDecDesc> desc(m);
+        for (int g = 0; g < m; g++) {
+            const GifFileInfo &f = info[group[g]];
+            GifDecDesc &d = desc[g];
+            memset(&d, 0, sizeof d);
+            d.data_off = data_bytes;
+            d.code_off = codes;
+            d.data_len = f.data_len;
+            d.last_start = f.last_start;
+            d.code_cap = gif_code_cap(f);
+            d.w = (uint32_t)f.w;
+            d.h = (uint32_t)f.h;
+            d.pal_len = std::min<uint32_t>(f.pal_len, 256);
+            d.slot = (uint32_t)group[g];
+            d.lit = (uint16_t)f.lit;
+            d.flags = (uint8_t)((f.terminated ? kGifTerminated : 0) | (f.last_is_one ? kGifLastIsOne : 0) | (f.interlaced ? kGifInterlaced : 0));
+            data_bytes += (f.data_len + 15) & ~(size_t)15;
+            codes += d.code_cap;
+            max_cap = std::max(max_cap, d.code_cap);
+        }
+        const size_t desc_bytes = align256(sizeof(GifDecDesc) * m);
+        uint8_t *hblob = (uint8_t *)ipx_host_alloc(ctx, desc_bytes + data_bytes);
+        if (!hblob) return IPX_ERR_NOMEM;
+        pinned.push_back(hblob);
+        memcpy(hblob, desc.data(), sizeof(GifDecDesc) * m);
+        HostPool::instance().parallel_for(m, std::max(1, std::min(m / 8, 16)), [&](int g) {
+            const int i = group[g];
+            gif_gather(files[i].data, files[i].len, info[i], hblob + desc_bytes + desc[g].data_off);
+        });
+        uint8_t *dblob;
+        GifCode *dcodes;
+        IPX_HIP(mem.get(&dblob, desc_bytes + data_bytes));
+        IPX_HIP(mem.get(&dcodes, codes * sizeof(GifCode)));
+        IPX_HIP(hipMemcpyAsync(dblob, hblob, desc_bytes + data_bytes, hipMemcpyHostToDevice, s));
+        const GifDecDesc *ddesc = (const GifDecDesc *)dblob;
+        IPX_HIP(launch_gif_walk(dblob + desc_bytes, ddesc, m, dcodes, dstate, s));
+        const int bpf = (int)std::max<uint32_t>(1, std::min<uint32_t>((max_cap + 255) / 256, (uint32_t)std::max(1, 16384 / m)));
+        IPX_HIP(launch_gif_expand(ddesc, m, dcodes, dstate, frames, frame_stride, bpf, s));
+        group.clear();
+        return IPX_OK;
+    };
+    size_t group_bytes = 0;
+    for (int i = 0; i < n; i++) {
+        if (status[i] != IPX_OK) continue;
+        const size_t need = (size_t)gif_code_cap(info[i]) * sizeof(GifCode) + info[i].data_len;
+        if (!group.empty() && group_bytes + need > budget) {
+            const int rc = run_group();
+            if (rc) return rc;
+            group_bytes = 0;
+        }
+        group.push_back(i);
+        group_bytes += need;
+    }
+    int rc = run_group();
+    if (rc) return rc;
+    std::vector<uint32_t> st((size_t)n * kGifStateWords);
+    IPX_HIP(hipMemcpyAsync(st.data(), dstate, st.size() * 4, hipMemcpyDeviceToHost, s));
+    IPX_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < n; i++) {
+        if (status[i] != IPX_OK) continue;
+        const uint32_t v = st[(size_t)kGifStateWords * i];
+        status[i] = v == 0 ? IPX_OK : v == 1 ? IPX_ERR_INVALID : IPX_ERR_UNSUPPORTED;   // 2: scratch too small (cannot happen)
+    }
+    return IPX_OK;
+}
+
+// ---- the entries -----------------------------------------------------------------------------------------------------------------
+struct ipx_gif_frames { std::vector<void *> dev; hipStream_t stream = nullptr; };   // stream-ordered allocations of `stream`
+
+extern "C" {
+
+void ipx_gif_frames_free(ipx_ctx *ctx, ipx_gif_frames *o)
+{
+    if (!o) return;
+    if (ctx) (void)hipSetDevice(ctx->device);
+    for (void *p : o->dev) (void)hipFreeAsync(p, o->stream);
+    delete o;
+}
+
+int ipx_gif_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *gifs, int n, int *w, int *h, ipx_paletted_batch *frames,
+                         int *status, ipx_gif_frames **owner) try
+{
+    IPX_ENTER(ctx);
+    if (!gifs || n < 0 || !w || !h || !frames || !status || !owner || *w < 0 || *h < 0 || (*w == 0) != (*h == 0)) {
+        set_error("ipx_gif_decode_batch: bad argument");
+        return IPX_ERR_INVALID;
+    }
+    *owner = nullptr;
+    memset(frames, 0, sizeof *frames);
+    if (n == 0) return IPX_OK;
+    if (n > 65535) { set_error("ipx_gif_decode_batch: at most 65535 files per call"); return IPX_ERR_UNSUPPORTED; }
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    std::vector<GifFileInfo> info(n);
+    int bw = *w, bh = *h;
+    int rc = gif_parse_batch(gifs, n, &bw, &bh, info, status);
+    if (rc) return rc;
+    bool any = false;
+    for (int i = 0; i < n; i++) any |= status[i] == IPX_OK;
+    if (!any) return IPX_OK;
+    std::unique_ptr<ipx_gif_frames> o(new ipx_gif_frames);
+    o->stream = s;
+    const size_t fs = align256((size_t)bw * bh);
+    uint8_t *dframes = nullptr, *dpal = nullptr;
+    hipError_t e = hipMallocAsync((void **)&dframes, fs * n, s);
+    if (e == hipSuccess) { o->dev.push_back(dframes); e = hipMallocAsync((void **)&dpal, (size_t)n * 1024, s); }
+    if (e == hipSuccess) o->dev.push_back(dpal);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        ipx_gif_frames_free(ctx, o.release());
+        set_error("ipx_gif_decode_batch: device allocation failed: %s", hipGetErrorString(e));
+        return IPX_ERR_NOMEM;
+    }
+    rc = gif_decode_files(ctx, s, gifs, n, info, dframes, fs, dpal, status);
+    if (rc) { ipx_gif_frames_free(ctx, o.release()); return rc; }
+    *w = bw;
+    *h = bh;
+    any = false;
+    for (int i = 0; i < n; i++) any |= status[i] == IPX_OK;
+    if (!any) { ipx_gif_frames_free(ctx, o.release()); return IPX_OK; }     // every image failed in its data: no frames
+    frames->index = dframes;
+    frames->stride = bw;
+    frames->frame_stride = fs;
+    frames->palettes = dpal;
+    *owner = o.release();
+    return IPX_OK;
+}
+IPX_CATCH_STATUS
+
+// The GIF task's GPU leg from the uploads on: per chunk of files, the host parse and the upload of the LZW data, the walk and the
+// expansion into HBM, ipx_plan_run_dev_paletted, then gif.Encode of the resize and thumbnail outputs and jpeg.Encode of the watermark
+// output (a GIF watermark becomes a JPEG, watermark.go:73).  Chunks are bounded as in ipx_plan_run_host_paletted_gif.  The operators run
+// on every slot of a chunk (a failed file's slot holds whatever its frame holds); only OK files' streams are handed out.
+int ipx_plan_run_gif_gif(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, int quality, ipx_bytes *resize_out,
+                         ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result) try
+{
+    IPX_ENTER(ctx);
+    if (!pl || n < 0 || !files || !status || !result) { set_error("ipx_plan_run_gif_gif: bad argument"); return IPX_ERR_INVALID; }
+    *result = nullptr;
+    const ipx_plan_info &in = pl->info;
+    const int sw = pl->p.sw, sh = pl->p.sh;
+    if ((resize_out && in.resize_bytes && (in.resize_w >= 1 << 16 || in.resize_h >= 1 << 16)) ||
+        (thumb_out && in.thumb_bytes && (in.thumb_w >= 1 << 16 || in.thumb_h >= 1 << 16))) {
+        set_error("gif: image is too large to encode");
+        return IPX_ERR_INVALID;
+    }
+    for (int i = 0; i < n; i++) {
+        for (ipx_bytes *o : {resize_out, thumb_out, wm_out})
+            if (o) o[i] = ipx_bytes{nullptr, 0};
+    }
+    if (n == 0) return IPX_OK;
+    if (!frame_span_ok(sw, sh, sw, 1)) {
+        for (int i = 0; i < n; i++) status[i] = IPX_ERR_UNSUPPORTED;
+        return IPX_OK;
+    }
+    const size_t fsrc = align256((size_t)sw * sh);
+    const size_t fres = resize_out ? align256(in.resize_bytes) : 0, fth = thumb_out ? align256(in.thumb_bytes) : 0;
+    const size_t fwm = wm_out ? align256(in.wm_bytes) : 0;
+    const size_t cwm = fwm ? align256(ipx_jpeg_coef_count(sw, sh) * 2) : 0;
+    const size_t per_frame = fsrc + 1024 + fres + fth + fwm + cwm;
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n, (size_t)env_int("IPX_HOST_CHUNK_GIF", 64),
+                                                                 ((size_t)1 << 30) / per_frame}));
+    struct ResultGuard {
+        ipx_ctx *ctx;
+        ipx_jpeg_result *r;
+        ~ResultGuard() { ipx_jpeg_result_free(ctx, r); }
+    } res{ctx, new ipx_jpeg_result};
+    LaneLease lane(ctx);
+    hipStream_t s = lane->stream;
+    std::vector<size_t> offs(chunk), lens(chunk);
+    std::vector<GifFileInfo> info(chunk);
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+        const int m = std::min(chunk, n - i0);
+        int bw = sw, bh = sh;
+        int rc = gif_parse_batch(files + i0, m, &bw, &bh, info, status + i0);
+        if (rc) return rc;
+        bool any = false;
+        for (int i = 0; i < m; i++) any |= status[i0 + i] == IPX_OK;
+        if (!any) continue;
+        struct SyncOnExit { hipStream_t s; ~SyncOnExit() { (void)hipStreamSynchronize(s); } } sync_on_exit{s};
+        AsyncFree mem{s, {}};
+        uint8_t *didx, *dpal, *dres = nullptr, *dth = nullptr, *dwm = nullptr;
+        IPX_HIP(mem.get(&didx, fsrc * m));
+        IPX_HIP(mem.get(&dpal, (size_t)1024 * m));
+        if (fres) IPX_HIP(mem.get(&dres, fres * m));
+        if (fth) IPX_HIP(mem.get(&dth, fth * m));
+        if (fwm) IPX_HIP(mem.get(&dwm, fwm * m));
+        rc = gif_decode_files(ctx, s, files + i0, m, info, didx, fsrc, dpal, status + i0);
+        if (rc) return rc;
+        any = false;
+        for (int i = 0; i < m; i++) any |= status[i0 + i] == IPX_OK;
+        if (!any) continue;
+        rc = ipx_plan_run_dev_paletted(ctx, s, pl, m, didx, sw, fsrc, dpal, dres, fres, dth, fth, dwm, fwm);
+        if (rc) return rc;
+        struct Out { uint8_t *dev; size_t fs; int w, h; ipx_bytes *dst; };
+        const Out gifs[2] = {{dres, fres, in.resize_w, in.resize_h, resize_out}, {dth, fth, in.thumb_w, in.thumb_h, thumb_out}};
+        for (const Out &o : gifs) {
+            if (!o.dev || o.w <= 0 || o.h <= 0) continue;
+            uint8_t *blob = nullptr;
+            rc = gif_encode_core(ctx, s, o.dev, o.w, o.h, o.w * 4, o.fs, m, &blob, offs.data(), lens.data());
+            if (rc) return rc;
+            res.r->blobs.push_back(blob);
+            for (int i = 0; i < m; i++)
+                if (status[i0 + i] == IPX_OK) o.dst[i0 + i] = ipx_bytes{blob + offs[i], lens[i]};
+        }
+        if (dwm) {
+            int16_t *dcoef;
+            IPX_HIP(mem.get(&dcoef, cwm * m));
+            const JpegEncSet set{dcoef, dwm, sw, sh, sw * 4, fwm, offs.data(), lens.data()};
+            uint8_t *blob = nullptr;
+            rc = jpeg_encode_sets(ctx, s, &set, 1, m, quality, &blob);
+            if (rc) return rc;
+            if (blob) res.r->blobs.push_back(blob);
+            for (int i = 0; i < m; i++)
+                if (status[i0 + i] == IPX_OK) wm_out[i0 + i] = ipx_bytes{blob + offs[i], lens[i]};
+        }
+    }
+    *result = res.r;
+    res.r = nullptr;
+    return IPX_OK;
+}
+IPX_CATCH_STATUS
+
+}  // extern "C"
+

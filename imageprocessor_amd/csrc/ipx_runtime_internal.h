@@ -285,5 +285,9 @@ struct AsyncFree {
 struct JpegEncSet { int16_t *dcoefs; const uint8_t *src; int w, h, stride; size_t frame_stride; size_t *offs, *lens; };   // offs / lens: [n], into *blob
 int jpeg_encode_sets(ipx_ctx *ctx, hipStream_t s, const JpegEncSet *sets, int K, int n, int quality, uint8_t **blob);
 
+// gif.Encode of n frames in HBM into one pinned block *blob (ipx_gif.hip); also the GIF outputs of ipx_plan_run_gif_gif (ipx_gif_dec.hip)
+int gif_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w, int h, int stride, size_t frame_stride, int n,
+                    uint8_t **blob, size_t *offs, size_t *lens);
+
 // the pinned blocks the streams of the *_jpeg / *_gif batch entries live in (ipx_jpeg_result_free)
 struct ipx_jpeg_result { std::vector<uint8_t *> blobs; };

@@ -511,6 +511,29 @@ int ipx_jpeg_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *jpegs, in
                           ipx_ycbcr_batch *planes, int *status, ipx_jpeg_planes **owner);
 void ipx_jpeg_planes_free(ipx_ctx *ctx, ipx_jpeg_planes *owner);
 
+/* ---- image.Decode for GIFs (decoder side) ---------------------------------------------
+ * For a GIF upload image.Decode is gif.Decode: the FIRST image of the file as an *image.Paletted.  The host reads the container
+ * (header, tables, extensions, descriptor) and strips the sub-block framing; the LZW data go up, one lane per file walks the codes
+ * (every validity rule of compress/lzw's reader, O(1) work per code) and the workgroups of a second kernel expand the codes' strings in
+ * parallel straight into row order (interlace undone).  Frames stay in HBM, ready for ipx_plan_run_dev_paletted: frame i (file i) at
+ * index + i * frame_stride, rows `stride` bytes apart, its 256 x (R, G, B, A) palette at palettes + i * 1024 (the layout
+ * ipx_plan_run_dev_paletted takes).  *w, *h: 0, or the size the batch must have; on return the batch's size (the first image's, not
+ * the logical screen's).  status[i]: IPX_OK, IPX_ERR_INVALID (Go's decoder fails on the file too) or IPX_ERR_UNSUPPORTED (a first
+ * image not at (0, 0), an empty one, one of another size than the batch's or beyond ipx_frame_supported: the worker decodes those
+ * with Go as before).  The frames of non-OK files are undefined; index == NULL when no file was decodable.  Free the frames with
+ * ipx_gif_frames_free: stream-ordered allocations of `stream` (NULL: the context's default stream).  DESIGN.md section 4.8. */
+typedef struct { uint8_t *index; int32_t stride; size_t frame_stride; uint8_t *palettes; } ipx_paletted_batch;
+typedef struct ipx_gif_frames ipx_gif_frames;
+int ipx_gif_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *gifs, int n, int *w, int *h, ipx_paletted_batch *frames,
+                         int *status, ipx_gif_frames **owner);
+void ipx_gif_frames_free(ipx_ctx *ctx, ipx_gif_frames *owner);
+/* The GIF task compressed in, compressed out: the uploads as the object store returns them, gif.Decode, every operator of the plan
+ * (the plan's frame size is the batch's size), gif.Encode of the resize and thumbnail outputs and jpeg.Encode at `quality` of the
+ * watermark output (watermark.go:66-79), all on the GPU; only compressed bytes cross the link.  status[i] as for
+ * ipx_gif_decode_batch; outputs of non-OK files are {NULL, 0}.  Streams as for ipx_plan_run_host_paletted_gif (ipx_jpeg_result_free). */
+int ipx_plan_run_gif_gif(ipx_ctx *ctx, const ipx_plan *plan, int n, const ipx_bytes *files, int quality, ipx_bytes *resize_out,
+                         ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result);
+
 /* ---- one process, several GPUs, asynchronous jobs ----------------------------------------------------------
  * The reference worker is ONE process whose goroutines pull independent messages (worker.go:88-96, 112-149); it scales by
  * running more consumers, nothing is exchanged (kafka/consumer.go:23).  A pool is that shape behind the C ABI: one context per
