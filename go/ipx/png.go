@@ -1,0 +1,40 @@
+package ipx
+
+/*
+#include "ipx.h"
+*/
+import "C"
+
+import "unsafe"
+
+// EncodePNG: png.Encode(buf, img) of one w x h *image.RGBA frame in Go memory (rows stride bytes apart), on the GPU.  Go's visible
+// decisions are kept (colour type, un-premultiply, the filter of every row); the zlib stream is the library's own, so the bytes are a
+// valid PNG of the same pixels but not Go's compressed bytes (DESIGN.md section 4.9).
+func (x *Context) EncodePNG(pix []byte, w, h, stride int) ([]byte, error) {
+	var out *C.uint8_t
+	var n C.size_t
+	err := call(func() C.int {
+		return C.ipx_png_encode_rgba8(x.c, ptr(pix), C.int(w), C.int(h), C.int(stride), &out, &n)
+	})
+	if err != nil {
+		return nil, err
+	}
+	b := C.GoBytes(unsafe.Pointer(out), C.int(n))
+	C.ipx_buffer_free(unsafe.Pointer(out))
+	return b, nil
+}
+
+// RunHostPNG: the PNG task's whole GPU leg.  Decoded RGBA frames in (RunHost's arguments), operators on the GPU, then png.Encode of
+// all three outputs (resize.go:83, thumbnail.go:73, watermark.go:71: a PNG watermark stays PNG), all on the GPU; only the finished
+// streams cross the link.  Release the Streams once they are written out.
+func (p *Plan) RunHostPNG(n int, src []byte) (*Streams, error) {
+	s := &Streams{x: p.x, resize: make([]C.ipx_bytes, n), thumb: make([]C.ipx_bytes, n), watermark: make([]C.ipx_bytes, n)}
+	err := call(func() C.int {
+		return C.ipx_plan_run_host_png(p.x.c, p.c, C.int(n), ptr(src), C.int(p.w*4), C.size_t(p.w*p.h*4),
+			&s.resize[0], &s.thumb[0], &s.watermark[0], &s.res)
+	})
+	if err != nil {
+		return nil, err
+	}
+	return s, nil
+}

@@ -297,6 +297,23 @@ class Plan:
         lib().ipx_jpeg_result_free(self.ctx.handle, res)
         return out
 
+    def run_host_png(self, frames, want=("resize", "thumbnail", "watermark"), copy=True):
+        """frames: n x H x W x 4 uint8 (host) -> {operator: [png bytes] * n}: operators and png.Encode of every output on the GPU, only
+        the streams come back.  copy=False: lengths only (the streams are released unread; for timing)."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        n, i = frames.shape[0], self.info
+        assert frames.shape[1:] == (self._sh, self._sw, 4)
+        arrs = {}
+        for k, present in (("resize", i.resize_bytes), ("thumbnail", i.thumb_bytes), ("watermark", i.wm_bytes)):
+            if k in want and present:
+                arrs[k] = (_lib.Bytes * n)()
+        res = C.c_void_p()
+        _check(lib().ipx_plan_run_host_png(self.ctx.handle, self.handle, n, frames.ctypes.data, self._sw * 4, self._sw * self._sh * 4,
+                                           arrs.get("resize"), arrs.get("thumbnail"), arrs.get("watermark"), C.byref(res)))
+        out = {k: [C.string_at(a[j].data, a[j].len) if copy else a[j].len for j in range(n)] for k, a in arrs.items()}
+        lib().ipx_jpeg_result_free(self.ctx.handle, res)
+        return out
+
     def run_host_ycbcr_jpeg(self, y, cb, cr, ratio, quality=85, want=("resize", "thumbnail", "watermark"), copy=True):
         """Decoded JPEG planes (host) -> {operator: [jpeg bytes] * n}; see run_host_jpeg."""
         y, cb, cr = (np.ascontiguousarray(a, dtype=np.uint8) for a in (y, cb, cr))
@@ -652,6 +669,32 @@ class Context:
         """n frames in HBM -> n GIF streams.  copy=False returns (memoryviews into the pinned block, release()) instead of bytes."""
         blob, offs, lens = C.c_void_p(), (C.c_size_t * max(n, 1))(), (C.c_size_t * max(n, 1))()
         _check(lib().ipx_gif_encode_batch_dev(self.handle, src_ptr, w, h, stride or w * 4,
+                                              frame_stride if frame_stride is not None else w * h * 4, n, C.byref(blob), offs, lens))
+        if n == 0:
+            return ([], (lambda: None)) if not copy else []
+        if not copy:
+            total = offs[n - 1] + lens[n - 1]
+            buf = (C.c_uint8 * total).from_address(blob.value)
+            mv = memoryview(buf)
+            return [mv[offs[i]:offs[i] + lens[i]] for i in range(n)], (lambda: lib().ipx_host_free(self.handle, blob))
+        res = [C.string_at(blob.value + offs[i], lens[i]) for i in range(n)]
+        lib().ipx_host_free(self.handle, blob)
+        return res
+
+    def png_encode(self, frame):
+        """png.Encode(w, *image.RGBA) of one host frame (H x W x 4 uint8, premultiplied) -> bytes (the zlib stream is this project's own)"""
+        frame = np.ascontiguousarray(frame, dtype=np.uint8)
+        h, w = frame.shape[:2]
+        out, n = C.c_void_p(), C.c_size_t()
+        _check(lib().ipx_png_encode_rgba8(self.handle, frame.ctypes.data, w, h, w * 4, C.byref(out), C.byref(n)))
+        data = C.string_at(out, n.value)
+        lib().ipx_buffer_free(out)
+        return data
+
+    def png_encode_batch_dev(self, src_ptr, w, h, n, stride=None, frame_stride=None, copy=True):
+        """n frames in HBM -> n PNG streams.  copy=False returns (memoryviews into the pinned block, release()) instead of bytes."""
+        blob, offs, lens = C.c_void_p(), (C.c_size_t * max(n, 1))(), (C.c_size_t * max(n, 1))()
+        _check(lib().ipx_png_encode_batch_dev(self.handle, src_ptr, w, h, stride or w * 4,
                                               frame_stride if frame_stride is not None else w * h * 4, n, C.byref(blob), offs, lens))
         if n == 0:
             return ([], (lambda: None)) if not copy else []

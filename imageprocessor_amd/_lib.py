@@ -213,6 +213,9 @@ SIGNATURES = {
     "ipx_dev_gif_dither_rgba8": (_I, [_P, _P, _P, _I, _I, _I, _Z, _I, _P]),
     "ipx_plan_run_host_paletted_gif": (_I, [_P, _P, _I, _P, _I, _Z, _P, _I, C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(Bytes),
                                             C.POINTER(_P)]),
+    "ipx_png_encode_rgba8": (_I, [_P, _P, _I, _I, _I, C.POINTER(_P), C.POINTER(_Z)]),
+    "ipx_png_encode_batch_dev": (_I, [_P, _P, _I, _I, _I, _Z, _I, C.POINTER(_P), C.POINTER(_Z), C.POINTER(_Z)]),
+    "ipx_plan_run_host_png": (_I, [_P, _P, _I, _P, _I, _Z, C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(_P)]),
     "ipx_gif_decode_batch": (_I, [_P, _P, C.POINTER(Bytes), _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(PalettedBatch), C.POINTER(_I),
                                   C.POINTER(_P)]),
     "ipx_gif_frames_free": (None, [_P, _P]),

@@ -1,0 +1,71 @@
+// ipx_png.h -- png.Encode(w, *image.RGBA) on the GPU: what the kernels (ipx_png.hip) and the host half (ipx_png_host.cpp) share.
+// Not part of the ABI.  Go's visible decisions (colour type, un-premultiply, filter per row) are kept exactly; the zlib stream is this
+// project's own and is held byte for byte to tests/png_model.py, which defines the same constants.  DESIGN.md section 4.9.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+namespace ipx {
+
+constexpr int kPngSegMin = 65536;      // a segment: whole rows, at least this many filtered bytes (the frame's last takes the remainder)
+constexpr int kPngTile = 256;          // the hashed candidate of i lies before the start of i's tile (tiles counted from segment start)
+constexpr int kPngHashBits = 15;       // hash(j) = (u32le(data + j) * kPngHashMul) >> (32 - kPngHashBits), for j + 4 <= frame bytes
+constexpr uint32_t kPngHashMul = 0x9E3779B1u;
+constexpr int kPngWindow = 32768;
+constexpr int kPngMaxMatch = 258;
+constexpr int kPngMinMatch = 3;
+constexpr int kPngHeadBytes = 8 + 25;  // signature + IHDR
+constexpr int kPngTailBytes = 16 + 12; // the Adler-32 IDAT chunk + IEND
+
+// the segments of a w x h frame of bpp 3 or 4: rows_per_seg rows each, nseg of them, the last one taking the remaining rows
+struct PngSegs {
+    int stride, rps, nseg;   // stride: filtered row bytes, 1 + w * bpp
+    PngSegs(int w, int h, int bpp)
+    {
+        stride = 1 + w * bpp;
+        rps = (kPngSegMin + stride - 1) / stride;
+        if (rps < 1) rps = 1;
+        nseg = h / rps;
+        if (nseg < 1) nseg = 1;
+    }
+    int row0(int s, int h) const { return s == nseg ? h : s * rps; }
+};
+
+// chunk data bytes of a segment of `len` filtered bytes sent as stored blocks (<= 65535 bytes each) and the empty stored block
+__host__ __device__ inline size_t png_stored_bytes(size_t len, bool first) { return (first ? 2 : 0) + 5 * ((len + 65534) / 65535) + len + 5; }
+
+// one segment to compress (a workgroup of png_deflate_kernel): frame, byte range [s0, s1) of the frame's filtered stream, where its
+// IDAT chunk goes in the output regions (4-byte aligned) and whether it is the frame's first / last
+struct PngSeg {
+    uint32_t frame, s0, s1, flags;   // flags: 1 first, 2 last
+    unsigned long long out;
+};
+// a copy of the pack kernel: len bytes from the regions to the packed block
+struct PngPiece {
+    unsigned long long src, dst;
+    uint32_t len, pad;
+};
+
+// signature + IHDR for colour type 2 (bpp 3) and 6 (bpp 4) of a w x h frame: out[0] and out[1]
+void png_write_heads(int w, int h, uint8_t out[2][kPngHeadBytes]);
+
+// ---- kernel launchers (ipx_png.hip) ----
+// alpha[i] |= 1 when frame i has an alpha byte other than 0xff (alpha: n zeroed words)
+hipError_t launch_png_opacity(const uint8_t *src, int w, int h, int stride, size_t frame_stride, int n, uint32_t *alpha, hipStream_t s);
+// frame i's filtered stream (h rows of 1 + w * bpp bytes, bpp = alpha[i] ? 4 : 3) at filt + i * fbytes
+hipError_t launch_png_filter(const uint8_t *src, int w, int h, int stride, size_t frame_stride, int n, const uint32_t *alpha,
+                             uint8_t *filt, size_t fbytes, hipStream_t s);
+// one workgroup per segment: match candidates (scratch: match, 4 bytes per filtered byte), the greedy parse, the block and its IDAT
+// chunk at out + seg.out (zeroed beforehand); lens[k]: the chunk's bytes; adler[2k], adler[2k + 1]: the segment's Adler sums
+hipError_t launch_png_deflate(const uint8_t *filt, uint32_t *match, size_t fbytes, int w, int h, const uint32_t *alpha, const PngSeg *segs,
+                              int nseg, uint8_t *out, uint32_t *lens, uint32_t *adler, hipStream_t s);
+// per frame: signature + IHDR (heads: the two variants) at out + i * region, the Adler-32 chunk and IEND at out + i * region + tail;
+// item0[i] .. item0[i + 1]: frame i's segments
+hipError_t launch_png_frame(const uint8_t *heads, const uint32_t *alpha, const uint32_t *item0, const PngSeg *segs, const uint32_t *adler,
+                            int n, uint8_t *out, size_t region, size_t tail, hipStream_t s);
+hipError_t launch_png_pack(const uint8_t *out, const PngPiece *pieces, int npieces, uint8_t *dst, hipStream_t s);
+
+}  // namespace ipx

@@ -485,6 +485,25 @@ int ipx_plan_run_host_paletted_gif(ipx_ctx *ctx, const ipx_plan *plan, int n, co
                                    const uint8_t *palettes, int quality, ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out,
                                    ipx_jpeg_result **result);
 
+/* ---- png.Encode (PNG half) ---------------------------------------------------------
+ * resize.go:83, thumbnail.go:73 and watermark.go:71 end a PNG task in png.Encode(buf, img) on the operator's *image.RGBA.  Go's
+ * visible decisions are kept exactly: colour type 2 (RGB 8) when every alpha byte is 0xff, else 6 (RGBA 8) with the writer's
+ * un-premultiply; per row the filter Go's heuristic picks (smallest sum of abs8; Up, Paeth, None, Sub, Average on ties); IHDR, IDAT
+ * chunks, IEND and nothing else.  The zlib stream is this project's own (segments of whole rows deflated independently on the GPU,
+ * one IDAT chunk each, the Adler-32 in a last 4-byte IDAT chunk): any inflater decodes it to the rows png.Encode would have
+ * compressed, but the compressed bytes are not Go's.  A width or height below 1 is refused (IPX_ERR_INVALID), as Go refuses it;
+ * frames beyond ipx_frame_supported get IPX_ERR_UNSUPPORTED.  DESIGN.md section 4.9. */
+/* one frame in host memory -> *out, malloc'd (ipx_buffer_free) */
+int ipx_png_encode_rgba8(ipx_ctx *ctx, const uint8_t *pix, int w, int h, int stride, uint8_t **out, size_t *len);
+/* n frames resident in HBM (e.g. after any ipx_plan_run_dev_*) -> n streams in ONE pinned block, the ownership rules of
+ * ipx_gif_encode_batch_dev: *blob is freed with ipx_host_free; stream i is blob[offs[i] .. offs[i] + lens[i]). */
+int ipx_png_encode_batch_dev(ipx_ctx *ctx, const uint8_t *src, int w, int h, int stride, size_t frame_stride, int n, uint8_t **blob,
+                             size_t *offs, size_t *lens);
+/* The PNG task's whole GPU leg (ipx_plan_run_host's inputs): upload, every requested operator, then png.Encode of all three outputs
+ * (a PNG watermark stays PNG).  The streams land in pinned blocks owned by *result, released with ipx_jpeg_result_free. */
+int ipx_plan_run_host_png(ipx_ctx *ctx, const ipx_plan *plan, int n, const uint8_t *src, int sstride, size_t src_frame_stride,
+                          ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, ipx_jpeg_result **result);
+
 /* ---- image.Decode for JPEGs (decoder side) -------------------------------------------
  * image_processor.go:47 decodes every upload; for JPEG files that is Go's image/jpeg.  A batch of
  * files of one size and one kind (three components at 4:4:4 / 4:2:2 / 4:2:0 / 4:4:0, or one component) is decoded here.  Baseline files:
