@@ -38,3 +38,39 @@ func (p *Plan) RunHostPNG(n int, src []byte) (*Streams, error) {
 	}
 	return s, nil
 }
+
+// RunPNGPNG: the PNG task compressed in, compressed out -- the objects as fileRepo.GetOriginal returned them, image.Decode
+// (image_processor.go:47: png.Decode), every operator and png.Encode of all three outputs (resize.go:83, thumbnail.go:73,
+// watermark.go:71), all on the GPU.  Files of any PNG kind may be mixed.  files must stay valid for the duration of the call (they are
+// pinned here); Status[i] != OK marks the files Go has to decode itself (Unsupported) or that Go's decoder rejects too (Invalid); their
+// outputs are nil.
+func (p *Plan) RunPNGPNG(files [][]byte) (*Streams, error) {
+	n := len(files)
+	s := &Streams{x: p.x, resize: make([]C.ipx_bytes, n), thumb: make([]C.ipx_bytes, n), watermark: make([]C.ipx_bytes, n),
+		Status: make([]Status, n)}
+	if n == 0 {
+		return s, nil
+	}
+	cf := (*[1 << 24]C.ipx_bytes)(C.malloc(C.size_t(n) * C.size_t(unsafe.Sizeof(C.ipx_bytes{}))))
+	defer C.free(unsafe.Pointer(cf))
+	var pin runtimePinner
+	defer pin.Unpin()
+	for i, f := range files {
+		cf[i] = C.ipx_bytes{}
+		if len(f) > 0 {
+			pin.Pin(&f[0])
+			cf[i] = C.ipx_bytes{data: (*C.uint8_t)(unsafe.Pointer(&f[0])), len: C.size_t(len(f))}
+		}
+	}
+	st := make([]C.int, n)
+	err := call(func() C.int {
+		return C.ipx_plan_run_png_png(p.x.c, p.c, C.int(n), &cf[0], &s.resize[0], &s.thumb[0], &s.watermark[0], &st[0], &s.res)
+	})
+	if err != nil {
+		return nil, err
+	}
+	for i := range st {
+		s.Status[i] = Status(st[i])
+	}
+	return s, nil
+}

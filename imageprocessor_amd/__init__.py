@@ -10,6 +10,7 @@ from ._lib import Config, Glyph, PlanInfo, PlanParams, Rect
 
 OP_OVER = 0
 DEEP_NRGBA64, DEEP_RGBA64, DEEP_GRAY16, DEEP_CMYK = 0, 1, 2, 3   # ipx.h IPX_DEEP_*
+PNG_GRAY, PNG_NRGBA, PNG_RGBA, PNG_PALETTED, PNG_GRAY16, PNG_RGBA64, PNG_NRGBA64 = range(7)   # ipx.h IPX_PNG_*
 OP_SRC = 1
 
 
@@ -371,6 +372,29 @@ class Plan:
         status = (C.c_int * max(n, 1))()
         res = C.c_void_p()
         _check(lib().ipx_plan_run_gif_gif(self.ctx.handle, self.handle, n, arr, int(quality), outs.get("resize"), outs.get("thumbnail"),
+                                          outs.get("watermark"), status, C.byref(res)))
+        out = {k: [(C.string_at(a[j].data, a[j].len) if copy else a[j].len) if a[j].data else None for j in range(n)] for k, a in outs.items()}
+        if res:
+            lib().ipx_jpeg_result_free(self.ctx.handle, res)
+        return out, list(status)[:n]
+
+    def run_png_png(self, files, want=("resize", "thumbnail", "watermark"), copy=True):
+        """PNG byte strings of any kind in -> ({operator: [png bytes | None] * n}, status list): png.Decode, operators and png.Encode of
+        every output on the GPU."""
+        n = len(files)
+        keep = [bytes(f) for f in files]
+        arr = (_lib.Bytes * max(n, 1))()
+        for j, f in enumerate(keep):
+            arr[j].data = C.cast(C.c_char_p(f), C.c_void_p)
+            arr[j].len = len(f)
+        i = self.info
+        outs = {}
+        for k, present in (("resize", i.resize_bytes), ("thumbnail", i.thumb_bytes), ("watermark", i.wm_bytes)):
+            if k in want and present:
+                outs[k] = (_lib.Bytes * max(n, 1))()
+        status = (C.c_int * max(n, 1))()
+        res = C.c_void_p()
+        _check(lib().ipx_plan_run_png_png(self.ctx.handle, self.handle, n, arr, outs.get("resize"), outs.get("thumbnail"),
                                           outs.get("watermark"), status, C.byref(res)))
         out = {k: [(C.string_at(a[j].data, a[j].len) if copy else a[j].len) if a[j].data else None for j in range(n)] for k, a in outs.items()}
         if res:
@@ -771,6 +795,42 @@ class Context:
             lib().ipx_gif_frames_free(self.handle, owner)
         else:
             info.update(batch=b, free=lambda: lib().ipx_gif_frames_free(self.handle, owner))
+        return info, st
+
+    PNG_BPP = (1, 4, 4, 1, 2, 8, 8)     # bytes per pixel of the PNG_* frame layouts
+
+    def png_decode_batch(self, files, w=0, h=0, kind=-1, download=True):
+        """image.Decode of a batch of PNG byte strings on the GPU.  -> (info, status list); info = dict(w, h, kind, stride, pix, palettes)
+        with pix as n x h x (w * bytes per pixel) uint8 (Go's Pix rows) and palettes as n x 256 x 4 uint8 (PNG_PALETTED) or None
+        (download=True), or the device batch (PngBatch) + `free()`; None when no file was decodable."""
+        n = len(files)
+        keep = [bytes(f) for f in files]
+        arr = (_lib.Bytes * max(n, 1))()
+        for i, f in enumerate(keep):
+            arr[i].data = C.cast(C.c_char_p(f), C.c_void_p)
+            arr[i].len = len(f)
+        cw, chh, ck = C.c_int(w), C.c_int(h), C.c_int(kind)
+        b = _lib.PngBatch()
+        status = (C.c_int * max(n, 1))()
+        owner = C.c_void_p()
+        _check(lib().ipx_png_decode_batch(self.handle, None, arr, n, C.byref(cw), C.byref(chh), C.byref(ck), C.byref(b), status,
+                                          C.byref(owner)))
+        st = list(status)[:n]
+        if not b.pix:
+            return None, st
+        info = {"w": cw.value, "h": chh.value, "kind": ck.value, "stride": b.stride}
+        if download:
+            fr = np.empty((n, b.frame_stride), np.uint8)
+            _check(lib().ipx_memcpy_d2h(self.handle, fr.ctypes.data, b.pix, fr.nbytes))
+            info["pix"] = fr[:, :b.stride * chh.value].reshape(n, chh.value, b.stride)
+            info["palettes"] = None
+            if b.palettes:
+                pal = np.empty((n, 256, 4), np.uint8)
+                _check(lib().ipx_memcpy_d2h(self.handle, pal.ctypes.data, b.palettes, pal.nbytes))
+                info["palettes"] = pal
+            lib().ipx_png_frames_free(self.handle, owner)
+        else:
+            info.update(batch=b, free=lambda: lib().ipx_png_frames_free(self.handle, owner))
         return info, st
 
     def composite_glyphs(self, dst, glyphs, col):

@@ -52,6 +52,10 @@ class PalettedBatch(C.Structure):
     _fields_ = [("index", C.c_void_p), ("stride", C.c_int32), ("frame_stride", C.c_size_t), ("palettes", C.c_void_p)]
 
 
+class PngBatch(C.Structure):
+    _fields_ = [("pix", C.c_void_p), ("stride", C.c_int32), ("frame_stride", C.c_size_t), ("palettes", C.c_void_p)]
+
+
 class Param(C.Structure):
     _fields_ = [("key", C.c_char_p), ("type", C.c_int32), ("f64", C.c_double), ("i64", C.c_int64),
                 ("str", C.c_char_p)]
@@ -220,6 +224,11 @@ SIGNATURES = {
                                   C.POINTER(_P)]),
     "ipx_gif_frames_free": (None, [_P, _P]),
     "ipx_plan_run_gif_gif": (_I, [_P, _P, _I, C.POINTER(Bytes), _I, C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(_I),
+                                  C.POINTER(_P)]),
+    "ipx_png_decode_batch": (_I, [_P, _P, C.POINTER(Bytes), _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(PngBatch),
+                                  C.POINTER(_I), C.POINTER(_P)]),
+    "ipx_png_frames_free": (None, [_P, _P]),
+    "ipx_plan_run_png_png": (_I, [_P, _P, _I, C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(_I),
                                   C.POINTER(_P)]),
     "ipx_font_create": (_I, [_P, _Z, C.POINTER(_P)]),
     "ipx_font_destroy": (None, [_P]),

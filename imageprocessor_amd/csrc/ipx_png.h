@@ -49,6 +49,68 @@ struct PngPiece {
     uint32_t len, pad;
 };
 
+// ---- CRC-32 of chunks and the Paeth predictor: shared by the encoder (ipx_png.hip) and the decoder (ipx_png_dec.hip) ----------------
+// crc: the byte table of the reflected polynomial 0xEDB88320; x2n[k]: x^(2^k) mod P (zlib's x2n_table).  Each translation unit that
+// uses them keeps its own copy in constant memory.
+struct PngCrcTables {
+    uint32_t crc[256];
+    uint32_t x2n[32];
+    constexpr PngCrcTables() : crc{}, x2n{}
+    {
+        for (uint32_t i = 0; i < 256; i++) {
+            uint32_t c = i;
+            for (int k = 0; k < 8; k++) c = c & 1 ? (c >> 1) ^ 0xEDB88320u : c >> 1;
+            crc[i] = c;
+        }
+        uint32_t p = 1u << 30;   // x^1
+        for (int k = 0; k < 32; k++) {
+            x2n[k] = p;
+            p = mult(p, p);
+        }
+    }
+    static constexpr uint32_t mult(uint32_t a, uint32_t b)
+    {
+        uint32_t m = 1u << 31, p = 0;
+        for (;;) {
+            if (a & m) {
+                p ^= b;
+                if ((a & (m - 1)) == 0) break;
+            }
+            m >>= 1;
+            b = b & 1 ? (b >> 1) ^ 0xEDB88320u : b >> 1;
+        }
+        return p;
+    }
+};
+
+__device__ inline uint32_t crc_mult(uint32_t a, uint32_t b)   // a * b mod P (reflected)
+{
+    uint32_t p = 0;
+    for (int k = 31; k >= 0; k--) {
+        if (a & (1u << k)) p ^= b;
+        b = b & 1 ? (b >> 1) ^ 0xEDB88320u : b >> 1;
+    }
+    return p;
+}
+// the raw CRC state c after nbytes zero bytes (x2n: PngCrcTables::x2n in constant memory)
+__device__ inline uint32_t crc_shift(uint32_t c, uint32_t nbytes, const uint32_t *x2n)
+{
+    uint32_t p = 1u << 31;
+    for (int k = 3; nbytes; nbytes >>= 1, k++)
+        if (nbytes & 1) p = crc_mult(x2n[k & 31], p);
+    return crc_mult(p, c);
+}
+
+__device__ inline int paeth(int a, int b, int c)
+{
+    int pa = b - c, pb = a - c;
+    const int pc = abs(pa + pb);
+    pa = abs(pa);
+    pb = abs(pb);
+    if (pa <= pb && pa <= pc) return a;
+    return pb <= pc ? b : c;
+}
+
 // signature + IHDR for colour type 2 (bpp 3) and 6 (bpp 4) of a w x h frame: out[0] and out[1]
 void png_write_heads(int w, int h, uint8_t out[2][kPngHeadBytes]);
 
@@ -67,5 +129,14 @@ hipError_t launch_png_deflate(const uint8_t *filt, uint32_t *match, size_t fbyte
 hipError_t launch_png_frame(const uint8_t *heads, const uint32_t *alpha, const uint32_t *item0, const PngSeg *segs, const uint32_t *adler,
                             int n, uint8_t *out, size_t region, size_t tail, hipStream_t s);
 hipError_t launch_png_pack(const uint8_t *out, const PngPiece *pieces, int npieces, uint8_t *dst, hipStream_t s);
+
+}  // namespace ipx
+
+struct ipx_ctx;
+namespace ipx {
+// png.Encode of n RGBA8 frames in HBM -> streams in one pinned block (ipx_host_alloc), everything on stream s; returns once the block
+// is filled (ipx_png.hip; the PNG legs of ipx_png.hip and ipx_png_dec.hip)
+int png_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w, int h, int stride, size_t frame_stride, int n,
+                    uint8_t **blob, size_t *offs, size_t *lens);
 
 }  // namespace ipx

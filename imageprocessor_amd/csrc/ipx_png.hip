@@ -16,9 +16,7 @@ struct PngTables {
     uint16_t len_base[29];
     uint8_t len_extra[29];
     uint16_t dist_base[30];
-    uint32_t crc[256];
-    uint32_t x2n[32];                    // x^(2^k) mod P (zlib's x2n_table)
-    constexpr PngTables() : len_sym{}, len_base{}, len_extra{}, dist_base{}, crc{}, x2n{}
+    constexpr PngTables() : len_sym{}, len_base{}, len_extra{}, dist_base{}
     {
         const int lb[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
         for (int s = 0; s < 29; s++) {
@@ -28,49 +26,10 @@ struct PngTables {
         }
         len_sym[258] = 28;
         for (int s = 0; s < 30; s++) dist_base[s] = (uint16_t)(s < 4 ? s + 1 : (1 << ((s >> 1) - 1)) * (2 + (s & 1)) + 1);
-        for (uint32_t i = 0; i < 256; i++) {
-            uint32_t c = i;
-            for (int k = 0; k < 8; k++) c = c & 1 ? (c >> 1) ^ 0xEDB88320u : c >> 1;
-            crc[i] = c;
-        }
-        uint32_t p = 1u << 30;   // x^1
-        for (int k = 0; k < 32; k++) {
-            x2n[k] = p;
-            p = mult(p, p);
-        }
-    }
-    static constexpr uint32_t mult(uint32_t a, uint32_t b)
-    {
-        uint32_t m = 1u << 31, p = 0;
-        for (;;) {
-            if (a & m) {
-                p ^= b;
-                if ((a & (m - 1)) == 0) break;
-            }
-            m >>= 1;
-            b = b & 1 ? (b >> 1) ^ 0xEDB88320u : b >> 1;
-        }
-        return p;
     }
 };
 __constant__ PngTables c_png = PngTables();
-
-__device__ inline uint32_t crc_mult(uint32_t a, uint32_t b)   // a * b mod P (reflected)
-{
-    uint32_t p = 0;
-    for (int k = 31; k >= 0; k--) {
-        if (a & (1u << k)) p ^= b;
-        b = b & 1 ? (b >> 1) ^ 0xEDB88320u : b >> 1;
-    }
-    return p;
-}
-__device__ inline uint32_t crc_shift(uint32_t c, uint32_t nbytes)   // the raw CRC state c after nbytes zero bytes
-{
-    uint32_t p = 1u << 31;
-    for (int k = 3; nbytes; nbytes >>= 1, k++)
-        if (nbytes & 1) p = crc_mult(c_png.x2n[k & 31], p);
-    return crc_mult(p, c);
-}
+__constant__ PngCrcTables c_png_crc = PngCrcTables();
 
 __device__ inline uint32_t png_hash(const uint8_t *p)
 {
@@ -114,16 +73,6 @@ __device__ inline int raw_byte(const uint8_t *row, int k, int bpp)
     if (c == 3 || a == 0xFF) return p[c];
     if (a == 0) return 0;
     return (int)(((uint32_t)p[c] * 0x101u * 0xFFFFu / (a * 0x101u)) >> 8) & 0xFF;
-}
-
-__device__ inline int paeth(int a, int b, int c)
-{
-    int pa = b - c, pb = a - c;
-    const int pc = abs(pa + pb);
-    pa = abs(pa);
-    pb = abs(pb);
-    if (pa <= pb && pa <= pc) return a;
-    return pb <= pc ? b : c;
 }
 
 __device__ inline int abs8(int d) { return d < 128 ? d : 256 - d; }
@@ -582,17 +531,17 @@ __global__ __launch_bounds__(kDefThreads) void png_deflate_kernel(const uint8_t 
     for (size_t q = b0; q < b1; q++) {
         const uint32_t wd = __hip_atomic_load((const uint32_t *)(o + 4) + (q >> 2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const uint32_t byte = (wd >> (8 * (q & 3))) & 0xFF;
-        c = c_png.crc[(c ^ byte) & 0xFF] ^ (c >> 8);
+        c = c_png_crc.crc[(c ^ byte) & 0xFF] ^ (c >> 8);
     }
     // contribution of this lane's range: shifted by the bytes after it; the initial ~0 state shifted by all of them
-    const unsigned long long contrib = b1 > b0 ? crc_shift(c, (uint32_t)(cn - b1)) : 0;
+    const unsigned long long contrib = b1 > b0 ? crc_shift(c, (uint32_t)(cn - b1), c_png_crc.x2n) : 0;
     unsigned long long x = contrib;
     for (int off = 32; off > 0; off >>= 1) x ^= __shfl_xor(x, off, 64);
     __syncthreads();
     if ((t & 63) == 0) S.wsum[t >> 6] = x;
     __syncthreads();
     if (t == 0) {
-        uint32_t crc = crc_shift(0xFFFFFFFFu, (uint32_t)cn);
+        uint32_t crc = crc_shift(0xFFFFFFFFu, (uint32_t)cn, c_png_crc.x2n);
         for (int i = 0; i < kDefThreads / 64; i++) crc ^= (uint32_t)S.wsum[i];
         crc = ~crc;
         uint8_t *cp = o + 8 + dlen;
@@ -644,7 +593,7 @@ __global__ void png_frame_kernel(const uint8_t *__restrict__ heads, const uint32
     uint8_t *p = o + tail;
     const uint8_t body[8] = {'I', 'D', 'A', 'T', (uint8_t)(ad >> 24), (uint8_t)(ad >> 16), (uint8_t)(ad >> 8), (uint8_t)ad};
     uint32_t c = 0xFFFFFFFFu;
-    for (int i = 0; i < 8; i++) c = c_png.crc[(c ^ body[i]) & 0xFF] ^ (c >> 8);
+    for (int i = 0; i < 8; i++) c = c_png_crc.crc[(c ^ body[i]) & 0xFF] ^ (c >> 8);
     c = ~c;
     p[0] = p[1] = p[2] = 0;
     p[3] = 4;
@@ -705,7 +654,7 @@ size_t segs_bytes(int w, int h, int bpp)
 }  // namespace
 
 // n frames in HBM -> streams in one pinned block (ipx_host_alloc), everything on stream s; returns once the block is filled
-static int png_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w, int h, int stride, size_t frame_stride, int n,
+int ipx::png_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w, int h, int stride, size_t frame_stride, int n,
                            uint8_t **blob, size_t *offs, size_t *lens)
 {
     *blob = nullptr;

@@ -1,0 +1,74 @@
+// ipx_png_dec.h -- png.Decode (non-interlaced files) on the GPU: what the kernels (ipx_png_dec.hip) and the host half
+// (ipx_png_dec_host.cpp) share.  Not part of the ABI.  The restatement of Go's reader is in DESIGN.md section 4.10;
+// tests/png_decode_model.py is the model it is held to.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+namespace ipx {
+
+// the frame layouts (IPX_PNG_* of include/ipx.h) and their bytes per pixel
+constexpr int kPngKinds = 7;
+inline int png_kind_bpp(int kind) { static const int b[kPngKinds] = {1, 4, 4, 1, 2, 8, 8}; return b[kind]; }
+
+// ---- host parse ----------------------------------------------------------------------------------------------------------------
+// What the host reads of one file: the chunk headers up to IEND (never the image data).  status: IPX_OK (the chunks' CRCs and the zlib
+// stream still have to be checked), IPX_ERR_INVALID (Go's reader fails on the container) or IPX_ERR_UNSUPPORTED (outside the GPU
+// path: Adam7, another chunk order, sub-byte gray with tRNS, ...).
+struct PngSpan { uint32_t off, len; };   // bytes of the file
+struct PngFileInfo {
+    int status = 0;
+    int w = 0, h = 0, kind = -1;
+    int depth = 0, ctype = 0;
+    int bpp = 1;                  // the filters' bytes per pixel: max(1, bits per pixel / 8)
+    uint32_t rowbytes = 0;        // 1 + (bits per pixel * w + 7) / 8
+    uint64_t raw_len = 0;         // h * rowbytes
+    uint32_t file_len = 0;        // through IEND's CRC
+    uint32_t idat_len = 0;        // the zlib stream: every IDAT payload
+    uint32_t idat_last = 0;       // where the last IDAT's payload starts in that stream
+    bool trns = false;
+    uint16_t trns_v[3] = {0, 0, 0};   // gray or R, G, B sample of tRNS
+    std::vector<PngSpan> crc;     // per chunk: type + data (the CRC follows)
+    std::vector<PngSpan> idat;    // IDAT payloads in file order
+    uint8_t pal[1024];            // palette kinds: 256 x (R, G, B, A), tRNS applied, entries past PLTE opaque black
+};
+int png_parse(const uint8_t *p, size_t n, PngFileInfo *info);
+
+// ---- device side ---------------------------------------------------------------------------------------------------------------
+// One piece of a chunk's CRC (a workgroup of png_crc_kernel): the piece's bytes at blob + src, its chunk, the bytes of the chunk after
+// it; IDAT payload bytes are also copied to the file's zlib stream (from byte `skip` of the piece on, to zlib + dst; dst ~0: no copy).
+struct PngCrcPiece {
+    uint64_t src, dst;
+    uint32_t len, chunk, after, skip;
+};
+// A chunk to check: its type + data at blob + off (cn bytes), the stored CRC right after, the file it belongs to.
+struct PngChunk {
+    uint64_t off;
+    uint32_t cn, file;
+};
+// One file of an inflate / unfilter launch.
+struct PngDecDesc {
+    uint64_t zoff;      // its zlib stream at zlib + zoff (zlen bytes)
+    uint64_t roff;      // its filtered rows at raw + roff (raw_len bytes), unfiltered in place
+    uint64_t foff;      // its frame at frames + foff
+    uint32_t zlen, raw_len;
+    uint32_t zlast;     // the last IDAT's payload starts here in the stream: at or after the Adler-32's end is UNSUPPORTED
+    uint32_t w, h, rowbytes, slot;
+    uint16_t ctype, depth, kind, trns;   // trns: 1 when tRNS samples are compared (gray / truecolour)
+    uint16_t tv[3], bpp;
+};
+// per-file status word, written by the kernels: 0 OK; bit 0 a chunk CRC differs; bit 1 the zlib stream breaks a rule of Go's reader;
+// bit 2 a row's filter type is above 4; bit 3 bytes or an IDAT chunk follow the Adler-32 (UNSUPPORTED unless another bit is set)
+enum : uint32_t { kPngBadCrc = 1, kPngBadZlib = 2, kPngBadFilter = 4, kPngTrailing = 8 };
+
+hipError_t launch_png_crc(const uint8_t *blob, const PngCrcPiece *pieces, int npieces, uint32_t *acc, uint8_t *zlib, hipStream_t s);
+hipError_t launch_png_crc_check(const uint8_t *blob, const PngChunk *chunks, int nchunks, const uint32_t *acc, uint32_t *status,
+                                hipStream_t s);
+hipError_t launch_png_inflate(const uint8_t *zlib, const PngDecDesc *desc, int n, uint8_t *raw, uint32_t *status, hipStream_t s);
+hipError_t launch_png_unfilter(const PngDecDesc *desc, int n, uint8_t *raw, uint8_t *frames, uint32_t *status, hipStream_t s);
+
+}  // namespace ipx

@@ -1,0 +1,930 @@
+// ipx_png_dec.hip -- png.Decode (image/png reader.go, compress/zlib, compress/flate) of a batch of non-interlaced files on the GPU, and
+// the ABI entries built on it.  Kernels: the CRC of every chunk in pieces (combined with crc_shift) that also gathers the IDAT payloads
+// into one zlib stream per file, the per-chunk check, the inflate (one wave per file: input, Huffman tables and the 32 KiB window in
+// LDS, match copies spread over the lanes, coalesced flushes with the Adler-32) and the unfilter (a diagonal wavefront of 64 rows that
+// writes the frame layout of the type Go returns).  Host half: ipx_png_dec_host.cpp.  DESIGN.md section 4.10.
+#include <memory>
+#include <vector>
+
+#include "ipx_png.h"
+#include "ipx_png_dec.h"
+#include "ipx_runtime_internal.h"
+#include "ipx_threads.h"
+
+namespace ipx {
+
+__constant__ PngCrcTables c_dec_crc = PngCrcTables();
+
+// ---- CRC and gather --------------------------------------------------------------------------------------------------------------
+// A workgroup per piece: each lane the CRC of a contiguous range, shifted by the bytes of the chunk after it; the XOR of the shifted
+// states is the chunk's raw CRC (the initial ~0 is added by the check).  IDAT payload bytes are copied to the zlib streams on the way.
+__global__ __launch_bounds__(256) void png_crc_kernel(const uint8_t *__restrict__ blob, const PngCrcPiece *__restrict__ pieces,
+                                                      uint32_t *__restrict__ acc, uint8_t *__restrict__ zlib)
+{
+    __shared__ uint32_t s_tab[256];
+    __shared__ uint32_t s_sum[4];
+    const int t = threadIdx.x;
+    s_tab[t] = c_dec_crc.crc[t];
+    const PngCrcPiece pc = pieces[blockIdx.x];
+    const uint8_t *src = blob + pc.src;
+    if (pc.dst != ~0ull)
+        for (uint32_t i = pc.skip + t; i < pc.len; i += 256) zlib[pc.dst + (i - pc.skip)] = src[i];
+    __syncthreads();
+    const uint32_t per = (pc.len + 255) / 256, b0 = min(pc.len, per * t), b1 = min(pc.len, b0 + per);
+    uint32_t c = 0;
+    for (uint32_t q = b0; q < b1; q++) c = s_tab[(c ^ src[q]) & 0xFF] ^ (c >> 8);
+    uint32_t x = b1 > b0 ? crc_shift(c, pc.len - b1 + pc.after, c_dec_crc.x2n) : 0;
+    for (int off = 32; off > 0; off >>= 1) x ^= __shfl_xor(x, off, 64);
+    if ((t & 63) == 0) s_sum[t >> 6] = x;
+    __syncthreads();
+    if (t == 0) atomicXor(acc + pc.chunk, s_sum[0] ^ s_sum[1] ^ s_sum[2] ^ s_sum[3]);
+}
+
+__global__ __launch_bounds__(256) void png_crc_check_kernel(const uint8_t *__restrict__ blob, const PngChunk *__restrict__ chunks, int n,
+                                                            const uint32_t *__restrict__ acc, uint32_t *__restrict__ status)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const PngChunk ch = chunks[k];
+    const uint32_t crc = ~(crc_shift(0xFFFFFFFFu, ch.cn, c_dec_crc.x2n) ^ acc[k]);
+    const uint8_t *p = blob + ch.off + ch.cn;
+    const uint32_t stored = (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3];
+    if (crc != stored) atomicOr(status + ch.file, kPngBadCrc);
+}
+
+hipError_t launch_png_crc(const uint8_t *blob, const PngCrcPiece *pieces, int npieces, uint32_t *acc, uint8_t *zlib, hipStream_t s)
+{
+    if (npieces <= 0) return hipSuccess;
+    hipLaunchKernelGGL(png_crc_kernel, dim3(npieces), dim3(256), 0, s, blob, pieces, acc, zlib);
+    return hipGetLastError();
+}
+
+hipError_t launch_png_crc_check(const uint8_t *blob, const PngChunk *chunks, int nchunks, const uint32_t *acc, uint32_t *status,
+                                hipStream_t s)
+{
+    if (nchunks <= 0) return hipSuccess;
+    hipLaunchKernelGGL(png_crc_check_kernel, dim3((nchunks + 255) / 256), dim3(256), 0, s, blob, chunks, nchunks, acc, status);
+    return hipGetLastError();
+}
+
+// ---- inflate ---------------------------------------------------------------------------------------------------------------------
+// One workgroup of one wave per file.  Every lane runs the same decoder on the same LDS bytes (broadcast reads; readfirstlane keeps
+// the state scalar), so the symbol loop has no cross-lane hand-off; a match is copied by all 64 lanes, lane k taking bytes k, k + 64, ...
+// from (k mod distance) behind the match for overlaps.  Nothing from global memory is on the per-symbol chain: the input is staged into
+// LDS 8 KiB at a time, and finished window bytes leave in 16 KiB units.  Rules are Go's; every loop consumes
+// input bits or produces output bytes, no write goes past raw_len, and input past the stream's end reads as zero bits that only count
+// against the stream (consumed > 8 * zlen is an error).
+constexpr int kInBytes = 8192;
+constexpr int kWinBytes = 32768;
+constexpr int kFlush = 16384;
+constexpr int kLitRoot = 10, kDistRoot = 8, kClenRoot = 7;
+
+struct PngFlate {
+    uint16_t len_base[29], dist_base[30];
+    uint8_t len_extra[29], dist_extra[30];
+    uint8_t clen_order[19];
+    constexpr PngFlate() : len_base{}, dist_base{}, len_extra{}, dist_extra{}, clen_order{16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15}
+    {
+        const int lb[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
+        for (int s = 0; s < 29; s++) {
+            len_base[s] = (uint16_t)lb[s];
+            len_extra[s] = (uint8_t)(s < 8 || s == 28 ? 0 : (s - 4) / 4);
+        }
+        for (int s = 0; s < 30; s++) {
+            dist_base[s] = (uint16_t)(s < 4 ? s + 1 : (1 << ((s >> 1) - 1)) * (2 + (s & 1)) + 1);
+            dist_extra[s] = (uint8_t)(s < 4 ? 0 : (s >> 1) - 1);
+        }
+    }
+};
+__constant__ PngFlate c_flate = PngFlate();
+
+struct HuffLds { uint16_t count[16], first[16], offset[16], next[16]; };
+
+struct InflateLds {
+    uint8_t win[kWinBytes];
+    uint8_t in[kInBytes + 16];
+    uint16_t lit_root[1 << kLitRoot];
+    uint16_t dist_root[1 << kDistRoot];    // also the code-length code's table during a dynamic header
+    uint16_t lit_sorted[288], dist_sorted[32], clen_sorted[19];
+    HuffLds lit, dist, clen;
+    uint8_t lens[320];
+    uint8_t clens[20];
+    int ok;
+};
+
+__device__ inline uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// Go's huffmanDecoder.init over lens[0 .. n): false unless the code is complete, empty, or a single code of length 1.  On success
+// the canonical arrays (count / first / offset per length, symbols sorted by code) and the root table (entry: symbol << 4 | length,
+// 0 for a longer code or none) are built.  Called by every lane.
+__device__ bool huff_build(const uint8_t *lens, int n, HuffLds &h, uint16_t *sorted, uint16_t *root, int rbits, int lane, int *s_ok)
+{
+    if (lane == 0) {
+        for (int L = 0; L < 16; L++) h.count[L] = 0;
+        for (int s = 0; s < n; s++) h.count[lens[s]]++;
+        h.count[0] = 0;
+        int mn = 0, mx = 0;
+        for (int L = 1; L < 16; L++)
+            if (h.count[L]) { if (!mn) mn = L; mx = L; }
+        bool ok = true;
+        if (mx) {
+            int code = 0;
+            for (int L = mn; L <= mx; L++) code = (code << 1) + h.count[L];
+            ok = code == (1 << mx) || (code == 1 && mx == 1);
+        }
+        int c = 0, off = 0;
+        h.first[0] = 0;
+        h.offset[0] = 0;
+        for (int L = 1; L < 16; L++) {
+            c = (c + (L > 1 ? h.count[L - 1] : 0)) << 1;
+            h.first[L] = (uint16_t)c;
+            h.offset[L] = (uint16_t)off;
+            h.next[L] = (uint16_t)off;
+            off += h.count[L];
+        }
+        if (ok)
+            for (int s = 0; s < n; s++)
+                if (lens[s]) sorted[h.next[lens[s]]++] = (uint16_t)s;
+        *s_ok = ok;
+    }
+    __syncthreads();
+    if (!uni((uint32_t)*s_ok)) return false;
+    for (int e = lane; e < (1 << rbits); e += 64) root[e] = 0;
+    __syncthreads();
+    const int total = h.offset[15] + h.count[15];
+    for (int p = lane; p < total; p += 64) {
+        const int s = sorted[p], L = lens[s];
+        if (L > rbits) continue;
+        const uint32_t code = h.first[L] + (uint32_t)(p - h.offset[L]);
+        const uint32_t r = __brev(code) >> (32 - L);
+        for (uint32_t e = r; e < (1u << rbits); e += 1u << L) root[e] = (uint16_t)(s << 4 | L);
+    }
+    __syncthreads();
+    return true;
+}
+
+// the symbol at the head of bb (its length in *len), or -1 when no code matches (Go: "invalid code")
+__device__ inline int huff_decode(uint64_t bb, const uint16_t *root, int rbits, const HuffLds &h, const uint16_t *sorted, int *len)
+{
+    const uint32_t e = uni(root[bb & ((1u << rbits) - 1)]);
+    if (e) { *len = (int)(e & 15); return (int)(e >> 4); }
+    const uint32_t rev = __brev((uint32_t)bb & 0x7FFF) >> 17;   // the next 15 bits, the first one most significant
+    for (int L = rbits + 1; L <= 15; L++) {
+        const uint32_t k = (rev >> (15 - L)) - uni(h.first[L]);
+        if (k < uni(h.count[L])) { *len = L; return (int)uni(sorted[uni(h.offset[L]) + k]); }
+    }
+    *len = 0;
+    return -1;
+}
+
+__global__ __launch_bounds__(64) void png_inflate_kernel(const uint8_t *__restrict__ zlib, const PngDecDesc *__restrict__ desc,
+                                                         uint8_t *__restrict__ raw, uint32_t *__restrict__ status)
+{
+    __shared__ InflateLds S;
+    const int lane = threadIdx.x;
+    const PngDecDesc d = desc[blockIdx.x];
+    const uint8_t *z = zlib + d.zoff;
+    uint8_t *out = raw + d.roff;
+    const uint32_t zlen = d.zlen, raw_len = d.raw_len;
+    const uint64_t zbits = 8ull * zlen;
+    uint32_t in_base = 0, bpos = 0, pos = 0, flushed = 0, a1 = 1, b1 = 0;
+    uint64_t bb = 0;
+    uint32_t nb = 0;
+    bool err = false, final_block = false, fixed_built = false;
+    if (status[d.slot] & kPngBadCrc) return;
+
+    auto stage = [&](uint32_t at) {          // in[] <- stream bytes [at & ~15, +kInBytes), zero past the end
+        in_base = at & ~15u;
+        for (int i = lane; i < kInBytes / 16; i += 64) {
+            const uint32_t g = in_base + 16 * i;
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (g < zlen) v = *(const uint4 *)(z + g);
+            *(uint4 *)(S.in + 16 * i) = v;
+            if (g < zlen && g + 16 > zlen)
+                for (uint32_t j = zlen - g; j < 16; j++) S.in[16 * i + j] = 0;
+        }
+        __syncthreads();
+    };
+    auto restage = [&]() { if (bpos - in_base > (uint32_t)kInBytes - 64) stage(bpos); };
+    auto refill = [&]() {
+        if (nb < 32) {
+            const uint32_t o = bpos - in_base;
+            const uint32_t v = uni((uint32_t)S.in[o] | (uint32_t)S.in[o + 1] << 8 | (uint32_t)S.in[o + 2] << 16 | (uint32_t)S.in[o + 3] << 24);
+            bb |= (uint64_t)v << nb;
+            nb += 32;
+            bpos += 4;
+        }
+    };
+    auto take = [&](uint32_t k) -> uint32_t { const uint32_t v = (uint32_t)bb & ((1u << k) - 1); bb >>= k; nb -= k; return v; };
+    auto over = [&]() { return (uint64_t)bpos * 8 - nb > zbits; };
+    auto adler = [&](uint32_t F, uint64_t A, uint64_t B) {
+        for (int off = 32; off > 0; off >>= 1) { A += __shfl_xor(A, off, 64); B += __shfl_xor(B, off, 64); }
+        b1 = (uint32_t)((b1 + (uint64_t)(F % 65521) * a1 + B % 65521) % 65521);
+        a1 = (uint32_t)((a1 + A % 65521) % 65521);
+    };
+    auto flush_units = [&]() {               // every whole 16 KiB unit behind pos: coalesced 16-byte stores
+        while (pos - flushed >= (uint32_t)kFlush) {
+            const uint4 *src = (const uint4 *)(S.win + (flushed & (kWinBytes - 1)));
+            uint4 *dst = (uint4 *)(out + flushed);
+            uint64_t A = 0, B = 0;
+            for (int i = lane; i < kFlush / 16; i += 64) {
+                const uint4 v = src[i];
+                dst[i] = v;
+                const uint32_t wd[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int k = 0; k < 16; k++) {
+                    const uint32_t byte = (wd[k >> 2] >> (8 * (k & 3))) & 0xFF;
+                    A += byte;
+                    B += (uint64_t)(kFlush - (16 * i + k)) * byte;
+                }
+            }
+            adler(kFlush, A, B);
+            flushed += kFlush;
+        }
+    };
+
+    stage(0);
+    refill();
+    {
+        const uint32_t cmf = take(8), flg = take(8);
+        if (zlen < 2 || (cmf & 15) != 8 || (cmf >> 4) > 7 || ((cmf << 8) | flg) % 31 != 0 || (flg & 0x20)) err = true;
+    }
+    while (!err && !final_block) {
+        restage();
+        refill();
+        final_block = take(1);
+        const uint32_t type = take(2);
+        if (over()) { err = true; break; }
+        if (type == 0) {                                         // stored
+            take(nb & 7);
+            bpos -= nb >> 3;
+            bb = 0;
+            nb = 0;
+            restage();
+            if (bpos + 4 > zlen) { err = true; break; }
+            const uint32_t o = bpos - in_base;
+            const uint32_t len = uni(S.in[o] | (uint32_t)S.in[o + 1] << 8), nlen = uni(S.in[o + 2] | (uint32_t)S.in[o + 3] << 8);
+            bpos += 4;
+            if (len != (~nlen & 0xFFFF) || bpos + len > zlen || pos + len > raw_len) { err = true; break; }
+            uint32_t left = len;
+            while (left) {
+                restage();
+                const uint32_t k = min(min(left, in_base + kInBytes - 16 - bpos), (uint32_t)kFlush);
+                const uint32_t o2 = bpos - in_base;
+                for (uint32_t j = lane; j < k; j += 64) S.win[(pos + j) & (kWinBytes - 1)] = S.in[o2 + j];
+                pos += k;
+                bpos += k;
+                left -= k;
+                __syncthreads();
+                flush_units();
+            }
+            continue;
+        }
+        if (type == 3) { err = true; break; }
+        const uint16_t *lroot = S.lit_root, *droot = S.dist_root;
+        if (type == 1) {
+            if (!fixed_built) {
+                for (int s = lane; s < 320; s += 64) S.lens[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : s < 288 ? 8 : 5;
+                __syncthreads();
+                huff_build(S.lens, 288, S.lit, S.lit_sorted, S.lit_root, kLitRoot, lane, &S.ok);
+                huff_build(S.lens + 288, 32, S.dist, S.dist_sorted, S.dist_root, kDistRoot, lane, &S.ok);
+                fixed_built = true;
+            }
+        } else {                                                 // dynamic: the header, the code-length code, the two codes
+            fixed_built = false;
+            refill();
+            const uint32_t hlit = take(5) + 257, hdist = take(5) + 1, hclen = take(4) + 4;
+            if (hlit > 286 || hdist > 30) { err = true; break; }
+            for (uint32_t k = 0; k < 19; k++) {
+                uint32_t v = 0;
+                if (k < hclen) { refill(); v = take(3); }
+                if (lane == 0) S.clens[c_flate.clen_order[k]] = (uint8_t)v;
+            }
+            __syncthreads();
+            if (over() || !huff_build(S.clens, 19, S.clen, S.clen_sorted, S.dist_root, kClenRoot, lane, &S.ok)) { err = true; break; }
+            const uint32_t n = hlit + hdist;
+            for (uint32_t i = 0; i < n;) {
+                restage();
+                refill();
+                int L;
+                const int sym = huff_decode(bb, S.dist_root, kClenRoot, S.clen, S.clen_sorted, &L);
+                if (sym < 0) { err = true; break; }
+                take(L);
+                if (sym < 16) {
+                    if (lane == 0) S.lens[i] = (uint8_t)sym;
+                    i++;
+                } else {
+                    uint32_t rep, val = 0;
+                    if (sym == 16) {
+                        if (i == 0) { err = true; break; }
+                        rep = 3 + take(2);
+                        val = uni(S.lens[i - 1]);
+                    } else if (sym == 17) {
+                        rep = 3 + take(3);
+                    } else {
+                        rep = 11 + take(7);
+                    }
+                    if (i + rep > n) { err = true; break; }
+                    for (uint32_t j = lane; j < rep; j += 64) S.lens[i + j] = (uint8_t)val;
+                    i += rep;
+                }
+                __syncthreads();
+                if (over()) { err = true; break; }
+            }
+            if (err) break;
+            if (!huff_build(S.lens, hlit, S.lit, S.lit_sorted, S.lit_root, kLitRoot, lane, &S.ok) ||
+                !huff_build(S.lens + hlit, hdist, S.dist, S.dist_sorted, S.dist_root, kDistRoot, lane, &S.ok)) { err = true; break; }
+        }
+        for (;;) {                                               // the block's symbols
+            restage();
+            refill();
+            int L;
+            const int sym = huff_decode(bb, lroot, kLitRoot, S.lit, S.lit_sorted, &L);
+            if (sym < 0) { err = true; break; }
+            take(L);
+            if (sym < 256) {
+                if (pos >= raw_len) { err = true; break; }       // too much pixel data
+                if (lane == 0) S.win[pos & (kWinBytes - 1)] = (uint8_t)sym;
+                pos++;
+            } else if (sym == 256) {
+                if (over()) err = true;
+                break;
+            } else if (sym > 285) {
+                err = true;
+                break;
+            } else {
+                const int li = sym - 257;
+                const uint32_t len = c_flate.len_base[li] + take(c_flate.len_extra[li]);
+                refill();
+                const int ds = huff_decode(bb, droot, kDistRoot, S.dist, S.dist_sorted, &L);
+                if (ds < 0 || ds >= 30) { err = true; break; }
+                take(L);
+                const uint32_t dist = c_flate.dist_base[ds] + take(c_flate.dist_extra[ds]);
+                if (over() || dist > pos || pos + len > raw_len) { err = true; break; }
+                __syncthreads();
+                const uint32_t from = pos - dist;
+                for (uint32_t j = lane; j < len; j += 64)
+                    S.win[(pos + j) & (kWinBytes - 1)] = S.win[(from + (dist >= len ? j : j % dist)) & (kWinBytes - 1)];
+                pos += len;
+                __syncthreads();
+            }
+            if (over()) { err = true; break; }
+            if (pos - flushed >= (uint32_t)kFlush) {
+                __syncthreads();
+                flush_units();
+            }
+        }
+    }
+    if (!err && pos != raw_len) err = true;                      // not enough pixel data
+    bool trailing = false;
+    if (!err) {
+        __syncthreads();
+        const uint32_t F = pos - flushed;                        // the last partial unit, byte by byte
+        uint64_t A = 0, B = 0;
+        for (uint32_t j = lane; j < F; j += 64) {
+            const uint32_t byte = S.win[(flushed + j) & (kWinBytes - 1)];
+            out[flushed + j] = (uint8_t)byte;
+            A += byte;
+            B += (uint64_t)(F - j) * byte;
+        }
+        adler(F, A, B);
+        take(nb & 7);                                            // the Adler-32 follows at the next byte
+        bpos -= nb >> 3;
+        bb = 0;
+        nb = 0;
+        restage();
+        if (bpos + 4 > zlen) {
+            err = true;
+        } else {
+            const uint32_t o = bpos - in_base;
+            const uint32_t want = uni((uint32_t)S.in[o] << 24 | (uint32_t)S.in[o + 1] << 16 | (uint32_t)S.in[o + 2] << 8 | S.in[o + 3]);
+            if (want != (b1 << 16 | a1)) err = true;
+            else trailing = bpos + 4 < zlen || d.zlast >= bpos + 4;
+        }
+    }
+    if (lane == 0 && (err || trailing)) atomicOr(status + d.slot, err ? kPngBadZlib : kPngTrailing);
+}
+
+hipError_t launch_png_inflate(const uint8_t *zlib, const PngDecDesc *desc, int n, uint8_t *raw, uint32_t *status, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(png_inflate_kernel, dim3(n), dim3(64), 0, s, zlib, desc, raw, status);
+    return hipGetLastError();
+}
+
+// ---- unfilter and convert --------------------------------------------------------------------------------------------------------
+// One wave per file, bands of 64 rows: lane i owns row r0 + i and at step t reconstructs its unit (bpp bytes; one byte at sub-byte
+// depths) t - i.  The unit above comes from lane i - 1's result of the step before by a cross-lane shift, the one above-left from the
+// step before that; lane 0 reads the band above's last row, which lane 63 wrote back in place (agent-scope loads after a release
+// fence: the bytes were stored in this launch).  Each unit is converted and written to the frame at once.
+__device__ inline uint32_t byte_of(uint32_t u0, uint32_t u1, int k) { return ((k < 4 ? u0 : u1) >> (8 * (k & 3))) & 0xFF; }
+
+__device__ inline void unit_load(const uint8_t *p, int bpp, uint32_t &u0, uint32_t &u1)
+{
+    u0 = u1 = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+        if (k < bpp) { if (k < 4) u0 |= (uint32_t)p[k] << (8 * k); else u1 |= (uint32_t)p[k] << (8 * (k - 4)); }
+}
+
+__device__ inline uint32_t load_above_byte(const uint8_t *p)
+{
+    const uintptr_t a = (uintptr_t)p;
+    const uint32_t wd = __hip_atomic_load((const uint32_t *)(a & ~(uintptr_t)3), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return (wd >> (8 * (a & 3))) & 0xFF;
+}
+
+// the unit's pixels in the frame layout of the file's kind
+__device__ inline void emit(const PngDecDesc &d, uint8_t *fr, uint32_t r, uint32_t x, uint32_t u0, uint32_t u1)
+{
+    const uint32_t w = d.w;
+    if (d.depth < 8) {
+        const uint32_t dep = d.depth, ppb = 8 / dep, mask = (1u << dep) - 1, scale = d.ctype == 0 ? 255 / mask : 1;
+        uint8_t *o = fr + (size_t)r * w;
+        for (uint32_t j = 0; j < ppb; j++) {
+            const uint32_t px = x * ppb + j;
+            if (px < w) o[px] = (uint8_t)(((u0 >> (8 - dep * (j + 1))) & mask) * scale);
+        }
+        return;
+    }
+    const bool t = d.trns != 0;
+    if (d.depth == 8) {
+        switch (d.ctype) {
+        case 0: {
+            const uint32_t v = u0 & 0xFF;
+            if (!t) fr[(size_t)r * w + x] = (uint8_t)v;
+            else ((uint32_t *)(fr + (size_t)r * w * 4))[x] = v | v << 8 | v << 16 | (v == d.tv[0] ? 0u : 0xFFu) << 24;
+            return;
+        }
+        case 2: {
+            const bool m = t && (u0 & 0xFF) == d.tv[0] && ((u0 >> 8) & 0xFF) == d.tv[1] && ((u0 >> 16) & 0xFF) == d.tv[2];
+            ((uint32_t *)(fr + (size_t)r * w * 4))[x] = (u0 & 0xFFFFFF) | (m ? 0u : 0xFFu) << 24;
+            return;
+        }
+        case 3: fr[(size_t)r * w + x] = (uint8_t)u0; return;
+        case 4: {
+            const uint32_t v = u0 & 0xFF;
+            ((uint32_t *)(fr + (size_t)r * w * 4))[x] = v | v << 8 | v << 16 | ((u0 >> 8) & 0xFF) << 24;
+            return;
+        }
+        default: ((uint32_t *)(fr + (size_t)r * w * 4))[x] = u0; return;
+        }
+    }
+    uint32_t *o = (uint32_t *)(fr + (size_t)r * w * (d.kind == IPX_PNG_GRAY16 ? 2 : 8));
+    switch (d.ctype) {
+    case 0: {
+        const uint32_t y = u0 & 0xFFFF;                          // the two bytes as stored (big-endian)
+        if (!t) { ((uint16_t *)o)[x] = (uint16_t)y; return; }
+        const bool m = ((y & 0xFF) << 8 | y >> 8) == d.tv[0];
+        o[2 * x] = y | y << 16;
+        o[2 * x + 1] = y | (m ? 0u : 0xFFFFu) << 16;
+        return;
+    }
+    case 2: {
+        const bool m = t && (byte_of(u0, u1, 0) << 8 | byte_of(u0, u1, 1)) == d.tv[0] &&
+                       (byte_of(u0, u1, 2) << 8 | byte_of(u0, u1, 3)) == d.tv[1] && (byte_of(u0, u1, 4) << 8 | byte_of(u0, u1, 5)) == d.tv[2];
+        o[2 * x] = u0;
+        o[2 * x + 1] = (u1 & 0xFFFF) | (m ? 0u : 0xFFFFu) << 16;
+        return;
+    }
+    case 4: {
+        const uint32_t y = u0 & 0xFFFF, a = u0 >> 16;
+        o[2 * x] = y | y << 16;
+        o[2 * x + 1] = y | a << 16;
+        return;
+    }
+    default: o[2 * x] = u0; o[2 * x + 1] = u1; return;
+    }
+}
+
+__global__ __launch_bounds__(64) void png_unfilter_kernel(const PngDecDesc *__restrict__ desc, uint8_t *__restrict__ raw,
+                                                          uint8_t *__restrict__ frames, uint32_t *__restrict__ status)
+{
+    const PngDecDesc d = desc[blockIdx.x];
+    if (status[d.slot] & (kPngBadZlib | kPngBadCrc)) return;
+    const int lane = threadIdx.x;
+    uint8_t *base = raw + d.roff, *fr = frames + d.foff;
+    const int bpp = d.bpp;
+    const uint32_t rb = d.rowbytes, units = (rb - 1) / bpp;
+    bool bad = false;
+    for (uint32_t r0 = 0; r0 < d.h; r0 += 64) {
+        const uint32_t r = r0 + lane;
+        const bool act = r < d.h;
+        uint8_t *row = base + (size_t)(act ? r : 0) * rb;
+        uint32_t ft = act ? row[0] : 0;
+        if (ft > 4) { bad = true; ft = 0; }
+        const uint8_t *above = r0 > 0 ? base + (size_t)(r0 - 1) * rb + 1 : nullptr;
+        uint32_t c0 = 0, c1 = 0, up0 = 0, up1 = 0, ul0 = 0, ul1 = 0, f0, f1;
+        for (uint32_t t = 0; t < units + 63; t++) {
+            const int x = (int)t - lane;
+            ul0 = up0;
+            ul1 = up1;
+            up0 = __shfl_up(c0, 1, 64);
+            up1 = __shfl_up(c1, 1, 64);
+            if (lane == 0) {
+                up0 = up1 = 0;
+                if (above && x < (int)units) {
+#pragma unroll
+                    for (int k = 0; k < 8; k++)
+                        if (k < bpp) {
+                            const uint32_t v = load_above_byte(above + (size_t)x * bpp + k);
+                            if (k < 4) up0 |= v << (8 * k); else up1 |= v << (8 * (k - 4));
+                        }
+                }
+            }
+            if (act && x >= 0 && x < (int)units) {
+                uint8_t *fp = row + 1 + (size_t)x * bpp;
+                unit_load(fp, bpp, f0, f1);
+                uint32_t n0 = 0, n1 = 0;
+#pragma unroll
+                for (int k = 0; k < 8; k++) {
+                    if (k >= bpp) break;
+                    const int f = (int)byte_of(f0, f1, k);
+                    const int a = x > 0 ? (int)byte_of(c0, c1, k) : 0;
+                    const int b = (int)byte_of(up0, up1, k);
+                    const int c = x > 0 ? (int)byte_of(ul0, ul1, k) : 0;
+                    int v;
+                    switch (ft) {
+                    case 1: v = f + a; break;
+                    case 2: v = f + b; break;
+                    case 3: v = f + ((a + b) >> 1); break;
+                    case 4: v = f + paeth(a, b, c); break;
+                    default: v = f; break;
+                    }
+                    v &= 0xFF;
+                    if (k < 4) n0 |= (uint32_t)v << (8 * k); else n1 |= (uint32_t)v << (8 * (k - 4));
+                    if (lane == 63) fp[k] = (uint8_t)v;
+                }
+                c0 = n0;
+                c1 = n1;
+                emit(d, fr, r, (uint32_t)x, n0, n1);
+            }
+        }
+        __threadfence();
+        __syncthreads();
+    }
+    if (__any(bad) && lane == 0) atomicOr(status + d.slot, kPngBadFilter);
+}
+
+hipError_t launch_png_unfilter(const PngDecDesc *desc, int n, uint8_t *raw, uint8_t *frames, uint32_t *status, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(png_unfilter_kernel, dim3(n), dim3(64), 0, s, desc, raw, frames, status);
+    return hipGetLastError();
+}
+
+}  // namespace ipx
+
+// ---- the decode core -------------------------------------------------------------------------------------------------------------
+
+namespace {
+constexpr uint32_t kCrcPiece = 16384;
+
+// parse n files (a thread per eight of them); status[i] from the container
+int png_parse_all(const ipx_bytes *files, int n, std::vector<PngFileInfo> &info, int *status)
+{
+    std::atomic<int> failed{IPX_OK};
+    HostPool::instance().parallel_for(n, std::max(1, std::min(n / 8, 16)), [&](int i) {
+        const int rc = guarded_status([&] { status[i] = png_parse(files[i].data, files[i].data ? files[i].len : 0, &info[i]); }, nullptr);
+        if (rc) failed = rc;
+    });
+    if (failed) { set_error("png decode: host parse failed"); return failed; }
+    return IPX_OK;
+}
+
+// the batch's size and kind: *w x *h (or the first parsed file's when *w == 0) and *kind (or the first's when -1); others UNSUPPORTED
+void png_select(const std::vector<PngFileInfo> &info, int n, int *w, int *h, int *kind, int *status)
+{
+    for (int i = 0; i < n; i++) {
+        if (status[i] != IPX_OK) continue;
+        if (*w <= 0) { *w = info[i].w; *h = info[i].h; }
+        if (*kind < 0 && info[i].w == *w && info[i].h == *h) *kind = info[i].kind;
+        if (info[i].w != *w || info[i].h != *h || info[i].kind != *kind) status[i] = IPX_ERR_UNSUPPORTED;
+    }
+}
+
+size_t png_group_bytes(const PngFileInfo &f) { return align256(f.file_len) + align256(f.idat_len + 32) + align256(f.raw_len); }
+}  // namespace
+
+// Decodes files[idx[g]] (status IPX_OK, all of one size and kind) into frames + slot[g] * frame_stride and, when palettes is set,
+// their palettes to palettes + slot[g] * 1024, on stream s; the verdicts land in status[idx[g]].  The scratch (the files' pinned upload
+// block and, in HBM, the files, zlib streams, filtered rows and tables) is cut into groups of at most IPX_PNG_DEC_SCRATCH_MB, and each
+// group's scratch is released before the next group takes its own; one read-back of the per-file words at the end.
+static int png_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files, const std::vector<int> &idx, const std::vector<int> &slot,
+                            const std::vector<PngFileInfo> &info, uint8_t *frames, size_t frame_stride, uint8_t *palettes, int *status)
+{
+    const int n = (int)idx.size();
+    if (n == 0) return IPX_OK;
+    std::vector<uint8_t *> pinned;
+    struct Release {
+        ipx_ctx *ctx; hipStream_t s; std::vector<uint8_t *> &p;
+        ~Release() { (void)hipStreamSynchronize(s); for (uint8_t *q : p) (void)ipx_host_free(ctx, q); }
+    } release{ctx, s, pinned};
+    AsyncFree mem{s, {}};
+    uint32_t *dstate;
+    IPX_HIP(mem.get(&dstate, (size_t)n * 4));
+    IPX_HIP(hipMemsetAsync(dstate, 0, (size_t)n * 4, s));
+    if (palettes) {     // one upload of every slot up to the last (zero for slots not decoded here)
+        const int nslot = *std::max_element(slot.begin(), slot.end()) + 1;
+        uint8_t *hpal = (uint8_t *)ipx_host_alloc(ctx, (size_t)nslot * 1024);
+        if (!hpal) return IPX_ERR_NOMEM;
+        pinned.push_back(hpal);
+        memset(hpal, 0, (size_t)nslot * 1024);
+        for (int g = 0; g < n; g++) memcpy(hpal + (size_t)slot[g] * 1024, info[idx[g]].pal, 1024);
+        IPX_HIP(hipMemcpyAsync(palettes, hpal, (size_t)nslot * 1024, hipMemcpyHostToDevice, s));
+    }
+    const size_t budget = (size_t)env_int("IPX_PNG_DEC_SCRATCH_MB", 8192) << 20;
+    std::vector<int> group;     // positions in idx
+    auto run_group = [&]() -> int {
+        const int m = (int)group.size();
+        if (m == 0) return IPX_OK;
+        // this group's scratch: the device blocks go back (stream-ordered) first, then the pinned block once the stream is past its copy
+        std::vector<uint8_t *> gpinned;
+        Release grelease{ctx, s, gpinned};
+        AsyncFree gmem{s, {}};
+        std::vector<PngDecDesc> desc(m);
+        std::vector<PngCrcPiece> pieces;
+        std::vector<PngChunk> chunks;
+        std::vector<size_t> foff(m);
+        size_t fbytes = 0, zbytes = 0, rbytes = 0;
+        for (int g = 0; g < m; g++) {
+            const PngFileInfo &f = info[idx[group[g]]];
+            PngDecDesc &d = desc[g];
+            memset(&d, 0, sizeof d);
+            foff[g] = fbytes;
+            d.zoff = zbytes;
+            d.roff = rbytes;
+            d.foff = (uint64_t)slot[group[g]] * frame_stride;
+            d.zlen = f.idat_len;
+            d.zlast = f.idat_last;
+            d.raw_len = (uint32_t)f.raw_len;
+            d.w = (uint32_t)f.w;
+            d.h = (uint32_t)f.h;
+            d.rowbytes = f.rowbytes;
+            d.slot = (uint32_t)group[g];
+            d.ctype = (uint16_t)f.ctype;
+            d.depth = (uint16_t)f.depth;
+            d.kind = (uint16_t)f.kind;
+            d.trns = f.trns ? 1 : 0;
+            for (int k = 0; k < 3; k++) d.tv[k] = f.trns_v[k];
+            d.bpp = (uint16_t)f.bpp;
+            // the chunks' CRC pieces; IDAT payloads land back to back at zoff
+            size_t zat = zbytes;
+            uint32_t ii = 0;
+            for (const PngSpan &c : f.crc) {
+                const uint32_t k = (uint32_t)chunks.size();
+                chunks.push_back(PngChunk{foff[g] + c.off, c.len, (uint32_t)group[g]});
+                const bool is_idat = ii < f.idat.size() && f.idat[ii].off == c.off + 4;
+                for (uint32_t p0 = 0; p0 < c.len; p0 += kCrcPiece) {
+                    const uint32_t p1 = std::min(c.len, p0 + kCrcPiece);
+                    PngCrcPiece pc;
+                    pc.src = foff[g] + c.off + p0;
+                    pc.len = p1 - p0;
+                    pc.chunk = k;
+                    pc.after = c.len - p1;
+                    pc.skip = p0 < 4 ? 4 - p0 : 0;
+                    pc.dst = is_idat && pc.len > pc.skip ? zat + (p0 + pc.skip - 4) : ~0ull;
+                    pieces.push_back(pc);
+                }
+                if (is_idat) { zat += f.idat[ii].len; ii++; }
+            }
+            fbytes += align256(f.file_len);
+            zbytes += align256((size_t)f.idat_len + 32);
+            rbytes += align256(f.raw_len);
+        }
+        uint8_t *hblob = (uint8_t *)ipx_host_alloc(ctx, fbytes);
+        if (!hblob) return IPX_ERR_NOMEM;
+        gpinned.push_back(hblob);
+        HostPool::instance().parallel_for(m, std::max(1, std::min(m / 8, 16)), [&](int g) {
+            const int i = idx[group[g]];
+            memcpy(hblob + foff[g], files[i].data, info[i].file_len);
+        });
+        uint8_t *dblob, *dz, *draw;
+        uint32_t *dacc;
+        PngCrcPiece *dpieces;
+        PngChunk *dchunks;
+        PngDecDesc *ddesc;
+        IPX_HIP(gmem.get(&dblob, fbytes));
+        IPX_HIP(gmem.get(&dz, zbytes));
+        IPX_HIP(gmem.get(&draw, rbytes));
+        IPX_HIP(gmem.get(&dacc, chunks.size() * 4));
+        IPX_HIP(gmem.get(&dpieces, pieces.size() * sizeof(PngCrcPiece)));
+        IPX_HIP(gmem.get(&dchunks, chunks.size() * sizeof(PngChunk)));
+        IPX_HIP(gmem.get(&ddesc, (size_t)m * sizeof(PngDecDesc)));
+        IPX_HIP(hipMemcpyAsync(dblob, hblob, fbytes, hipMemcpyHostToDevice, s));
+        IPX_HIP(hipMemcpyAsync(dpieces, pieces.data(), pieces.size() * sizeof(PngCrcPiece), hipMemcpyHostToDevice, s));
+        IPX_HIP(hipMemcpyAsync(dchunks, chunks.data(), chunks.size() * sizeof(PngChunk), hipMemcpyHostToDevice, s));
+        IPX_HIP(hipMemcpyAsync(ddesc, desc.data(), (size_t)m * sizeof(PngDecDesc), hipMemcpyHostToDevice, s));
+        IPX_HIP(hipMemsetAsync(dacc, 0, chunks.size() * 4, s));
+        IPX_HIP(launch_png_crc(dblob, dpieces, (int)pieces.size(), dacc, dz, s));
+        IPX_HIP(launch_png_crc_check(dblob, dchunks, (int)chunks.size(), dacc, dstate, s));
+        IPX_HIP(launch_png_inflate(dz, ddesc, m, draw, dstate, s));
+        IPX_HIP(launch_png_unfilter(ddesc, m, draw, frames, dstate, s));
+        // the host vectors must outlive the copies: wait before they go
+        IPX_HIP(hipStreamSynchronize(s));
+        group.clear();
+        return IPX_OK;
+    };
+    size_t group_bytes = 0;
+    for (int g = 0; g < n; g++) {
+        const size_t need = png_group_bytes(info[idx[g]]);
+        if (!group.empty() && group_bytes + need > budget) {
+            const int rc = run_group();
+            if (rc) return rc;
+            group_bytes = 0;
+        }
+        group.push_back(g);
+        group_bytes += need;
+    }
+    int rc = run_group();
+    if (rc) return rc;
+    std::vector<uint32_t> st(n);
+    IPX_HIP(hipMemcpyAsync(st.data(), dstate, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    IPX_HIP(hipStreamSynchronize(s));
+    for (int g = 0; g < n; g++) {
+        const uint32_t v = st[g];
+        status[idx[g]] = v == 0 ? IPX_OK : (v & ~kPngTrailing) ? IPX_ERR_INVALID : IPX_ERR_UNSUPPORTED;
+    }
+    return IPX_OK;
+}
+
+// ---- the entries -----------------------------------------------------------------------------------------------------------------
+struct ipx_png_frames { std::vector<void *> dev; hipStream_t stream = nullptr; };   // stream-ordered allocations of `stream`
+
+extern "C" {
+
+void ipx_png_frames_free(ipx_ctx *ctx, ipx_png_frames *o)
+{
+    if (!o) return;
+    if (ctx) (void)hipSetDevice(ctx->device);
+    for (void *p : o->dev) (void)hipFreeAsync(p, o->stream);
+    delete o;
+}
+
+int ipx_png_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *files, int n, int *w, int *h, int *kind, ipx_png_batch *frames,
+                         int *status, ipx_png_frames **owner) try
+{
+    IPX_ENTER(ctx);
+    if (!files || n < 0 || !w || !h || !kind || !frames || !status || !owner || *w < 0 || *h < 0 || (*w == 0) != (*h == 0) ||
+        *kind < -1 || *kind >= kPngKinds) {
+        set_error("ipx_png_decode_batch: bad argument");
+        return IPX_ERR_INVALID;
+    }
+    *owner = nullptr;
+    memset(frames, 0, sizeof *frames);
+    if (n == 0) return IPX_OK;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    std::vector<PngFileInfo> info(n);
+    int rc = png_parse_all(files, n, info, status);
+    if (rc) return rc;
+    int bw = *w, bh = *h, bk = *kind;
+    png_select(info, n, &bw, &bh, &bk, status);
+    std::vector<int> idx;
+    for (int i = 0; i < n; i++)
+        if (status[i] == IPX_OK) idx.push_back(i);
+    if (idx.empty()) return IPX_OK;
+    std::unique_ptr<ipx_png_frames> o(new ipx_png_frames);
+    o->stream = s;
+    const int kb = png_kind_bpp(bk);
+    const size_t fs = align256((size_t)bw * bh * kb);
+    uint8_t *dframes = nullptr, *dpal = nullptr;
+    hipError_t e = hipMallocAsync((void **)&dframes, fs * n, s);
+    if (e == hipSuccess) o->dev.push_back(dframes);
+    if (e == hipSuccess && bk == IPX_PNG_PALETTED) {
+        e = hipMallocAsync((void **)&dpal, (size_t)n * 1024, s);
+        if (e == hipSuccess) o->dev.push_back(dpal);
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        ipx_png_frames_free(ctx, o.release());
+        set_error("ipx_png_decode_batch: device allocation failed: %s", hipGetErrorString(e));
+        return IPX_ERR_NOMEM;
+    }
+    if (dpal) IPX_HIP(hipMemsetAsync(dpal, 0, (size_t)n * 1024, s));
+    rc = png_decode_files(ctx, s, files, idx, idx, info, dframes, fs, dpal, status);     // frame i of file i
+    if (rc) { ipx_png_frames_free(ctx, o.release()); return rc; }
+    *w = bw;
+    *h = bh;
+    *kind = bk;
+    bool any = false;
+    for (int i = 0; i < n; i++) any |= status[i] == IPX_OK;
+    if (!any) { ipx_png_frames_free(ctx, o.release()); return IPX_OK; }
+    frames->pix = dframes;
+    frames->stride = bw * kb;
+    frames->frame_stride = fs;
+    frames->palettes = dpal;
+    *owner = o.release();
+    return IPX_OK;
+}
+IPX_CATCH_STATUS
+
+}  // extern "C"
+
+// ---- the PNG leg -----------------------------------------------------------------------------------------------------------------
+
+// the plan's operators on m frames of one kind in HBM (the matching ipx_plan_run_dev_*)
+static int png_run_ops(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, int kind, int m, const uint8_t *src, size_t fs, const uint8_t *pal,
+                       uint8_t *dres, size_t fres, uint8_t *dth, size_t fth, uint8_t *dwm, size_t fwm)
+{
+    const int w = pl->p.sw;
+    switch (kind) {
+    case IPX_PNG_GRAY: return ipx_plan_run_dev_gray(ctx, s, pl, m, src, w, fs, dres, fres, dth, fth, dwm, fwm);
+    case IPX_PNG_NRGBA: return ipx_plan_run_dev_nrgba(ctx, s, pl, m, src, w * 4, fs, dres, fres, dth, fth, dwm, fwm);
+    case IPX_PNG_RGBA: return ipx_plan_run_dev(ctx, s, pl, m, src, w * 4, fs, dres, fres, dth, fth, dwm, fwm);
+    case IPX_PNG_PALETTED: return ipx_plan_run_dev_paletted(ctx, s, pl, m, src, w, fs, pal, dres, fres, dth, fth, dwm, fwm);
+    case IPX_PNG_GRAY16: return ipx_plan_run_dev_deep(ctx, s, pl, m, IPX_DEEP_GRAY16, src, w * 2, fs, dres, fres, dth, fth, dwm, fwm);
+    case IPX_PNG_RGBA64: return ipx_plan_run_dev_deep(ctx, s, pl, m, IPX_DEEP_RGBA64, src, w * 8, fs, dres, fres, dth, fth, dwm, fwm);
+    default: return ipx_plan_run_dev_deep(ctx, s, pl, m, IPX_DEEP_NRGBA64, src, w * 8, fs, dres, fres, dth, fth, dwm, fwm);
+    }
+}
+
+extern "C" {
+
+// The PNG task's GPU leg from the uploads on: the host parse of every file, then per kind, per decode group (IPX_HOST_CHUNK_PNG_DEC
+// files, at most ~4 GiB of frames): upload, CRC, inflate and unfilter into HBM; then per chunk of IPX_HOST_CHUNK_PNG frames the
+// matching ipx_plan_run_dev_* and png.Encode of all three outputs.  The operators run on every slot of a chunk (a failed file's slot
+// holds whatever its frame holds); only OK files' streams are handed out.
+int ipx_plan_run_png_png(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, ipx_bytes *resize_out, ipx_bytes *thumb_out,
+                         ipx_bytes *wm_out, int *status, ipx_jpeg_result **result) try
+{
+    IPX_ENTER(ctx);
+    if (!pl || n < 0 || !files || !status || !result) { set_error("ipx_plan_run_png_png: bad argument"); return IPX_ERR_INVALID; }
+    *result = nullptr;
+    const ipx_plan_info &in = pl->info;
+    const int sw = pl->p.sw, sh = pl->p.sh;
+    for (int i = 0; i < n; i++) {
+        for (ipx_bytes *o : {resize_out, thumb_out, wm_out})
+            if (o) o[i] = ipx_bytes{nullptr, 0};
+    }
+    if (n == 0) return IPX_OK;
+    std::vector<PngFileInfo> info(n);
+    int rc = png_parse_all(files, n, info, status);
+    if (rc) return rc;
+    for (int i = 0; i < n; i++)
+        if (status[i] == IPX_OK && (info[i].w != sw || info[i].h != sh)) status[i] = IPX_ERR_UNSUPPORTED;
+    const size_t fres = resize_out ? align256(in.resize_bytes) : 0, fth = thumb_out ? align256(in.thumb_bytes) : 0;
+    const size_t fwm = wm_out ? align256(in.wm_bytes) : 0;
+    const size_t per_out = fres + fth + fwm;
+    const int chunk_max = std::max(1, env_int("IPX_HOST_CHUNK_PNG", 64)), group_max = std::max(1, env_int("IPX_HOST_CHUNK_PNG_DEC", 1024));
+    struct ResultGuard {
+        ipx_ctx *ctx;
+        ipx_jpeg_result *r;
+        ~ResultGuard() { ipx_jpeg_result_free(ctx, r); }
+    } res{ctx, new ipx_jpeg_result};
+    LaneLease lane(ctx);
+    hipStream_t s = lane->stream;
+    for (int kind = 0; kind < kPngKinds; kind++) {
+        std::vector<int> of_kind;
+        for (int i = 0; i < n; i++)
+            if (status[i] == IPX_OK && info[i].kind == kind) of_kind.push_back(i);
+        if (of_kind.empty()) continue;
+        const int kb = png_kind_bpp(kind);
+        const size_t fs = align256((size_t)sw * sh * kb);
+        const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)group_max, ((size_t)4 << 30) / (fs + 1024)));
+        const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)chunk_max, per_out ? ((size_t)1 << 30) / per_out : (size_t)chunk_max));
+        std::vector<size_t> offs(chunk), lens(chunk);
+        for (size_t g0 = 0; g0 < of_kind.size(); g0 += group) {
+            const int m = (int)std::min<size_t>(group, of_kind.size() - g0);
+            std::vector<int> idx(of_kind.begin() + g0, of_kind.begin() + g0 + m), slot(m);
+            for (int g = 0; g < m; g++) slot[g] = g;
+            struct SyncOnExit { hipStream_t s; ~SyncOnExit() { (void)hipStreamSynchronize(s); } } sync_on_exit{s};
+            AsyncFree mem{s, {}};
+            uint8_t *dfr, *dpal = nullptr;
+            IPX_HIP(mem.get(&dfr, fs * m));
+            if (kind == IPX_PNG_PALETTED) IPX_HIP(mem.get(&dpal, (size_t)1024 * m));
+            rc = png_decode_files(ctx, s, files, idx, slot, info, dfr, fs, dpal, status);
+            if (rc) return rc;
+            for (int c0 = 0; c0 < m; c0 += chunk) {
+                const int cm = std::min(chunk, m - c0);
+                bool any = false;
+                for (int g = c0; g < c0 + cm; g++) any |= status[idx[g]] == IPX_OK;
+                if (!any) continue;
+                AsyncFree omem{s, {}};
+                uint8_t *dres = nullptr, *dth = nullptr, *dwm = nullptr;
+                if (fres) IPX_HIP(omem.get(&dres, fres * cm));
+                if (fth) IPX_HIP(omem.get(&dth, fth * cm));
+                if (fwm) IPX_HIP(omem.get(&dwm, fwm * cm));
+                rc = png_run_ops(ctx, s, pl, kind, cm, dfr + fs * c0, fs, dpal ? dpal + (size_t)1024 * c0 : nullptr, dres, fres, dth, fth, dwm, fwm);
+                if (rc) return rc;
+                struct Out { uint8_t *dev; size_t fs; int w, h; ipx_bytes *dst; };
+                const Out outs[3] = {{dres, fres, in.resize_w, in.resize_h, resize_out}, {dth, fth, in.thumb_w, in.thumb_h, thumb_out},
+                                     {dwm, fwm, in.wm_w, in.wm_h, wm_out}};
+                for (const Out &o : outs) {
+                    if (!o.dev || o.w <= 0 || o.h <= 0) continue;
+                    uint8_t *blob = nullptr;
+                    rc = png_encode_core(ctx, s, o.dev, o.w, o.h, o.w * 4, o.fs, cm, &blob, offs.data(), lens.data());
+                    if (rc) return rc;
+                    res.r->blobs.push_back(blob);
+                    for (int g = 0; g < cm; g++)
+                        if (status[idx[c0 + g]] == IPX_OK) o.dst[idx[c0 + g]] = ipx_bytes{blob + offs[g], lens[g]};
+                }
+            }
+        }
+    }
+    *result = res.r;
+    res.r = nullptr;
+    return IPX_OK;
+}
+IPX_CATCH_STATUS
+
+}  // extern "C"

@@ -553,6 +553,42 @@ void ipx_gif_frames_free(ipx_ctx *ctx, ipx_gif_frames *owner);
 int ipx_plan_run_gif_gif(ipx_ctx *ctx, const ipx_plan *plan, int n, const ipx_bytes *files, int quality, ipx_bytes *resize_out,
                          ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result);
 
+/* ---- image.Decode for PNGs (decoder side) ---------------------------------------------
+ * For a PNG upload image.Decode is png.Decode.  The host walks the chunk headers only (signature, IHDR, PLTE, tRNS, IDAT, IEND); the
+ * whole files go up, and on the GPU the CRC of every chunk is checked in parallel pieces, the IDAT payloads are gathered into one zlib
+ * stream per file, one wave per file inflates it with its Huffman tables, input and 32 KiB window in LDS, and a diagonal wavefront of
+ * rows unfilters it and writes the frame layout of the type Go returns (IPX_PNG_*):
+ *   IPX_PNG_GRAY     *image.Gray     1 byte per pixel     gray 1/2/4/8 without tRNS             -> ipx_plan_run_dev_gray
+ *   IPX_PNG_NRGBA    *image.NRGBA    4                    gray 8 + tRNS, gray-alpha 8, RGB 8 + tRNS, RGBA 8 -> ipx_plan_run_dev_nrgba
+ *   IPX_PNG_RGBA     *image.RGBA     4 (A = 0xff)         RGB 8 without tRNS                    -> ipx_plan_run_dev
+ *   IPX_PNG_PALETTED *image.Paletted 1 + 256 x 4 palette  palette 1/2/4/8                       -> ipx_plan_run_dev_paletted
+ *   IPX_PNG_GRAY16   *image.Gray16   2 (big-endian)       gray 16 without tRNS                  -> ipx_plan_run_dev_deep, IPX_DEEP_GRAY16
+ *   IPX_PNG_RGBA64   *image.RGBA64   8 (A = 0xffff)       RGB 16 without tRNS                   -> _deep, IPX_DEEP_RGBA64
+ *   IPX_PNG_NRGBA64  *image.NRGBA64  8                    gray 16 + tRNS, gray-alpha 16, RGB 16 + tRNS, RGBA 16 -> _deep, IPX_DEEP_NRGBA64
+ * Frame i (file i) at pix + i * frame_stride, rows `stride` (w * bytes per pixel) bytes apart; for IPX_PNG_PALETTED the palettes at
+ * palettes + i * 1024 (256 x (R, G, B, A), non-premultiplied: tRNS entries as color.NRGBA, entries past PLTE opaque black, as Go pads
+ * them), else palettes == NULL.  *w, *h: 0, or the size the batch must have; *kind: -1, or the kind it must have; on return the batch's
+ * size and kind (the first decodable file's).  status[i]: IPX_OK, IPX_ERR_INVALID (Go's decoder fails on the file too) or
+ * IPX_ERR_UNSUPPORTED (Adam7, another chunk order, bytes after the zlib stream, sub-byte gray with tRNS, another size or kind than the
+ * batch's, frames beyond ipx_frame_supported, ...: the worker decodes those with Go as before; the full list is in DESIGN.md section
+ * 4.10).  The frames of non-OK files are undefined; pix == NULL when no file was decodable.  Free the frames with ipx_png_frames_free:
+ * stream-ordered allocations of `stream` (NULL: the context's default stream). */
+enum { IPX_PNG_GRAY = 0, IPX_PNG_NRGBA = 1, IPX_PNG_RGBA = 2, IPX_PNG_PALETTED = 3, IPX_PNG_GRAY16 = 4, IPX_PNG_RGBA64 = 5,
+       IPX_PNG_NRGBA64 = 6 };
+typedef struct { uint8_t *pix; int32_t stride; size_t frame_stride; uint8_t *palettes; } ipx_png_batch;
+typedef struct ipx_png_frames ipx_png_frames;
+int ipx_png_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *files, int n, int *w, int *h, int *kind, ipx_png_batch *frames,
+                         int *status, ipx_png_frames **owner);
+void ipx_png_frames_free(ipx_ctx *ctx, ipx_png_frames *owner);
+/* The PNG task compressed in, compressed out: the uploads as the object store returns them, png.Decode, every operator of the plan
+ * (the plan's frame size is the batch's size) and png.Encode of all three outputs (a PNG watermark stays PNG), all on the GPU; only
+ * compressed bytes cross the link.  Files of any kind may be mixed: they are grouped by kind on the host, decoded in large groups
+ * (IPX_HOST_CHUNK_PNG_DEC files, bounded by memory) and fed to the operators and the encoder in chunks of IPX_HOST_CHUNK_PNG.
+ * status[i] as for ipx_png_decode_batch; outputs of non-OK files are {NULL, 0}.  Streams as for ipx_plan_run_host_png
+ * (ipx_jpeg_result_free). */
+int ipx_plan_run_png_png(ipx_ctx *ctx, const ipx_plan *plan, int n, const ipx_bytes *files, ipx_bytes *resize_out, ipx_bytes *thumb_out,
+                         ipx_bytes *wm_out, int *status, ipx_jpeg_result **result);
+
 /* ---- one process, several GPUs, asynchronous jobs ----------------------------------------------------------
  * The reference worker is ONE process whose goroutines pull independent messages (worker.go:88-96, 112-149); it scales by
  * running more consumers, nothing is exchanged (kafka/consumer.go:23).  A pool is that shape behind the C ABI: one context per
