@@ -110,12 +110,18 @@ TYPES = [("gray1", 0, 1, False), ("gray2", 0, 2, False), ("gray4", 0, 4, False),
          ("gray16_trns", 0, 16, True), ("ga16", 4, 16, False), ("rgb16_trns", 2, 16, True), ("rgba16", 6, 16, False)]
 
 
+def samples_of_type(ctype, depth, h, w, seed, kind="photo"):
+    """the samples of_type writes"""
+    c = dm.CHANNELS[ctype]
+    return (photo if kind == "photo" else flat)(h, w, c, seed, 255) * ((1 << depth) - 1) // 255
+
+
 def of_type(ctype, depth, trns, h, w, seed, kind="photo", **kw):
     """a file of the type with seeded samples; tRNS picks a sample value that occurs, palettes hold fewer entries than indices reach"""
     rng = np.random.default_rng(seed)
     maxv = (1 << depth) - 1
     c = dm.CHANNELS[ctype]
-    s = (photo if kind == "photo" else flat)(h, w, c, seed, 255) * maxv // 255
+    s = samples_of_type(ctype, depth, h, w, seed, kind)
     plte = t = None
     if ctype == 3:
         npal = max(1, min(256, (maxv + 1) * 3 // 4))
