@@ -19,7 +19,8 @@
 //                      not memory.  The remedy is parallelism inside a file (restart intervals where present,
 //                      self-synchronising sub-sequences otherwise), not a faster lane.
 //   jpeg_idct_kernel   parallel over blocks: b[unzig[zig]] *= qt[zig]; idct (the Chen-Wang integer transform of
-//                      idct.go, row pass in registers, column pass through LDS); level shift, clip, 8-byte row stores
+//                      idct.go with its all-zero-AC row shortcut, in wrapping 32-bit arithmetic; row pass in registers,
+//                      column pass through LDS); level shift, clip, 8-byte row stores
 //                      into the MCU-padded planes of image.NewYCbCr.
 // The planes feed band_conv_kernel directly (ipx_plan_run_dev_ycbcr): decoded pixels never leave HBM.
 #include "ipx_internal.h"
@@ -228,12 +229,20 @@ __global__ __launch_bounds__(64) void jpeg_huff_kernel(JpegDecArgs a)
 }
 
 // ---- reconstruction -----------------------------------------------------------------------------------------
-constexpr int W1 = 2841, W2 = 2676, W3 = 2408, W5 = 1609, W6 = 1108, W7 = 565, R2 = 181;
+// idct.go computes in int32 and Go defines its overflow as wrapping; signed overflow in C++ is undefined, so the transform runs in
+// uint32_t (which wraps by definition) and turns a value into int32_t only for the arithmetic shifts.
+constexpr uint32_t W1 = 2841, W2 = 2676, W3 = 2408, W5 = 1609, W6 = 1108, W7 = 565, R2 = 181;
 
-__device__ __forceinline__ void idct_row(int (&s)[8])   // idct.go, horizontal pass (the all-zero-AC shortcut gives the same values)
+__device__ __forceinline__ uint32_t asr(uint32_t v, int n) { return (uint32_t)((int32_t)v >> n); }
+
+__device__ __forceinline__ void idct_row(uint32_t (&s)[8])   // idct.go, horizontal pass
 {
-    int x0 = (int)((uint32_t)s[0] << 11) + 128, x1 = (int)((uint32_t)s[4] << 11), x2 = s[6], x3 = s[2], x4 = s[1], x5 = s[7], x6 = s[5], x7 = s[3];
-    int x8 = W7 * (x4 + x5);
+    // idct.go's shortcut: a row whose seven AC terms are zero becomes s[0] << 3.  The full path gives the same values only while
+    // |s[0]| < 2^20 (s[0] << 11 wraps beyond), so the shortcut is kept -- as a select, since the lanes of a wave hold different rows.
+    const bool dc_only = (s[1] | s[2] | s[3] | s[4] | s[5] | s[6] | s[7]) == 0;
+    const uint32_t dc = s[0] << 3;
+    uint32_t x0 = (s[0] << 11) + 128, x1 = s[4] << 11, x2 = s[6], x3 = s[2], x4 = s[1], x5 = s[7], x6 = s[5], x7 = s[3];
+    uint32_t x8 = W7 * (x4 + x5);
     x4 = x8 + (W1 - W7) * x4;
     x5 = x8 - (W1 + W7) * x5;
     x8 = W3 * (x6 + x7);
@@ -252,25 +261,27 @@ __device__ __forceinline__ void idct_row(int (&s)[8])   // idct.go, horizontal p
     x8 -= x3;
     x3 = x0 + x2;
     x0 -= x2;
-    x2 = (R2 * (x4 + x5) + 128) >> 8;
-    x4 = (R2 * (x4 - x5) + 128) >> 8;
-    s[0] = (x7 + x1) >> 8; s[1] = (x3 + x2) >> 8; s[2] = (x0 + x4) >> 8; s[3] = (x8 + x6) >> 8;
-    s[4] = (x8 - x6) >> 8; s[5] = (x0 - x4) >> 8; s[6] = (x3 - x2) >> 8; s[7] = (x7 - x1) >> 8;
+    x2 = asr(R2 * (x4 + x5) + 128, 8);
+    x4 = asr(R2 * (x4 - x5) + 128, 8);
+    s[0] = dc_only ? dc : asr(x7 + x1, 8); s[1] = dc_only ? dc : asr(x3 + x2, 8);
+    s[2] = dc_only ? dc : asr(x0 + x4, 8); s[3] = dc_only ? dc : asr(x8 + x6, 8);
+    s[4] = dc_only ? dc : asr(x8 - x6, 8); s[5] = dc_only ? dc : asr(x0 - x4, 8);
+    s[6] = dc_only ? dc : asr(x3 - x2, 8); s[7] = dc_only ? dc : asr(x7 - x1, 8);
 }
-__device__ __forceinline__ void idct_col(int (&s)[8])   // vertical pass
+__device__ __forceinline__ void idct_col(uint32_t (&s)[8])   // vertical pass (idct.go has no shortcut here)
 {
-    int y0 = (int)((uint32_t)s[0] << 8) + 8192, y1 = (int)((uint32_t)s[4] << 8), y2 = s[6], y3 = s[2], y4 = s[1], y5 = s[7], y6 = s[5], y7 = s[3];
-    int y8 = W7 * (y4 + y5) + 4;
-    y4 = (y8 + (W1 - W7) * y4) >> 3;
-    y5 = (y8 - (W1 + W7) * y5) >> 3;
+    uint32_t y0 = (s[0] << 8) + 8192, y1 = s[4] << 8, y2 = s[6], y3 = s[2], y4 = s[1], y5 = s[7], y6 = s[5], y7 = s[3];
+    uint32_t y8 = W7 * (y4 + y5) + 4;
+    y4 = asr(y8 + (W1 - W7) * y4, 3);
+    y5 = asr(y8 - (W1 + W7) * y5, 3);
     y8 = W3 * (y6 + y7) + 4;
-    y6 = (y8 - (W3 - W5) * y6) >> 3;
-    y7 = (y8 - (W3 + W5) * y7) >> 3;
+    y6 = asr(y8 - (W3 - W5) * y6, 3);
+    y7 = asr(y8 - (W3 + W5) * y7, 3);
     y8 = y0 + y1;
     y0 -= y1;
     y1 = W6 * (y3 + y2) + 4;
-    y2 = (y1 - (W2 + W6) * y2) >> 3;
-    y3 = (y1 + (W2 - W6) * y3) >> 3;
+    y2 = asr(y1 - (W2 + W6) * y2, 3);
+    y3 = asr(y1 + (W2 - W6) * y3, 3);
     y1 = y4 + y6;
     y4 -= y6;
     y6 = y5 + y7;
@@ -279,10 +290,10 @@ __device__ __forceinline__ void idct_col(int (&s)[8])   // vertical pass
     y8 -= y3;
     y3 = y0 + y2;
     y0 -= y2;
-    y2 = (R2 * (y4 + y5) + 128) >> 8;
-    y4 = (R2 * (y4 - y5) + 128) >> 8;
-    s[0] = (y7 + y1) >> 14; s[1] = (y3 + y2) >> 14; s[2] = (y0 + y4) >> 14; s[3] = (y8 + y6) >> 14;
-    s[4] = (y8 - y6) >> 14; s[5] = (y0 - y4) >> 14; s[6] = (y3 - y2) >> 14; s[7] = (y7 - y1) >> 14;
+    y2 = asr(R2 * (y4 + y5) + 128, 8);
+    y4 = asr(R2 * (y4 - y5) + 128, 8);
+    s[0] = asr(y7 + y1, 14); s[1] = asr(y3 + y2, 14); s[2] = asr(y0 + y4, 14); s[3] = asr(y8 + y6, 14);
+    s[4] = asr(y8 - y6, 14); s[5] = asr(y0 - y4, 14); s[6] = asr(y3 - y2, 14); s[7] = asr(y7 - y1, 14);
 }
 
 // A workgroup takes kIdctMcus consecutive MCUs of ONE MCU row (32 for one-component files): up to 48 blocks, eight threads each.
@@ -294,7 +305,7 @@ __device__ __forceinline__ void idct_col(int (&s)[8])   // vertical pass
 constexpr int kIdctMcus = 8, kIdctMaxBlocks = 48, kIdctThreads = kIdctMaxBlocks * 8;
 __global__ __launch_bounds__(kIdctThreads) void jpeg_idct_kernel(JpegDecArgs a, JpegPlanes pl, int wgs_per_row, int mcus_per_wg)
 {
-    __shared__ int ws[kIdctMaxBlocks * 72];
+    __shared__ uint32_t ws[kIdctMaxBlocks * 72];
     __shared__ __attribute__((aligned(8))) uint8_t ob[kIdctMaxBlocks * 64];     // the strips: Y (8 * v0 rows), then Cb, then Cr (8 rows each)
     const int t = threadIdx.x, blk = t >> 3, r = t & 7;
     const int img = blockIdx.y;
@@ -319,14 +330,14 @@ __global__ __launch_bounds__(kIdctThreads) void jpeg_idct_kernel(JpegDecArgs a, 
     const uint16_t *qnat = &a.tab[img].qnat[0][0];
     const int ypitch = 8 * a.h0 * mcus_per_wg, cpitch = 8 * mcus_per_wg;   // bytes per strip row
     const int ybytes = 8 * a.v0 * ypitch, cbytes = 8 * cpitch;
-    int s[8];
+    uint32_t s[8];
     if (live) {
         const uint4 v = *(const uint4 *)(coefs + (gb * 64u + (uint32_t)r * 8u));
         const uint4 qv = *(const uint4 *)(qnat + ((uint32_t)c * 64u + (uint32_t)r * 8u));
         const uint32_t wv[4] = {v.x, v.y, v.z, v.w}, qw[4] = {qv.x, qv.y, qv.z, qv.w};
 #pragma unroll
-        for (int i = 0; i < 8; i++) s[i] = (int)(int16_t)(wv[i >> 1] >> (16 * (i & 1))) * (int)((qw[i >> 1] >> (16 * (i & 1))) & 0xffffu);   // b[unzig[zig]] *= qt[zig]
-        if (r == 0) s[0] = (int)dcs[gb] * (int)(qw[0] & 0xffffu);                                        // the DC values live in their own dense array
+        for (int i = 0; i < 8; i++) s[i] = (uint32_t)(int32_t)(int16_t)(wv[i >> 1] >> (16 * (i & 1))) * ((qw[i >> 1] >> (16 * (i & 1))) & 0xffffu);   // b[unzig[zig]] *= qt[zig]
+        if (r == 0) s[0] = (uint32_t)(int32_t)dcs[gb] * (qw[0] & 0xffffu);                                         // the DC values live in their own dense array
         idct_row(s);
 #pragma unroll
         for (int i = 0; i < 8; i++) ws[blk * 72 + r * 8 + i] = s[i];
@@ -345,7 +356,7 @@ __global__ __launch_bounds__(kIdctThreads) void jpeg_idct_kernel(JpegDecArgs a, 
             pitch = cpitch; base = ybytes + (c - 1) * cbytes + mxl * 8 + r;
         }
 #pragma unroll
-        for (int i = 0; i < 8; i++) ob[base + i * pitch] = (uint8_t)(min(max(s[i], -128), 127) + 128);   // level shift, clip
+        for (int i = 0; i < 8; i++) ob[base + i * pitch] = (uint8_t)(min(max((int32_t)s[i], -128), 127) + 128);   // level shift, clip
     }
     __syncthreads();
     // the strips, 8 bytes (one block row) per thread and step

@@ -31,26 +31,31 @@ static const uint8_t k_unzig[64] = {
     0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
     35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
-/* ---- idct.go ---- */
-#define W1 2841
-#define W2 2676
-#define W3 2408
-#define W5 1609
-#define W6 1108
-#define W7 565
-#define R2 181
+/* ---- idct.go ----
+ * Go's int32 arithmetic wraps by definition; C's signed overflow is undefined, so the transform computes in uint32_t (which wraps) and
+ * goes through int32_t only for the arithmetic shifts. */
+#define W1 2841u
+#define W2 2676u
+#define W3 2408u
+#define W5 1609u
+#define W6 1108u
+#define W7 565u
+#define R2 181u
+
+static uint32_t asr(uint32_t v, int n) { return (uint32_t)((int32_t)v >> n); }
 
 static void idct(int32_t *src)
 {
     for (int y = 0; y < 8; y++) {
         int32_t *s = src + 8 * y;
         if (s[1] == 0 && s[2] == 0 && s[3] == 0 && s[4] == 0 && s[5] == 0 && s[6] == 0 && s[7] == 0) {
-            int32_t dc = (int32_t)((uint32_t)s[0] << 3);
+            const int32_t dc = (int32_t)((uint32_t)s[0] << 3);
             for (int i = 0; i < 8; i++) s[i] = dc;
             continue;
         }
-        int32_t x0 = (int32_t)((uint32_t)s[0] << 11) + 128, x1 = (int32_t)((uint32_t)s[4] << 11), x2 = s[6], x3 = s[2], x4 = s[1], x5 = s[7], x6 = s[5], x7 = s[3];
-        int32_t x8 = W7 * (x4 + x5);
+        uint32_t x0 = ((uint32_t)s[0] << 11) + 128, x1 = (uint32_t)s[4] << 11, x2 = (uint32_t)s[6], x3 = (uint32_t)s[2], x4 = (uint32_t)s[1],
+                 x5 = (uint32_t)s[7], x6 = (uint32_t)s[5], x7 = (uint32_t)s[3];
+        uint32_t x8 = W7 * (x4 + x5);
         x4 = x8 + (W1 - W7) * x4;
         x5 = x8 - (W1 + W7) * x5;
         x8 = W3 * (x6 + x7);
@@ -69,25 +74,26 @@ static void idct(int32_t *src)
         x8 -= x3;
         x3 = x0 + x2;
         x0 -= x2;
-        x2 = (R2 * (x4 + x5) + 128) >> 8;
-        x4 = (R2 * (x4 - x5) + 128) >> 8;
-        s[0] = (x7 + x1) >> 8; s[1] = (x3 + x2) >> 8; s[2] = (x0 + x4) >> 8; s[3] = (x8 + x6) >> 8;
-        s[4] = (x8 - x6) >> 8; s[5] = (x0 - x4) >> 8; s[6] = (x3 - x2) >> 8; s[7] = (x7 - x1) >> 8;
+        x2 = asr(R2 * (x4 + x5) + 128, 8);
+        x4 = asr(R2 * (x4 - x5) + 128, 8);
+        s[0] = (int32_t)asr(x7 + x1, 8); s[1] = (int32_t)asr(x3 + x2, 8); s[2] = (int32_t)asr(x0 + x4, 8); s[3] = (int32_t)asr(x8 + x6, 8);
+        s[4] = (int32_t)asr(x8 - x6, 8); s[5] = (int32_t)asr(x0 - x4, 8); s[6] = (int32_t)asr(x3 - x2, 8); s[7] = (int32_t)asr(x7 - x1, 8);
     }
     for (int x = 0; x < 8; x++) {
         int32_t *s = src + x;
-        int32_t y0 = (int32_t)((uint32_t)s[0] << 8) + 8192, y1 = (int32_t)((uint32_t)s[32] << 8), y2 = s[48], y3 = s[16], y4 = s[8], y5 = s[56], y6 = s[40], y7 = s[24];
-        int32_t y8 = W7 * (y4 + y5) + 4;
-        y4 = (y8 + (W1 - W7) * y4) >> 3;
-        y5 = (y8 - (W1 + W7) * y5) >> 3;
+        uint32_t y0 = ((uint32_t)s[0] << 8) + 8192, y1 = (uint32_t)s[32] << 8, y2 = (uint32_t)s[48], y3 = (uint32_t)s[16], y4 = (uint32_t)s[8],
+                 y5 = (uint32_t)s[56], y6 = (uint32_t)s[40], y7 = (uint32_t)s[24];
+        uint32_t y8 = W7 * (y4 + y5) + 4;
+        y4 = asr(y8 + (W1 - W7) * y4, 3);
+        y5 = asr(y8 - (W1 + W7) * y5, 3);
         y8 = W3 * (y6 + y7) + 4;
-        y6 = (y8 - (W3 - W5) * y6) >> 3;
-        y7 = (y8 - (W3 + W5) * y7) >> 3;
+        y6 = asr(y8 - (W3 - W5) * y6, 3);
+        y7 = asr(y8 - (W3 + W5) * y7, 3);
         y8 = y0 + y1;
         y0 -= y1;
         y1 = W6 * (y3 + y2) + 4;
-        y2 = (y1 - (W2 + W6) * y2) >> 3;
-        y3 = (y1 + (W2 - W6) * y3) >> 3;
+        y2 = asr(y1 - (W2 + W6) * y2, 3);
+        y3 = asr(y1 + (W2 - W6) * y3, 3);
         y1 = y4 + y6;
         y4 -= y6;
         y6 = y5 + y7;
@@ -96,10 +102,10 @@ static void idct(int32_t *src)
         y8 -= y3;
         y3 = y0 + y2;
         y0 -= y2;
-        y2 = (R2 * (y4 + y5) + 128) >> 8;
-        y4 = (R2 * (y4 - y5) + 128) >> 8;
-        s[0] = (y7 + y1) >> 14; s[8] = (y3 + y2) >> 14; s[16] = (y0 + y4) >> 14; s[24] = (y8 + y6) >> 14;
-        s[32] = (y8 - y6) >> 14; s[40] = (y0 - y4) >> 14; s[48] = (y3 - y2) >> 14; s[56] = (y7 - y1) >> 14;
+        y2 = asr(R2 * (y4 + y5) + 128, 8);
+        y4 = asr(R2 * (y4 - y5) + 128, 8);
+        s[0] = (int32_t)asr(y7 + y1, 14); s[8] = (int32_t)asr(y3 + y2, 14); s[16] = (int32_t)asr(y0 + y4, 14); s[24] = (int32_t)asr(y8 + y6, 14);
+        s[32] = (int32_t)asr(y8 - y6, 14); s[40] = (int32_t)asr(y0 - y4, 14); s[48] = (int32_t)asr(y3 - y2, 14); s[56] = (int32_t)asr(y7 - y1, 14);
     }
 }
 
@@ -277,7 +283,7 @@ int ipxo_jpeg_decode(const uint8_t *data, size_t len, ipxo_decoded *out, int16_t
                             memset(b, 0, sizeof b);
                             int t = decode_huff(&br, &hf[0][td[c]]);
                             if (br.err || t > 16) { ipxo_decoded_free(out); return -1; }
-                            dc[c] += receive_extend(&br, t);
+                            dc[c] = (int32_t)((uint32_t)dc[c] + (uint32_t)receive_extend(&br, t));   /* Go's int32 wraps */
                             if (dc[c] < -32768 || dc[c] > 32767) out->dc_wide = 1;
                             b[0] = dc[c];
                             for (int zig = 1; zig < 64; zig++) {
@@ -298,7 +304,7 @@ int ipxo_jpeg_decode(const uint8_t *data, size_t len, ipxo_decoded *out, int16_t
                                 for (int z = 0; z < 64; z++) coefs[nblk * 64 + z] = (int16_t)b[z];
                             nblk++;
                             const uint16_t *qt = quant[ctq[c]];
-                            for (int zig = 0; zig < 64; zig++) b[k_unzig[zig]] *= qt[zig];
+                            for (int zig = 0; zig < 64; zig++) b[k_unzig[zig]] = (int32_t)((uint32_t)b[k_unzig[zig]] * (uint32_t)qt[zig]);
                             idct(b);
                             uint8_t *dst = c == 0 ? out->y : (c == 1 ? out->cb : out->cr);
                             const int stride = c == 0 ? out->ystride : out->cstride;
@@ -570,7 +576,7 @@ static void d_sos(jdec *d, const uint8_t *s, size_t n)
                             const int value = d_huff(d, &d->hf[0][td[i]]);
                             if (d->err) return;
                             if (value > 16) { d_fail(d, -2); return; }            /* UnsupportedError("excessive DC component") */
-                            dc[ci] += d_receive_extend(d, value);
+                            dc[ci] = (int32_t)((uint32_t)dc[ci] + (uint32_t)d_receive_extend(d, value));
                             if (d->err) return;
                             if (dc[ci] < -32768 || dc[ci] > 32767) d->out->dc_wide = 1;
                             b[0] = (int32_t)((uint32_t)dc[ci] << al);
