@@ -35,6 +35,17 @@ def _rect(r):
     return r if isinstance(r, Rect) else Rect(*[int(v) for v in r])
 
 
+def _bytes_array(files):
+    """ipx_bytes[max(n, 1)] over the byte strings in `files`; the array keeps them alive"""
+    keep = [bytes(f) for f in files]
+    arr = (_lib.Bytes * max(len(keep), 1))()
+    for i, f in enumerate(keep):
+        arr[i].data = C.cast(C.c_char_p(f), C.c_void_p)
+        arr[i].len = len(f)
+    arr._keep = keep
+    return arr
+
+
 def _frame(a):
     a = np.ascontiguousarray(a, dtype=np.uint8)
     if a.ndim != 3 or a.shape[2] != 4:
@@ -260,60 +271,53 @@ class Plan:
                                                 p("watermark"), i.wm_bytes))
         return out
 
+    def _run_streams(self, entry, n, want, copy, args, status=None):
+        """One compressed-out entry: output arrays for the wanted outputs the plan has, the call (args go between the plan and the
+        arrays), then per output the streams (their lengths when copy=False; None for a slot the entry left unpublished); the
+        result is freed."""
+        i = self.info
+        arrs = {k: (_lib.Bytes * max(n, 1))() for k, present in (("resize", i.resize_bytes), ("thumbnail", i.thumb_bytes),
+                                                                  ("watermark", i.wm_bytes)) if k in want and present}
+        res = C.c_void_p()
+        extra = () if status is None else (status,)
+        _check(entry(self.ctx.handle, self.handle, n, *args, arrs.get("resize"), arrs.get("thumbnail"), arrs.get("watermark"), *extra,
+                     C.byref(res)))
+        out = {k: [(C.string_at(a[j].data, a[j].len) if copy else a[j].len) if a[j].data else None for j in range(n)]
+               for k, a in arrs.items()}
+        lib().ipx_jpeg_result_free(self.ctx.handle, res)
+        return out
+
+    def _run_files(self, entry, files, want, copy, args=()):
+        """A file-in entry: ({operator: [bytes | None] * n}, status list)."""
+        n = len(files)
+        status = (C.c_int * max(n, 1))()
+        out = self._run_streams(entry, n, want, copy, (_bytes_array(files),) + args, status)
+        return out, list(status)[:n]
+
     def run_host_jpeg(self, frames, quality=85, want=("resize", "thumbnail", "watermark"), copy=True):
         """frames: n x H x W x 4 uint8 (host, ideally pinned) -> {operator: [jpeg bytes] * n}: operators and jpeg.Encode on
         the GPU, only the streams come back.  copy=False: lengths only (the streams are released unread; for timing)."""
         frames = np.ascontiguousarray(frames, dtype=np.uint8)
-        n = frames.shape[0]
-        i = self.info
-        arrs = {}
-        for k, present in (("resize", i.resize_bytes), ("thumbnail", i.thumb_bytes), ("watermark", i.wm_bytes)):
-            if k in want and present:
-                arrs[k] = (_lib.Bytes * n)()
-        res = C.c_void_p()
-        _check(lib().ipx_plan_run_host_jpeg(self.ctx.handle, self.handle, n, frames.ctypes.data, self._sw * 4, self._sw * self._sh * 4,
-                                            int(quality), arrs.get("resize"), arrs.get("thumbnail"), arrs.get("watermark"), C.byref(res)))
-        out = {}
-        for k, a in arrs.items():
-            out[k] = [C.string_at(a[j].data, a[j].len) if copy else a[j].len for j in range(n)]
-        lib().ipx_jpeg_result_free(self.ctx.handle, res)
-        return out
+        return self._run_streams(lib().ipx_plan_run_host_jpeg, frames.shape[0], want, copy,
+                                 (frames.ctypes.data, self._sw * 4, self._sw * self._sh * 4, int(quality)))
 
     def run_host_paletted_gif(self, index, palettes, quality=85, want=("resize", "thumbnail", "watermark"), copy=True):
         """Decoded GIF frames (index: n x H x W uint8, palettes: n x 256 x 4 uint8, host) -> {operator: [bytes] * n}: operators,
         gif.Encode of resize / thumbnail and jpeg.Encode (at `quality`) of the watermark on the GPU; only the streams come back."""
         index = np.ascontiguousarray(index, dtype=np.uint8)
         palettes = np.ascontiguousarray(palettes, dtype=np.uint8)
-        n, i = index.shape[0], self.info
+        n = index.shape[0]
         assert index.shape[1:] == (self._sh, self._sw) and palettes.shape == (n, 256, 4)
-        arrs = {}
-        for k, present in (("resize", i.resize_bytes), ("thumbnail", i.thumb_bytes), ("watermark", i.wm_bytes)):
-            if k in want and present:
-                arrs[k] = (_lib.Bytes * n)()
-        res = C.c_void_p()
-        _check(lib().ipx_plan_run_host_paletted_gif(self.ctx.handle, self.handle, n, index.ctypes.data, self._sw, self._sw * self._sh,
-                                                    palettes.ctypes.data, int(quality), arrs.get("resize"), arrs.get("thumbnail"),
-                                                    arrs.get("watermark"), C.byref(res)))
-        out = {k: [C.string_at(a[j].data, a[j].len) if copy else a[j].len for j in range(n)] for k, a in arrs.items()}
-        lib().ipx_jpeg_result_free(self.ctx.handle, res)
-        return out
+        return self._run_streams(lib().ipx_plan_run_host_paletted_gif, n, want, copy,
+                                 (index.ctypes.data, self._sw, self._sw * self._sh, palettes.ctypes.data, int(quality)))
 
     def run_host_png(self, frames, want=("resize", "thumbnail", "watermark"), copy=True):
         """frames: n x H x W x 4 uint8 (host) -> {operator: [png bytes] * n}: operators and png.Encode of every output on the GPU, only
         the streams come back.  copy=False: lengths only (the streams are released unread; for timing)."""
         frames = np.ascontiguousarray(frames, dtype=np.uint8)
-        n, i = frames.shape[0], self.info
         assert frames.shape[1:] == (self._sh, self._sw, 4)
-        arrs = {}
-        for k, present in (("resize", i.resize_bytes), ("thumbnail", i.thumb_bytes), ("watermark", i.wm_bytes)):
-            if k in want and present:
-                arrs[k] = (_lib.Bytes * n)()
-        res = C.c_void_p()
-        _check(lib().ipx_plan_run_host_png(self.ctx.handle, self.handle, n, frames.ctypes.data, self._sw * 4, self._sw * self._sh * 4,
-                                           arrs.get("resize"), arrs.get("thumbnail"), arrs.get("watermark"), C.byref(res)))
-        out = {k: [C.string_at(a[j].data, a[j].len) if copy else a[j].len for j in range(n)] for k, a in arrs.items()}
-        lib().ipx_jpeg_result_free(self.ctx.handle, res)
-        return out
+        return self._run_streams(lib().ipx_plan_run_host_png, frames.shape[0], want, copy,
+                                 (frames.ctypes.data, self._sw * 4, self._sw * self._sh * 4))
 
     def run_host_ycbcr_jpeg(self, y, cb, cr, ratio, quality=85, want=("resize", "thumbnail", "watermark"), copy=True):
         """Decoded JPEG planes (host) -> {operator: [jpeg bytes] * n}; see run_host_jpeg."""
@@ -321,85 +325,21 @@ class Plan:
         n, h, w = y.shape
         assert (w, h) == (self._sw, self._sh) and cb.shape == cr.shape and cb.shape[0] == n
         b = _lib.YCbCrBatch(y.ctypes.data, cb.ctypes.data, cr.ctypes.data, w, cb.shape[2], h * w, cb.shape[1] * cb.shape[2], int(ratio))
-        i = self.info
-        arrs = {}
-        for k, present in (("resize", i.resize_bytes), ("thumbnail", i.thumb_bytes), ("watermark", i.wm_bytes)):
-            if k in want and present:
-                arrs[k] = (_lib.Bytes * n)()
-        res = C.c_void_p()
-        _check(lib().ipx_plan_run_host_ycbcr_jpeg(self.ctx.handle, self.handle, n, C.byref(b), int(quality), arrs.get("resize"),
-                                                  arrs.get("thumbnail"), arrs.get("watermark"), C.byref(res)))
-        out = {k: [C.string_at(a[j].data, a[j].len) if copy else a[j].len for j in range(n)] for k, a in arrs.items()}
-        lib().ipx_jpeg_result_free(self.ctx.handle, res)
-        return out
+        return self._run_streams(lib().ipx_plan_run_host_ycbcr_jpeg, n, want, copy, (C.byref(b), int(quality)))
 
     def run_jpeg_jpeg(self, files, quality=85, want=("resize", "thumbnail", "watermark"), copy=True):
         """JPEG byte strings in -> ({operator: [jpeg bytes | None] * n}, status list): decode, operators, encode on the GPU."""
-        n = len(files)
-        keep = [bytes(f) for f in files]
-        arr = (_lib.Bytes * n)()
-        for j, f in enumerate(keep):
-            arr[j].data = C.cast(C.c_char_p(f), C.c_void_p)
-            arr[j].len = len(f)
-        i = self.info
-        outs = {}
-        for k, present in (("resize", i.resize_bytes), ("thumbnail", i.thumb_bytes), ("watermark", i.wm_bytes)):
-            if k in want and present:
-                outs[k] = (_lib.Bytes * n)()
-        status = (C.c_int * n)()
-        res = C.c_void_p()
-        _check(lib().ipx_plan_run_jpeg_jpeg(self.ctx.handle, self.handle, n, arr, int(quality), outs.get("resize"), outs.get("thumbnail"),
-                                            outs.get("watermark"), status, C.byref(res)))
-        out = {k: [(C.string_at(a[j].data, a[j].len) if copy else a[j].len) if a[j].data else None for j in range(n)] for k, a in outs.items()}
-        if res:
-            lib().ipx_jpeg_result_free(self.ctx.handle, res)
-        return out, list(status)
+        return self._run_files(lib().ipx_plan_run_jpeg_jpeg, files, want, copy, (int(quality),))
 
     def run_gif_gif(self, files, quality=85, want=("resize", "thumbnail", "watermark"), copy=True):
         """GIF byte strings in -> ({operator: [bytes | None] * n}, status list): gif.Decode, operators, gif.Encode of resize / thumbnail
         and jpeg.Encode (at `quality`) of the watermark on the GPU."""
-        n = len(files)
-        keep = [bytes(f) for f in files]
-        arr = (_lib.Bytes * max(n, 1))()
-        for j, f in enumerate(keep):
-            arr[j].data = C.cast(C.c_char_p(f), C.c_void_p)
-            arr[j].len = len(f)
-        i = self.info
-        outs = {}
-        for k, present in (("resize", i.resize_bytes), ("thumbnail", i.thumb_bytes), ("watermark", i.wm_bytes)):
-            if k in want and present:
-                outs[k] = (_lib.Bytes * max(n, 1))()
-        status = (C.c_int * max(n, 1))()
-        res = C.c_void_p()
-        _check(lib().ipx_plan_run_gif_gif(self.ctx.handle, self.handle, n, arr, int(quality), outs.get("resize"), outs.get("thumbnail"),
-                                          outs.get("watermark"), status, C.byref(res)))
-        out = {k: [(C.string_at(a[j].data, a[j].len) if copy else a[j].len) if a[j].data else None for j in range(n)] for k, a in outs.items()}
-        if res:
-            lib().ipx_jpeg_result_free(self.ctx.handle, res)
-        return out, list(status)[:n]
+        return self._run_files(lib().ipx_plan_run_gif_gif, files, want, copy, (int(quality),))
 
     def run_png_png(self, files, want=("resize", "thumbnail", "watermark"), copy=True):
         """PNG byte strings of any kind in -> ({operator: [png bytes | None] * n}, status list): png.Decode, operators and png.Encode of
         every output on the GPU."""
-        n = len(files)
-        keep = [bytes(f) for f in files]
-        arr = (_lib.Bytes * max(n, 1))()
-        for j, f in enumerate(keep):
-            arr[j].data = C.cast(C.c_char_p(f), C.c_void_p)
-            arr[j].len = len(f)
-        i = self.info
-        outs = {}
-        for k, present in (("resize", i.resize_bytes), ("thumbnail", i.thumb_bytes), ("watermark", i.wm_bytes)):
-            if k in want and present:
-                outs[k] = (_lib.Bytes * max(n, 1))()
-        status = (C.c_int * max(n, 1))()
-        res = C.c_void_p()
-        _check(lib().ipx_plan_run_png_png(self.ctx.handle, self.handle, n, arr, outs.get("resize"), outs.get("thumbnail"),
-                                          outs.get("watermark"), status, C.byref(res)))
-        out = {k: [(C.string_at(a[j].data, a[j].len) if copy else a[j].len) if a[j].data else None for j in range(n)] for k, a in outs.items()}
-        if res:
-            lib().ipx_jpeg_result_free(self.ctx.handle, res)
-        return out, list(status)[:n]
+        return self._run_files(lib().ipx_plan_run_png_png, files, want, copy)
 
     def run_dev_nrgba(self, n, src_ptr, resize_ptr=None, thumb_ptr=None, wm_ptr=None, stream=None):
         """*image.NRGBA frames (tightly packed) resident in HBM (ipx_plan_run_dev_nrgba)"""
@@ -735,11 +675,7 @@ class Context:
         """image.Decode of a batch of JPEG byte strings on the GPU.  -> (info, status list); info = dict(w, h, ratio, ystride,
         cstride, y, cb, cr) with the planes as n x rows x stride arrays (download=True) or device pointers + `free()`."""
         n = len(files)
-        keep = [bytes(f) for f in files]
-        arr = (_lib.Bytes * n)()
-        for i, f in enumerate(keep):
-            arr[i].data = C.cast(C.c_char_p(f), C.c_void_p)
-            arr[i].len = len(f)
+        arr = _bytes_array(files)
         cw, chh = C.c_int(w), C.c_int(h)
         b = _lib.YCbCrBatch()
         status = (C.c_int * n)()
@@ -771,11 +707,7 @@ class Context:
         stride, index, palettes) with index as n x h x w and palettes as n x 256 x 4 uint8 arrays (download=True), or the device
         batch (PalettedBatch) + `free()`; None when no file was decodable."""
         n = len(files)
-        keep = [bytes(f) for f in files]
-        arr = (_lib.Bytes * max(n, 1))()
-        for i, f in enumerate(keep):
-            arr[i].data = C.cast(C.c_char_p(f), C.c_void_p)
-            arr[i].len = len(f)
+        arr = _bytes_array(files)
         cw, chh = C.c_int(w), C.c_int(h)
         b = _lib.PalettedBatch()
         status = (C.c_int * max(n, 1))()
@@ -804,11 +736,7 @@ class Context:
         with pix as n x h x (w * bytes per pixel) uint8 (Go's Pix rows) and palettes as n x 256 x 4 uint8 (PNG_PALETTED) or None
         (download=True), or the device batch (PngBatch) + `free()`; None when no file was decodable."""
         n = len(files)
-        keep = [bytes(f) for f in files]
-        arr = (_lib.Bytes * max(n, 1))()
-        for i, f in enumerate(keep):
-            arr[i].data = C.cast(C.c_char_p(f), C.c_void_p)
-            arr[i].len = len(f)
+        arr = _bytes_array(files)
         cw, chh, ck = C.c_int(w), C.c_int(h), C.c_int(kind)
         b = _lib.PngBatch()
         status = (C.c_int * max(n, 1))()
@@ -977,11 +905,7 @@ class Pool:
         """JPEG byte strings of sw x sh images in -> PoolJob; wait() gives ({operator: [bytes | None]}, status list)."""
         n = len(files)
         ops, keep = self._ops(sw, sh, resize, thumbnail, glyphs, col, watermark)
-        blobs = [bytes(f) for f in files]
-        arr = (_lib.Bytes * max(1, n))()
-        for i, f in enumerate(blobs):
-            arr[i].data = C.cast(C.c_char_p(f), C.c_void_p)
-            arr[i].len = len(f)
+        arr = _bytes_array(files)
         status = (C.c_int32 * max(1, n))()
         outs = {}
         j = _lib.Job()
@@ -995,7 +919,7 @@ class Pool:
         if ops.do_watermark:
             outs["watermark"] = (_lib.Bytes * max(1, n))()
             j.wm_jpeg = outs["watermark"]
-        return PoolJob(self, j, {"blobs": blobs, "files": arr, "status": status, "glyphs": keep}, outs, n)
+        return PoolJob(self, j, {"files": arr, "status": status, "glyphs": keep}, outs, n)
 
 
 def jpeg_entropy_encode(coefs, w, h, quality=85):

@@ -267,8 +267,7 @@ int gif_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w, int 
     gif_write_header(w, h, hdr);
     std::vector<uint32_t> hl(n);
     std::vector<unsigned long long> ob(n);
-    // every way out of this function waits for the stream: the queued copies read and write the buffers above
-    struct SyncOnExit { hipStream_t s; ~SyncOnExit() { (void)hipStreamSynchronize(s); } } sync_on_exit{s};
+    StreamSync sync{s};                           // after the host buffers above: the queued copies read and write them
     AsyncFree mem{s, {}};
     const size_t npix = (size_t)w * h, region = align256(gif_stream_bound(w, h));
     uint8_t *didx, *dout, *dhdr;
@@ -384,69 +383,35 @@ int ipx_plan_run_host_paletted_gif(ipx_ctx *ctx, const ipx_plan *pl, int n, cons
                   pl->p.sw, pl->p.sh, stride);
         return IPX_ERR_UNSUPPORTED;
     }
-    const ipx_plan_info &in = pl->info;
     const int sw = pl->p.sw, sh = pl->p.sh;
-    // every frame handed to gif.Encode must fit its limits: checked before anything runs
-    if ((resize_out && in.resize_bytes && (in.resize_w >= 1 << 16 || in.resize_h >= 1 << 16)) ||
-        (thumb_out && in.thumb_bytes && (in.thumb_w >= 1 << 16 || in.thumb_h >= 1 << 16))) {
-        set_error("gif: image is too large to encode");
-        return IPX_ERR_INVALID;
-    }
+    const PlanOutputs outs(pl, resize_out, thumb_out, wm_out, Codec::Gif, Codec::Gif, Codec::Jpeg);
+    const int rc0 = outs.check_gif();             // every frame handed to gif.Encode must fit its limits: checked before anything runs
+    if (rc0) return rc0;
     if (n == 0) return IPX_OK;
     const size_t fsrc = align256((size_t)sw * sh);
-    const size_t fres = resize_out ? align256(in.resize_bytes) : 0, fth = thumb_out ? align256(in.thumb_bytes) : 0;
-    const size_t fwm = wm_out ? align256(in.wm_bytes) : 0;
-    const size_t cwm = fwm ? align256(ipx_jpeg_coef_count(sw, sh) * 2) : 0;
-    const size_t per_frame = fsrc + 1024 + fres + fth + fwm + cwm;
+    const size_t per_frame = fsrc + 1024 + outs.frame_bytes();
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n, (size_t)env_int("IPX_HOST_CHUNK_GIF", 64),
                                                                  ((size_t)1 << 30) / per_frame}));
-    // the blocks of finished chunks go back to the cache on every way out but success
-    struct ResultGuard {
-        ipx_ctx *ctx;
-        ipx_jpeg_result *r;
-        ~ResultGuard() { ipx_jpeg_result_free(ctx, r); }
-    } res{ctx, new ipx_jpeg_result};
+    ResultOwner res(ctx);                         // the blocks of finished chunks go back to the cache on every way out but success
     LaneLease lane(ctx);
     hipStream_t s = lane->stream;
-    std::vector<size_t> offs(chunk), lens(chunk);
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const int m = std::min(chunk, n - i0);
-        struct SyncOnExit { hipStream_t s; ~SyncOnExit() { (void)hipStreamSynchronize(s); } } sync_on_exit{s};
+        StreamSync sync{s};
         AsyncFree mem{s, {}};
-        uint8_t *didx, *dpal, *dres = nullptr, *dth = nullptr, *dwm = nullptr;
+        uint8_t *didx, *dpal, *dout = nullptr;
         IPX_HIP(mem.get(&didx, fsrc * m));
         IPX_HIP(mem.get(&dpal, (size_t)1024 * m));
-        if (fres) IPX_HIP(mem.get(&dres, fres * m));
-        if (fth) IPX_HIP(mem.get(&dth, fth * m));
-        if (fwm) IPX_HIP(mem.get(&dwm, fwm * m));
+        if (outs.frame_bytes()) IPX_HIP(mem.get(&dout, outs.frame_bytes() * m));
         for (int i = 0; i < m; i++)
             IPX_HIP(hipMemcpy2DAsync(didx + fsrc * i, sw, index + frame_stride * (size_t)(i0 + i), stride, sw, sh, hipMemcpyHostToDevice, s));
         IPX_HIP(hipMemcpyAsync(dpal, palettes + (size_t)1024 * i0, (size_t)1024 * m, hipMemcpyHostToDevice, s));
-        int rc = ipx_plan_run_dev_paletted(ctx, s, pl, m, didx, sw, fsrc, dpal, dres, fres, dth, fth, dwm, fwm);
+        const PlanOutputs::Frames f = outs.place(dout, m);
+        int rc = ipx_plan_run_dev_paletted(ctx, s, pl, m, didx, sw, fsrc, dpal, f.dev[0], outs.o[0].fs, f.dev[1], outs.o[1].fs, f.dev[2], outs.o[2].fs);
+        if (!rc) rc = encode_outputs(ctx, s, outs, f, m, i0, quality, nullptr, res);
         if (rc) return rc;
-        struct Out { uint8_t *dev; size_t fs; int w, h; ipx_bytes *dst; };
-        const Out gifs[2] = {{dres, fres, in.resize_w, in.resize_h, resize_out}, {dth, fth, in.thumb_w, in.thumb_h, thumb_out}};
-        for (const Out &o : gifs) {
-            if (!o.dev || o.w <= 0 || o.h <= 0) continue;
-            uint8_t *blob = nullptr;
-            rc = gif_encode_core(ctx, s, o.dev, o.w, o.h, o.w * 4, o.fs, m, &blob, offs.data(), lens.data());
-            if (rc) return rc;
-            res.r->blobs.push_back(blob);
-            for (int i = 0; i < m; i++) { o.dst[i0 + i].data = blob + offs[i]; o.dst[i0 + i].len = lens[i]; }
-        }
-        if (dwm) {
-            int16_t *dcoef;
-            IPX_HIP(mem.get(&dcoef, cwm * m));
-            const JpegEncSet set{dcoef, dwm, sw, sh, sw * 4, fwm, offs.data(), lens.data()};
-            uint8_t *blob = nullptr;
-            rc = jpeg_encode_sets(ctx, s, &set, 1, m, quality, &blob);
-            if (rc) return rc;
-            if (blob) res.r->blobs.push_back(blob);
-            for (int i = 0; i < m; i++) { wm_out[i0 + i].data = blob + offs[i]; wm_out[i0 + i].len = lens[i]; }
-        }
     }
-    *result = res.r;
-    res.r = nullptr;
+    *result = res.release();
     return IPX_OK;
 }
 IPX_CATCH_STATUS

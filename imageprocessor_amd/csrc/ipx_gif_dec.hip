@@ -367,86 +367,49 @@ int ipx_plan_run_gif_gif(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_byte
     IPX_ENTER(ctx);
     if (!pl || n < 0 || !files || !status || !result) { set_error("ipx_plan_run_gif_gif: bad argument"); return IPX_ERR_INVALID; }
     *result = nullptr;
-    const ipx_plan_info &in = pl->info;
     const int sw = pl->p.sw, sh = pl->p.sh;
-    if ((resize_out && in.resize_bytes && (in.resize_w >= 1 << 16 || in.resize_h >= 1 << 16)) ||
-        (thumb_out && in.thumb_bytes && (in.thumb_w >= 1 << 16 || in.thumb_h >= 1 << 16))) {
-        set_error("gif: image is too large to encode");
-        return IPX_ERR_INVALID;
-    }
-    for (int i = 0; i < n; i++) {
-        for (ipx_bytes *o : {resize_out, thumb_out, wm_out})
-            if (o) o[i] = ipx_bytes{nullptr, 0};
-    }
+    const PlanOutputs outs(pl, resize_out, thumb_out, wm_out, Codec::Gif, Codec::Gif, Codec::Jpeg);
+    int rc = outs.check_gif();
+    if (rc) return rc;
+    outs.clear(n);
     if (n == 0) return IPX_OK;
     if (!frame_span_ok(sw, sh, sw, 1)) {
         for (int i = 0; i < n; i++) status[i] = IPX_ERR_UNSUPPORTED;
         return IPX_OK;
     }
     const size_t fsrc = align256((size_t)sw * sh);
-    const size_t fres = resize_out ? align256(in.resize_bytes) : 0, fth = thumb_out ? align256(in.thumb_bytes) : 0;
-    const size_t fwm = wm_out ? align256(in.wm_bytes) : 0;
-    const size_t cwm = fwm ? align256(ipx_jpeg_coef_count(sw, sh) * 2) : 0;
-    const size_t per_frame = fsrc + 1024 + fres + fth + fwm + cwm;
+    const size_t per_frame = fsrc + 1024 + outs.frame_bytes();
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n, (size_t)env_int("IPX_HOST_CHUNK_GIF", 64),
                                                                  ((size_t)1 << 30) / per_frame}));
-    struct ResultGuard {
-        ipx_ctx *ctx;
-        ipx_jpeg_result *r;
-        ~ResultGuard() { ipx_jpeg_result_free(ctx, r); }
-    } res{ctx, new ipx_jpeg_result};
+    ResultOwner res(ctx);
     LaneLease lane(ctx);
     hipStream_t s = lane->stream;
-    std::vector<size_t> offs(chunk), lens(chunk);
     std::vector<GifFileInfo> info(chunk);
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const int m = std::min(chunk, n - i0);
         int bw = sw, bh = sh;
-        int rc = gif_parse_batch(files + i0, m, &bw, &bh, info, status + i0);
+        rc = gif_parse_batch(files + i0, m, &bw, &bh, info, status + i0);
         if (rc) return rc;
         bool any = false;
         for (int i = 0; i < m; i++) any |= status[i0 + i] == IPX_OK;
         if (!any) continue;
-        struct SyncOnExit { hipStream_t s; ~SyncOnExit() { (void)hipStreamSynchronize(s); } } sync_on_exit{s};
+        StreamSync sync{s};
         AsyncFree mem{s, {}};
-        uint8_t *didx, *dpal, *dres = nullptr, *dth = nullptr, *dwm = nullptr;
+        uint8_t *didx, *dpal, *dout = nullptr;
         IPX_HIP(mem.get(&didx, fsrc * m));
         IPX_HIP(mem.get(&dpal, (size_t)1024 * m));
-        if (fres) IPX_HIP(mem.get(&dres, fres * m));
-        if (fth) IPX_HIP(mem.get(&dth, fth * m));
-        if (fwm) IPX_HIP(mem.get(&dwm, fwm * m));
+        if (outs.frame_bytes()) IPX_HIP(mem.get(&dout, outs.frame_bytes() * m));
         rc = gif_decode_files(ctx, s, files + i0, m, info, didx, fsrc, dpal, status + i0);
         if (rc) return rc;
         any = false;
         for (int i = 0; i < m; i++) any |= status[i0 + i] == IPX_OK;
         if (!any) continue;
-        rc = ipx_plan_run_dev_paletted(ctx, s, pl, m, didx, sw, fsrc, dpal, dres, fres, dth, fth, dwm, fwm);
+        const PlanOutputs::Frames f = outs.place(dout, m);
+        rc = ipx_plan_run_dev_paletted(ctx, s, pl, m, didx, sw, fsrc, dpal, f.dev[0], outs.o[0].fs, f.dev[1], outs.o[1].fs, f.dev[2], outs.o[2].fs);
+        if (!rc) rc = encode_outputs(ctx, s, outs, f, m, i0, quality, status, res);
         if (rc) return rc;
-        struct Out { uint8_t *dev; size_t fs; int w, h; ipx_bytes *dst; };
-        const Out gifs[2] = {{dres, fres, in.resize_w, in.resize_h, resize_out}, {dth, fth, in.thumb_w, in.thumb_h, thumb_out}};
-        for (const Out &o : gifs) {
-            if (!o.dev || o.w <= 0 || o.h <= 0) continue;
-            uint8_t *blob = nullptr;
-            rc = gif_encode_core(ctx, s, o.dev, o.w, o.h, o.w * 4, o.fs, m, &blob, offs.data(), lens.data());
-            if (rc) return rc;
-            res.r->blobs.push_back(blob);
-            for (int i = 0; i < m; i++)
-                if (status[i0 + i] == IPX_OK) o.dst[i0 + i] = ipx_bytes{blob + offs[i], lens[i]};
-        }
-        if (dwm) {
-            int16_t *dcoef;
-            IPX_HIP(mem.get(&dcoef, cwm * m));
-            const JpegEncSet set{dcoef, dwm, sw, sh, sw * 4, fwm, offs.data(), lens.data()};
-            uint8_t *blob = nullptr;
-            rc = jpeg_encode_sets(ctx, s, &set, 1, m, quality, &blob);
-            if (rc) return rc;
-            if (blob) res.r->blobs.push_back(blob);
-            for (int i = 0; i < m; i++)
-                if (status[i0 + i] == IPX_OK) wm_out[i0 + i] = ipx_bytes{blob + offs[i], lens[i]};
-        }
     }
-    *result = res.r;
-    res.r = nullptr;
+    *result = res.release();
     return IPX_OK;
 }
 IPX_CATCH_STATUS

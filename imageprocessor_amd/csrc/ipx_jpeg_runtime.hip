@@ -8,6 +8,7 @@
 #include <string>
 #include <thread>
 
+#include "ipx_png.h"
 #include "ipx_runtime_internal.h"
 #include "ipx_threads.h"
 
@@ -124,8 +125,6 @@ int jpeg_encode_sets(ipx_ctx *ctx, hipStream_t s, const JpegEncSet *sets, int K,
 {
     *blob = nullptr;
     if (K <= 0 || K > 3 || n <= 0) return IPX_OK;
-    // every way out of this function waits for the stream: the queued copies read and write the vectors below
-    struct SyncOnExit { hipStream_t s; ~SyncOnExit() { (void)hipStreamSynchronize(s); } } sync_on_exit{s};
     const bool trace = env_int("IPX_DEBUG_J2J", 0) != 0;
     const auto te0 = std::chrono::steady_clock::now();
     auto ems = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - te0).count(); };
@@ -136,10 +135,6 @@ int jpeg_encode_sets(ipx_ctx *ctx, hipStream_t s, const JpegEncSet *sets, int K,
     jpeg_tables(quality, &t);
     uint32_t packed[1024];
     jpeg_huff_packed(packed);
-    AsyncFree mem{s, {}};
-    uint32_t *d_tab;
-    IPX_HIP(mem.get(&d_tab, sizeof packed));
-    IPX_HIP(hipMemcpyAsync(d_tab, packed, sizeof packed, hipMemcpyHostToDevice, s));
     struct Dev {
         int nblk = 0, max_chunks = 0;
         std::vector<uint8_t> hdr;
@@ -147,6 +142,13 @@ int jpeg_encode_sets(ipx_ctx *ctx, hipStream_t s, const JpegEncSet *sets, int K,
         unsigned long long *d_ubase = nullptr, *d_obase = nullptr;
         uint8_t *d_hdr = nullptr;
     } dv[3];
+    std::vector<uint32_t> tot((size_t)K * n), ubytes((size_t)K * n), ff((size_t)K * n);
+    std::vector<unsigned long long> ubase((size_t)K * n), obase((size_t)K * n);
+    StreamSync sync{s};                           // after the host buffers above: the queued copies read and write them
+    AsyncFree mem{s, {}};
+    uint32_t *d_tab;
+    IPX_HIP(mem.get(&d_tab, sizeof packed));
+    IPX_HIP(hipMemcpyAsync(d_tab, packed, sizeof packed, hipMemcpyHostToDevice, s));
     uint32_t *d_tot, *d_fftot;                    // [K][n]
     IPX_HIP(mem.get(&d_tot, (size_t)K * n * 4));
     IPX_HIP(mem.get(&d_fftot, (size_t)K * n * 4));
@@ -177,12 +179,10 @@ int jpeg_encode_sets(ipx_ctx *ctx, hipStream_t s, const JpegEncSet *sets, int K,
         IPX_HIP(launch_scan(d.d_len, d.nblk, n, d_tot + (size_t)k * n, s));
         if (trace) fprintf(stderr, "[ipx]   set %d (%dx%d) transform and sizes queued at %.2f ms\n", k, o.w, o.h, ems());
     }
-    std::vector<uint32_t> tot((size_t)K * n), ubytes((size_t)K * n), ff((size_t)K * n);
     IPX_HIP(hipMemcpyAsync(tot.data(), d_tot, (size_t)K * n * 4, hipMemcpyDeviceToHost, s));
     t_q1 = ems();
     IPX_HIP(hipStreamSynchronize(s));
     t_s1 = ems();
-    std::vector<unsigned long long> ubase((size_t)K * n), obase((size_t)K * n);
     unsigned long long utotal = 0;
     const int chunk = jpeg_chunk_bytes();
     size_t ff_words = 0;
@@ -236,7 +236,7 @@ int jpeg_encode_sets(ipx_ctx *ctx, hipStream_t s, const JpegEncSet *sets, int K,
         IPX_HIP(launch_jpeg_stuff(d_ustream, d.d_ubase, d.d_ubytes, d.max_chunks, n, d.d_ff, d.d_hdr, (int)d.hdr.size(), d.d_obase, d_ostream, s));
     }
     uint8_t *host = (uint8_t *)ipx_host_alloc(ctx, (size_t)ototal ? (size_t)ototal : 1);   // pinned: the download runs at link speed
-    if (!host) { (void)hipStreamSynchronize(s); return IPX_ERR_NOMEM; }
+    if (!host) return IPX_ERR_NOMEM;
     hipError_t e = hipMemcpyAsync(host, d_ostream, (size_t)ototal, hipMemcpyDeviceToHost, s);
     t_q3 = ems();
     { const hipError_t e2 = hipStreamSynchronize(s); if (e == hipSuccess) e = e2; }          // (ubase / obase are read by the queued copies until here)
@@ -268,6 +268,82 @@ void ipx_jpeg_result_free(ipx_ctx *ctx, ipx_jpeg_result *r)
 
 }  // extern "C"
 
+void ResultOwner::adopt(ipx_jpeg_result *o)
+{
+    if (!o) return;
+    r_->blobs.insert(r_->blobs.end(), o->blobs.begin(), o->blobs.end());
+    delete o;
+}
+
+PlanOutputs::PlanOutputs(const ipx_plan *pl, ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, Codec res, Codec thumb, Codec wm)
+{
+    const ipx_plan_info &in = pl->info;
+    o[0] = {resize_out, in.resize_w, in.resize_h, resize_out ? align256(in.resize_bytes) : 0, 0, res};
+    o[1] = {thumb_out, in.thumb_w, in.thumb_h, thumb_out ? align256(in.thumb_bytes) : 0, 0, thumb};
+    o[2] = {wm_out, in.wm_w, in.wm_h, wm_out ? align256(in.wm_bytes) : 0, 0, wm};
+    for (Output &x : o)
+        if (x.fs && x.codec == Codec::Jpeg) x.coef = align256(ipx_jpeg_coef_count(x.w, x.h) * 2);
+}
+
+PlanOutputs::Frames PlanOutputs::place(uint8_t *block, int chunk) const
+{
+    Frames f{};
+    size_t at = 0;
+    for (int k = 0; k < 3; k++) { f.dev[k] = o[k].fs ? block + at * chunk : nullptr; at += o[k].fs; }
+    for (int k = 0; k < 3; k++) { f.coef[k] = o[k].coef ? (int16_t *)(block + at * chunk) : nullptr; at += o[k].coef; }
+    return f;
+}
+
+void PlanOutputs::clear(int n) const
+{
+    for (const Output &x : o)
+        if (x.dst)
+            for (int i = 0; i < n; i++) x.dst[i] = ipx_bytes{nullptr, 0};
+}
+
+int PlanOutputs::check_gif() const
+{
+    for (const Output &x : o)
+        if (x.codec == Codec::Gif && x.fs && (x.w >= 1 << 16 || x.h >= 1 << 16)) { set_error("gif: image is too large to encode"); return IPX_ERR_INVALID; }
+    return IPX_OK;
+}
+
+int encode_outputs(ipx_ctx *ctx, hipStream_t s, const PlanOutputs &outs, const PlanOutputs::Frames &f, int m, int i0, int quality,
+                   const int *status, ResultOwner &res, const int *idx)
+{
+    std::vector<size_t> offs(3 * (size_t)m), lens(3 * (size_t)m);
+    auto publish = [&](const PlanOutputs::Output &o, const uint8_t *blob, const size_t *off, const size_t *len) {
+        for (int i = 0; i < m; i++) {
+            const int j = idx ? idx[i] : i0 + i;
+            if (!status || status[j] == IPX_OK) o.dst[j] = ipx_bytes{blob + off[i], len[i]};
+        }
+    };
+    JpegEncSet sets[3];
+    int who[3], K = 0;
+    for (int k = 0; k < 3; k++) {
+        const PlanOutputs::Output &o = outs.o[k];
+        if (!o.fs || o.w <= 0 || o.h <= 0) continue;
+        if (o.codec == Codec::Jpeg) {
+            sets[K] = JpegEncSet{f.coef[k], f.dev[k], o.w, o.h, o.w * 4, o.fs, offs.data() + (size_t)K * m, lens.data() + (size_t)K * m};
+            who[K++] = k;
+            continue;
+        }
+        uint8_t *blob = nullptr;
+        const int rc = (o.codec == Codec::Png ? png_encode_core : gif_encode_core)(ctx, s, f.dev[k], o.w, o.h, o.w * 4, o.fs, m, &blob,
+                                                                                   offs.data(), lens.data());
+        if (rc) return rc;
+        res.add(blob);
+        publish(o, blob, offs.data(), lens.data());
+    }
+    if (K == 0) return IPX_OK;
+    uint8_t *blob = nullptr;
+    const int rc = jpeg_encode_sets(ctx, s, sets, K, m, quality, &blob);
+    if (rc) return rc;
+    res.add(blob);
+    for (int k = 0; k < K; k++) publish(outs.o[who[k]], blob, sets[k].offs, sets[k].lens);
+    return IPX_OK;
+}
+
 // one implementation for both source kinds: ysrc == nullptr -> RGBA frames at src
 static int run_host_jpeg_impl(ipx_ctx *ctx, const ipx_plan *pl, int n, const uint8_t *src, int sstride, size_t src_frame_stride,
                               const ipx_ycbcr_batch *ysrc, int quality, ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out,
@@ -280,13 +356,9 @@ static int run_host_jpeg_impl(ipx_ctx *ctx, const ipx_plan *pl, int n, const uin
     const int ch = ysrc ? ((ysrc->ratio == IPX_YCBCR_420 || ysrc->ratio == IPX_YCBCR_440) ? (sh + 1) / 2 : sh) : 0;
     const size_t yb = ysrc ? align256((size_t)sw * sh) : 0, cbb = ysrc ? align256((size_t)cw * ch) : 0;
     const size_t fsrc = ysrc ? yb + 2 * cbb : align256((size_t)sw * sh * 4);
-    const size_t fres = resize_out ? align256(pl->info.resize_bytes) : 0, fth = thumb_out ? align256(pl->info.thumb_bytes) : 0;
-    const size_t fwm = wm_out ? align256(pl->info.wm_bytes) : 0;
-    const size_t cres = fres ? ipx_jpeg_coef_count(pl->info.resize_w, pl->info.resize_h) * 2 : 0;
-    const size_t cth = fth ? ipx_jpeg_coef_count(pl->info.thumb_w, pl->info.thumb_h) * 2 : 0;
-    const size_t cwm = fwm ? ipx_jpeg_coef_count(sw, sh) * 2 : 0;
-    const size_t ccoef[3] = {align256(cres), align256(cth), align256(cwm)};     // a coefficient buffer per output (jpeg_encode_sets)
-    const size_t per_frame = fsrc + fres + fth + fwm + ccoef[0] + ccoef[1] + ccoef[2];
+    const PlanOutputs outs(pl, resize_out, thumb_out, wm_out, Codec::Jpeg, Codec::Jpeg, Codec::Jpeg);
+    const size_t fres = outs.o[0].fs, fth = outs.o[1].fs, fwm = outs.o[2].fs;
+    const size_t per_frame = fsrc + outs.frame_bytes();
     // every lane runs its own host thread: upload, operators, the three encodes together (two small read-backs) --
     // the threads block independently, so copies and kernels of different chunks overlap
     std::vector<Lane *> lanes;
@@ -299,7 +371,7 @@ static int run_host_jpeg_impl(ipx_ctx *ctx, const ipx_plan *pl, int n, const uin
     int chunk = std::max(1, (n + 2 * nl - 1) / (2 * nl));
     chunk = (int)std::min<size_t>((size_t)chunk, std::max<size_t>(1, ctx->lane_bytes / per_frame));
     chunk = std::max(1, std::min(chunk, env_int("IPX_HOST_CHUNK_JPEG", 32)));
-    std::unique_ptr<ipx_jpeg_result> res(new ipx_jpeg_result);
+    ResultOwner res(ctx);
     std::mutex res_mu;
     std::atomic<int> next{0};
     std::atomic<int> status{IPX_OK};
@@ -307,15 +379,13 @@ static int run_host_jpeg_impl(ipx_ctx *ctx, const ipx_plan *pl, int n, const uin
     const int nchunks = (n + chunk - 1) / chunk;
     auto worker = [&](Lane *l) {
         if (hipSetDevice(ctx->device) != hipSuccess) { status = IPX_ERR_HIP; return; }
+        ResultOwner mine(ctx);                    // this lane's blocks, handed to `res` once its chunks are done
         int rc = lane_reserve(*l, per_frame * chunk + 256);
-        std::vector<size_t> offs(3 * (size_t)chunk), lens(3 * (size_t)chunk);
         for (int c = next.fetch_add(1); !rc && c < nchunks && status == IPX_OK; c = next.fetch_add(1)) {
             const int i0 = c * chunk, m = std::min(chunk, n - i0);
             uint8_t *dsrc = (uint8_t *)(((uintptr_t)l->dev + 255) & ~(uintptr_t)255);
-            uint8_t *dres = fres ? dsrc + fsrc * chunk : nullptr;
-            uint8_t *dth = fth ? dsrc + (fsrc + fres) * chunk : nullptr;
-            uint8_t *dwm = fwm ? dsrc + (fsrc + fres + fth) * chunk : nullptr;
-            uint8_t *cbase = dsrc + (fsrc + fres + fth + fwm) * chunk;
+            const PlanOutputs::Frames f = outs.place(dsrc + fsrc * chunk, chunk);
+            uint8_t *dres = f.dev[0], *dth = f.dev[1], *dwm = f.dev[2];
             hipError_t e = hipSuccess;
             if (ysrc) {
                 // planes of the chunk: [m x Y][m x Cb][m x Cr]
@@ -345,36 +415,12 @@ static int run_host_jpeg_impl(ipx_ctx *ctx, const ipx_plan *pl, int n, const uin
                 if (e != hipSuccess) { set_error("upload failed: %s", hipGetErrorString(e)); rc = IPX_ERR_HIP; break; }
                 rc = ipx_plan_run_dev(ctx, l->stream, pl, m, dsrc, sw * 4, fsrc, dres, fres, dth, fth, dwm, fwm);
             }
-            struct Out { uint8_t *dev; size_t fs; int w, h; ipx_bytes *dst; };
-            const Out outs[3] = {{dres, fres, pl->info.resize_w, pl->info.resize_h, resize_out},
-                                 {dth, fth, pl->info.thumb_w, pl->info.thumb_h, thumb_out},
-                                 {dwm, fwm, sw, sh, wm_out}};
-            if (rc) break;
-            JpegEncSet sets[3];
-            const Out *who[3];
-            int K = 0;
-            size_t cat = 0;
-            for (int k = 0; k < 3; k++) {
-                const Out &o = outs[k];
-                if (o.dev && o.w > 0 && o.h > 0) {
-                    sets[K] = JpegEncSet{(int16_t *)(cbase + cat * chunk), o.dev, o.w, o.h, o.w * 4, o.fs, offs.data() + (size_t)K * chunk, lens.data() + (size_t)K * chunk};
-                    who[K++] = &o;
-                }
-                cat += ccoef[k];
-            }
-            uint8_t *blob = nullptr;
-            rc = jpeg_encode_sets(ctx, l->stream, sets, K, m, quality, &blob);
-            if (rc) break;
-            for (int k = 0; k < K; k++)
-                for (int i = 0; i < m; i++) { who[k]->dst[i0 + i].data = blob + sets[k].offs[i]; who[k]->dst[i0 + i].len = sets[k].lens[i]; }
-            if (blob) {
-                std::lock_guard<std::mutex> lk(res_mu);
-                res->blobs.push_back(blob);
-            }
+            if (!rc) rc = encode_outputs(ctx, l->stream, outs, f, m, i0, quality, nullptr, mine);
         }
-        if (rc) {
+        {
             std::lock_guard<std::mutex> lk(res_mu);
-            if (status == IPX_OK) { status = rc; err_text = ipx_last_error(); }
+            res.adopt(mine.release());
+            if (rc && status == IPX_OK) { status = rc; err_text = ipx_last_error(); }
         }
         (void)hipStreamSynchronize(l->stream);
     };
@@ -393,7 +439,6 @@ static int run_host_jpeg_impl(ipx_ctx *ctx, const ipx_plan *pl, int n, const uin
     }
     ctx->cv.notify_all();
     if (status != IPX_OK) {
-        ipx_jpeg_result_free(ctx, res.release());
         set_error("%s", err_text.c_str());
         return status;
     }
@@ -904,12 +949,8 @@ static int run_jpeg_jpeg_one(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_
     IPX_ENTER(ctx);
     *result = nullptr;
     if (n == 0) return IPX_OK;
-    const int sw = pl->p.sw, sh = pl->p.sh;
-    for (int i = 0; i < n; i++) {
-        if (resize_out) resize_out[i] = ipx_bytes{nullptr, 0};
-        if (thumb_out) thumb_out[i] = ipx_bytes{nullptr, 0};
-        if (wm_out) wm_out[i] = ipx_bytes{nullptr, 0};
-    }
+    const PlanOutputs outs(pl, resize_out, thumb_out, wm_out, Codec::Jpeg, Codec::Jpeg, Codec::Jpeg);
+    outs.clear(n);
     const bool dbg = getenv("IPX_DEBUG") != nullptr;
     struct Slot {
         ipx_ctx *c;
@@ -931,7 +972,7 @@ static int run_jpeg_jpeg_one(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_
     LaneLease lane(ctx);
     const double t_lane = ms_since(t0);
     hipStream_t s = lane->stream;
-    int w = sw, h = sh;
+    int w = pl->p.sw, h = pl->p.sh;
     ipx_ycbcr_batch planes;
     ipx_jpeg_planes *owner = nullptr;
     memset(&planes, 0, sizeof planes);
@@ -940,59 +981,28 @@ static int run_jpeg_jpeg_one(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_
     if (rc) return rc;
     if (!planes.y) return IPX_OK;                         // nothing decodable: every status says why
     struct Guard { ipx_ctx *c; ipx_jpeg_planes *o; ~Guard() { ipx_jpeg_planes_free(c, o); } } guard{ctx, owner};
-    const size_t fres = resize_out ? align256(pl->info.resize_bytes) : 0, fth = thumb_out ? align256(pl->info.thumb_bytes) : 0;
-    const size_t fwm = wm_out ? align256(pl->info.wm_bytes) : 0;
-    const size_t cres = fres ? ipx_jpeg_coef_count(pl->info.resize_w, pl->info.resize_h) * 2 : 0;
-    const size_t cth = fth ? ipx_jpeg_coef_count(pl->info.thumb_w, pl->info.thumb_h) * 2 : 0;
-    const size_t cwm = fwm ? ipx_jpeg_coef_count(sw, sh) * 2 : 0;
     // (a coefficient buffer per output: the three encodes run stage by stage together, jpeg_encode_sets)
-    const size_t ccoef[3] = {align256(cres), align256(cth), align256(cwm)};
-    const size_t per_frame = fres + fth + fwm + ccoef[0] + ccoef[1] + ccoef[2];
+    const size_t per_frame = outs.frame_bytes();
     if (per_frame == 0) return IPX_OK;
     const int chunk = std::max(1, std::min(n, env_int("IPX_JPEG_JPEG_CHUNK", 256)));
     rc = lane_reserve(lane.get(), per_frame * chunk + 256);
     if (rc) return rc;
     const double t_res = ms_since(t0);
-    std::unique_ptr<ipx_jpeg_result> res(new ipx_jpeg_result);
-    std::vector<size_t> offs(3 * (size_t)chunk), lens(3 * (size_t)chunk);
+    ResultOwner res(ctx);
     for (int i0 = 0; i0 < n && !rc; i0 += chunk) {
         const int m = std::min(chunk, n - i0);
-        uint8_t *base = (uint8_t *)(((uintptr_t)lane->dev + 255) & ~(uintptr_t)255);
-        uint8_t *dres = fres ? base : nullptr, *dth = fth ? base + fres * chunk : nullptr, *dwm = fwm ? base + (fres + fth) * chunk : nullptr;
-        uint8_t *cbase = base + (fres + fth + fwm) * chunk;
+        const PlanOutputs::Frames f = outs.place((uint8_t *)(((uintptr_t)lane->dev + 255) & ~(uintptr_t)255), chunk);
+        const size_t fres = outs.o[0].fs, fth = outs.o[1].fs, fwm = outs.o[2].fs;
         ipx_ycbcr_batch d = planes;
         d.y += planes.y_frame_stride * i0;
         if (d.cb) { d.cb += planes.c_frame_stride * i0; d.cr += planes.c_frame_stride * i0; }
-        if (planes.ratio == IPX_GRAY) rc = ipx_plan_run_dev_gray(ctx, s, pl, m, d.y, d.ystride, d.y_frame_stride, dres, fres, dth, fth, dwm, fwm);
-        else rc = ipx_plan_run_dev_ycbcr(ctx, s, pl, m, &d, dres, fres, dth, fth, dwm, fwm);
-        if (rc) break;
-        struct Out { uint8_t *dev; size_t fs; int w, h; ipx_bytes *dst; };
-        const Out outs[3] = {{dres, fres, pl->info.resize_w, pl->info.resize_h, resize_out},
-                             {dth, fth, pl->info.thumb_w, pl->info.thumb_h, thumb_out},
-                             {dwm, fwm, sw, sh, wm_out}};
-        JpegEncSet sets[3];
-        const Out *who[3];
-        int K = 0;
-        size_t cat = 0;
-        for (int k = 0; k < 3; k++) {
-            const Out &o = outs[k];
-            if (o.dev && o.w > 0 && o.h > 0) {
-                sets[K] = JpegEncSet{(int16_t *)(cbase + cat * chunk), o.dev, o.w, o.h, o.w * 4, o.fs, offs.data() + (size_t)K * chunk, lens.data() + (size_t)K * chunk};
-                who[K++] = &o;
-            }
-            cat += ccoef[k];
-        }
-        uint8_t *blob = nullptr;
-        rc = jpeg_encode_sets(ctx, s, sets, K, m, quality, &blob);
-        if (rc) break;
-        if (blob) res->blobs.push_back(blob);
-        for (int k = 0; k < K; k++)
-            for (int i = 0; i < m; i++)
-                if (status[i0 + i] == IPX_OK) { who[k]->dst[i0 + i].data = blob + sets[k].offs[i]; who[k]->dst[i0 + i].len = sets[k].lens[i]; }
+        if (planes.ratio == IPX_GRAY) rc = ipx_plan_run_dev_gray(ctx, s, pl, m, d.y, d.ystride, d.y_frame_stride, f.dev[0], fres, f.dev[1], fth, f.dev[2], fwm);
+        else rc = ipx_plan_run_dev_ycbcr(ctx, s, pl, m, &d, f.dev[0], fres, f.dev[1], fth, f.dev[2], fwm);
+        if (!rc) rc = encode_outputs(ctx, s, outs, f, m, i0, quality, status, res);
     }
     (void)hipStreamSynchronize(s);
     if (dbg) fprintf(stderr, "[ipx] jpeg->jpeg part of %d files: lane after %.1f ms, decoded at %.1f, scratch at %.1f, done at %.1f\n", n, t_lane, t_dec, t_res, ms_since(t0));
-    if (rc) { ipx_jpeg_result_free(ctx, res.release()); return rc; }
+    if (rc) return rc;
     *result = res.release();
     return IPX_OK;
 }
@@ -1022,13 +1032,13 @@ int ipx_plan_run_jpeg_jpeg(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_by
     };
     auto guarded = [&](int k) { const int rc = guarded_status([&] { work(k); }, &errs[k]); if (rc) rcs[k] = rc; };
     HostPool::instance().parallel_for(parts, parts, [&](int k) { guarded(k); });      // one host thread per part (each drives a lane)
-    std::unique_ptr<ipx_jpeg_result> all(new ipx_jpeg_result);
+    ResultOwner all(ctx);
     int rc = IPX_OK;
     for (int k = 0; k < parts; k++) {
-        if (res[k]) { all->blobs.insert(all->blobs.end(), res[k]->blobs.begin(), res[k]->blobs.end()); delete res[k]; }
+        all.adopt(res[k]);
         if (rcs[k] && !rc) { rc = rcs[k]; set_error("%s", errs[k].c_str()); }
     }
-    if (rc) { ipx_jpeg_result_free(ctx, all.release()); return rc; }
+    if (rc) return rc;
     *result = all.release();
     return IPX_OK;
 }

@@ -661,7 +661,10 @@ int ipx::png_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w,
     if (n == 0) return IPX_OK;
     uint8_t heads[2][kPngHeadBytes];
     png_write_heads(w, h, heads);
-    struct SyncOnExit { hipStream_t s; ~SyncOnExit() { (void)hipStreamSynchronize(s); } } sync_on_exit{s};
+    std::vector<uint32_t> alpha(n), item0(n + 1), sl;
+    std::vector<PngSeg> segs;
+    std::vector<PngPiece> pieces;
+    StreamSync sync{s};                           // after the host buffers above: the queued copies read and write them
     AsyncFree mem{s, {}};
     const size_t fbytes = align256((size_t)h * (1 + 4 * (size_t)w));
     const size_t tail = kSegBase + std::max(segs_bytes(w, h, 3), segs_bytes(w, h, 4)), region = align256(tail + kPngTailBytes);
@@ -669,12 +672,9 @@ int ipx::png_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w,
     IPX_HIP(mem.get(&dalpha, (size_t)n * 4));
     IPX_HIP(hipMemsetAsync(dalpha, 0, (size_t)n * 4, s));
     IPX_HIP(launch_png_opacity(src, w, h, stride, frame_stride, n, dalpha, s));
-    std::vector<uint32_t> alpha(n);
     IPX_HIP(hipMemcpyAsync(alpha.data(), dalpha, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     IPX_HIP(hipStreamSynchronize(s));
     // the segments of every frame, by its colour type
-    std::vector<PngSeg> segs;
-    std::vector<uint32_t> item0(n + 1);
     for (int f = 0; f < n; f++) {
         item0[f] = (uint32_t)segs.size();
         const PngSegs g(w, h, alpha[f] ? 4 : 3);
@@ -710,11 +710,10 @@ int ipx::png_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w,
     IPX_HIP(launch_png_filter(src, w, h, stride, frame_stride, n, dalpha, dfilt, fbytes, s));
     IPX_HIP(launch_png_deflate(dfilt, dmatch, fbytes, w, h, dalpha, dsegs, nseg, dout, dlens, dadler, s));
     IPX_HIP(launch_png_frame(dheads, dalpha, ditem0, dsegs, dadler, n, dout, region, tail, s));
-    std::vector<uint32_t> sl(nseg);
+    sl.resize(nseg);
     IPX_HIP(hipMemcpyAsync(sl.data(), dlens, (size_t)nseg * 4, hipMemcpyDeviceToHost, s));
     IPX_HIP(hipStreamSynchronize(s));
     // the pieces: head, the segments' chunks, tail, frame after frame, each stream starting 16-byte aligned
-    std::vector<PngPiece> pieces;
     pieces.reserve(nseg + 2 * (size_t)n);
     size_t total = 0;
     for (int f = 0; f < n; f++) {
@@ -812,50 +811,31 @@ int ipx_plan_run_host_png(ipx_ctx *ctx, const ipx_plan *pl, int n, const uint8_t
         return IPX_ERR_UNSUPPORTED;
     }
     if (n == 0) return IPX_OK;
-    const ipx_plan_info &in = pl->info;
     const int sw = pl->p.sw, sh = pl->p.sh;
     const size_t fsrc = align256((size_t)sw * sh * 4);
-    const size_t fres = resize_out ? align256(in.resize_bytes) : 0, fth = thumb_out ? align256(in.thumb_bytes) : 0;
-    const size_t fwm = wm_out ? align256(in.wm_bytes) : 0;
-    const size_t per_frame = fsrc + fres + fth + fwm;
+    const PlanOutputs outs(pl, resize_out, thumb_out, wm_out, Codec::Png, Codec::Png, Codec::Png);
+    const size_t per_frame = fsrc + outs.frame_bytes();
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n, (size_t)env_int("IPX_HOST_CHUNK_PNG", 64),
                                                                  ((size_t)1 << 30) / per_frame}));
-    struct ResultGuard {
-        ipx_ctx *ctx;
-        ipx_jpeg_result *r;
-        ~ResultGuard() { ipx_jpeg_result_free(ctx, r); }
-    } res{ctx, new ipx_jpeg_result};
+    ResultOwner res(ctx);
     LaneLease lane(ctx);
     hipStream_t s = lane->stream;
-    std::vector<size_t> offs(chunk), lens(chunk);
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const int m = std::min(chunk, n - i0);
-        struct SyncOnExit { hipStream_t s; ~SyncOnExit() { (void)hipStreamSynchronize(s); } } sync_on_exit{s};
+        StreamSync sync{s};
         AsyncFree mem{s, {}};
-        uint8_t *dsrc, *dres = nullptr, *dth = nullptr, *dwm = nullptr;
+        uint8_t *dsrc, *dout = nullptr;
         IPX_HIP(mem.get(&dsrc, fsrc * m));
-        if (fres) IPX_HIP(mem.get(&dres, fres * m));
-        if (fth) IPX_HIP(mem.get(&dth, fth * m));
-        if (fwm) IPX_HIP(mem.get(&dwm, fwm * m));
+        if (outs.frame_bytes()) IPX_HIP(mem.get(&dout, outs.frame_bytes() * m));
         for (int i = 0; i < m; i++)
             IPX_HIP(hipMemcpy2DAsync(dsrc + fsrc * i, (size_t)sw * 4, src + src_frame_stride * (size_t)(i0 + i), sstride, (size_t)sw * 4, sh,
                                      hipMemcpyHostToDevice, s));
-        int rc = ipx_plan_run_dev(ctx, s, pl, m, dsrc, sw * 4, fsrc, dres, fres, dth, fth, dwm, fwm);
+        const PlanOutputs::Frames f = outs.place(dout, m);
+        int rc = ipx_plan_run_dev(ctx, s, pl, m, dsrc, sw * 4, fsrc, f.dev[0], outs.o[0].fs, f.dev[1], outs.o[1].fs, f.dev[2], outs.o[2].fs);
+        if (!rc) rc = encode_outputs(ctx, s, outs, f, m, i0, 0, nullptr, res);
         if (rc) return rc;
-        struct Out { uint8_t *dev; size_t fs; int w, h; ipx_bytes *dst; };
-        const Out outs[3] = {{dres, fres, in.resize_w, in.resize_h, resize_out}, {dth, fth, in.thumb_w, in.thumb_h, thumb_out},
-                             {dwm, fwm, in.wm_w, in.wm_h, wm_out}};
-        for (const Out &o : outs) {
-            if (!o.dev || o.w <= 0 || o.h <= 0) continue;
-            uint8_t *blob = nullptr;
-            rc = png_encode_core(ctx, s, o.dev, o.w, o.h, o.w * 4, o.fs, m, &blob, offs.data(), lens.data());
-            if (rc) return rc;
-            res.r->blobs.push_back(blob);
-            for (int i = 0; i < m; i++) { o.dst[i0 + i].data = blob + offs[i]; o.dst[i0 + i].len = lens[i]; }
-        }
     }
-    *result = res.r;
-    res.r = nullptr;
+    *result = res.release();
     return IPX_OK;
 }
 IPX_CATCH_STATUS

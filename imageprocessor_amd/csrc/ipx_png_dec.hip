@@ -850,27 +850,18 @@ int ipx_plan_run_png_png(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_byte
     IPX_ENTER(ctx);
     if (!pl || n < 0 || !files || !status || !result) { set_error("ipx_plan_run_png_png: bad argument"); return IPX_ERR_INVALID; }
     *result = nullptr;
-    const ipx_plan_info &in = pl->info;
     const int sw = pl->p.sw, sh = pl->p.sh;
-    for (int i = 0; i < n; i++) {
-        for (ipx_bytes *o : {resize_out, thumb_out, wm_out})
-            if (o) o[i] = ipx_bytes{nullptr, 0};
-    }
+    const PlanOutputs outs(pl, resize_out, thumb_out, wm_out, Codec::Png, Codec::Png, Codec::Png);
+    outs.clear(n);
     if (n == 0) return IPX_OK;
     std::vector<PngFileInfo> info(n);
     int rc = png_parse_all(files, n, info, status);
     if (rc) return rc;
     for (int i = 0; i < n; i++)
         if (status[i] == IPX_OK && (info[i].w != sw || info[i].h != sh)) status[i] = IPX_ERR_UNSUPPORTED;
-    const size_t fres = resize_out ? align256(in.resize_bytes) : 0, fth = thumb_out ? align256(in.thumb_bytes) : 0;
-    const size_t fwm = wm_out ? align256(in.wm_bytes) : 0;
-    const size_t per_out = fres + fth + fwm;
+    const size_t per_out = outs.frame_bytes();
     const int chunk_max = std::max(1, env_int("IPX_HOST_CHUNK_PNG", 64)), group_max = std::max(1, env_int("IPX_HOST_CHUNK_PNG_DEC", 1024));
-    struct ResultGuard {
-        ipx_ctx *ctx;
-        ipx_jpeg_result *r;
-        ~ResultGuard() { ipx_jpeg_result_free(ctx, r); }
-    } res{ctx, new ipx_jpeg_result};
+    ResultOwner res(ctx);
     LaneLease lane(ctx);
     hipStream_t s = lane->stream;
     for (int kind = 0; kind < kPngKinds; kind++) {
@@ -882,12 +873,11 @@ int ipx_plan_run_png_png(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_byte
         const size_t fs = align256((size_t)sw * sh * kb);
         const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)group_max, ((size_t)4 << 30) / (fs + 1024)));
         const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)chunk_max, per_out ? ((size_t)1 << 30) / per_out : (size_t)chunk_max));
-        std::vector<size_t> offs(chunk), lens(chunk);
         for (size_t g0 = 0; g0 < of_kind.size(); g0 += group) {
             const int m = (int)std::min<size_t>(group, of_kind.size() - g0);
             std::vector<int> idx(of_kind.begin() + g0, of_kind.begin() + g0 + m), slot(m);
             for (int g = 0; g < m; g++) slot[g] = g;
-            struct SyncOnExit { hipStream_t s; ~SyncOnExit() { (void)hipStreamSynchronize(s); } } sync_on_exit{s};
+            StreamSync sync{s};
             AsyncFree mem{s, {}};
             uint8_t *dfr, *dpal = nullptr;
             IPX_HIP(mem.get(&dfr, fs * m));
@@ -900,29 +890,17 @@ int ipx_plan_run_png_png(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_byte
                 for (int g = c0; g < c0 + cm; g++) any |= status[idx[g]] == IPX_OK;
                 if (!any) continue;
                 AsyncFree omem{s, {}};
-                uint8_t *dres = nullptr, *dth = nullptr, *dwm = nullptr;
-                if (fres) IPX_HIP(omem.get(&dres, fres * cm));
-                if (fth) IPX_HIP(omem.get(&dth, fth * cm));
-                if (fwm) IPX_HIP(omem.get(&dwm, fwm * cm));
-                rc = png_run_ops(ctx, s, pl, kind, cm, dfr + fs * c0, fs, dpal ? dpal + (size_t)1024 * c0 : nullptr, dres, fres, dth, fth, dwm, fwm);
+                uint8_t *dout = nullptr;
+                if (per_out) IPX_HIP(omem.get(&dout, per_out * cm));
+                const PlanOutputs::Frames f = outs.place(dout, cm);
+                rc = png_run_ops(ctx, s, pl, kind, cm, dfr + fs * c0, fs, dpal ? dpal + (size_t)1024 * c0 : nullptr, f.dev[0], outs.o[0].fs, f.dev[1],
+                                 outs.o[1].fs, f.dev[2], outs.o[2].fs);
+                if (!rc) rc = encode_outputs(ctx, s, outs, f, cm, 0, 0, status, res, idx.data() + c0);
                 if (rc) return rc;
-                struct Out { uint8_t *dev; size_t fs; int w, h; ipx_bytes *dst; };
-                const Out outs[3] = {{dres, fres, in.resize_w, in.resize_h, resize_out}, {dth, fth, in.thumb_w, in.thumb_h, thumb_out},
-                                     {dwm, fwm, in.wm_w, in.wm_h, wm_out}};
-                for (const Out &o : outs) {
-                    if (!o.dev || o.w <= 0 || o.h <= 0) continue;
-                    uint8_t *blob = nullptr;
-                    rc = png_encode_core(ctx, s, o.dev, o.w, o.h, o.w * 4, o.fs, cm, &blob, offs.data(), lens.data());
-                    if (rc) return rc;
-                    res.r->blobs.push_back(blob);
-                    for (int g = 0; g < cm; g++)
-                        if (status[idx[c0 + g]] == IPX_OK) o.dst[idx[c0 + g]] = ipx_bytes{blob + offs[g], lens[g]};
-                }
             }
         }
     }
-    *result = res.r;
-    res.r = nullptr;
+    *result = res.release();
     return IPX_OK;
 }
 IPX_CATCH_STATUS

@@ -620,14 +620,10 @@ int ipx_dev_scale_bilinear_rgba8(ipx_ctx *ctx, void *stream, uint8_t *dst, int d
     IPX_FRAME("ipx_dev_scale_bilinear_rgba8", "destination", dst, dw, dh, dstride);
     IPX_FRAME("ipx_dev_scale_bilinear_rgba8", "source", src, sw, sh, sstride);
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    AsyncFree mem{s, {}};
     int *flag = nullptr;
-    if (op == IPX_OP_OVER) {
-        // the opaque() flag must outlive the launch: one device int per call, freed stream-ordered
-        IPX_HIP(hipMallocAsync((void **)&flag, sizeof(int), s));
-    }
-    int rc = dev_scale(ctx, s, flag, dst, dw, dh, dstride, to_rect(dr), src, sw, sh, sstride, to_rect(sr), op);
-    if (flag) (void)hipFreeAsync(flag, s);
-    return rc;
+    if (op == IPX_OP_OVER) IPX_HIP(mem.get(&flag, sizeof(int)));   // the opaque() flag must outlive the launch: one device int per call
+    return dev_scale(ctx, s, flag, dst, dw, dh, dstride, to_rect(dr), src, sw, sh, sstride, to_rect(sr), op);
 }
 IPX_CATCH_STATUS
 
@@ -1229,6 +1225,7 @@ static int run_dev_any(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, int n, c
         // 1 / 96 of the output's pixels each, twenty times what photographs put there (IPX_KS_STATS=1 prints the fill); a frame that fills
         // its list is redone in float64.
         // One stream-ordered block: [flags][counts][lists].
+        AsyncFree mem{s, {}};
         int *redo = nullptr;
         KsFix fixv, *fix = nullptr;
         const int max_items = n * fp.nstrips * std::max(fp.whole.nseg, fp.split.nseg);
@@ -1242,7 +1239,7 @@ static int run_dev_any(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, int n, c
             for (int k = 0; k < 2; k++)
                 if (fast && outs[k]) cap[k] = cap_env > 0 ? cap_env : (int)std::min<size_t>(std::max<size_t>((size_t)pl->sc[k].dw * pl->sc[k].dh / 96, 256), (size_t)1 << 20);
             const size_t flags = align256((size_t)max_items * sizeof(int)), counts = fast ? align256((size_t)n * 2 * sizeof(int)) : 0;
-            IPX_HIP(hipMallocAsync((void **)&redo, flags + counts + (size_t)n * (cap[0] + cap[1]) * sizeof(uint2), s));
+            IPX_HIP(mem.get(&redo, flags + counts + (size_t)n * (cap[0] + cap[1]) * sizeof(uint2)));
             if (fast) {
                 fixv.count = (int *)((uint8_t *)redo + flags);
                 fixv.list = (uint2 *)((uint8_t *)redo + flags + counts);
@@ -1274,7 +1271,6 @@ static int run_dev_any(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, int n, c
             fprintf(stderr, "[ipx ks stats] %d frames: undecided pixels per frame resize mean %.1f max %d (room %d), thumbnail mean %.1f max %d (room %d); %d of %d items redone in float64\n", n,
                     (double)tot[0] / n, mx[0], fixv.cap[0], (double)tot[1] / n, mx[1], fixv.cap[1], nredo, max_items);
         }
-        if (redo) (void)hipFreeAsync(redo, s);
 #if IPX_DIAG
         if (a.stamps && matched) {
             unsigned long long h[24];
@@ -1658,9 +1654,9 @@ int ipx_plan_run_dev_deep(ipx_ctx *ctx, void *stream, const ipx_plan *pl, int n,
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     const int sw = pl->p.sw, sh = pl->p.sh;
     const size_t tfs = align256((size_t)sw * sh * 8);
+    AsyncFree mem{s, {}};
     uint8_t *taps = nullptr;
-    IPX_HIP(hipMallocAsync((void **)&taps, tfs * n, s));
-    struct Free { uint8_t *p; hipStream_t s; ~Free() { if (p) (void)hipFreeAsync(p, s); } } free_taps{taps, s};
+    IPX_HIP(mem.get(&taps, tfs * n));
     {
         hipError_t e = launch_deep_expand(taps, tfs, src, sstride, src_frame_stride, kind, sw, sh, n, s);
         if (e != hipSuccess) { set_error("tap expansion failed: %s", hipGetErrorString(e)); return IPX_ERR_HIP; }
@@ -1707,15 +1703,13 @@ int ipx_plan_run_dev_paletted(ipx_ctx *ctx, void *stream, const ipx_plan *pl, in
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     const int sw = pl->p.sw, sh = pl->p.sh;
     const size_t fs = align256((size_t)sw * sh * 4);
+    AsyncFree mem{s, {}};
     uint8_t *nrgba = nullptr;
-    IPX_HIP(hipMallocAsync((void **)&nrgba, fs * n, s));
+    IPX_HIP(mem.get(&nrgba, fs * n));
     hipError_t e = launch_palette_expand(nrgba, fs, index, stride, frame_stride, palettes, sw, sh, n, s);
-    int rc = IPX_OK;
-    if (e != hipSuccess) { set_error("palette expansion failed: %s", hipGetErrorString(e)); rc = IPX_ERR_HIP; }
-    if (!rc) rc = ipx_plan_run_dev_nrgba(ctx, s, pl, n, nrgba, sw * 4, fs, resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out,
-                                         wm_frame_stride);
-    (void)hipFreeAsync(nrgba, s);
-    return rc;
+    if (e != hipSuccess) { set_error("palette expansion failed: %s", hipGetErrorString(e)); return IPX_ERR_HIP; }
+    return ipx_plan_run_dev_nrgba(ctx, s, pl, n, nrgba, sw * 4, fs, resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out,
+                                  wm_frame_stride);
 }
 IPX_CATCH_STATUS
 

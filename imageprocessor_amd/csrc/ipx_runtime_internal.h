@@ -280,14 +280,60 @@ struct AsyncFree {
     }
 };
 
+// Waits for its stream on every way out of the scope.  Declare it AFTER every host buffer that copies queued on the stream read or write:
+// locals go in reverse order, so the wait then comes before those buffers are destroyed.
+struct StreamSync {
+    hipStream_t s;
+    ~StreamSync() { (void)hipStreamSynchronize(s); }
+};
+
 // jpeg.Encode of up to three sets of n frames in HBM into one pinned block *blob (ipx_jpeg_runtime.hip); dcoefs: n * ipx_jpeg_coef_count
-// int16 of scratch per set.  Also the watermark leg of ipx_plan_run_host_paletted_gif (ipx_gif.hip).
+// int16 of scratch per set.
 struct JpegEncSet { int16_t *dcoefs; const uint8_t *src; int w, h, stride; size_t frame_stride; size_t *offs, *lens; };   // offs / lens: [n], into *blob
 int jpeg_encode_sets(ipx_ctx *ctx, hipStream_t s, const JpegEncSet *sets, int K, int n, int quality, uint8_t **blob);
 
-// gif.Encode of n frames in HBM into one pinned block *blob (ipx_gif.hip); also the GIF outputs of ipx_plan_run_gif_gif (ipx_gif_dec.hip)
+// gif.Encode of n frames in HBM into one pinned block *blob (ipx_gif.hip)
 int gif_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w, int h, int stride, size_t frame_stride, int n,
                     uint8_t **blob, size_t *offs, size_t *lens);
 
-// the pinned blocks the streams of the *_jpeg / *_gif batch entries live in (ipx_jpeg_result_free)
+// the pinned blocks the streams of the compressed-out batch entries live in (ipx_jpeg_result_free)
 struct ipx_jpeg_result { std::vector<uint8_t *> blobs; };
+
+// ---- the output stage of the compressed-out batch entries (ipx_jpeg_runtime.hip) ----------------------------------------------------
+
+// An entry's result while it runs: freed on every way out but release(), which hands it to the caller.
+class ResultOwner {
+public:
+    explicit ResultOwner(ipx_ctx *ctx) : ctx_(ctx), r_(new ipx_jpeg_result) {}
+    ~ResultOwner() { ipx_jpeg_result_free(ctx_, r_); }
+    ResultOwner(const ResultOwner &) = delete;
+    ResultOwner &operator=(const ResultOwner &) = delete;
+    void add(uint8_t *blob) { if (blob) r_->blobs.push_back(blob); }
+    void adopt(ipx_jpeg_result *o);                    // moves o's blocks in and deletes o (null: nothing)
+    ipx_jpeg_result *release() { ipx_jpeg_result *r = r_; r_ = nullptr; return r; }
+private:
+    ipx_ctx *ctx_;
+    ipx_jpeg_result *r_;
+};
+
+enum class Codec { Jpeg, Png, Gif };
+
+// The plan's three outputs (resize, thumbnail, watermark) as one compressed-out entry hands them out: the caller's array, the size, the
+// frame bytes in HBM (0: not wanted, or not made by the plan) and, for JPEG, the coefficient scratch of jpeg_encode_sets.
+struct PlanOutputs {
+    struct Output { ipx_bytes *dst; int w, h; size_t fs, coef; Codec codec; };
+    struct Frames { uint8_t *dev[3]; int16_t *coef[3]; };     // one chunk's outputs in a device block (place)
+    Output o[3];
+    PlanOutputs(const ipx_plan *pl, ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, Codec res, Codec thumb, Codec wm);
+    size_t frame_bytes() const { return o[0].fs + o[1].fs + o[2].fs + o[0].coef + o[1].coef + o[2].coef; }   // per frame of a block
+    // a block of `chunk` frames: [chunk x resize][chunk x thumbnail][chunk x watermark][chunk x coefficients of each JPEG output]
+    Frames place(uint8_t *block, int chunk) const;
+    void clear(int n) const;      // nulls the first n slots of every array the caller passed
+    int check_gif() const;        // every GIF output within gif.Encode's limits: IPX_OK, or IPX_ERR_INVALID with the error text set
+};
+
+// Encodes the m frames of every present output and publishes {blob + off, len} into dst[i0 + i] (dst[idx[i]] when idx is given) --
+// every slot when status is null, else only those whose status is IPX_OK -- with the blocks going to *res.  All JPEG outputs go into one
+// jpeg_encode_sets call (three waits for the device in all); PNG and GIF outputs are encoded one after the other.
+int encode_outputs(ipx_ctx *ctx, hipStream_t s, const PlanOutputs &outs, const PlanOutputs::Frames &f, int m, int i0, int quality,
+                   const int *status, ResultOwner &res, const int *idx = nullptr);

@@ -195,8 +195,9 @@ def test_empty_and_bad_arguments(ctx):
     L = m.lib()
     plan = ctx.plan(8, 8, resize=(4, 4, False))
     try:
-        out, st0 = plan.run_gif_gif([])
-        assert st0 == [] and "resize" in out and all(v == [] for v in out.values())
+        for run in (plan.run_gif_gif, plan.run_jpeg_jpeg, plan.run_png_png):
+            out, st0 = run([])
+            assert st0 == [] and "resize" in out and all(v == [] for v in out.values()), run.__name__
         assert ctx.gif_decode_batch([]) == (None, [])
         files = (m._lib.Bytes * 1)()
         st = (C.c_int * 1)(7)

@@ -154,6 +154,26 @@ def test_plan_run_host_paletted_gif(ctx):
     gs.close()
 
 
+def test_plan_run_host_paletted_gif_chunks(ctx, monkeypatch):
+    """chunks of 2 frames: the GIF and JPEG streams do not depend on where the chunks fall"""
+    w, h, n = 96, 64, 7
+    rng = np.random.default_rng(22)
+    idx = rng.integers(0, 256, (n, h, w), dtype=np.uint8)
+    pal = rng.integers(0, 256, (n, 256, 4), dtype=np.uint8)
+    pal[..., 3] = 255
+    pal[:, 7] = 0
+    gs = ctx.glyphset(text_glyphs(w, h, n=4, width_px=60, height_px=20), DEFAULT_COL)
+    plan = ctx.plan(w, h, resize=(50, 30, False), thumbnail=(32, True), watermark=gs)
+    try:
+        whole = plan.run_host_paletted_gif(idx, pal, quality=80)
+        monkeypatch.setenv("IPX_HOST_CHUNK_GIF", "2")
+        parts = plan.run_host_paletted_gif(idx, pal, quality=80)
+        assert set(whole) == {"resize", "thumbnail", "watermark"} and whole == parts
+    finally:
+        plan.close()
+        gs.close()
+
+
 def test_plan_watermark_matches_run_host_jpeg(ctx):
     """with an opaque palette the expanded frames are plain RGBA: the watermark stream is run_host_jpeg's"""
     w, h, n = 96, 64, 2

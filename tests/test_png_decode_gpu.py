@@ -285,6 +285,45 @@ def test_leg_every_kind_mixed_with_broken_files(ctx):
     gs.close()
 
 
+def _bad_idat_crc(data):
+    """the IDAT's stored CRC flipped: the host parse accepts the file, the GPU's CRC check fails it"""
+    off, n = _idat_span(data)
+    b = bytearray(data)
+    b[off + n] ^= 0x40
+    return bytes(b)
+
+
+def test_leg_chunks(ctx, monkeypatch):
+    """output chunks of 2 inside decode groups of 3: the statuses and streams do not depend on where the chunks and groups fall.  Two
+    files fail on the GPU (bad IDAT CRC) inside output chunks beside OK files -- one at the first slot of a decode group's first chunk,
+    one at the second slot of a chunk -- so only the status mask keeps their slots unpublished; a truncated file fails in the host parse"""
+    sw, sh = 40, 30
+    gs, plan = _plan(ctx, sw, sh)
+    rgb = [pc.of_type(2, 8, False, sh, sw, seed=60 + k, kind=("photo", "flat")[k % 2], filters=(k % 5,)) for k in range(9)]
+    rgb[3] = _bad_idat_crc(rgb[3])
+    rgb[7] = _bad_idat_crc(rgb[7])
+    # RGB files in order of their kind: decode groups [0 1 3] [5 6 7] [8 9 10], output chunks [0 1] [3] [5 6] [7] [8 9] [10]
+    files = rgb[:2] + [pc.of_type(0, 8, False, sh, sw, seed=70)] + rgb[2:3] + [rgb[0][:-20]] + rgb[3:]
+    gpu_bad, host_bad = (5, 9), 4
+    try:
+        whole, st = plan.run_png_png(files)
+        rs = [dm.decode(f) for f in files]
+        assert st == [dm.entry_status(r, (sw, sh)) for r in rs]
+        assert [i for i, s in enumerate(st) if s != dm.OK] == sorted(gpu_bad + (host_bad,))
+        assert all((v is None) == (s != dm.OK) for k in whole for v, s in zip(whole[k], st))
+        ok_rgb = [i for i in range(len(files)) if st[i] == dm.OK and rs[i]["kind"] == rs[0]["kind"]]
+        want = plan.run_host_png(np.stack([rs[i]["pix"].reshape(sh, sw, 4) for i in ok_rgb]))
+        for k in want:
+            assert [whole[k][i] for i in ok_rgb] == want[k], k
+        monkeypatch.setenv("IPX_HOST_CHUNK_PNG", "2")
+        monkeypatch.setenv("IPX_HOST_CHUNK_PNG_DEC", "3")
+        parts, st2 = plan.run_png_png(files)
+        assert st == st2 and whole == parts
+    finally:
+        plan.close()
+        gs.close()
+
+
 def test_bad_arguments(ctx):
     import imageprocessor_amd as m
     from imageprocessor_amd import _lib

@@ -176,3 +176,21 @@ def test_run_host_png_matches_model_of_run_host(ctx):
     assert lens == {"thumbnail": [len(s) for s in got["thumbnail"]]}
     plan.close()
     gs.close()
+
+
+def test_run_host_png_chunks(ctx, monkeypatch):
+    """chunks of 3 frames: the streams do not depend on where the chunks fall"""
+    sw, sh, n = 96, 64, 7
+    frames = rgba_frames(n, sw, sh, seed=12)
+    frames[4, ..., 3] = 128
+    frames[4, ..., :3] //= 2
+    gs = ctx.glyphset(text_glyphs(sw, sh), DEFAULT_COL)
+    plan = ctx.plan(sw, sh, resize=(50, 30, False), thumbnail=(32, True), watermark=gs)
+    try:
+        whole = plan.run_host_png(frames)
+        monkeypatch.setenv("IPX_HOST_CHUNK_PNG", "3")
+        parts = plan.run_host_png(frames)
+        assert set(whole) == {"resize", "thumbnail", "watermark"} and whole == parts
+    finally:
+        plan.close()
+        gs.close()
