@@ -187,89 +187,61 @@ class Plan:
         self.info = PlanInfo()
         _check(lib().ipx_plan_query(self.handle, C.byref(self.info)))
 
+    def _run(self, entry, head, n, src, ptrs, strides=(None, None, None)):
+        """One pixel-out entry.  head: () for frames in host memory, (stream,) for frames in HBM; src: the entry's source arguments;
+        ptrs: the addresses of the resize, thumbnail and watermark outputs (None: not wanted); strides: their frame strides
+        (None: tightly packed)."""
+        i = self.info
+        fs = [d if s is None else s for s, d in zip(strides, (i.resize_bytes, i.thumb_bytes, i.wm_bytes))]
+        _check(entry(self.ctx.handle, *head, self.handle, n, *src, ptrs[0], fs[0], ptrs[1], fs[1], ptrs[2], fs[2]))
+
+    def _run_host(self, entry, n, src, want, out=None):
+        """A host entry: arrays for the wanted outputs the plan has (those in `out` are used as they are), the call, the dict."""
+        i = self.info
+        out = dict(out) if out else {}
+        for k, nbytes, h, w in (("resize", i.resize_bytes, i.resize_h, i.resize_w), ("thumbnail", i.thumb_bytes, i.thumb_h, i.thumb_w),
+                                ("watermark", i.wm_bytes, i.wm_h, i.wm_w)):
+            if k in want and nbytes and k not in out:
+                out[k] = np.empty((n, h, w, 4), np.uint8)
+        self._run(entry, (), n, src, [out[k].ctypes.data if k in out else None for k in ("resize", "thumbnail", "watermark")])
+        return out
+
     def run_dev(self, n, src_ptr, resize_ptr=None, thumb_ptr=None, wm_ptr=None, stream=None,
                 sstride=None, src_frame_stride=None, resize_frame_stride=None,
                 thumb_frame_stride=None, wm_frame_stride=None):
-        i = self.info
-        _check(lib().ipx_plan_run_dev(
-            self.ctx.handle, stream, self.handle, n, src_ptr,
-            sstride if sstride is not None else self._sw * 4,
-            src_frame_stride if src_frame_stride is not None else self._sw * self._sh * 4,
-            resize_ptr, resize_frame_stride if resize_frame_stride is not None else i.resize_bytes,
-            thumb_ptr, thumb_frame_stride if thumb_frame_stride is not None else i.thumb_bytes,
-            wm_ptr, wm_frame_stride if wm_frame_stride is not None else i.wm_bytes))
+        self._run(lib().ipx_plan_run_dev, (stream,), n,
+                  (src_ptr, sstride if sstride is not None else self._sw * 4,
+                   src_frame_stride if src_frame_stride is not None else self._sw * self._sh * 4),
+                  (resize_ptr, thumb_ptr, wm_ptr), (resize_frame_stride, thumb_frame_stride, wm_frame_stride))
 
     def run_host(self, frames, want=("resize", "thumbnail", "watermark"), out=None):
         """frames: n x H x W x 4 uint8 (host).  Returns dict of output batches (`out` may supply
         preallocated, e.g. pinned, arrays)."""
         frames = np.ascontiguousarray(frames, dtype=np.uint8)
-        n = frames.shape[0]
-        i = self.info
-        out = dict(out) if out else {}
-        if "resize" in want and i.resize_bytes and "resize" not in out:
-            out["resize"] = np.empty((n, i.resize_h, i.resize_w, 4), np.uint8)
-        if "thumbnail" in want and i.thumb_bytes and "thumbnail" not in out:
-            out["thumbnail"] = np.empty((n, i.thumb_h, i.thumb_w, 4), np.uint8)
-        if "watermark" in want and i.wm_bytes and "watermark" not in out:
-            out["watermark"] = np.empty((n, i.wm_h, i.wm_w, 4), np.uint8)
-
-        def p(k):
-            return out[k].ctypes.data if k in out else None
-        _check(lib().ipx_plan_run_host(self.ctx.handle, self.handle, n, frames.ctypes.data,
-                                       self._sw * 4, self._sw * self._sh * 4,
-                                       p("resize"), i.resize_bytes, p("thumbnail"), i.thumb_bytes,
-                                       p("watermark"), i.wm_bytes))
-        return out
-
-    def _host_outs(self, n, want):
-        i = self.info
-        out = {}
-        if "resize" in want and i.resize_bytes:
-            out["resize"] = np.empty((n, i.resize_h, i.resize_w, 4), np.uint8)
-        if "thumbnail" in want and i.thumb_bytes:
-            out["thumbnail"] = np.empty((n, i.thumb_h, i.thumb_w, 4), np.uint8)
-        if "watermark" in want and i.wm_bytes:
-            out["watermark"] = np.empty((n, i.wm_h, i.wm_w, 4), np.uint8)
-        return out, lambda k: out[k].ctypes.data if k in out else None
+        return self._run_host(lib().ipx_plan_run_host, frames.shape[0], (frames.ctypes.data, self._sw * 4, self._sw * self._sh * 4), want, out)
 
     def run_host_nrgba(self, frames, want=("resize", "thumbnail", "watermark")):
         """frames: n x H x W x 4 uint8, non-premultiplied (*image.NRGBA, host) -> dict of output batches"""
         frames = np.ascontiguousarray(frames, dtype=np.uint8)
-        n, i = frames.shape[0], self.info
-        out, p = self._host_outs(n, want)
-        _check(lib().ipx_plan_run_host_nrgba(self.ctx.handle, self.handle, n, frames.ctypes.data, self._sw * 4, self._sw * self._sh * 4,
-                                             p("resize"), i.resize_bytes, p("thumbnail"), i.thumb_bytes, p("watermark"), i.wm_bytes))
-        return out
+        return self._run_host(lib().ipx_plan_run_host_nrgba, frames.shape[0], (frames.ctypes.data, self._sw * 4, self._sw * self._sh * 4), want)
 
     def run_host_deep(self, pix, kind, want=("resize", "thumbnail", "watermark")):
         """pix: n x H x (W * bpp) uint8, Go's Pix rows of *image.NRGBA64 / RGBA64 / Gray16 / CMYK frames (kind: DEEP_*, host)"""
         pix = np.ascontiguousarray(pix, dtype=np.uint8)
-        n, i = pix.shape[0], self.info
-        out, p = self._host_outs(n, want)
-        _check(lib().ipx_plan_run_host_deep(self.ctx.handle, self.handle, n, kind, pix.ctypes.data, pix.shape[2], pix.shape[1] * pix.shape[2],
-                                            p("resize"), i.resize_bytes, p("thumbnail"), i.thumb_bytes, p("watermark"), i.wm_bytes))
-        return out
+        return self._run_host(lib().ipx_plan_run_host_deep, pix.shape[0], (kind, pix.ctypes.data, pix.shape[2], pix.shape[1] * pix.shape[2]), want)
 
     def run_host_gray(self, frames, want=("resize", "thumbnail", "watermark")):
         """frames: n x H x W uint8 (*image.Gray, host) -> dict of output batches"""
         frames = np.ascontiguousarray(frames, dtype=np.uint8)
-        n, i = frames.shape[0], self.info
-        out, p = self._host_outs(n, want)
-        _check(lib().ipx_plan_run_host_gray(self.ctx.handle, self.handle, n, frames.ctypes.data, self._sw, self._sw * self._sh,
-                                            p("resize"), i.resize_bytes, p("thumbnail"), i.thumb_bytes, p("watermark"), i.wm_bytes))
-        return out
+        return self._run_host(lib().ipx_plan_run_host_gray, frames.shape[0], (frames.ctypes.data, self._sw, self._sw * self._sh), want)
 
     def run_host_paletted(self, index, palettes, want=("resize", "thumbnail", "watermark")):
         """index: n x H x W uint8, palettes: n x 256 x 4 uint8 (R, G, B, A) non-premultiplied (*image.Paletted, host)"""
         index = np.ascontiguousarray(index, dtype=np.uint8)
         palettes = np.ascontiguousarray(palettes, dtype=np.uint8)
-        n, i = index.shape[0], self.info
+        n = index.shape[0]
         assert palettes.shape == (n, 256, 4)
-        out, p = self._host_outs(n, want)
-        _check(lib().ipx_plan_run_host_paletted(self.ctx.handle, self.handle, n, index.ctypes.data, self._sw, self._sw * self._sh,
-                                                palettes.ctypes.data, p("resize"), i.resize_bytes, p("thumbnail"), i.thumb_bytes,
-                                                p("watermark"), i.wm_bytes))
-        return out
+        return self._run_host(lib().ipx_plan_run_host_paletted, n, (index.ctypes.data, self._sw, self._sw * self._sh, palettes.ctypes.data), want)
 
     def _run_streams(self, entry, n, want, copy, args, status=None):
         """One compressed-out entry: output arrays for the wanted outputs the plan has, the call (args go between the plan and the
@@ -343,34 +315,24 @@ class Plan:
 
     def run_dev_nrgba(self, n, src_ptr, resize_ptr=None, thumb_ptr=None, wm_ptr=None, stream=None):
         """*image.NRGBA frames (tightly packed) resident in HBM (ipx_plan_run_dev_nrgba)"""
-        i = self.info
-        _check(lib().ipx_plan_run_dev_nrgba(self.ctx.handle, stream, self.handle, n, src_ptr, self._sw * 4, self._sw * self._sh * 4,
-                                            resize_ptr, i.resize_bytes, thumb_ptr, i.thumb_bytes, wm_ptr, i.wm_bytes))
+        self._run(lib().ipx_plan_run_dev_nrgba, (stream,), n, (src_ptr, self._sw * 4, self._sw * self._sh * 4), (resize_ptr, thumb_ptr, wm_ptr))
 
     def run_dev_deep(self, n, kind, src_ptr, stride, frame_stride, resize_ptr=None, thumb_ptr=None, wm_ptr=None, stream=None):
         """*image.NRGBA64 / RGBA64 / Gray16 / CMYK frames (Go's Pix) resident in HBM (ipx_plan_run_dev_deep)"""
-        i = self.info
-        _check(lib().ipx_plan_run_dev_deep(self.ctx.handle, stream, self.handle, n, kind, src_ptr, stride, frame_stride, resize_ptr,
-                                           i.resize_bytes, thumb_ptr, i.thumb_bytes, wm_ptr, i.wm_bytes))
+        self._run(lib().ipx_plan_run_dev_deep, (stream,), n, (kind, src_ptr, stride, frame_stride), (resize_ptr, thumb_ptr, wm_ptr))
 
     def run_dev_gray(self, n, gray_ptr, stride, frame_stride, resize_ptr=None, thumb_ptr=None, wm_ptr=None, stream=None):
         """*image.Gray frames resident in HBM (ipx_plan_run_dev_gray)"""
-        i = self.info
-        _check(lib().ipx_plan_run_dev_gray(self.ctx.handle, stream, self.handle, n, gray_ptr, stride, frame_stride, resize_ptr,
-                                           i.resize_bytes, thumb_ptr, i.thumb_bytes, wm_ptr, i.wm_bytes))
+        self._run(lib().ipx_plan_run_dev_gray, (stream,), n, (gray_ptr, stride, frame_stride), (resize_ptr, thumb_ptr, wm_ptr))
 
     def run_dev_paletted(self, n, index_ptr, stride, frame_stride, palettes_ptr, resize_ptr=None, thumb_ptr=None, wm_ptr=None, stream=None):
         """*image.Paletted frames resident in HBM: index bytes plus 256 x (R, G, B, A) per frame (ipx_plan_run_dev_paletted)"""
-        i = self.info
-        _check(lib().ipx_plan_run_dev_paletted(self.ctx.handle, stream, self.handle, n, index_ptr, stride, frame_stride, palettes_ptr,
-                                               resize_ptr, i.resize_bytes, thumb_ptr, i.thumb_bytes, wm_ptr, i.wm_bytes))
+        self._run(lib().ipx_plan_run_dev_paletted, (stream,), n, (index_ptr, stride, frame_stride, palettes_ptr), (resize_ptr, thumb_ptr, wm_ptr))
 
     def run_dev_ycbcr(self, n, y_ptr, cb_ptr, cr_ptr, ratio, ystride, cstride, y_frame_stride, c_frame_stride,
                       resize_ptr=None, thumb_ptr=None, wm_ptr=None, stream=None):
-        i = self.info
         b = _lib.YCbCrBatch(y_ptr, cb_ptr, cr_ptr, ystride, cstride, y_frame_stride, c_frame_stride, int(ratio))
-        _check(lib().ipx_plan_run_dev_ycbcr(self.ctx.handle, stream, self.handle, n, C.byref(b), resize_ptr,
-                                            i.resize_bytes, thumb_ptr, i.thumb_bytes, wm_ptr, i.wm_bytes))
+        self._run(lib().ipx_plan_run_dev_ycbcr, (stream,), n, (C.byref(b),), (resize_ptr, thumb_ptr, wm_ptr))
 
     def run_host_ycbcr(self, y, cb, cr, ratio, want=("resize", "thumbnail", "watermark")):
         """A batch of decoded JPEG frames: y n x H x W, cb / cr n x CH x CW uint8 (image.YCbCr planes)."""
@@ -379,20 +341,7 @@ class Plan:
         assert (w, h) == (self._sw, self._sh) and cb.shape == cr.shape and cb.shape[0] == n
         b = _lib.YCbCrBatch(y.ctypes.data, cb.ctypes.data, cr.ctypes.data, w, cb.shape[2], h * w,
                             cb.shape[1] * cb.shape[2], int(ratio))
-        i = self.info
-        out = {}
-        if "resize" in want and i.resize_bytes:
-            out["resize"] = np.empty((n, i.resize_h, i.resize_w, 4), np.uint8)
-        if "thumbnail" in want and i.thumb_bytes:
-            out["thumbnail"] = np.empty((n, i.thumb_h, i.thumb_w, 4), np.uint8)
-        if "watermark" in want and i.wm_bytes:
-            out["watermark"] = np.empty((n, i.wm_h, i.wm_w, 4), np.uint8)
-
-        def p(k):
-            return out[k].ctypes.data if k in out else None
-        _check(lib().ipx_plan_run_host_ycbcr(self.ctx.handle, self.handle, n, C.byref(b), p("resize"), i.resize_bytes,
-                                             p("thumbnail"), i.thumb_bytes, p("watermark"), i.wm_bytes))
-        return out
+        return self._run_host(lib().ipx_plan_run_host_ycbcr, n, (C.byref(b),), want)
 
     def close(self):
         if self.handle:

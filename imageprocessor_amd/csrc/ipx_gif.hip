@@ -366,30 +366,24 @@ int ipx_gif_encode_rgba8(ipx_ctx *ctx, const uint8_t *pix, int w, int h, int str
 IPX_CATCH_STATUS
 
 // The GIF task's GPU leg (resize.go:78-91, thumbnail.go:68-81 with gif.Encode; watermark.go:66-79, where a GIF watermark becomes a JPEG):
-// chunks of paletted frames go up, the operators run (ipx_plan_run_dev_paletted), resize and thumbnail outputs are GIF-encoded and the
+// chunks of paletted frames go up, the operators run, resize and thumbnail outputs are GIF-encoded and the
 // watermark output JPEG-encoded, all in HBM; only the streams come back, into pinned blocks owned by *result.
 int ipx_plan_run_host_paletted_gif(ipx_ctx *ctx, const ipx_plan *pl, int n, const uint8_t *index, int stride, size_t frame_stride,
                                    const uint8_t *palettes, int quality, ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out,
                                    ipx_jpeg_result **result) try
 {
     IPX_ENTER(ctx);
-    if (!pl || n < 0 || !index || !palettes || !result || stride < pl->p.sw) {
-        set_error("ipx_plan_run_host_paletted_gif: bad argument");
-        return IPX_ERR_INVALID;
-    }
+    if (!result) { set_error("ipx_plan_run_host_paletted_gif: bad argument"); return IPX_ERR_INVALID; }
     *result = nullptr;
-    if (!frame_span_ok(pl->p.sw, pl->p.sh, stride, 1)) {
-        set_error("ipx_plan_run_host_paletted_gif: %dx%d frames with a row stride of %d bytes are beyond the span the kernels address",
-                  pl->p.sw, pl->p.sh, stride);
-        return IPX_ERR_UNSUPPORTED;
-    }
-    const int sw = pl->p.sw, sh = pl->p.sh;
+    const BatchSrc host = packed_src(kSrcPaletted, index, stride, frame_stride, palettes);
+    int rc0 = src_check("ipx_plan_run_host_paletted_gif", pl, host, n, false);
+    if (rc0) return rc0;
     const PlanOutputs outs(pl, resize_out, thumb_out, wm_out, Codec::Gif, Codec::Gif, Codec::Jpeg);
-    const int rc0 = outs.check_gif();             // every frame handed to gif.Encode must fit its limits: checked before anything runs
+    rc0 = outs.check_gif();                       // every frame handed to gif.Encode must fit its limits: checked before anything runs
     if (rc0) return rc0;
     if (n == 0) return IPX_OK;
-    const size_t fsrc = align256((size_t)sw * sh);
-    const size_t per_frame = fsrc + 1024 + outs.frame_bytes();
+    const SrcLayout L = src_layout(pl, host);
+    const size_t per_frame = L.frame_bytes() + outs.frame_bytes();
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n, (size_t)env_int("IPX_HOST_CHUNK_GIF", 64),
                                                                  ((size_t)1 << 30) / per_frame}));
     ResultOwner res(ctx);                         // the blocks of finished chunks go back to the cache on every way out but success
@@ -399,15 +393,13 @@ int ipx_plan_run_host_paletted_gif(ipx_ctx *ctx, const ipx_plan *pl, int n, cons
         const int m = std::min(chunk, n - i0);
         StreamSync sync{s};
         AsyncFree mem{s, {}};
-        uint8_t *didx, *dpal, *dout = nullptr;
-        IPX_HIP(mem.get(&didx, fsrc * m));
-        IPX_HIP(mem.get(&dpal, (size_t)1024 * m));
+        uint8_t *dsrc, *dout = nullptr;
+        IPX_HIP(mem.get(&dsrc, L.frame_bytes() * m));        // [m x index plane][m x palette]
         if (outs.frame_bytes()) IPX_HIP(mem.get(&dout, outs.frame_bytes() * m));
-        for (int i = 0; i < m; i++)
-            IPX_HIP(hipMemcpy2DAsync(didx + fsrc * i, sw, index + frame_stride * (size_t)(i0 + i), stride, sw, sh, hipMemcpyHostToDevice, s));
-        IPX_HIP(hipMemcpyAsync(dpal, palettes + (size_t)1024 * i0, (size_t)1024 * m, hipMemcpyHostToDevice, s));
+        BatchSrc d;
+        IPX_HIP(src_upload(host, L, i0, m, dsrc, m, s, kCopyFrameRows, &d));
         const PlanOutputs::Frames f = outs.place(dout, m);
-        int rc = ipx_plan_run_dev_paletted(ctx, s, pl, m, didx, sw, fsrc, dpal, f.dev[0], outs.o[0].fs, f.dev[1], outs.o[1].fs, f.dev[2], outs.o[2].fs);
+        int rc = run_dev_src(ctx, s, pl, m, d, f.dev[0], outs.o[0].fs, f.dev[1], outs.o[1].fs, f.dev[2], outs.o[2].fs);
         if (!rc) rc = encode_outputs(ctx, s, outs, f, m, i0, quality, nullptr, res);
         if (rc) return rc;
     }

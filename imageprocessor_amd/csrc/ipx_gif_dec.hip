@@ -358,7 +358,7 @@ int ipx_gif_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *gifs, int 
 IPX_CATCH_STATUS
 
 // The GIF task's GPU leg from the uploads on: per chunk of files, the host parse and the upload of the LZW data, the walk and the
-// expansion into HBM, ipx_plan_run_dev_paletted, then gif.Encode of the resize and thumbnail outputs and jpeg.Encode of the watermark
+// expansion into HBM, the operators (run_dev_src), then gif.Encode of the resize and thumbnail outputs and jpeg.Encode of the watermark
 // output (a GIF watermark becomes a JPEG, watermark.go:73).  Chunks are bounded as in ipx_plan_run_host_paletted_gif.  The operators run
 // on every slot of a chunk (a failed file's slot holds whatever its frame holds); only OK files' streams are handed out.
 int ipx_plan_run_gif_gif(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, int quality, ipx_bytes *resize_out,
@@ -405,7 +405,7 @@ int ipx_plan_run_gif_gif(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_byte
         for (int i = 0; i < m; i++) any |= status[i0 + i] == IPX_OK;
         if (!any) continue;
         const PlanOutputs::Frames f = outs.place(dout, m);
-        rc = ipx_plan_run_dev_paletted(ctx, s, pl, m, didx, sw, fsrc, dpal, f.dev[0], outs.o[0].fs, f.dev[1], outs.o[1].fs, f.dev[2], outs.o[2].fs);
+        rc = run_dev_src(ctx, s, pl, m, packed_src(kSrcPaletted, didx, sw, fsrc, dpal), f.dev[0], outs.o[0].fs, f.dev[1], outs.o[1].fs, f.dev[2], outs.o[2].fs);
         if (!rc) rc = encode_outputs(ctx, s, outs, f, m, i0, quality, status, res);
         if (rc) return rc;
     }

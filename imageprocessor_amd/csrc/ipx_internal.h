@@ -61,6 +61,30 @@ inline Rect to_rect(const ipx_rect &r) { return Rect{r.x0, r.y0, r.x1, r.y1}; }
 bool draw_clip(Rect &r, int dw, int dh, bool has_src, int sw, int sh, int &spx, int &spy,
                bool has_mask, int mw, int mh, int &mpx, int &mpy);
 
+// ---- the Go image types a batch of source frames can have ---------------------------------------------------------------------
+// The one enumeration of source types (BatchSrc in ipx_runtime_internal.h).  The deep types keep the order of IPX_DEEP_*.
+enum SrcType { kSrcRGBA, kSrcNRGBA, kSrcGray, kSrcPaletted, kSrcYCbCr, kSrcNRGBA64, kSrcRGBA64, kSrcGray16, kSrcCMYK, kSrcTypes };
+// bytes per pixel of plane 0 (Pix, the index plane, Y)
+inline int src_bpp(int type) { static const int b[kSrcTypes] = {4, 4, 1, 1, 1, 8, 8, 2, 4}; return b[type]; }
+// the ABI's own numberings -> SrcType; -1 for a value that names no source of pixels
+inline int src_of_deep(int k) { return k >= IPX_DEEP_NRGBA64 && k <= IPX_DEEP_CMYK ? kSrcNRGBA64 + k : -1; }
+inline int src_of_png(int k)
+{
+    static const int t[] = {kSrcGray, kSrcNRGBA, kSrcRGBA, kSrcPaletted, kSrcGray16, kSrcRGBA64, kSrcNRGBA64};      // IPX_PNG_*
+    return k >= 0 && k < 7 ? t[k] : -1;
+}
+inline int src_of_job(int k)
+{
+    static const int t[] = {kSrcRGBA, -1, kSrcNRGBA, kSrcGray, kSrcNRGBA64, kSrcRGBA64, kSrcGray16, kSrcCMYK};      // IPX_JOB_*
+    return k >= 0 && k < 8 ? t[k] : -1;
+}
+// size of the chroma planes of a w x h *image.YCbCr (image.NewYCbCr)
+inline void chroma_size(int ratio, int w, int h, int *cw, int *ch)
+{
+    *cw = ratio == IPX_YCBCR_422 || ratio == IPX_YCBCR_420 ? (w + 1) / 2 : w;
+    *ch = ratio == IPX_YCBCR_420 || ratio == IPX_YCBCR_440 ? (h + 1) / 2 : h;
+}
+
 // ---- kernel launchers (ipx_kernels.hip) --------------------------------------------------------
 // how the pixels of a source image in HBM are laid out (the tap kinds built on them: ipx_ks.h)
 enum { IPX_SRC_RGBA = 0, IPX_SRC_NRGBA = 1, IPX_SRC_YCBCR = 2,

@@ -22,7 +22,8 @@
 //                      idct.go with its all-zero-AC row shortcut, in wrapping 32-bit arithmetic; row pass in registers,
 //                      column pass through LDS); level shift, clip, 8-byte row stores
 //                      into the MCU-padded planes of image.NewYCbCr.
-// The planes feed band_conv_kernel directly (ipx_plan_run_dev_ycbcr): decoded pixels never leave HBM.
+// The planes are the source of the one-pass scaler kernel as they lie (ipx_plan_run_dev_ycbcr; Gray files: ipx_plan_run_dev_gray): decoded
+// pixels never leave HBM.
 #include "ipx_internal.h"
 
 namespace ipx {

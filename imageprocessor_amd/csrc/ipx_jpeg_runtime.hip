@@ -344,20 +344,17 @@ int encode_outputs(ipx_ctx *ctx, hipStream_t s, const PlanOutputs &outs, const P
     return IPX_OK;
 }
 
-// one implementation for both source kinds: ysrc == nullptr -> RGBA frames at src
-static int run_host_jpeg_impl(ipx_ctx *ctx, const ipx_plan *pl, int n, const uint8_t *src, int sstride, size_t src_frame_stride,
-                              const ipx_ycbcr_batch *ysrc, int quality, ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out,
-                              ipx_jpeg_result **result)
+// frames of any source type in host memory through the plan, every output JPEG-encoded
+static int run_host_jpeg_impl(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n, const BatchSrc &host, int quality, ipx_bytes *resize_out,
+                              ipx_bytes *thumb_out, ipx_bytes *wm_out, ipx_jpeg_result **result)
 {
+    if (!result) { set_error("%s: bad argument", who); return IPX_ERR_INVALID; }
     *result = nullptr;
-    if (n == 0) return IPX_OK;
-    const int sw = pl->p.sw, sh = pl->p.sh;
-    const int cw = ysrc ? ((ysrc->ratio == IPX_YCBCR_422 || ysrc->ratio == IPX_YCBCR_420) ? (sw + 1) / 2 : sw) : 0;
-    const int ch = ysrc ? ((ysrc->ratio == IPX_YCBCR_420 || ysrc->ratio == IPX_YCBCR_440) ? (sh + 1) / 2 : sh) : 0;
-    const size_t yb = ysrc ? align256((size_t)sw * sh) : 0, cbb = ysrc ? align256((size_t)cw * ch) : 0;
-    const size_t fsrc = ysrc ? yb + 2 * cbb : align256((size_t)sw * sh * 4);
+    const int rc0 = src_check(who, pl, host, n, false);
+    if (rc0 || n == 0) return rc0;
+    const SrcLayout L = src_layout(pl, host);
+    const size_t fsrc = L.frame_bytes();
     const PlanOutputs outs(pl, resize_out, thumb_out, wm_out, Codec::Jpeg, Codec::Jpeg, Codec::Jpeg);
-    const size_t fres = outs.o[0].fs, fth = outs.o[1].fs, fwm = outs.o[2].fs;
     const size_t per_frame = fsrc + outs.frame_bytes();
     // every lane runs its own host thread: upload, operators, the three encodes together (two small read-backs) --
     // the threads block independently, so copies and kernels of different chunks overlap
@@ -385,36 +382,10 @@ static int run_host_jpeg_impl(ipx_ctx *ctx, const ipx_plan *pl, int n, const uin
             const int i0 = c * chunk, m = std::min(chunk, n - i0);
             uint8_t *dsrc = (uint8_t *)(((uintptr_t)l->dev + 255) & ~(uintptr_t)255);
             const PlanOutputs::Frames f = outs.place(dsrc + fsrc * chunk, chunk);
-            uint8_t *dres = f.dev[0], *dth = f.dev[1], *dwm = f.dev[2];
-            hipError_t e = hipSuccess;
-            if (ysrc) {
-                // planes of the chunk: [m x Y][m x Cb][m x Cr]
-                uint8_t *dy = dsrc, *dcb = dy + yb * chunk, *dcr = dcb + cbb * chunk;
-                auto up = [&](uint8_t *d, size_t dfs, int w, int h, const uint8_t *hsrc, int hstride, size_t hfs) {
-                    if (hstride == w && hfs == dfs) return hipMemcpyAsync(d, hsrc + hfs * i0, dfs * m, hipMemcpyHostToDevice, l->stream);
-                    hipError_t r = hipSuccess;
-                    for (int i = 0; i < m && r == hipSuccess; i++)
-                        r = hipMemcpy2DAsync(d + dfs * i, w, hsrc + hfs * (size_t)(i0 + i), hstride, w, h, hipMemcpyHostToDevice, l->stream);
-                    return r;
-                };
-                e = up(dy, yb, sw, sh, ysrc->y, ysrc->ystride, ysrc->y_frame_stride);
-                if (e == hipSuccess) e = up(dcb, cbb, cw, ch, ysrc->cb, ysrc->cstride, ysrc->c_frame_stride);
-                if (e == hipSuccess) e = up(dcr, cbb, cw, ch, ysrc->cr, ysrc->cstride, ysrc->c_frame_stride);
-                if (e != hipSuccess) { set_error("upload failed: %s", hipGetErrorString(e)); rc = IPX_ERR_HIP; break; }
-                ipx_ycbcr_batch d;
-                d.y = dy; d.cb = dcb; d.cr = dcr; d.ystride = sw; d.cstride = cw; d.y_frame_stride = yb; d.c_frame_stride = cbb;
-                d.ratio = ysrc->ratio;
-                rc = ipx_plan_run_dev_ycbcr(ctx, l->stream, pl, m, &d, dres, fres, dth, fth, dwm, fwm);
-            } else {
-                if (sstride == sw * 4 && src_frame_stride == fsrc)
-                    e = hipMemcpyAsync(dsrc, src + (size_t)i0 * src_frame_stride, fsrc * m, hipMemcpyHostToDevice, l->stream);
-                else
-                    for (int i = 0; i < m && e == hipSuccess; i++)
-                        e = hipMemcpy2DAsync(dsrc + fsrc * i, (size_t)sw * 4, src + (size_t)(i0 + i) * src_frame_stride, sstride,
-                                             (size_t)sw * 4, sh, hipMemcpyHostToDevice, l->stream);
-                if (e != hipSuccess) { set_error("upload failed: %s", hipGetErrorString(e)); rc = IPX_ERR_HIP; break; }
-                rc = ipx_plan_run_dev(ctx, l->stream, pl, m, dsrc, sw * 4, fsrc, dres, fres, dth, fth, dwm, fwm);
-            }
+            BatchSrc d;
+            const hipError_t e = src_upload(host, L, i0, m, dsrc, chunk, l->stream, kCopyWholePlanes, &d);
+            if (e != hipSuccess) { set_error("upload failed: %s", hipGetErrorString(e)); rc = IPX_ERR_HIP; break; }
+            rc = run_dev_src(ctx, l->stream, pl, m, d, f.dev[0], outs.o[0].fs, f.dev[1], outs.o[1].fs, f.dev[2], outs.o[2].fs);
             if (!rc) rc = encode_outputs(ctx, l->stream, outs, f, m, i0, quality, nullptr, mine);
         }
         {
@@ -452,11 +423,8 @@ int ipx_plan_run_host_jpeg(ipx_ctx *ctx, const ipx_plan *pl, int n, const uint8_
                            int quality, ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, ipx_jpeg_result **result) try
 {
     IPX_ENTER(ctx);
-    if (!pl || n < 0 || !src || !result || (long long)sstride < (long long)pl->p.sw * 4) {
-        set_error("ipx_plan_run_host_jpeg: bad argument");
-        return IPX_ERR_INVALID;
-    }
-    return run_host_jpeg_impl(ctx, pl, n, src, sstride, src_frame_stride, nullptr, quality, resize_out, thumb_out, wm_out, result);
+    return run_host_jpeg_impl("ipx_plan_run_host_jpeg", ctx, pl, n, packed_src(kSrcRGBA, src, sstride, src_frame_stride), quality, resize_out, thumb_out,
+                              wm_out, result);
 }
 IPX_CATCH_STATUS
 
@@ -464,12 +432,7 @@ int ipx_plan_run_host_ycbcr_jpeg(ipx_ctx *ctx, const ipx_plan *pl, int n, const 
                                  ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, ipx_jpeg_result **result) try
 {
     IPX_ENTER(ctx);
-    if (!pl || n < 0 || !result || !src || !src->y || !src->cb || !src->cr || src->ratio < 0 || src->ratio > IPX_YCBCR_440 ||
-        src->ystride < pl->p.sw) {
-        set_error("ipx_plan_run_host_ycbcr_jpeg: bad argument");
-        return IPX_ERR_INVALID;
-    }
-    return run_host_jpeg_impl(ctx, pl, n, nullptr, 0, 0, src, quality, resize_out, thumb_out, wm_out, result);
+    return run_host_jpeg_impl("ipx_plan_run_host_ycbcr_jpeg", ctx, pl, n, ycbcr_src(src), quality, resize_out, thumb_out, wm_out, result);
 }
 IPX_CATCH_STATUS
 
@@ -992,12 +955,11 @@ static int run_jpeg_jpeg_one(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_
     for (int i0 = 0; i0 < n && !rc; i0 += chunk) {
         const int m = std::min(chunk, n - i0);
         const PlanOutputs::Frames f = outs.place((uint8_t *)(((uintptr_t)lane->dev + 255) & ~(uintptr_t)255), chunk);
-        const size_t fres = outs.o[0].fs, fth = outs.o[1].fs, fwm = outs.o[2].fs;
-        ipx_ycbcr_batch d = planes;
-        d.y += planes.y_frame_stride * i0;
-        if (d.cb) { d.cb += planes.c_frame_stride * i0; d.cr += planes.c_frame_stride * i0; }
-        if (planes.ratio == IPX_GRAY) rc = ipx_plan_run_dev_gray(ctx, s, pl, m, d.y, d.ystride, d.y_frame_stride, f.dev[0], fres, f.dev[1], fth, f.dev[2], fwm);
-        else rc = ipx_plan_run_dev_ycbcr(ctx, s, pl, m, &d, f.dev[0], fres, f.dev[1], fth, f.dev[2], fwm);
+        BatchSrc d = ycbcr_src(&planes);                      // (ratio IPX_GRAY: only y is set)
+        if (planes.ratio == IPX_GRAY) d.type = kSrcGray;
+        d.plane[0] += d.frame_stride[0] * i0;
+        if (d.plane[1]) { d.plane[1] += d.frame_stride[1] * i0; d.plane[2] += d.frame_stride[1] * i0; }
+        rc = run_dev_src(ctx, s, pl, m, d, f.dev[0], outs.o[0].fs, f.dev[1], outs.o[1].fs, f.dev[2], outs.o[2].fs);
         if (!rc) rc = encode_outputs(ctx, s, outs, f, m, i0, quality, status, res);
     }
     (void)hipStreamSynchronize(s);

@@ -795,24 +795,18 @@ int ipx_png_encode_rgba8(ipx_ctx *ctx, const uint8_t *pix, int w, int h, int str
 IPX_CATCH_STATUS
 
 // The PNG task's GPU leg (resize.go:83, thumbnail.go:73, watermark.go:71 with png.Encode): chunks of RGBA frames go up, the operators
-// run (ipx_plan_run_dev), every output is PNG-encoded in HBM; only the streams come back, into pinned blocks owned by *result.
+// run, every output is PNG-encoded in HBM; only the streams come back, into pinned blocks owned by *result.
 int ipx_plan_run_host_png(ipx_ctx *ctx, const ipx_plan *pl, int n, const uint8_t *src, int sstride, size_t src_frame_stride,
                           ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, ipx_jpeg_result **result) try
 {
     IPX_ENTER(ctx);
-    if (!pl || n < 0 || !src || !result || (long long)sstride < (long long)pl->p.sw * 4) {
-        set_error("ipx_plan_run_host_png: bad argument");
-        return IPX_ERR_INVALID;
-    }
+    if (!result) { set_error("ipx_plan_run_host_png: bad argument"); return IPX_ERR_INVALID; }
     *result = nullptr;
-    if (!frame_span_ok(pl->p.sw, pl->p.sh, sstride, 4)) {
-        set_error("ipx_plan_run_host_png: %dx%d frames with a row stride of %d bytes are beyond the span the kernels address",
-                  pl->p.sw, pl->p.sh, sstride);
-        return IPX_ERR_UNSUPPORTED;
-    }
-    if (n == 0) return IPX_OK;
-    const int sw = pl->p.sw, sh = pl->p.sh;
-    const size_t fsrc = align256((size_t)sw * sh * 4);
+    const BatchSrc host = packed_src(kSrcRGBA, src, sstride, src_frame_stride);
+    const int rc0 = src_check("ipx_plan_run_host_png", pl, host, n, false);
+    if (rc0 || n == 0) return rc0;
+    const SrcLayout L = src_layout(pl, host);
+    const size_t fsrc = L.frame_bytes();
     const PlanOutputs outs(pl, resize_out, thumb_out, wm_out, Codec::Png, Codec::Png, Codec::Png);
     const size_t per_frame = fsrc + outs.frame_bytes();
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n, (size_t)env_int("IPX_HOST_CHUNK_PNG", 64),
@@ -827,11 +821,10 @@ int ipx_plan_run_host_png(ipx_ctx *ctx, const ipx_plan *pl, int n, const uint8_t
         uint8_t *dsrc, *dout = nullptr;
         IPX_HIP(mem.get(&dsrc, fsrc * m));
         if (outs.frame_bytes()) IPX_HIP(mem.get(&dout, outs.frame_bytes() * m));
-        for (int i = 0; i < m; i++)
-            IPX_HIP(hipMemcpy2DAsync(dsrc + fsrc * i, (size_t)sw * 4, src + src_frame_stride * (size_t)(i0 + i), sstride, (size_t)sw * 4, sh,
-                                     hipMemcpyHostToDevice, s));
+        BatchSrc d;
+        IPX_HIP(src_upload(host, L, i0, m, dsrc, m, s, kCopyFrameRows, &d));
         const PlanOutputs::Frames f = outs.place(dout, m);
-        int rc = ipx_plan_run_dev(ctx, s, pl, m, dsrc, sw * 4, fsrc, f.dev[0], outs.o[0].fs, f.dev[1], outs.o[1].fs, f.dev[2], outs.o[2].fs);
+        int rc = run_dev_src(ctx, s, pl, m, d, f.dev[0], outs.o[0].fs, f.dev[1], outs.o[1].fs, f.dev[2], outs.o[2].fs);
         if (!rc) rc = encode_outputs(ctx, s, outs, f, m, i0, 0, nullptr, res);
         if (rc) return rc;
     }

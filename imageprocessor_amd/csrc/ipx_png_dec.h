@@ -9,11 +9,13 @@
 #include <cstdint>
 #include <vector>
 
+#include "ipx_internal.h"
+
 namespace ipx {
 
 // the frame layouts (IPX_PNG_* of include/ipx.h) and their bytes per pixel
 constexpr int kPngKinds = 7;
-inline int png_kind_bpp(int kind) { static const int b[kPngKinds] = {1, 4, 4, 1, 2, 8, 8}; return b[kind]; }
+inline int png_kind_bpp(int kind) { return src_bpp(src_of_png(kind)); }
 
 // ---- host parse ----------------------------------------------------------------------------------------------------------------
 // What the host reads of one file: the chunk headers up to IEND (never the image data).  status: IPX_OK (the chunks' CRCs and the zlib

@@ -822,27 +822,11 @@ IPX_CATCH_STATUS
 
 // ---- the PNG leg -----------------------------------------------------------------------------------------------------------------
 
-// the plan's operators on m frames of one kind in HBM (the matching ipx_plan_run_dev_*)
-static int png_run_ops(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, int kind, int m, const uint8_t *src, size_t fs, const uint8_t *pal,
-                       uint8_t *dres, size_t fres, uint8_t *dth, size_t fth, uint8_t *dwm, size_t fwm)
-{
-    const int w = pl->p.sw;
-    switch (kind) {
-    case IPX_PNG_GRAY: return ipx_plan_run_dev_gray(ctx, s, pl, m, src, w, fs, dres, fres, dth, fth, dwm, fwm);
-    case IPX_PNG_NRGBA: return ipx_plan_run_dev_nrgba(ctx, s, pl, m, src, w * 4, fs, dres, fres, dth, fth, dwm, fwm);
-    case IPX_PNG_RGBA: return ipx_plan_run_dev(ctx, s, pl, m, src, w * 4, fs, dres, fres, dth, fth, dwm, fwm);
-    case IPX_PNG_PALETTED: return ipx_plan_run_dev_paletted(ctx, s, pl, m, src, w, fs, pal, dres, fres, dth, fth, dwm, fwm);
-    case IPX_PNG_GRAY16: return ipx_plan_run_dev_deep(ctx, s, pl, m, IPX_DEEP_GRAY16, src, w * 2, fs, dres, fres, dth, fth, dwm, fwm);
-    case IPX_PNG_RGBA64: return ipx_plan_run_dev_deep(ctx, s, pl, m, IPX_DEEP_RGBA64, src, w * 8, fs, dres, fres, dth, fth, dwm, fwm);
-    default: return ipx_plan_run_dev_deep(ctx, s, pl, m, IPX_DEEP_NRGBA64, src, w * 8, fs, dres, fres, dth, fth, dwm, fwm);
-    }
-}
-
 extern "C" {
 
 // The PNG task's GPU leg from the uploads on: the host parse of every file, then per kind, per decode group (IPX_HOST_CHUNK_PNG_DEC
 // files, at most ~4 GiB of frames): upload, CRC, inflate and unfilter into HBM; then per chunk of IPX_HOST_CHUNK_PNG frames the
-// matching ipx_plan_run_dev_* and png.Encode of all three outputs.  The operators run on every slot of a chunk (a failed file's slot
+// operators on frames of that kind (run_dev_src) and png.Encode of all three outputs.  The operators run on every slot of a chunk (a failed file's slot
 // holds whatever its frame holds); only OK files' streams are handed out.
 int ipx_plan_run_png_png(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, ipx_bytes *resize_out, ipx_bytes *thumb_out,
                          ipx_bytes *wm_out, int *status, ipx_jpeg_result **result) try
@@ -893,8 +877,8 @@ int ipx_plan_run_png_png(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_byte
                 uint8_t *dout = nullptr;
                 if (per_out) IPX_HIP(omem.get(&dout, per_out * cm));
                 const PlanOutputs::Frames f = outs.place(dout, cm);
-                rc = png_run_ops(ctx, s, pl, kind, cm, dfr + fs * c0, fs, dpal ? dpal + (size_t)1024 * c0 : nullptr, f.dev[0], outs.o[0].fs, f.dev[1],
-                                 outs.o[1].fs, f.dev[2], outs.o[2].fs);
+                const BatchSrc d = packed_src(src_of_png(kind), dfr + fs * c0, sw * kb, fs, dpal ? dpal + (size_t)1024 * c0 : nullptr);
+                rc = run_dev_src(ctx, s, pl, cm, d, f.dev[0], outs.o[0].fs, f.dev[1], outs.o[1].fs, f.dev[2], outs.o[2].fs);
                 if (!rc) rc = encode_outputs(ctx, s, outs, f, cm, 0, 0, status, res, idx.data() + c0);
                 if (rc) return rc;
             }

@@ -66,16 +66,7 @@ struct ipx_pool {
 namespace {
 
 // bytes per pixel of a pixel job's frames; 0 for a kind that is none
-int pixel_job_bpp(int kind)
-{
-    switch (kind) {
-    case IPX_JOB_RGBA8: case IPX_JOB_NRGBA8: case IPX_JOB_CMYK: return 4;
-    case IPX_JOB_GRAY8: return 1;
-    case IPX_JOB_GRAY16: return 2;
-    case IPX_JOB_NRGBA64: case IPX_JOB_RGBA64: return 8;
-    default: return 0;
-    }
-}
+int pixel_job_bpp(int kind) { return src_of_job(kind) < 0 ? 0 : src_bpp(src_of_job(kind)); }
 
 double chunk_cost(const JobState &j, int m)
 {
@@ -140,9 +131,9 @@ int run_pixel_chunk(Slot &s, Feeder &f, const JobState &j, ipx_plan *plan, int i
     ipx_plan_info info;
     int rc = ipx_plan_query(plan, &info);
     if (rc) return rc;
-    const int sw = j.ops.p.sw, sh = j.ops.p.sh;
-    const int bpp = pixel_job_bpp(q.kind);
-    const size_t fsrc = align256((size_t)sw * sh * bpp);
+    const BatchSrc host = packed_src(src_of_job(q.kind), q.src, q.sstride, q.src_frame_stride);      // (job_check has seen the arguments)
+    const SrcLayout L = src_layout(plan, host);
+    const size_t fsrc = L.frame_bytes();
     const size_t fres = q.resize_out ? align256(info.resize_bytes) : 0, fth = q.thumb_out ? align256(info.thumb_bytes) : 0;
     const size_t fwm = q.wm_out ? align256(info.wm_bytes) : 0;
     // outputs in pinned memory are written by the kernels themselves, over the link (run_host_packed in ipx_runtime.hip has the why)
@@ -163,30 +154,17 @@ int run_pixel_chunk(Slot &s, Feeder &f, const JobState &j, ipx_plan *plan, int i
         dth = vth; sth = q.thumb_frame_stride;
         dwm = vwm; swm = q.wm_frame_stride;
     }
-    hipError_t e = hipSuccess;
     // direct outputs: the upload goes on the slot's shared stream and the feeder's own stream (kernels) waits for it
     const hipStream_t up = direct && s.up_stream && f.uploaded ? s.up_stream : f.stream;
-    if (q.sstride == sw * bpp)
-        for (int i = 0; i < m && e == hipSuccess; i++)
-            e = hipMemcpyAsync(dsrc + fsrc * i, q.src + (size_t)(i0 + i) * q.src_frame_stride, (size_t)sw * sh * bpp, hipMemcpyHostToDevice, up);
-    else for (int i = 0; i < m && e == hipSuccess; i++)
-        e = hipMemcpy2DAsync(dsrc + fsrc * i, (size_t)sw * bpp, q.src + (size_t)(i0 + i) * q.src_frame_stride, q.sstride, (size_t)sw * bpp, sh,
-                             hipMemcpyHostToDevice, up);
+    BatchSrc d;
+    hipError_t e = src_upload(host, L, i0, m, dsrc, m, up, kCopyFrames, &d);
     if (e == hipSuccess && up != f.stream) {
         e = hipEventRecord(f.uploaded, up);
         if (e == hipSuccess) e = hipStreamWaitEvent(f.stream, f.uploaded, 0);
     }
     if (e != hipSuccess && up != f.stream) (void)hipStreamSynchronize(up);
     if (e != hipSuccess) { (void)hipStreamSynchronize(f.stream); set_error("pool: upload failed: %s", hipGetErrorString(e)); return IPX_ERR_HIP; }
-    switch (q.kind) {
-    case IPX_JOB_RGBA8: rc = ipx_plan_run_dev(s.ctx, f.stream, plan, m, dsrc, sw * 4, fsrc, dres, sres, dth, sth, dwm, swm); break;
-    case IPX_JOB_NRGBA8: rc = ipx_plan_run_dev_nrgba(s.ctx, f.stream, plan, m, dsrc, sw * 4, fsrc, dres, sres, dth, sth, dwm, swm); break;
-    case IPX_JOB_GRAY8: rc = ipx_plan_run_dev_gray(s.ctx, f.stream, plan, m, dsrc, sw, fsrc, dres, sres, dth, sth, dwm, swm); break;
-    default:
-        rc = ipx_plan_run_dev_deep(s.ctx, f.stream, plan, m, q.kind == IPX_JOB_NRGBA64 ? IPX_DEEP_NRGBA64 : q.kind == IPX_JOB_RGBA64 ? IPX_DEEP_RGBA64 :
-                                   q.kind == IPX_JOB_GRAY16 ? IPX_DEEP_GRAY16 : IPX_DEEP_CMYK, dsrc, sw * bpp, fsrc, dres, sres, dth, sth, dwm, swm);
-        break;
-    }
+    rc = run_dev_src(s.ctx, f.stream, plan, m, d, dres, sres, dth, sth, dwm, swm);
     if (rc) { (void)hipStreamSynchronize(f.stream); return rc; }
     for (int i = 0; i < m && e == hipSuccess && !direct; i++) {
         if (dres && info.resize_bytes) e = hipMemcpyAsync(q.resize_out + (size_t)(i0 + i) * q.resize_frame_stride, dres + fres * i, info.resize_bytes, hipMemcpyDeviceToHost, f.stream);

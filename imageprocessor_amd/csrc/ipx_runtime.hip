@@ -806,8 +806,7 @@ int stage_and_run(ipx_ctx *ctx, uint8_t *dst, int dw, int dh, int dstride, size_
 bool ycbcr_ok(const ipx_ycbcr *y, int *cw, int *ch)
 {
     if (!y || !y->y || !y->cb || !y->cr || y->w <= 0 || y->h <= 0 || y->ratio < 0 || y->ratio > IPX_YCBCR_440) return false;
-    *cw = (y->ratio == IPX_YCBCR_422 || y->ratio == IPX_YCBCR_420) ? (y->w + 1) / 2 : y->w;   // image.NewYCbCr
-    *ch = (y->ratio == IPX_YCBCR_420 || y->ratio == IPX_YCBCR_440) ? (y->h + 1) / 2 : y->h;
+    chroma_size(y->ratio, y->w, y->h, cw, ch);
     return y->ystride >= y->w && y->cstride >= *cw;
 }
 
@@ -858,7 +857,7 @@ IPX_CATCH_STATUS
 // a deep frame from host memory -> frame of taps in the lane's scratch (the Pix copy sits behind it)
 static int upload_deep(hipStream_t s, const uint8_t *src, int sw, int sh, int sstride, int kind, uint8_t *dsrc, DevSrc *out)
 {
-    const int bpp = kind == IPX_DEEP_GRAY16 ? 2 : (kind == IPX_DEEP_CMYK ? 4 : 8);
+    const int bpp = src_bpp(src_of_deep(kind));
     uint8_t *pix = dsrc + align256((size_t)sw * sh * 8);
     IPX_HIP(hipMemcpy2DAsync(pix, (size_t)sw * bpp, src, sstride, (size_t)sw * bpp, sh, hipMemcpyHostToDevice, s));
     IPX_HIP(launch_deep_expand(dsrc, 0, pix, sw * bpp, 0, kind, sw, sh, 1, s));
@@ -867,12 +866,9 @@ static int upload_deep(hipStream_t s, const uint8_t *src, int sw, int sh, int ss
 }
 static int deep_args_status(const char *who, const void *dst, int dw, int dh, int dstride, const void *src, int sw, int sh, int sstride, int kind)
 {
-    if (kind != IPX_DEEP_NRGBA64 && kind != IPX_DEEP_RGBA64 && kind != IPX_DEEP_GRAY16 && kind != IPX_DEEP_CMYK) {
-        set_error("%s: unknown source type %d", who, kind);
-        return IPX_ERR_INVALID;
-    }
+    if (src_of_deep(kind) < 0) { set_error("%s: unknown source type %d", who, kind); return IPX_ERR_INVALID; }
     int rc = frame_status(who, "destination", dst, dw, dh, dstride);
-    if (!rc) rc = frame_status(who, "source", src, sw, sh, sstride, kind == IPX_DEEP_GRAY16 ? 2 : (kind == IPX_DEEP_CMYK ? 4 : 8));
+    if (!rc) rc = frame_status(who, "source", src, sw, sh, sstride, src_bpp(src_of_deep(kind)));
     if (!rc) rc = frame_status(who, "source", src, sw, sh, (long long)sw * 8, 8);       // the frame of taps
     return rc;
 }
@@ -1170,14 +1166,7 @@ int ipx_plan_query(const ipx_plan *plan, ipx_plan_info *info) try
 }
 IPX_CATCH_STATUS
 
-// the source rows of a batch entry: stride given by the caller, size by the plan
-static int plan_src_status(const char *who, const ipx_plan *pl, long long stride, int bpp)
-{
-    if (frame_span_ok(pl->p.sw, pl->p.sh, stride, bpp)) return IPX_OK;
-    set_error("%s: %dx%d frames with a row stride of %lld bytes are beyond the 2 GiB span the kernels address", who, pl->p.sw, pl->p.sh, stride);
-    return IPX_ERR_UNSUPPORTED;
-}
-#define IPX_PLAN_SRC(who, pl, stride, bpp) do { const int rc_ = plan_src_status(who, pl, stride, bpp); if (rc_) return rc_; } while (0)
+}  // extern "C"
 
 // ---- one batch of decoded frames of any source type through a plan --------------------------------------------------------------------
 // The one-pass kernel where it is built for the source type and the shapes; else per output: draw.Draw into the watermark frames
@@ -1308,46 +1297,148 @@ static int run_dev_any(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, int n, c
     return IPX_OK;
 }
 
-int ipx_plan_run_dev(ipx_ctx *ctx, void *stream, const ipx_plan *pl, int n, const uint8_t *src,
-                     int sstride, size_t src_frame_stride, uint8_t *resize_out,
-                     size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride,
-                     uint8_t *wm_out, size_t wm_frame_stride) try
+// ---- the input side of the plan entries: one description of a source batch (BatchSrc), checked, laid out, uploaded and dispatched here ----
+
+int src_check(const char *who, const ipx_plan *pl, const BatchSrc &b, int n, bool in_hbm)
 {
-    IPX_ENTER(ctx);
-    if (!pl || n < 0 || !src || (long long)sstride < (long long)pl->p.sw * 4) {
-        set_error("ipx_plan_run_dev: bad argument");
-        return IPX_ERR_INVALID;
+    if (b.type < 0 || b.type >= kSrcTypes) { set_error("%s: unknown source type", who); return IPX_ERR_INVALID; }
+    const int bpp = src_bpp(b.type);
+    bool ok = pl && n >= 0 && b.plane[0] && (long long)b.stride[0] >= (long long)pl->p.sw * bpp;
+    if (ok && b.type == kSrcYCbCr) {
+        int cw = 0, ch = 0;
+        chroma_size(b.ratio, pl->p.sw, pl->p.sh, &cw, &ch);
+        ok = b.plane[1] && b.plane[2] && b.ratio >= 0 && b.ratio <= IPX_YCBCR_440 && b.stride[1] >= cw;
     }
-    IPX_PLAN_SRC("ipx_plan_run_dev", pl, sstride, 4);
-    if (n == 0) return IPX_OK;
-    if (n > 65535) { set_error("ipx_plan_run_dev: at most 65535 frames per call"); return IPX_ERR_UNSUPPORTED; }
-    DevSrc d = rgba_src(src, pl->p.sw, pl->p.sh, sstride);
-    d.nframes = n; d.frame_stride = src_frame_stride;
-    return run_dev_any(ctx, stream ? (hipStream_t)stream : ctx->stream, pl, n, d, resize_out, resize_frame_stride, thumb_out, thumb_frame_stride,
+    if (ok && b.type == kSrcPaletted) ok = b.palettes && !(in_hbm && ((uintptr_t)b.palettes & 3));
+    if (ok && in_hbm && b.type >= kSrcNRGBA64)       // the expansion reads whole 16-bit samples (CMYK: whole pixels)
+        ok = !(((uintptr_t)b.plane[0] | (uintptr_t)b.stride[0] | b.frame_stride[0]) & (b.type == kSrcCMYK ? 3 : 1));
+    if (!ok) { set_error("%s: bad argument", who); return IPX_ERR_INVALID; }
+    const int sw = pl->p.sw, sh = pl->p.sh;
+    if (!frame_span_ok(sw, sh, b.stride[0], bpp) || (b.type == kSrcYCbCr && !frame_span_ok(sw, sh, b.stride[1], 1)) ||
+        (b.type >= kSrcNRGBA64 && !frame_span_ok(sw, sh, (long long)sw * 8, 8))) {
+        set_error("%s: %dx%d frames with row strides of %d / %d bytes are beyond the 2 GiB span the kernels address", who, sw, sh, b.stride[0], b.stride[1]);
+        return IPX_ERR_UNSUPPORTED;
+    }
+    if (in_hbm && n > 65535) { set_error("%s: at most 65535 frames per call", who); return IPX_ERR_UNSUPPORTED; }
+    return IPX_OK;
+}
+
+SrcLayout src_layout(const ipx_plan *pl, const BatchSrc &b, size_t (*frame_rule)(size_t))
+{
+    SrcLayout L{};
+    int cw = 0, ch = 0;
+    if (b.type == kSrcYCbCr) chroma_size(b.ratio, pl->p.sw, pl->p.sh, &cw, &ch);
+    L.planes = b.type == kSrcYCbCr ? 3 : 1;
+    L.row[0] = (size_t)pl->p.sw * src_bpp(b.type); L.h[0] = pl->p.sh; L.fs[0] = frame_rule(L.row[0] * L.h[0]);
+    L.row[1] = cw; L.h[1] = ch; L.fs[1] = frame_rule((size_t)cw * ch);
+    L.pal = b.type == kSrcPaletted ? 1024 : 0;
+    return L;
+}
+
+hipError_t src_upload(const BatchSrc &host, const SrcLayout &L, int i0, int m, uint8_t *scratch, int slots, hipStream_t s, const CopyPolicy &cp,
+                      BatchSrc *in_hbm)
+{
+    *in_hbm = host;
+    hipError_t e = hipSuccess;
+    uint8_t *d = scratch;
+    for (int p = 0; p < L.planes && e == hipSuccess; p++) {
+        const int k = p ? 1 : 0;
+        const size_t row = L.row[k], dfs = L.fs[k], hfs = host.frame_stride[k], bytes = dfs * m;
+        const uint8_t *h = host.plane[p] + hfs * i0;
+        const bool tight_rows = (size_t)host.stride[k] == row;
+        if (cp.join_frames && tight_rows && hfs == dfs) {
+            const size_t piece = cp.piece ? cp.piece : bytes;
+            for (size_t o = 0; o < bytes && e == hipSuccess; o += piece) e = hipMemcpyAsync(d + o, h + o, std::min(piece, bytes - o), hipMemcpyHostToDevice, s);
+        } else {
+            for (int i = 0; i < m && e == hipSuccess; i++)
+                e = cp.join_rows && tight_rows ? hipMemcpyAsync(d + dfs * i, h + hfs * i, row * L.h[k], hipMemcpyHostToDevice, s)
+                                               : hipMemcpy2DAsync(d + dfs * i, row, h + hfs * i, host.stride[k], row, L.h[k], hipMemcpyHostToDevice, s);
+        }
+        in_hbm->plane[p] = d; in_hbm->stride[k] = (int)row; in_hbm->frame_stride[k] = dfs;
+        d += dfs * slots;
+    }
+    if (L.pal && e == hipSuccess) {
+        e = hipMemcpyAsync(d, host.palettes + L.pal * i0, L.pal * m, hipMemcpyHostToDevice, s);
+        in_hbm->palettes = d;
+    }
+    return e;
+}
+
+int run_dev_src(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, int m, const BatchSrc &b, uint8_t *resize_out, size_t resize_frame_stride,
+                uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out, size_t wm_frame_stride)
+{
+    // (a leg's chunk size may come from an environment knob: the limit of one launch is held here too)
+    if (m > 65535) { set_error("at most 65535 frames per device call"); return IPX_ERR_UNSUPPORTED; }
+    const int sw = pl->p.sw, sh = pl->p.sh;
+    AsyncFree mem{s, {}};
+    DevSrc d;
+    d.pix = b.plane[0]; d.stride = b.stride[0]; d.frame_stride = b.frame_stride[0]; d.w = sw; d.h = sh; d.nframes = m;
+    switch (b.type) {
+    case kSrcRGBA: break;
+    case kSrcNRGBA: d.kind = IPX_SRC_NRGBA; break;
+    case kSrcYCbCr:
+        d.kind = IPX_SRC_YCBCR; d.cb = b.plane[1]; d.cr = b.plane[2]; d.cstride = b.stride[1]; d.ratio = b.ratio; d.c_frame_stride = b.frame_stride[1];
+        break;
+    case kSrcGray:
+        // scaleX_Gray / drawGray read a pixel as (y, y, y, 0xff), tmp alpha 1.  A YCbCr pixel with Cb = Cr = 128 converts to exactly that in both of the
+        // reference's conversions -- color.YCbCrToRGB: (y*0x10101) >> 16 = y; color.YCbCr.RGBA: (y*0x10101) >> 8 = y*0x101 = color.Gray.RGBA -- and
+        // scaleX_YCbCr4xx writes the same tmp alpha, so the batch runs as 4:4:4 planes with a stride-0 row of 128s as both chroma planes.
+        if ((size_t)sw + 8 > ipx_ctx::kFlatChromaBytes) { set_error("Gray frames wider than %zu pixels", ipx_ctx::kFlatChromaBytes - 8); return IPX_ERR_UNSUPPORTED; }
+        d.kind = IPX_SRC_YCBCR; d.cb = d.cr = ctx->flat_chroma; d.ratio = IPX_YCBCR_444;
+        break;
+    case kSrcPaletted: {    // Paletted.At(x, y) is the palette's color.NRGBA: one expansion pass, then the NRGBA route
+        const size_t fs = align256((size_t)sw * sh * 4);
+        uint8_t *nrgba = nullptr;
+        IPX_HIP(mem.get(&nrgba, fs * m));
+        const hipError_t e = launch_palette_expand(nrgba, fs, b.plane[0], b.stride[0], b.frame_stride[0], b.palettes, sw, sh, m, s);
+        if (e != hipSuccess) { set_error("palette expansion failed: %s", hipGetErrorString(e)); return IPX_ERR_HIP; }
+        d.kind = IPX_SRC_NRGBA; d.pix = nrgba; d.stride = sw * 4; d.frame_stride = fs;
+        break;
+    }
+    default: {
+        // The deep source types: one expansion pass to frames of 16-bit taps (what every consumer of these types reads: At(x, y).RGBA()), then
+        // the batch runner on them: top bytes into the watermark frames (drawRGBA / drawCMYK with Src), the scales from the taps.
+        const size_t tfs = align256((size_t)sw * sh * 8);
+        uint8_t *taps = nullptr;
+        IPX_HIP(mem.get(&taps, tfs * m));
+        const hipError_t e = launch_deep_expand(taps, tfs, b.plane[0], b.stride[0], b.frame_stride[0], b.type - kSrcNRGBA64, sw, sh, m, s);
+        if (e != hipSuccess) { set_error("tap expansion failed: %s", hipGetErrorString(e)); return IPX_ERR_HIP; }
+        d.kind = IPX_SRC_TAP64; d.pix = taps; d.stride = sw * 8; d.frame_stride = tfs;
+        d.le_alpha = b.type != kSrcRGBA64;     // (a premultiplied RGBA64 file may hold a colour above its alpha; the others cannot)
+        break;
+    }
+    }
+    return run_dev_any(ctx, s, pl, m, d, resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
+}
+
+// an entry on frames in HBM: the check, then the operators on the caller's stream (null: the context's)
+static int run_dev_entry(const char *who, ipx_ctx *ctx, void *stream, const ipx_plan *pl, int n, const BatchSrc &b, uint8_t *resize_out,
+                         size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out, size_t wm_frame_stride)
+{
+    const int rc = src_check(who, pl, b, n, true);
+    if (rc || n == 0) return rc;
+    return run_dev_src(ctx, stream ? (hipStream_t)stream : ctx->stream, pl, n, b, resize_out, resize_frame_stride, thumb_out, thumb_frame_stride,
                        wm_out, wm_frame_stride);
 }
-IPX_CATCH_STATUS
 
-// Frames in host memory, any packed source type: chunks over the lanes so that H2D of one chunk, the kernel of another and D2H of
-// a third overlap.  kind: IPX_SRC_RGBA / IPX_SRC_NRGBA (4 bytes per pixel), IPX_GRAY (1), kPalettedKind (1 + 1 KiB palette per frame).
-constexpr int kPalettedKind = 100;
-constexpr int kDeepKind = 200;    // + IPX_DEEP_*
-static int deep_bpp(int kind) { return kind == IPX_DEEP_GRAY16 ? 2 : (kind == IPX_DEEP_CMYK ? 4 : 8); }
-static int run_host_packed(ipx_ctx *ctx, const ipx_plan *pl, int n, int kind, const uint8_t *src, int sstride, size_t src_frame_stride,
-                           const uint8_t *palettes, uint8_t *resize_out, size_t resize_frame_stride, uint8_t *thumb_out,
-                           size_t thumb_frame_stride, uint8_t *wm_out, size_t wm_frame_stride, const char *who)
+// device-side frame strides of run_host_packed: tight when that keeps rows 16-byte aligned (then a whole chunk moves with one copy per
+// direction and buffer), padded to 256 otherwise
+static size_t tight16_or_align256(size_t bytes) { return (bytes & 15) == 0 ? bytes : align256(bytes); }
+
+// Frames in host memory, any single-plane source type: chunks over the lanes so that H2D of one chunk, the kernel of another and D2H of
+// a third overlap.
+static int run_host_packed(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n, const BatchSrc &host, uint8_t *resize_out,
+                           size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out, size_t wm_frame_stride)
 {
-    const int sw = pl->p.sw, sh = pl->p.sh;
-    const int bpp = kind >= kDeepKind ? deep_bpp(kind - kDeepKind) : (kind == IPX_SRC_RGBA || kind == IPX_SRC_NRGBA ? 4 : 1);
-    // device-side frame strides: tight when that keeps rows 16-byte aligned (then a whole chunk moves
-    // with one copy per direction and buffer), padded to 256 otherwise
-    auto dstride = [](size_t bytes) { return (bytes & 15) == 0 ? bytes : align256(bytes); };
-    const size_t fsrc = dstride((size_t)sw * sh * bpp);
-    const size_t fpal = kind == kPalettedKind ? 1024 : 0;
+    int rc = src_check(who, pl, host, n, false);
+    if (rc || n == 0) return rc;
+    const auto dstride = tight16_or_align256;
+    const SrcLayout L = src_layout(pl, host, dstride);
+    const size_t fsrc = L.frame_bytes();       // (the palette included)
     const size_t fres = resize_out ? dstride(pl->info.resize_bytes) : 0;
     const size_t fth = thumb_out ? dstride(pl->info.thumb_bytes) : 0;
     const size_t fwm = wm_out ? dstride(pl->info.wm_bytes) : 0;
-    const size_t per_frame = fsrc + fpal + fres + fth + fwm;
+    const size_t per_frame = fsrc + fres + fth + fwm;
     // chunk the batch so that H2D of one chunk, the kernel of another and D2H of a third overlap on
     // different lanes (one stream each); several chunks per lane keep all three engines busy
     const int nl = (int)ctx->lanes.size();
@@ -1373,7 +1464,6 @@ static int run_host_packed(ipx_ctx *ctx, const ipx_plan *pl, int n, int kind, co
             for (auto &l : ctx->lanes) if (!l.busy && (int)lanes.size() < want) { l.busy = true; lanes.push_back(&l); }
         }
     }
-    int rc = IPX_OK;
     hipError_t e = hipSuccess;
     const double t_lock = trace ? ms_since(t_in) : 0;
     for (auto *l : lanes) {
@@ -1381,15 +1471,14 @@ static int run_host_packed(ipx_ctx *ctx, const ipx_plan *pl, int n, int kind, co
         if (rc) break;
     }
     const double t_res = trace ? ms_since(t_in) : 0;
-    const bool src_tight = sstride == sw * bpp && src_frame_stride == fsrc;
     // A single small frame in PAGEABLE memory (the per-operator seam from a caller that does not pin): the runtime's staged path for
     // small pageable copies blocks the enqueueing thread behind other streams' work every few contexts (a 640x360 call then takes as
     // long as the batch running beside it; tools/seam_hunt.py), larger ones it pins on the fly and never did.  Such a call goes
     // through a pinned bounce buffer of its lane instead: two host memcpys of < 1 ms.
     bool bounce = false;
-    if (!rc && nchunks == 1 && n == 1 && kind != kPalettedKind && per_frame <= ((size_t)8 << 20)) {
+    if (!rc && nchunks == 1 && n == 1 && !L.pal && per_frame <= ((size_t)8 << 20)) {
         hipPointerAttribute_t at;
-        const bool pinned = hipPointerGetAttributes(&at, src) == hipSuccess && at.type == hipMemoryTypeHost;
+        const bool pinned = hipPointerGetAttributes(&at, host.plane[0]) == hipSuccess && at.type == hipMemoryTypeHost;
         (void)hipGetLastError();
         if (!pinned) {
             Lane &l = *lanes[0];
@@ -1408,6 +1497,7 @@ static int run_host_packed(ipx_ctx *ctx, const ipx_plan *pl, int n, int kind, co
     // pipeline over the lanes it took: every upload on the first lane's stream, every kernel on the third's, every download on the
     // second's, the lanes' scratch buffers as the slots chunks rotate through, events between the stages.
     const size_t piece = (size_t)std::max(1, env_int("IPX_COPY_PIECE_MB", 32)) << 20;
+    const CopyPolicy up_policy{true, false, piece};
     auto copy_pieces = [&](uint8_t *dst, const uint8_t *from, size_t bytes, hipMemcpyKind k, hipStream_t st) {
         hipError_t r = hipSuccess;
         for (size_t o = 0; o < bytes && r == hipSuccess; o += piece) r = hipMemcpyAsync(dst + o, from + o, std::min(piece, bytes - o), k, st);
@@ -1449,7 +1539,6 @@ static int run_host_packed(ipx_ctx *ctx, const ipx_plan *pl, int n, int kind, co
         uint8_t *dres = fres ? dsrc + fsrc * chunk : nullptr;
         uint8_t *dth = fth ? dsrc + (fsrc + fres) * chunk : nullptr;
         uint8_t *dwm = fwm ? dsrc + (fsrc + fres + fth) * chunk : nullptr;
-        uint8_t *dpal = fpal ? dsrc + (fsrc + fres + fth + fwm) * chunk : nullptr;
         size_t sres = fres, sth = fth, swm = fwm;
         if (direct) {
             dres = fres ? vres + (size_t)i0 * resize_frame_stride : nullptr; sres = resize_frame_stride;
@@ -1459,27 +1548,18 @@ static int run_host_packed(ipx_ctx *ctx, const ipx_plan *pl, int n, int kind, co
         // reuse of a lane's scratch: chunk c waits until chunk c - S has been downloaded (stream order when one stream does it all)
         if (staged && c >= (int)S) e = hipStreamWaitEvent(up, l.ev[2], 0);
         if (e != hipSuccess) break;
+        BatchSrc d;
         if (bounce) {
-            for (int y = 0; y < sh; y++) memcpy(l.pin + (size_t)y * sw * bpp, src + (size_t)y * sstride, (size_t)sw * bpp);
-            e = hipMemcpyAsync(dsrc, l.pin, (size_t)sw * sh * bpp, hipMemcpyHostToDevice, up);
-        } else if (src_tight) {
-            e = copy_pieces(dsrc, src + (size_t)i0 * src_frame_stride, fsrc * m, hipMemcpyHostToDevice, up);
+            for (int y = 0; y < L.h[0]; y++) memcpy(l.pin + y * L.row[0], host.plane[0] + (size_t)y * host.stride[0], L.row[0]);
+            e = hipMemcpyAsync(dsrc, l.pin, L.row[0] * L.h[0], hipMemcpyHostToDevice, up);
+            d = packed_src(host.type, dsrc, (int)L.row[0], L.fs[0]);
         } else {
-            for (int i = 0; i < m && e == hipSuccess; i++)
-                e = hipMemcpy2DAsync(dsrc + fsrc * i, (size_t)sw * bpp, src + (size_t)(i0 + i) * src_frame_stride, sstride,
-                                     (size_t)sw * bpp, sh, hipMemcpyHostToDevice, up);
+            e = src_upload(host, L, i0, m, dsrc, chunk, up, up_policy, &d);
         }
-        if (e == hipSuccess && dpal) e = hipMemcpyAsync(dpal, palettes + (size_t)i0 * 1024, (size_t)m * 1024, hipMemcpyHostToDevice, up);
         if (e == hipSuccess && staged) e = hipEventRecord(l.ev[0], up);
         if (e == hipSuccess && staged) e = hipStreamWaitEvent(run, l.ev[0], 0);
         if (e != hipSuccess) break;
-        switch (kind) {
-        case IPX_SRC_RGBA: rc = ipx_plan_run_dev(ctx, run, pl, m, dsrc, sw * 4, fsrc, dres, sres, dth, sth, dwm, swm); break;
-        case IPX_SRC_NRGBA: rc = ipx_plan_run_dev_nrgba(ctx, run, pl, m, dsrc, sw * 4, fsrc, dres, sres, dth, sth, dwm, swm); break;
-        case IPX_GRAY: rc = ipx_plan_run_dev_gray(ctx, run, pl, m, dsrc, sw, fsrc, dres, sres, dth, sth, dwm, swm); break;
-        case kPalettedKind: rc = ipx_plan_run_dev_paletted(ctx, run, pl, m, dsrc, sw, fsrc, dpal, dres, sres, dth, sth, dwm, swm); break;
-        default: rc = ipx_plan_run_dev_deep(ctx, run, pl, m, kind - kDeepKind, dsrc, sw * bpp, fsrc, dres, sres, dth, sth, dwm, swm); break;
-        }
+        rc = run_dev_src(ctx, run, pl, m, d, dres, sres, dth, sth, dwm, swm);
         if (rc) break;
         if (direct) {          // the outputs are where they belong when the kernels have finished
             if (staged) e = hipEventRecord(l.ev[2], run);
@@ -1522,95 +1602,29 @@ static int run_host_packed(ipx_ctx *ctx, const ipx_plan *pl, int n, int kind, co
     return rc;
 }
 
-int ipx_plan_run_host(ipx_ctx *ctx, const ipx_plan *pl, int n, const uint8_t *src, int sstride,
-                      size_t src_frame_stride, uint8_t *resize_out, size_t resize_frame_stride,
-                      uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out,
+extern "C" {
+
+// The twelve pixel-out batch entries: each describes its source (BatchSrc) and hands it on -- frames in HBM to run_dev_entry, frames in
+// host memory to run_host_packed (YCbCr planes: the entry's own single-lane schedule), which check them by the one rule (src_check).  The alignment the kernels need of a deep type's pixels
+// and of palettes is asked of HBM sources only: host frames are re-packed into aligned scratch on their way up.
+
+int ipx_plan_run_dev(ipx_ctx *ctx, void *stream, const ipx_plan *pl, int n, const uint8_t *src, int sstride, size_t src_frame_stride,
+                     uint8_t *resize_out, size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out,
+                     size_t wm_frame_stride) try
+{
+    IPX_ENTER(ctx);
+    return run_dev_entry("ipx_plan_run_dev", ctx, stream, pl, n, packed_src(kSrcRGBA, src, sstride, src_frame_stride),
+                         resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
+}
+IPX_CATCH_STATUS
+
+int ipx_plan_run_host(ipx_ctx *ctx, const ipx_plan *pl, int n, const uint8_t *src, int sstride, size_t src_frame_stride,
+                      uint8_t *resize_out, size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out,
                       size_t wm_frame_stride) try
 {
     IPX_ENTER(ctx);
-    if (!pl || n < 0 || !src || (long long)sstride < (long long)pl->p.sw * 4) {
-        set_error("ipx_plan_run_host: bad argument");
-        return IPX_ERR_INVALID;
-    }
-    IPX_PLAN_SRC("ipx_plan_run_host", pl, sstride, 4);
-    if (n == 0) return IPX_OK;
-    return run_host_packed(ctx, pl, n, IPX_SRC_RGBA, src, sstride, src_frame_stride, nullptr, resize_out, resize_frame_stride, thumb_out,
-                           thumb_frame_stride, wm_out, wm_frame_stride, "ipx_plan_run_host");
-}
-IPX_CATCH_STATUS
-
-int ipx_plan_run_host_nrgba(ipx_ctx *ctx, const ipx_plan *pl, int n, const uint8_t *src, int sstride, size_t src_frame_stride,
-                            uint8_t *resize_out, size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out,
-                            size_t wm_frame_stride) try
-{
-    IPX_ENTER(ctx);
-    if (!pl || n < 0 || !src || (long long)sstride < (long long)pl->p.sw * 4) { set_error("ipx_plan_run_host_nrgba: bad argument"); return IPX_ERR_INVALID; }
-    IPX_PLAN_SRC("ipx_plan_run_host_nrgba", pl, sstride, 4);
-    if (n == 0) return IPX_OK;
-    return run_host_packed(ctx, pl, n, IPX_SRC_NRGBA, src, sstride, src_frame_stride, nullptr, resize_out, resize_frame_stride, thumb_out,
-                           thumb_frame_stride, wm_out, wm_frame_stride, "ipx_plan_run_host_nrgba");
-}
-IPX_CATCH_STATUS
-
-int ipx_plan_run_host_gray(ipx_ctx *ctx, const ipx_plan *pl, int n, const uint8_t *gray, int stride, size_t frame_stride,
-                           uint8_t *resize_out, size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out,
-                           size_t wm_frame_stride) try
-{
-    IPX_ENTER(ctx);
-    if (!pl || n < 0 || !gray || stride < pl->p.sw) { set_error("ipx_plan_run_host_gray: bad argument"); return IPX_ERR_INVALID; }
-    IPX_PLAN_SRC("ipx_plan_run_host_gray", pl, stride, 1);
-    if (n == 0) return IPX_OK;
-    return run_host_packed(ctx, pl, n, IPX_GRAY, gray, stride, frame_stride, nullptr, resize_out, resize_frame_stride, thumb_out,
-                           thumb_frame_stride, wm_out, wm_frame_stride, "ipx_plan_run_host_gray");
-}
-IPX_CATCH_STATUS
-
-int ipx_plan_run_host_paletted(ipx_ctx *ctx, const ipx_plan *pl, int n, const uint8_t *index, int stride, size_t frame_stride,
-                               const uint8_t *palettes, uint8_t *resize_out, size_t resize_frame_stride, uint8_t *thumb_out,
-                               size_t thumb_frame_stride, uint8_t *wm_out, size_t wm_frame_stride) try
-{
-    IPX_ENTER(ctx);
-    if (!pl || n < 0 || !index || !palettes || stride < pl->p.sw) { set_error("ipx_plan_run_host_paletted: bad argument"); return IPX_ERR_INVALID; }
-    IPX_PLAN_SRC("ipx_plan_run_host_paletted", pl, stride, 1);
-    if (n == 0) return IPX_OK;
-    return run_host_packed(ctx, pl, n, kPalettedKind, index, stride, frame_stride, palettes, resize_out, resize_frame_stride, thumb_out,
-                           thumb_frame_stride, wm_out, wm_frame_stride, "ipx_plan_run_host_paletted");
-}
-IPX_CATCH_STATUS
-
-
-// ---- decoded JPEG batches ---------------------------------------------------------------------------
-// The reference treats a *image.YCbCr source differently per operator:
-//   resize, non-crop thumbnail: scale_RGBA_YCbCr4xx_Src -- every TAP converted to 16 bit, then the lerp;
-//   crop thumbnail: the crop copy converts to RGBA8 first (imageutil.DrawYCbCr), the scale then reads RGBA8;
-//   watermark: draw.Draw converts to RGBA8 (DrawYCbCr), the glyphs go over that.
-// So: one conversion pass into the watermark frame (or scratch), the RGBA band kernel for the crop
-// thumbnail on the converted frames, the glyph composite in place, and a batched YCbCr scale.
-// BandArgs of the fused kernels that convert their source on the fly (ipx_band_conv.hip, ipx_band_nrgba.hip): the plan's tiling, the
-// outputs that are wanted, and per scaled output the conversion rule -- mode 0 = 16-bit taps (resizeImage on the source image itself),
-// mode 1 = 8-bit RGBA first (the crop thumbnail scales the RGBA8 copy cropAndResize made, thumbnail.go:128-131)
-// The text composite as a pass of its own over the watermark frames' text box (composite_kernel) after the band kernel has copied /
-// converted every pixel, instead of inside the band kernel (IPX_FUSED_GLYPHS in ipx_internal.h has the why).
-int ipx_plan_run_dev_ycbcr(ipx_ctx *ctx, void *stream, const ipx_plan *pl, int n, const ipx_ycbcr_batch *src,
-                           uint8_t *resize_out, size_t resize_frame_stride, uint8_t *thumb_out,
-                           size_t thumb_frame_stride, uint8_t *wm_out, size_t wm_frame_stride) try
-{
-    IPX_ENTER(ctx);
-    if (!pl || n < 0 || !src || !src->y || !src->cb || !src->cr || src->ratio < 0 || src->ratio > IPX_YCBCR_440 ||
-        src->ystride < pl->p.sw) {
-        set_error("ipx_plan_run_dev_ycbcr: bad argument");
-        return IPX_ERR_INVALID;
-    }
-    IPX_PLAN_SRC("ipx_plan_run_dev_ycbcr", pl, src->ystride, 1);
-    if (!frame_span_ok(pl->p.sw, pl->p.sh, src->cstride, 1)) { set_error("ipx_plan_run_dev_ycbcr: chroma planes beyond the addressable span"); return IPX_ERR_UNSUPPORTED; }
-    if (n == 0) return IPX_OK;
-    if (n > 65535) { set_error("ipx_plan_run_dev_ycbcr: at most 65535 frames per call"); return IPX_ERR_UNSUPPORTED; }
-    DevSrc d;
-    d.kind = IPX_SRC_YCBCR; d.pix = src->y; d.stride = src->ystride; d.cb = src->cb; d.cr = src->cr;
-    d.cstride = src->cstride; d.ratio = src->ratio; d.w = pl->p.sw; d.h = pl->p.sh;
-    d.nframes = n; d.frame_stride = src->y_frame_stride; d.c_frame_stride = src->c_frame_stride;
-    return run_dev_any(ctx, stream ? (hipStream_t)stream : ctx->stream, pl, n, d, resize_out, resize_frame_stride, thumb_out, thumb_frame_stride,
-                       wm_out, wm_frame_stride);
+    return run_host_packed("ipx_plan_run_host", ctx, pl, n, packed_src(kSrcRGBA, src, sstride, src_frame_stride),
+                           resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
 }
 IPX_CATCH_STATUS
 
@@ -1619,97 +1633,18 @@ int ipx_plan_run_dev_nrgba(ipx_ctx *ctx, void *stream, const ipx_plan *pl, int n
                            size_t wm_frame_stride) try
 {
     IPX_ENTER(ctx);
-    if (!pl || n < 0 || !src || (long long)sstride < (long long)pl->p.sw * 4) { set_error("ipx_plan_run_dev_nrgba: bad argument"); return IPX_ERR_INVALID; }
-    IPX_PLAN_SRC("ipx_plan_run_dev_nrgba", pl, sstride, 4);
-    if (n == 0) return IPX_OK;
-    if (n > 65535) { set_error("ipx_plan_run_dev_nrgba: at most 65535 frames per call"); return IPX_ERR_UNSUPPORTED; }
-    DevSrc d = rgba_src(src, pl->p.sw, pl->p.sh, sstride, IPX_SRC_NRGBA);
-    d.nframes = n; d.frame_stride = src_frame_stride;
-    return run_dev_any(ctx, stream ? (hipStream_t)stream : ctx->stream, pl, n, d, resize_out, resize_frame_stride, thumb_out, thumb_frame_stride,
-                       wm_out, wm_frame_stride);
+    return run_dev_entry("ipx_plan_run_dev_nrgba", ctx, stream, pl, n, packed_src(kSrcNRGBA, src, sstride, src_frame_stride),
+                         resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
 }
 IPX_CATCH_STATUS
 
-// The deep source types: one expansion pass to frames of 16-bit taps (what every consumer of these types reads: At(x, y).RGBA()), then
-// the batch runner on them: top bytes into the watermark frames (drawRGBA / drawCMYK with Src), the scales from the taps.
-int ipx_plan_run_dev_deep(ipx_ctx *ctx, void *stream, const ipx_plan *pl, int n, int kind, const uint8_t *src, int sstride, size_t src_frame_stride,
-                          uint8_t *resize_out, size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out,
-                          size_t wm_frame_stride) try
+int ipx_plan_run_host_nrgba(ipx_ctx *ctx, const ipx_plan *pl, int n, const uint8_t *src, int sstride, size_t src_frame_stride,
+                            uint8_t *resize_out, size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out,
+                            size_t wm_frame_stride) try
 {
     IPX_ENTER(ctx);
-    if (kind != IPX_DEEP_NRGBA64 && kind != IPX_DEEP_RGBA64 && kind != IPX_DEEP_GRAY16 && kind != IPX_DEEP_CMYK) {
-        set_error("ipx_plan_run_dev_deep: unknown source type %d", kind);
-        return IPX_ERR_INVALID;
-    }
-    const int bpp = deep_bpp(kind);
-    const uintptr_t al = kind == IPX_DEEP_CMYK ? 3 : 1;
-    if (!pl || n < 0 || !src || (long long)sstride < (long long)pl->p.sw * bpp || ((((uintptr_t)src) | (uintptr_t)sstride | src_frame_stride) & al)) {
-        set_error("ipx_plan_run_dev_deep: bad argument");
-        return IPX_ERR_INVALID;
-    }
-    IPX_PLAN_SRC("ipx_plan_run_dev_deep", pl, sstride, bpp);
-    IPX_PLAN_SRC("ipx_plan_run_dev_deep", pl, (long long)pl->p.sw * 8, 8);        // the frames of taps
-    if (n == 0) return IPX_OK;
-    if (n > 65535) { set_error("ipx_plan_run_dev_deep: at most 65535 frames per call"); return IPX_ERR_UNSUPPORTED; }
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    const int sw = pl->p.sw, sh = pl->p.sh;
-    const size_t tfs = align256((size_t)sw * sh * 8);
-    AsyncFree mem{s, {}};
-    uint8_t *taps = nullptr;
-    IPX_HIP(mem.get(&taps, tfs * n));
-    {
-        hipError_t e = launch_deep_expand(taps, tfs, src, sstride, src_frame_stride, kind, sw, sh, n, s);
-        if (e != hipSuccess) { set_error("tap expansion failed: %s", hipGetErrorString(e)); return IPX_ERR_HIP; }
-    }
-    DevSrc d;
-    d.kind = IPX_SRC_TAP64; d.pix = taps; d.stride = sw * 8; d.w = sw; d.h = sh;
-    d.nframes = n; d.frame_stride = tfs;
-    d.le_alpha = kind != IPX_DEEP_RGBA64;     // (a premultiplied RGBA64 file may hold a colour above its alpha; the others cannot)
-    return run_dev_any(ctx, s, pl, n, d, resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
-}
-IPX_CATCH_STATUS
-
-int ipx_plan_run_host_deep(ipx_ctx *ctx, const ipx_plan *pl, int n, int kind, const uint8_t *src, int sstride, size_t src_frame_stride,
-                           uint8_t *resize_out, size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out,
-                           size_t wm_frame_stride) try
-{
-    IPX_ENTER(ctx);
-    if (kind != IPX_DEEP_NRGBA64 && kind != IPX_DEEP_RGBA64 && kind != IPX_DEEP_GRAY16 && kind != IPX_DEEP_CMYK) {
-        set_error("ipx_plan_run_host_deep: unknown source type %d", kind);
-        return IPX_ERR_INVALID;
-    }
-    const int bpp = deep_bpp(kind);
-    if (!pl || n < 0 || !src || (long long)sstride < (long long)pl->p.sw * bpp) { set_error("ipx_plan_run_host_deep: bad argument"); return IPX_ERR_INVALID; }
-    IPX_PLAN_SRC("ipx_plan_run_host_deep", pl, sstride, bpp);
-    IPX_PLAN_SRC("ipx_plan_run_host_deep", pl, (long long)pl->p.sw * 8, 8);
-    if (n == 0) return IPX_OK;
-    return run_host_packed(ctx, pl, n, kDeepKind + kind, src, sstride, src_frame_stride, nullptr, resize_out, resize_frame_stride, thumb_out,
-                           thumb_frame_stride, wm_out, wm_frame_stride, "ipx_plan_run_host_deep");
-}
-IPX_CATCH_STATUS
-
-int ipx_plan_run_dev_paletted(ipx_ctx *ctx, void *stream, const ipx_plan *pl, int n, const uint8_t *index, int stride, size_t frame_stride,
-                              const uint8_t *palettes, uint8_t *resize_out, size_t resize_frame_stride, uint8_t *thumb_out,
-                              size_t thumb_frame_stride, uint8_t *wm_out, size_t wm_frame_stride) try
-{
-    IPX_ENTER(ctx);
-    if (!pl || n < 0 || !index || !palettes || stride < pl->p.sw || ((uintptr_t)palettes & 3)) {
-        set_error("ipx_plan_run_dev_paletted: bad argument");
-        return IPX_ERR_INVALID;
-    }
-    IPX_PLAN_SRC("ipx_plan_run_dev_paletted", pl, stride, 1);
-    if (n == 0) return IPX_OK;
-    if (n > 65535) { set_error("ipx_plan_run_dev_paletted: at most 65535 frames per call"); return IPX_ERR_UNSUPPORTED; }
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    const int sw = pl->p.sw, sh = pl->p.sh;
-    const size_t fs = align256((size_t)sw * sh * 4);
-    AsyncFree mem{s, {}};
-    uint8_t *nrgba = nullptr;
-    IPX_HIP(mem.get(&nrgba, fs * n));
-    hipError_t e = launch_palette_expand(nrgba, fs, index, stride, frame_stride, palettes, sw, sh, n, s);
-    if (e != hipSuccess) { set_error("palette expansion failed: %s", hipGetErrorString(e)); return IPX_ERR_HIP; }
-    return ipx_plan_run_dev_nrgba(ctx, s, pl, n, nrgba, sw * 4, fs, resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out,
-                                  wm_frame_stride);
+    return run_host_packed("ipx_plan_run_host_nrgba", ctx, pl, n, packed_src(kSrcNRGBA, src, sstride, src_frame_stride),
+                           resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
 }
 IPX_CATCH_STATUS
 
@@ -1718,57 +1653,99 @@ int ipx_plan_run_dev_gray(ipx_ctx *ctx, void *stream, const ipx_plan *pl, int n,
                           size_t wm_frame_stride) try
 {
     IPX_ENTER(ctx);
-    if (!pl || n < 0 || !gray || stride < pl->p.sw) { set_error("ipx_plan_run_dev_gray: bad argument"); return IPX_ERR_INVALID; }
-    IPX_PLAN_SRC("ipx_plan_run_dev_gray", pl, stride, 1);
-    if (n == 0) return IPX_OK;
-    if (n > 65535) { set_error("ipx_plan_run_dev_gray: at most 65535 frames per call"); return IPX_ERR_UNSUPPORTED; }
-    // scaleX_Gray / drawGray read a pixel as (y, y, y, 0xff), tmp alpha 1.  A YCbCr pixel with Cb = Cr = 128 converts to exactly that in both of the
-    // reference's conversions -- color.YCbCrToRGB: (y*0x10101) >> 16 = y; color.YCbCr.RGBA: (y*0x10101) >> 8 = y*0x101 = color.Gray.RGBA -- and
-    // scaleX_YCbCr4xx writes the same tmp alpha, so the batch runs as 4:4:4 planes with a stride-0 row of 128s as both chroma planes.
-    if ((size_t)pl->p.sw + 8 > ipx_ctx::kFlatChromaBytes) { set_error("ipx_plan_run_dev_gray: frames wider than %zu pixels", ipx_ctx::kFlatChromaBytes - 8); return IPX_ERR_UNSUPPORTED; }
-    DevSrc d;
-    d.kind = IPX_SRC_YCBCR; d.pix = gray; d.stride = stride; d.cb = d.cr = ctx->flat_chroma;
-    d.cstride = 0; d.ratio = IPX_YCBCR_444; d.w = pl->p.sw; d.h = pl->p.sh;
-    d.nframes = n; d.frame_stride = frame_stride; d.c_frame_stride = 0;
-    return run_dev_any(ctx, stream ? (hipStream_t)stream : ctx->stream, pl, n, d, resize_out, resize_frame_stride, thumb_out, thumb_frame_stride,
-                       wm_out, wm_frame_stride);
+    return run_dev_entry("ipx_plan_run_dev_gray", ctx, stream, pl, n, packed_src(kSrcGray, gray, stride, frame_stride),
+                         resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
 }
 IPX_CATCH_STATUS
 
-int ipx_plan_run_host_ycbcr(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_ycbcr_batch *src, uint8_t *resize_out,
-                            size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride,
-                            uint8_t *wm_out, size_t wm_frame_stride) try
+int ipx_plan_run_host_gray(ipx_ctx *ctx, const ipx_plan *pl, int n, const uint8_t *gray, int stride, size_t frame_stride,
+                           uint8_t *resize_out, size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out,
+                           size_t wm_frame_stride) try
 {
     IPX_ENTER(ctx);
-    if (!pl || n < 0 || !src || !src->y || !src->cb || !src->cr || src->ratio < 0 || src->ratio > IPX_YCBCR_440) {
-        set_error("ipx_plan_run_host_ycbcr: bad argument");
-        return IPX_ERR_INVALID;
-    }
-    IPX_PLAN_SRC("ipx_plan_run_host_ycbcr", pl, src->ystride, 1);
-    if (!frame_span_ok(pl->p.sw, pl->p.sh, src->cstride, 1)) { set_error("ipx_plan_run_host_ycbcr: chroma planes beyond the addressable span"); return IPX_ERR_UNSUPPORTED; }
-    if (n == 0) return IPX_OK;
-    const int sw = pl->p.sw, sh = pl->p.sh;
-    const int cw = (src->ratio == IPX_YCBCR_422 || src->ratio == IPX_YCBCR_420) ? (sw + 1) / 2 : sw;
-    const int ch = (src->ratio == IPX_YCBCR_420 || src->ratio == IPX_YCBCR_440) ? (sh + 1) / 2 : sh;
-    const size_t yb = align256((size_t)sw * sh), cbb = align256((size_t)cw * ch);
+    return run_host_packed("ipx_plan_run_host_gray", ctx, pl, n, packed_src(kSrcGray, gray, stride, frame_stride),
+                           resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
+}
+IPX_CATCH_STATUS
+
+int ipx_plan_run_dev_paletted(ipx_ctx *ctx, void *stream, const ipx_plan *pl, int n, const uint8_t *index, int stride, size_t frame_stride,
+                              const uint8_t *palettes,
+                              uint8_t *resize_out, size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out,
+                              size_t wm_frame_stride) try
+{
+    IPX_ENTER(ctx);
+    return run_dev_entry("ipx_plan_run_dev_paletted", ctx, stream, pl, n, packed_src(kSrcPaletted, index, stride, frame_stride, palettes),
+                         resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
+}
+IPX_CATCH_STATUS
+
+int ipx_plan_run_host_paletted(ipx_ctx *ctx, const ipx_plan *pl, int n, const uint8_t *index, int stride, size_t frame_stride,
+                               const uint8_t *palettes,
+                               uint8_t *resize_out, size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out,
+                               size_t wm_frame_stride) try
+{
+    IPX_ENTER(ctx);
+    return run_host_packed("ipx_plan_run_host_paletted", ctx, pl, n, packed_src(kSrcPaletted, index, stride, frame_stride, palettes),
+                           resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
+}
+IPX_CATCH_STATUS
+
+int ipx_plan_run_dev_deep(ipx_ctx *ctx, void *stream, const ipx_plan *pl, int n, int kind, const uint8_t *src, int sstride, size_t src_frame_stride,
+                          uint8_t *resize_out, size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out,
+                          size_t wm_frame_stride) try
+{
+    IPX_ENTER(ctx);
+    return run_dev_entry("ipx_plan_run_dev_deep", ctx, stream, pl, n, packed_src(src_of_deep(kind), src, sstride, src_frame_stride),
+                         resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
+}
+IPX_CATCH_STATUS
+
+int ipx_plan_run_host_deep(ipx_ctx *ctx, const ipx_plan *pl, int n, int kind, const uint8_t *src, int sstride, size_t src_frame_stride,
+                           uint8_t *resize_out, size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out,
+                           size_t wm_frame_stride) try
+{
+    IPX_ENTER(ctx);
+    return run_host_packed("ipx_plan_run_host_deep", ctx, pl, n, packed_src(src_of_deep(kind), src, sstride, src_frame_stride),
+                           resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
+}
+IPX_CATCH_STATUS
+
+// ---- decoded JPEG batches ---------------------------------------------------------------------------
+// The reference treats a *image.YCbCr source differently per operator: resize and the non-crop thumbnail convert
+// every tap to 16 bit and then interpolate; the crop thumbnail scales an RGBA8 copy; the watermark is drawn on an RGBA8 conversion.  All
+// three are arms of the one-pass kernel (or of the per-output kernels behind it) chosen by tap kind in run_dev_any: IPX_SRC_YCBCR for
+// the first, its _CROP kind for the second, the draw of the source into the watermark frames for the third.
+int ipx_plan_run_dev_ycbcr(ipx_ctx *ctx, void *stream, const ipx_plan *pl, int n, const ipx_ycbcr_batch *src,
+                           uint8_t *resize_out, size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out,
+                           size_t wm_frame_stride) try
+{
+    IPX_ENTER(ctx);
+    return run_dev_entry("ipx_plan_run_dev_ycbcr", ctx, stream, pl, n, ycbcr_src(src),
+                         resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
+}
+IPX_CATCH_STATUS
+
+// One leased lane and one stream: every frame up, the operators, every output down.  (Not the pipeline of run_host_packed.)
+int ipx_plan_run_host_ycbcr(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_ycbcr_batch *src,
+                            uint8_t *resize_out, size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out,
+                            size_t wm_frame_stride) try
+{
+    IPX_ENTER(ctx);
+    const BatchSrc host = ycbcr_src(src);
+    int rc = src_check("ipx_plan_run_host_ycbcr", pl, host, n, false);
+    if (rc || n == 0) return rc;
+    const SrcLayout L = src_layout(pl, host);
     const size_t fres = resize_out ? align256(pl->info.resize_bytes) : 0, fth = thumb_out ? align256(pl->info.thumb_bytes) : 0;
     const size_t fwm = wm_out ? align256(pl->info.wm_bytes) : 0;
     LaneLease lane(ctx);
-    int rc = lane_reserve(lane.get(), (yb + 2 * cbb + fres + fth + fwm) * n + 1024);
+    rc = lane_reserve(lane.get(), (L.frame_bytes() + fres + fth + fwm) * n + 1024);
     if (rc) return rc;
     hipStream_t s = lane->stream;
-    uint8_t *dy = lane->dev, *dcb = dy + yb * n, *dcr = dcb + cbb * n;
-    uint8_t *dres = fres ? dcr + cbb * n : nullptr, *dth = fth ? dcr + cbb * n + fres * n : nullptr;
-    uint8_t *dwm = fwm ? dcr + cbb * n + (fres + fth) * n : nullptr;
-    for (int i = 0; i < n; i++) {
-        IPX_HIP(hipMemcpy2DAsync(dy + yb * i, sw, src->y + src->y_frame_stride * i, src->ystride, sw, sh, hipMemcpyHostToDevice, s));
-        IPX_HIP(hipMemcpy2DAsync(dcb + cbb * i, cw, src->cb + src->c_frame_stride * i, src->cstride, cw, ch, hipMemcpyHostToDevice, s));
-        IPX_HIP(hipMemcpy2DAsync(dcr + cbb * i, cw, src->cr + src->c_frame_stride * i, src->cstride, cw, ch, hipMemcpyHostToDevice, s));
-    }
-    ipx_ycbcr_batch d;
-    d.y = dy; d.cb = dcb; d.cr = dcr; d.ystride = sw; d.cstride = cw; d.y_frame_stride = yb; d.c_frame_stride = cbb;
-    d.ratio = src->ratio;
-    rc = ipx_plan_run_dev_ycbcr(ctx, s, pl, n, &d, dres, fres, dth, fth, dwm, fwm);
+    uint8_t *dres = fres ? lane->dev + L.frame_bytes() * n : nullptr, *dth = fth ? lane->dev + (L.frame_bytes() + fres) * n : nullptr;
+    uint8_t *dwm = fwm ? lane->dev + (L.frame_bytes() + fres + fth) * n : nullptr;
+    BatchSrc d;
+    IPX_HIP(src_upload(host, L, 0, n, lane->dev, n, s, kCopyFrameRows, &d));
+    rc = run_dev_src(ctx, s, pl, n, d, dres, fres, dth, fth, dwm, fwm);
     if (rc) { (void)hipStreamSynchronize(s); return rc; }
     for (int i = 0; i < n; i++) {
         if (dres && pl->info.resize_bytes)

@@ -287,6 +287,68 @@ struct StreamSync {
     ~StreamSync() { (void)hipStreamSynchronize(s); }
 };
 
+// ---- the input side of the plan entries (ipx_runtime.hip) ---------------------------------------------------------------------------
+
+// n equally sized frames of one Go image type, in host memory or in HBM: the size is the plan's, frame i of plane p starts at
+// plane[p] + i * frame_stride[p ? 1 : 0]
+struct BatchSrc {
+    int type = kSrcRGBA;                                   // SrcType
+    int ratio = 0;                                         // kSrcYCbCr: IPX_YCBCR_*
+    const uint8_t *plane[3] = {nullptr, nullptr, nullptr}; // pixels / index / Y, then Cb and Cr
+    int stride[2] = {0, 0};                                // bytes per row of plane 0, of the chroma planes
+    size_t frame_stride[2] = {0, 0};
+    const uint8_t *palettes = nullptr;                     // kSrcPaletted: 256 x RGBA per frame, 1024 bytes apart
+};
+inline BatchSrc packed_src(int type, const uint8_t *pix, int stride, size_t frame_stride, const uint8_t *palettes = nullptr)
+{
+    BatchSrc b;
+    b.type = type; b.plane[0] = pix; b.stride[0] = stride; b.frame_stride[0] = frame_stride; b.palettes = palettes;
+    return b;
+}
+inline BatchSrc ycbcr_src(const ipx_ycbcr_batch *y)        // (a null y: a batch src_check refuses)
+{
+    BatchSrc b;
+    b.type = kSrcYCbCr;
+    if (!y) return b;
+    b.ratio = y->ratio; b.plane[0] = y->y; b.plane[1] = y->cb; b.plane[2] = y->cr;
+    b.stride[0] = y->ystride; b.stride[1] = y->cstride; b.frame_stride[0] = y->y_frame_stride; b.frame_stride[1] = y->c_frame_stride;
+    return b;
+}
+
+// The one rule for the arguments of a batch entry `who`.  IPX_ERR_INVALID: no plan, n < 0, an unknown type or ratio, a null plane or
+// palette, a row stride below the row (for YCbCr: of the chroma planes too).  IPX_ERR_UNSUPPORTED: rows beyond the span the kernels
+// address (for the deep types: of their frames of taps too).  in_hbm -- the kernels read this memory themselves, not a re-packed copy in
+// scratch -- adds what they need of it: pixels, row and frame stride of a deep type on 2 bytes (CMYK: 4), palettes on 4
+// (IPX_ERR_INVALID), and at most 65535 frames per call (IPX_ERR_UNSUPPORTED).
+int src_check(const char *who, const ipx_plan *pl, const BatchSrc &b, int n, bool in_hbm);
+
+// How `slots` frames of a source lie in device scratch: [slots x plane 0][slots x Cb][slots x Cr][slots x palette], rows tight,
+// frames fs[] apart.  frame_rule: a plane's bytes -> its frame stride (align256, or run_host_packed's own).
+struct SrcLayout {
+    int planes;            // 1, or 3 (kSrcYCbCr)
+    size_t row[2];         // bytes per row: plane 0, chroma
+    int h[2];
+    size_t fs[2];
+    size_t pal;            // 1024 (kSrcPaletted) or 0
+    size_t frame_bytes() const { return fs[0] + (planes == 3 ? 2 * fs[1] : 0) + pal; }
+};
+SrcLayout src_layout(const ipx_plan *pl, const BatchSrc &b, size_t (*frame_rule)(size_t) = align256);
+
+// How a leg moves frames up: frames that lie in host memory as they will in scratch as one run of bytes
+// (join_frames; in pieces of `piece` bytes when that is not 0), else frame by frame -- a frame of tight rows as one run when
+// join_rows, else hipMemcpy2DAsync.
+struct CopyPolicy { bool join_frames, join_rows; size_t piece; };
+constexpr CopyPolicy kCopyWholePlanes{true, false, 0}, kCopyFrames{false, true, 0}, kCopyFrameRows{false, false, 0};
+
+// Queues the copies of frames i0 .. i0 + m of `host` into a block laid out for `slots` frames and describes them there in *in_hbm.
+hipError_t src_upload(const BatchSrc &host, const SrcLayout &L, int i0, int m, uint8_t *scratch, int slots, hipStream_t s, const CopyPolicy &cp,
+                      BatchSrc *in_hbm);
+
+// The plan's operators on m frames in HBM, outputs to device-addressable frames (null: not wanted).  The one place that knows what a
+// source type needs first: a palette or deep pixels are expanded (stream-ordered scratch), Gray gets the flat chroma row.
+int run_dev_src(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, int m, const BatchSrc &in_hbm, uint8_t *resize_out, size_t resize_frame_stride,
+                uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out, size_t wm_frame_stride);
+
 // jpeg.Encode of up to three sets of n frames in HBM into one pinned block *blob (ipx_jpeg_runtime.hip); dcoefs: n * ipx_jpeg_coef_count
 // int16 of scratch per set.
 struct JpegEncSet { int16_t *dcoefs; const uint8_t *src; int w, h, stride; size_t frame_stride; size_t *offs, *lens; };   // offs / lens: [n], into *blob

@@ -300,3 +300,127 @@ def test_host_variants_of_the_other_source_types(ctx, monkeypatch):
         np.testing.assert_array_equal(got["watermark"][k], oracle.composite_glyphs(oracle.draw_paletted(zeros(), (0, 0, w, h), gray[k], p16), glyphs, DEFAULT_COL))
     plan.close()
     gs.close()
+
+
+# ---- the arguments of the batch entries: one rule for every source type, host memory and HBM ------------------------------------------
+
+_AW, _AH = 64, 48                                   # the plan's frame size in the argument tests
+_OVER_SPAN = 46_000_000                             # a row stride (a multiple of 4) with 47 * stride beyond the 2 GiB span
+
+
+def _pixel_outs():
+    return (None, 0, None, 0, None, 0)
+
+
+def _stream_outs():
+    import ctypes as C
+    return (None, None, None, C.byref(C.c_void_p()))
+
+
+def _ycbcr_batch(p, ystride, cstride):
+    from imageprocessor_amd import _lib
+    return _lib.YCbCrBatch(p, p, p, ystride, cstride, 0, 0, 2)     # 4:2:0: chroma planes 32 x 24
+
+
+def _packed(bpp, before=(), after=(), hbm=False, outs=_pixel_outs):
+    """an entry on single-plane frames: (is the source in HBM, bytes per pixel, arguments from the source on)"""
+    return hbm, bpp, lambda p, stride, cstride: (*before, p, stride, 0, *(p if a is _PAL else a for a in after), *outs())
+
+
+def _planar(hbm=False, after=(), outs=_pixel_outs):
+    import ctypes as C
+    return hbm, 1, lambda p, stride, cstride: (C.byref(_ycbcr_batch(p, stride, cstride)), *after, *outs())
+
+
+_PAL = object()                                     # stands for the palettes: the same address as the index plane
+# every public batch entry on frames of pixels (include/ipx.h); test_every_batch_entry_is_listed holds the table to the header
+_ENTRIES = {
+    "ipx_plan_run_dev": _packed(4, hbm=True),
+    "ipx_plan_run_dev_nrgba": _packed(4, hbm=True),
+    "ipx_plan_run_dev_gray": _packed(1, hbm=True),
+    "ipx_plan_run_dev_paletted": _packed(1, after=(_PAL,), hbm=True),
+    "ipx_plan_run_dev_deep": _packed(8, before=(0,), hbm=True),
+    "ipx_plan_run_dev_ycbcr": _planar(hbm=True),
+    "ipx_plan_run_host": _packed(4),
+    "ipx_plan_run_host_nrgba": _packed(4),
+    "ipx_plan_run_host_gray": _packed(1),
+    "ipx_plan_run_host_paletted": _packed(1, after=(_PAL,)),
+    "ipx_plan_run_host_deep": _packed(8, before=(0,)),
+    "ipx_plan_run_host_ycbcr": _planar(),
+    "ipx_plan_run_host_jpeg": _packed(4, after=(85,), outs=_stream_outs),
+    "ipx_plan_run_host_ycbcr_jpeg": _planar(after=(85,), outs=_stream_outs),
+    "ipx_plan_run_host_png": _packed(4, outs=_stream_outs),
+    "ipx_plan_run_host_paletted_gif": _packed(1, after=(_PAL, 85), outs=_stream_outs),
+}
+
+
+def test_every_batch_entry_is_listed():
+    import re
+    with open(os.path.join(HERE, "..", "include", "ipx.h")) as f:
+        names = set(re.findall(r"\b(ipx_plan_run_(?:dev|host)\w*)\s*\(", f.read()))
+    assert names == set(_ENTRIES)
+
+
+def _refused(ctx, plan, name, p, stride, cstride=_AW // 2):
+    """(status, error text) of one call of the entry on a batch of one frame; nothing is launched: the call is refused"""
+    import imageprocessor_amd as m
+    hbm, _, args = _ENTRIES[name]
+    head = (ctx.handle, None, plan.handle, 1) if hbm else (ctx.handle, plan.handle, 1)
+    rc = getattr(m.lib(), name)(*head, *args(p, stride, cstride))
+    return rc, m.lib().ipx_last_error().decode()
+
+
+@pytest.mark.parametrize("name", sorted(_ENTRIES))
+def test_batch_entry_arguments(ctx, name):
+    """A null source and a row stride below the row are IPX_ERR_INVALID, a row stride beyond the addressable span IPX_ERR_UNSUPPORTED
+    with "span" in the text -- for every entry, before any device work (the addresses given are never read)."""
+    plan = ctx.plan(_AW, _AH, resize=(32, 24, False), thumbnail=(16, True), watermark=None)
+    buf = np.zeros(4096 + 64, np.uint8)
+    p = buf.ctypes.data + (-buf.ctypes.data) % 64
+    bpp = _ENTRIES[name][1]
+    assert _refused(ctx, plan, name, None, _AW * bpp)[0] == -1
+    rc, text = _refused(ctx, plan, name, p, _AW * bpp - 1)
+    assert rc == -1 and text.startswith(name)
+    rc, text = _refused(ctx, plan, name, p, _OVER_SPAN)
+    assert rc == -4 and "span" in text and text.startswith(name)
+    if "ycbcr" in name:           # the chroma planes' rows: one below the chroma width
+        rc, text = _refused(ctx, plan, name, p, _AW, _AW // 2 - 1)
+        assert rc == -1 and text.startswith(name)
+    plan.close()
+
+
+@pytest.mark.parametrize("ratio", [2, 3], ids=["420", "440"])
+def test_ycbcr_host_planes_with_padded_strides(ctx, ratio):
+    """ipx_plan_run_host_ycbcr and ipx_plan_run_host_ycbcr_jpeg on planes that are not tight in host memory -- padded rows of Y and of
+    chroma, frames further apart than a plane -- at an odd size: the row-copy upload of three planes, against the oracle."""
+    import ctypes as C
+    import imageprocessor_amd as m
+    from imageprocessor_amd import _lib
+    from helpers import DEFAULT_COL, text_glyphs
+    w, h, n, resize, thumb = 333, 251, 3, (200, 100, True), (64, True)
+    chh, cw = oracle.chroma_shape(w, h, ratio)
+    rng = np.random.default_rng(77 + ratio)
+    ystride, cstride, yrows, crows = w + 19, cw + 5, h + 3, chh + 2
+    ybuf, cbbuf, crbuf = (rng.integers(0, 256, s, dtype=np.uint8) for s in ((n, yrows, ystride), (n, crows, cstride), (n, crows, cstride)))
+    y, cb, cr = ybuf[:, :h, :w], cbbuf[:, :chh, :cw], crbuf[:, :chh, :cw]
+    b = _lib.YCbCrBatch(ybuf.ctypes.data, cbbuf.ctypes.data, crbuf.ctypes.data, ystride, cstride, yrows * ystride, crows * cstride, ratio)
+    glyphs = text_glyphs(w, h, n=6, width_px=150, height_px=30)
+    gs = ctx.glyphset(glyphs, DEFAULT_COL)
+    plan = ctx.plan(w, h, resize=resize, thumbnail=thumb, watermark=gs)
+    i = plan.info
+    want = [_expect_ycbcr_ops(y[k], cb[k], cr[k], ratio, resize, thumb, glyphs, DEFAULT_COL) for k in range(n)]
+
+    out = {"resize": np.zeros((n, i.resize_h, i.resize_w, 4), np.uint8), "thumbnail": np.zeros((n, i.thumb_h, i.thumb_w, 4), np.uint8),
+           "watermark": np.zeros((n, i.wm_h, i.wm_w, 4), np.uint8)}
+    m._check(m.lib().ipx_plan_run_host_ycbcr(ctx.handle, plan.handle, n, C.byref(b), out["resize"].ctypes.data, i.resize_bytes,
+                                             out["thumbnail"].ctypes.data, i.thumb_bytes, out["watermark"].ctypes.data, i.wm_bytes))
+    for k in range(n):
+        for key in ("resize", "thumbnail", "watermark"):
+            np.testing.assert_array_equal(out[key][k], want[k][key], err_msg="%s frame %d" % (key, k))
+
+    got = plan._run_streams(m.lib().ipx_plan_run_host_ycbcr_jpeg, n, ("resize", "thumbnail", "watermark"), True, (C.byref(b), 85))
+    for k in range(n):
+        for key in ("resize", "thumbnail", "watermark"):
+            assert got[key][k] == oracle.jpeg_encode_rgba(want[k][key], 85), (key, k)
+    plan.close()
+    gs.close()
