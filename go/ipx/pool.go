@@ -128,9 +128,26 @@ func (p *Pool) SubmitPixelsOf(kind PixelKind, w, h, n int, o Ops, src, resizeOut
 	return job, nil
 }
 
-// SubmitJPEG queues uploaded JPEG objects of w x h (worker.go:165-194: the bytes GetOriginal returned).  The files are copied into C memory
-// here, so the caller's slices are free at once; outputs are views into blocks the pool owns until Release.
+// FileFormat names the format of a file job's uploads: what image.Decode would take them for (image_processor.go:47).
+type FileFormat int
+
+const (
+	FormatJPEG FileFormat = C.IPX_JOB_JPEG
+	FormatPNG  FileFormat = C.IPX_JOB_PNG
+	FormatGIF  FileFormat = C.IPX_JOB_GIF
+)
+
+// SubmitJPEG queues uploaded JPEG objects of w x h: SubmitFiles(FormatJPEG, ...).
 func (p *Pool) SubmitJPEG(w, h int, o Ops, files [][]byte, quality int) (*Job, error) {
+	return p.SubmitFiles(FormatJPEG, w, h, o, files, quality)
+}
+
+// SubmitFiles queues uploaded objects of one format and of w x h (worker.go:165-194: the bytes GetOriginal returned).  The files are
+// copied into C memory here, so the caller's slices are free at once; outputs are views into blocks the pool owns until Release.
+// The streams are those of the upload's own format, as the reference's operators end in its encoder (resize.go:80-86,
+// thumbnail.go:70-74, watermark.go:66-79): a JPEG job three JPEGs, a PNG job three PNGs, a GIF job a GIF, a GIF and a JPEG for the
+// watermark.  quality is jpeg.Options.Quality (a PNG job ignores it).  FileStatus(i) != OK marks the files Go processes itself.
+func (p *Pool) SubmitFiles(format FileFormat, w, h int, o Ops, files [][]byte, quality int) (*Job, error) {
 	n := len(files)
 	ops, free := p.ops(w, h, o)
 	defer free()
@@ -150,7 +167,7 @@ func (p *Pool) SubmitJPEG(w, h int, o Ops, files [][]byte, quality int) (*Job, e
 	wo := (*C.ipx_bytes)(C.calloc(C.size_t(n), C.size_t(unsafe.Sizeof(C.ipx_bytes{}))))
 	job.cmem = append(job.cmem, unsafe.Pointer(ro), unsafe.Pointer(to), unsafe.Pointer(wo))
 	job.resize, job.thumb, job.wm = unsafe.Slice(ro, n), unsafe.Slice(to, n), unsafe.Slice(wo, n)
-	j := C.ipx_job{kind: C.IPX_JOB_JPEG, ops: ops, n: C.int32_t(n), files: &cf[0], quality: C.int32_t(quality),
+	j := C.ipx_job{kind: C.int32_t(format), ops: ops, n: C.int32_t(n), files: &cf[0], quality: C.int32_t(quality),
 		resize_jpeg: ro, thumb_jpeg: to, wm_jpeg: wo, status: &job.cstatus[0]}
 	if !o.Watermark {
 		j.wm_jpeg = nil
@@ -180,7 +197,7 @@ func (j *Job) Wait() error {
 	return call(func() C.int { return C.ipx_job_wait(j.p.c, j.ticket, nil) })
 }
 
-// FileStatus (JPEG jobs, after Wait): OK, or why Go has to process file i itself.
+// FileStatus (file jobs, after Wait): OK, or why Go has to process file i itself.
 func (j *Job) FileStatus(i int) Status { return Status(j.cstatus[i]) }
 func (j *Job) Resize(i int) []byte     { return view(j.resize[i]) }
 func (j *Job) Thumbnail(i int) []byte  { return view(j.thumb[i]) }
@@ -193,7 +210,7 @@ func (j *Job) freeC() {
 	j.cmem = nil
 }
 
-// Release forgets the job and frees the blocks its JPEG outputs live in (call it after the objects have been saved).
+// Release forgets the job and frees the blocks a file job's outputs live in (call it after the objects have been saved).
 func (j *Job) Release() {
 	C.ipx_job_release(j.p.c, j.ticket)
 	j.freeC()

@@ -12,9 +12,11 @@ import (
 
 // Batcher is the micro-batcher of the library (ipx_batcher_*, include/ipx.h): the goroutines of internal/worker/worker.go:112-149 pull ONE
 // message each from a channel of concurrency*2 (:88); every one of them hands its file over with Process and blocks until ITS objects are
-// back.  Grouping by frame size and operator content, the flush rules (size, timer, at once while the pool has a free feeder) and the
+// back.  Grouping by format (JPEG, PNG, GIF: the library tells them apart by the full signature, as image.Decode does), frame size and
+// operator content, the flush rules (size, timer, at once while the pool has a free feeder) and the
 // per-file status live below the ABI (and are tested
-// there: tests/test_batcher_gpu.py, tools/sanitize/batcher_host_test.cpp under ThreadSanitizer) -- round 2's Go-side batching is gone.
+// there: tests/test_batcher_gpu.py, tests/test_batcher_formats_gpu.py, tools/sanitize/batcher_host_test.cpp and
+// batcher_formats_host_test.cpp under ThreadSanitizer) -- round 2's Go-side batching is gone.
 // At-least-once semantics are unchanged: processMessage (worker.go:165-234) commits its message only after Process returned and
 // fileRepo.SaveProcessed stored the objects.
 type Batcher struct {
@@ -24,8 +26,8 @@ type Batcher struct {
 
 // NewBatcher: maxBatch files per job (0 = 256), maxWaitMicros how long the first file of a group waits for company while the pool is
 // busy (0 = 2000; with WORKER_CONCURRENCY = 3 goroutines a file leaves at once: 2.4 ms p50 per message on one MI355X),
-// a group = files of one frame size, one JPEG shape (components, luma sampling) and one operator content;
-// quality = domain.DefaultJPEGQuality (task.go:57; 0 = 85).
+// a group = files of one format, one frame size, for JPEGs one shape (components, luma sampling) and one operator content;
+// quality = domain.DefaultJPEGQuality (task.go:57; 0 = 85): of a JPEG's three outputs and of a GIF's watermark.
 func NewBatcher(p *Pool, maxBatch, maxWaitMicros, quality int) (*Batcher, error) {
 	cfg := C.ipx_batcher_config{max_batch: C.int32_t(maxBatch), max_wait_us: C.int32_t(maxWaitMicros), quality: C.int32_t(quality)}
 	var b *C.ipx_batcher
@@ -38,7 +40,8 @@ func NewBatcher(p *Pool, maxBatch, maxWaitMicros, quality int) (*Batcher, error)
 // Close flushes what is pending and waits for it.
 func (b *Batcher) Close() { C.ipx_batcher_destroy(b.c); b.c = nil }
 
-// Objects are the three streams of one message (nil for operators its task did not ask for).  They are views into blocks the library
+// Objects are the three streams of one message (nil for operators its task did not ask for), in the encoding the reference gives an
+// upload of that format: three JPEGs for a JPEG, three PNGs for a PNG, GIF / GIF / JPEG (the watermark, watermark.go:66-79) for a GIF.  They are views into blocks the library
 // owns: copy or store them (fileRepo.SaveProcessed, image_processor.go:76), then call Release.
 type Objects struct {
 	Resize, Thumbnail, Watermark []byte
@@ -52,10 +55,17 @@ func (o *Objects) Release() {
 	}
 }
 
-// Process is the drop-in for (*ImageProcessor).Process on the JPEG path (image_processor.go:39-102): the object bytes GetOriginal
-// returned (worker.go:177-186), the frame size from the file's header (image.DecodeConfig) and the operators of the task.  It blocks
-// until the file's batch has run.  IsUnsupported(err): this file is not one the GPU path decodes (progressive CMYK, 4:1:1, ...) -- run the
-// reference's own image.Decode path for this message; its neighbours in the batch are not affected.
+// Process is the drop-in for (*ImageProcessor).Process (image_processor.go:39-102) for JPEG, PNG and GIF uploads: the object bytes
+// GetOriginal returned (worker.go:177-186), the frame size from the file's header (image.DecodeConfig) and the operators of the task.
+// It blocks until the file's batch has run.  What falls back -- IsUnsupported(err), or an Invalid status Go's decoder will confirm:
+// run the reference's own image.Decode path for this message; its neighbours in the batch are not affected --
+//   - JPEG: CMYK and other four-component files, 4:1:1 and other samplings, damaged files;
+//   - PNG: Adam7, another chunk order, bytes after the zlib stream, sub-byte gray with tRNS, frames beyond the addressable span;
+//   - GIF: a first image away from (0, 0), an empty one, or one of another size than the logical screen (DecodeConfig reports the
+//     screen, the GPU leg decodes the first image: such a file falls back alone);
+//   - anything that is none of the three (a WebP, a BMP): it goes the JPEG way and that decoder refuses it.
+// A PNG upload alone is slower here than on a host thread (one file is one serial inflate walk: 535 ms for a photo-like 1024x768
+// file); the GPU path pays when many goroutines have PNG messages in flight, so that groups form.
 func (b *Batcher) Process(file []byte, w, h int, o Ops) (*Objects, error) {
 	ops, free := b.p.ops(w, h, o)
 	defer free() // copied by ipx_batcher_submit

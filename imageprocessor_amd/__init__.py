@@ -736,11 +736,12 @@ class PoolJob:
         return bool(d.value)
 
     def wait(self):
-        """-> dict of outputs (arrays for a pixel job; ({operator: [bytes | None]}, status list) for a JPEG job); releases the job"""
+        """-> dict of outputs (arrays for a pixel job; ({operator: [bytes | None]}, status list) for a file job: JPEG, PNG or GIF);
+        releases the job"""
         fd = C.c_int()
         try:
             _check(lib().ipx_job_wait(self.pool.handle, self.ticket, C.byref(fd)))
-            if self.job.kind != 1:          # every kind but IPX_JOB_JPEG hands pixels back
+            if self.job.kind not in Pool.FILE_KINDS.values():      # every kind but the file jobs hands pixels back
                 return self.outs
             out = {k: [C.string_at(a[j].data, a[j].len) if a[j].data else None for j in range(self.n)] for k, a in self.outs.items()}
             return out, list(self.keep["status"])[:self.n]
@@ -849,23 +850,32 @@ class Pool:
             j.wm_out, j.wm_frame_stride = outs["watermark"].ctypes.data, fs(outs["watermark"])
         return PoolJob(self, j, {"frames": frames, "glyphs": keep}, outs, n)
 
+    FILE_KINDS = {"jpeg": 1, "png": 8, "gif": 9}      # IPX_JOB_JPEG / _PNG / _GIF
+
     def submit_jpeg(self, files, sw, sh, quality=85, resize=(1024, 768, True), thumbnail=(200, True), glyphs=None, col=(0, 0, 0, 0),
                     watermark=False):
         """JPEG byte strings of sw x sh images in -> PoolJob; wait() gives ({operator: [bytes | None]}, status list)."""
+        return self.submit_files(files, sw, sh, "jpeg", quality, resize, thumbnail, glyphs, col, watermark)
+
+    def submit_files(self, files, sw, sh, format="jpeg", quality=85, resize=(1024, 768, True), thumbnail=(200, True), glyphs=None,
+                     col=(0, 0, 0, 0), watermark=False, want=("resize", "thumbnail", "watermark")):
+        """Uploaded files of one format ("jpeg", "png", "gif") and of sw x sh images in -> PoolJob; wait() gives ({operator: [bytes |
+        None]}, status list) with streams of the job's format (PNG: three PNGs; GIF: GIF, GIF and a JPEG at `quality` for the
+        watermark).  An operator not in `want` gets no output array and is left out."""
         n = len(files)
         ops, keep = self._ops(sw, sh, resize, thumbnail, glyphs, col, watermark)
         arr = _bytes_array(files)
         status = (C.c_int32 * max(1, n))()
         outs = {}
         j = _lib.Job()
-        j.kind, j.ops, j.n, j.files, j.quality, j.status = 1, ops, n, arr, int(quality), status
-        if resize:
+        j.kind, j.ops, j.n, j.files, j.quality, j.status = self.FILE_KINDS[format], ops, n, arr, int(quality), status
+        if resize and "resize" in want:
             outs["resize"] = (_lib.Bytes * max(1, n))()
             j.resize_jpeg = outs["resize"]
-        if thumbnail:
+        if thumbnail and "thumbnail" in want:
             outs["thumbnail"] = (_lib.Bytes * max(1, n))()
             j.thumb_jpeg = outs["thumbnail"]
-        if ops.do_watermark:
+        if ops.do_watermark and "watermark" in want:
             outs["watermark"] = (_lib.Bytes * max(1, n))()
             j.wm_jpeg = outs["watermark"]
         return PoolJob(self, j, {"files": arr, "status": status, "glyphs": keep}, outs, n)
@@ -891,7 +901,7 @@ def jpeg_quant_tables(quality):
 class Batcher:
     """Micro-batching of single uploads (ipx_batcher_*): what the goroutines of internal/worker/worker.go:112-149 would call, one file each.
 
-    submit(file bytes, frame size, operators) -> ticket; wait(ticket) -> (status, {operator: bytes | None}); the ticket is released by wait."""
+    submit(file bytes -- JPEG, PNG or GIF, told apart by the library --, frame size, operators) -> ticket; wait(ticket) -> (status, {operator: bytes | None}); the ticket is released by wait."""
 
     def __init__(self, pool, max_batch=0, max_wait_us=0, quality=0):
         self.pool = pool

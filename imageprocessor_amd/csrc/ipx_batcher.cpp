@@ -102,6 +102,17 @@ static void jpeg_shape(const ipx_bytes &f, uint8_t out[3])
     }
 }
 
+// The job kind an upload goes out in, by the FULL signature -- what image.Decode's registered formats go by (image/png: "\x89PNG\r\n\x1a\n",
+// image/gif: "GIF8?a", where the decoder itself takes 87a and 89a only).  A file that merely begins like a PNG or a GIF is neither: it goes
+// the JPEG way like every other file, and gets its status from that decoder.
+static int sniff_kind(const ipx_bytes &f)
+{
+    static const uint8_t png[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+    if (f.len >= 8 && !memcmp(f.data, png, 8)) return IPX_JOB_PNG;
+    if (f.len >= 6 && (!memcmp(f.data, "GIF87a", 6) || !memcmp(f.data, "GIF89a", 6))) return IPX_JOB_GIF;
+    return IPX_JOB_JPEG;
+}
+
 int Batcher::submit(const ipx_bytes &file, const ipx_pool_ops &ops, uint64_t *ticket, std::string *err)
 {
     if (!ticket || !file.data || !file.len) { *err = "ipx_batcher_submit: bad argument"; return IPX_ERR_INVALID; }
@@ -109,9 +120,12 @@ int Batcher::submit(const ipx_bytes &file, const ipx_pool_ops &ops, uint64_t *ti
     std::string key;
     const int rc = copy_ops(ops, &oc, &key, err);
     if (rc) return rc;
-    uint8_t shape[3];
-    jpeg_shape(file, shape);
-    key.append((const char *)shape, 3);
+    // four more key bytes: for a JPEG the shape (three bytes, zeros otherwise), then the format (the job kind).  PNG files are NOT split by colour type or depth: ipx_plan_run_png_png groups kinds itself,
+    // and splitting here would only make every group wait longer for company.
+    const int kind = sniff_kind(file);
+    uint8_t shape[4] = {0, 0, 0, (uint8_t)kind};
+    if (kind == IPX_JOB_JPEG) jpeg_shape(file, shape);
+    key.append((const char *)shape, 4);
     std::shared_ptr<Batch> full;
     Why why = BySize;
     {
@@ -121,6 +135,7 @@ int Batcher::submit(const ipx_bytes &file, const ipx_pool_ops &ops, uint64_t *ti
         if (it == pending_.end()) {
             auto b = std::make_shared<Batch>();
             b->key = key;
+            b->kind = kind;
             b->ops = std::move(oc);
             if (!b->ops.glyphs.empty()) {                       // the moved vectors kept their buffers; the pointers into them stay good
                 for (size_t i = 0; i < b->ops.glyphs.size(); i++) b->ops.glyphs[i].mask = b->ops.masks[i].data();
@@ -154,7 +169,7 @@ void Batcher::flush(const std::shared_ptr<Batch> &b, Why why)
     b->status.assign(n, IPX_OK);
     ipx_job j;
     memset(&j, 0, sizeof j);
-    j.kind = IPX_JOB_JPEG;
+    j.kind = b->kind;
     j.ops = b->ops.p;
     j.n = n;
     j.files = b->files.data();

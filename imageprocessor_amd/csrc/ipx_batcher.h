@@ -2,13 +2,14 @@
 //
 // The reference pulls ONE message per goroutine (internal/worker/worker.go:112-149) from a channel of concurrency * 2 (:88); a GPU
 // wants hundreds of files per launch.  The batcher stands between: every goroutine hands over its one file and waits for its ticket;
-// files are grouped by frame size, JPEG shape (components, luma sampling: a batch is one shape) and operator content (parameters,
-// colour, every glyph's rectangle and mask bytes), a group goes to
-// the pool as one JPEG job when it holds max_batch files or when its first file has waited max_wait_us, and every file gets its own
-// status -- a file the GPU path cannot decode does not fail its neighbours (the worker runs its own image.Decode path for it).
+// files are grouped by format (JPEG, PNG or GIF, by the full signature, as image.Decode tells them apart), frame size, JPEG shape
+// (components, luma sampling: a JPEG batch is one shape) and operator content (parameters, colour, every glyph's rectangle and mask
+// bytes), a group goes to the pool as one job of its format (IPX_JOB_JPEG / _PNG / _GIF) when it holds max_batch files or when its
+// first file has waited max_wait_us, and every file gets its own status -- a file the GPU path cannot decode does not fail its
+// neighbours (the worker runs its own image.Decode path for it).
 //
 // All of it is host logic over three calls of a backend (submit / wait / release of a job), so it builds and runs without a GPU: the
-// product binds the backend to ipx_job_* of a pool, tests/batcher_host_test.cpp binds it to a fake and runs under ThreadSanitizer.
+// product binds the backend to ipx_job_* of a pool, tools/sanitize/batcher_host_test.cpp and batcher_formats_host_test.cpp bind it to a fake and run under ThreadSanitizer.
 #pragma once
 
 #include <chrono>
@@ -53,6 +54,7 @@ private:
     };
     struct Batch {
         std::string key;
+        int kind = IPX_JOB_JPEG;                    // the file job the group goes out as: the format of its files
         OpsCopy ops;
         std::chrono::steady_clock::time_point deadline;
         std::vector<ipx_bytes> files;

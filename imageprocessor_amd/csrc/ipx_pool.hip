@@ -41,7 +41,7 @@ struct PoolOps {                 // a deep copy of ipx_pool_ops: the caller may 
 struct JobState {
     ipx_job job{};
     PoolOps ops;
-    std::vector<ipx_jpeg_result *> results;   // IPX_JOB_JPEG: pinned blocks the output streams live in, per slot that produced them
+    std::vector<ipx_jpeg_result *> results;   // file jobs: pinned blocks the output streams live in, per slot that produced them
     std::vector<ipx_ctx *> result_ctx;        // (chunks append under the job's State::mu)
 };
 typedef ipx::PoolCore<JobState> Core;
@@ -68,12 +68,28 @@ namespace {
 // bytes per pixel of a pixel job's frames; 0 for a kind that is none
 int pixel_job_bpp(int kind) { return src_of_job(kind) < 0 ? 0 : src_bpp(src_of_job(kind)); }
 
-double chunk_cost(const JobState &j, int m)
+// a job of uploaded files (one of the compressed-in, compressed-out legs runs a chunk of it) rather than of decoded frames
+bool is_file_job(int kind) { return kind == IPX_JOB_JPEG || kind == IPX_JOB_PNG || kind == IPX_JOB_GIF; }
+
+// files per chunk of a file job: every leg pipelines inside a part of a few hundred files
+int file_chunk(int kind)
 {
-    if (j.job.kind == IPX_JOB_JPEG) {
+    const char *name = kind == IPX_JOB_PNG ? "IPX_POOL_PNG_CHUNK" : kind == IPX_JOB_GIF ? "IPX_POOL_GIF_CHUNK" : "IPX_POOL_JPEG_CHUNK";
+    return std::max(1, env_int(name, 256));
+}
+
+// orders the queue, largest first: only has to be monotone in the chunk's work.  `files` is the chunk's own slice of a file job.
+double chunk_cost(const JobState &j, const ipx_bytes *files, int m)
+{
+    if (is_file_job(j.job.kind)) {
+        const double frame = (double)j.ops.p.sw * j.ops.p.sh;
         double b = 0;
-        for (int i = 0; i < m; i++) b += (double)j.job.files[i].len;   // callers pass the chunk's own slice
-        return b * 24 + (double)m * j.ops.p.sw * j.ops.p.sh * 8;         // decoded size dominates
+        for (int i = 0; i < m; i++) b += (double)files[i].len;
+        if (j.job.kind == IPX_JOB_JPEG) return b * 24 + (double)m * frame * 8;   // decoded size dominates
+        // PNG: the inflate walk, about proportional to the raw bytes (1 to 8 per pixel; the kind is not known before the parse).
+        // GIF: the LZW walk over the compressed bytes, then one byte per pixel.  Neither proxy has been measured.
+        if (j.job.kind == IPX_JOB_PNG) return (double)m * frame * 4 + b;
+        return b + (double)m * frame;
     }
     return (double)m * ((double)j.ops.p.sw * j.ops.p.sh * (4 + pixel_job_bpp(j.job.kind)) + 4.0 * 1024 * 768);
 }
@@ -186,11 +202,15 @@ int run_chunk(Slot &s, Feeder &f, JobState &j, int i0, int m, ipx_jpeg_result **
         int cached = 0;
         int rc = ipx_plan_acquire(s.ctx, &j.ops.p, &plan, &cached);     // plans and glyph sets by content, per context
         if (rc) return rc;
-        if (j.job.kind == IPX_JOB_JPEG)
-            rc = ipx_plan_run_jpeg_jpeg(s.ctx, plan, m, j.job.files + i0, j.job.quality, j.job.resize_jpeg ? j.job.resize_jpeg + i0 : nullptr,
-                                        j.job.thumb_jpeg ? j.job.thumb_jpeg + i0 : nullptr, j.job.wm_jpeg ? j.job.wm_jpeg + i0 : nullptr,
-                                        j.job.status + i0, res);
-        else rc = run_pixel_chunk(s, f, j, plan, i0, m);     // (both return with the chunk's GPU work finished)
+        const ipx_job &q = j.job;
+        ipx_bytes *ores = q.resize_jpeg ? q.resize_jpeg + i0 : nullptr, *oth = q.thumb_jpeg ? q.thumb_jpeg + i0 : nullptr;
+        ipx_bytes *owm = q.wm_jpeg ? q.wm_jpeg + i0 : nullptr;
+        switch (q.kind) {     // (every one returns with the chunk's GPU work finished)
+        case IPX_JOB_JPEG: rc = ipx_plan_run_jpeg_jpeg(s.ctx, plan, m, q.files + i0, q.quality, ores, oth, owm, q.status + i0, res); break;
+        case IPX_JOB_PNG: rc = ipx_plan_run_png_png(s.ctx, plan, m, q.files + i0, ores, oth, owm, q.status + i0, res); break;
+        case IPX_JOB_GIF: rc = ipx_plan_run_gif_gif(s.ctx, plan, m, q.files + i0, q.quality, ores, oth, owm, q.status + i0, res); break;
+        default: rc = run_pixel_chunk(s, f, j, plan, i0, m);
+        }
         if (!cached) {
             std::string keep = rc ? ipx_last_error() : "";
             ipx_plan_release(s.ctx, plan, cached);
@@ -239,8 +259,11 @@ int job_check(const ipx_job *job)
             set_error("ipx_job_submit: %dx%d frames are beyond the span the kernels address", o.sw, o.sh);
             return IPX_ERR_UNSUPPORTED;
         }
-    } else if (job->kind == IPX_JOB_JPEG) {
-        if (job->n && (!job->files || !job->status)) { set_error("ipx_job_submit: a JPEG job needs files and a status array"); return IPX_ERR_INVALID; }
+    } else if (is_file_job(job->kind)) {
+        if (job->n && (!job->files || !job->status)) {
+            set_error("ipx_job_submit: a %s job needs files and a status array", job->kind == IPX_JOB_PNG ? "PNG" : job->kind == IPX_JOB_GIF ? "GIF" : "JPEG");
+            return IPX_ERR_INVALID;
+        }
     } else {
         set_error("ipx_job_submit: unknown job kind %d", job->kind);
         return IPX_ERR_INVALID;
@@ -333,12 +356,14 @@ int ipx_job_submit(ipx_pool *pool, const ipx_job *job, ipx_ticket *ticket) try
     j->job = *job;
     rc = copy_ops(job->ops, &j->ops);
     if (rc) return rc;
-    if (job->kind == IPX_JOB_JPEG)
+    const bool of_files = is_file_job(job->kind);
+    if (of_files)
         for (int i = 0; i < job->n; i++) job->status[i] = IPX_OK;
     // chunks: about lane_bytes of frames each, and at least two per feeder so that uploads, kernels and downloads of different
-    // chunks overlap; a JPEG job goes in parts of a few hundred files (ipx_plan_run_jpeg_jpeg pipelines inside a part)
+    // chunks overlap; a file job goes in parts of a few hundred files (its leg pipelines inside a part, and bounds its own device
+    // memory by bytes whatever the part holds: DESIGN.md section 6)
     int per;
-    if (job->kind == IPX_JOB_JPEG) per = std::max(1, env_int("IPX_POOL_JPEG_CHUNK", 256));
+    if (of_files) per = file_chunk(job->kind);
     else {
         const size_t fb = (size_t)job->ops.sw * job->ops.sh * (4 + pixel_job_bpp(job->kind)) + ((size_t)4 << 20);
         per = (int)std::max<size_t>(1, pool->lane_bytes / fb);
@@ -349,11 +374,7 @@ int ipx_job_submit(ipx_pool *pool, const ipx_job *job, ipx_ticket *ticket) try
     for (int i0 = 0; i0 < job->n; i0 += per) {
         Core::Piece c;
         c.i0 = i0; c.m = std::min(per, job->n - i0);
-        if (job->kind == IPX_JOB_JPEG) {
-            JobState tmp;            // cost of this slice: its own file sizes
-            tmp.job = *job; tmp.job.files = job->files + i0; tmp.ops.p = job->ops;
-            c.cost = chunk_cost(tmp, c.m);
-        } else c.cost = chunk_cost(*j, c.m);
+        c.cost = chunk_cost(*j, of_files ? job->files + i0 : nullptr, c.m);
         pieces.push_back(c);
     }
     uint64_t t = 0;
@@ -401,7 +422,7 @@ int ipx_pool_run_host(ipx_pool *pool, const ipx_job *jobs, int n_jobs) try
     clear_error();
     if (!pool || n_jobs < 0 || (n_jobs && !jobs)) { set_error("ipx_pool_run_host: bad argument"); return IPX_ERR_INVALID; }
     for (int i = 0; i < n_jobs; i++)
-        if (!pixel_job_bpp(jobs[i].kind)) { set_error("ipx_pool_run_host: pixel jobs only (JPEG jobs keep their outputs until ipx_job_release)"); return IPX_ERR_INVALID; }
+        if (!pixel_job_bpp(jobs[i].kind)) { set_error("ipx_pool_run_host: pixel jobs only (file jobs keep their outputs until ipx_job_release)"); return IPX_ERR_INVALID; }
     std::vector<ipx_ticket> tickets;
     int rc = IPX_OK;
     std::string text;

@@ -637,18 +637,26 @@ enum { IPX_JOB_RGBA8 = 0,       /* decoded frames in, the operators' RGBA8 outpu
        /* decoded frames of the other packed image types, Pix as Go holds it (src / sstride / src_frame_stride describe it), RGBA8
         * outputs back: what ipx_plan_run_host_nrgba / _gray / _deep do */
        IPX_JOB_NRGBA8 = 2, IPX_JOB_GRAY8 = 3,
-       IPX_JOB_NRGBA64 = 4, IPX_JOB_RGBA64 = 5, IPX_JOB_GRAY16 = 6, IPX_JOB_CMYK = 7 };
+       IPX_JOB_NRGBA64 = 4, IPX_JOB_RGBA64 = 5, IPX_JOB_GRAY16 = 6, IPX_JOB_CMYK = 7,
+       /* uploaded PNG / GIF files in, three streams per file back (what ipx_plan_run_png_png / ipx_plan_run_gif_gif do): file jobs,
+        * shaped like IPX_JOB_JPEG */
+       IPX_JOB_PNG = 8, IPX_JOB_GIF = 9 };
 typedef struct {
     int32_t kind;
     ipx_pool_ops ops;
     int32_t n;                  /* frames / files, all of size ops.sw x ops.sh */
-    /* pixel jobs (every kind but IPX_JOB_JPEG): frame i at src + i*src_frame_stride; an output pointer may be NULL to skip it */
+    /* pixel jobs (every kind but the file jobs IPX_JOB_JPEG / _PNG / _GIF): frame i at src + i*src_frame_stride; an output pointer may be NULL to skip it */
     const uint8_t *src; int32_t sstride; size_t src_frame_stride;
     uint8_t *resize_out; size_t resize_frame_stride;
     uint8_t *thumb_out; size_t thumb_frame_stride;
     uint8_t *wm_out; size_t wm_frame_stride;
-    /* IPX_JOB_JPEG: n files; n entries per output array (or NULL), pointing into pinned blocks the pool owns until ipx_job_release;
-     * status[i] as ipx_plan_run_jpeg_jpeg reports it (files Go has to decode itself get IPX_ERR_UNSUPPORTED) */
+    /* file jobs (IPX_JOB_JPEG, IPX_JOB_PNG, IPX_JOB_GIF): n files of the job's format; n entries per output array (or NULL), pointing
+     * into pinned blocks the pool owns until ipx_job_release; status[i] as the format's leg (ipx_plan_run_jpeg_jpeg / _png_png /
+     * _gif_gif) reports it (files Go has to decode itself get IPX_ERR_UNSUPPORTED), preset to IPX_OK at submit; outputs of non-OK
+     * files are {NULL, 0}.  The three output arrays keep their names for every format and hold streams of the job's format, as the
+     * reference's operators end in the encoder of the upload's own format: a JPEG job three JPEG streams; a PNG job three PNG
+     * streams; a GIF job a GIF (resize), a GIF (thumbnail) and a JPEG for the watermark (watermark.go:66-79).  `quality` is
+     * jpeg.Options.Quality: a JPEG job's three outputs, a GIF job's watermark, ignored by a PNG job. */
     const ipx_bytes *files; int32_t quality;
     ipx_bytes *resize_jpeg, *thumb_jpeg, *wm_jpeg;
     int32_t *status;
@@ -657,18 +665,22 @@ typedef uint64_t ipx_ticket;
 int ipx_job_submit(ipx_pool *pool, const ipx_job *job, ipx_ticket *ticket);     /* returns at once */
 int ipx_job_poll(ipx_pool *pool, ipx_ticket ticket, int *done);                 /* *done = 1 when ipx_job_wait would not block */
 int ipx_job_wait(ipx_pool *pool, ipx_ticket ticket, int *frames_done);          /* blocks; the job's status (first failing chunk's) */
-int ipx_job_release(ipx_pool *pool, ipx_ticket ticket);                         /* forgets the job, frees a JPEG job's output blocks */
+int ipx_job_release(ipx_pool *pool, ipx_ticket ticket);                         /* forgets the job, frees a file job's output blocks */
 /* Synchronous convenience for pixel jobs: submit them all (mixed sizes welcome: the queue runs the largest first), wait, release. */
 int ipx_pool_run_host(ipx_pool *pool, const ipx_job *jobs, int n_jobs);
 
 /* ---- micro-batching of single uploads ---------------------------------------------------------------------------------------
  * The reference pulls ONE message per goroutine (internal/worker/worker.go:112-149) from a channel of concurrency * 2 (:88); what
  * turns those single files into GPU batches has to sit between the goroutines and the pool, and it sits here, below the ABI, so that
- * its policy is the library's (and tested) rather than every binding's.  ipx_batcher_submit takes ONE uploaded JPEG file with the
- * operators of its task (ops->sw x ops->sh = the frame size from the file's header, image.DecodeConfig) and returns a ticket at once;
- * files are grouped by frame size, JPEG shape (components and luma sampling of the frame header: a batch is one shape) and operator
- * content (parameters, colour, every glyph's rectangle and mask bytes); a group goes to the
- * pool as one IPX_JOB_JPEG when it holds max_batch files or when its first file has waited max_wait_us.  ipx_batcher_wait blocks until
+ * its policy is the library's (and tested) rather than every binding's.  ipx_batcher_submit takes ONE uploaded file -- JPEG, PNG or GIF, told apart by
+ * the full signature as image.Decode does (the 8 bytes 89 50 4E 47 0D 0A 1A 0A; the 6 bytes GIF87a or GIF89a; anything else goes the
+ * JPEG way and gets its status from that decoder) -- with the operators of its task (ops->sw x ops->sh = the frame size from the
+ * file's header, image.DecodeConfig) and returns a ticket at once; files are grouped by format, frame size, JPEG shape (components
+ * and luma sampling of the frame header: a JPEG batch is one shape; PNG files of every colour type and depth share a group, the leg
+ * sorts them itself) and operator content (parameters, colour, every glyph's rectangle and mask bytes); a group goes to the pool as
+ * one IPX_JOB_JPEG / IPX_JOB_PNG / IPX_JOB_GIF when it holds max_batch files or when its first file has waited max_wait_us.  The
+ * streams of a result are those of the job's format (ipx_job).  For a GIF image.DecodeConfig reports the logical screen while the
+ * leg goes by the first image: a file whose first image has another size gets IPX_ERR_UNSUPPORTED, alone.  ipx_batcher_wait blocks until
  * the ticket's group is done and fills the file's own result: status IPX_OK and three streams (NULL for operators the task did not ask
  * for), or IPX_ERR_UNSUPPORTED / IPX_ERR_INVALID for a file the GPU path does not decode -- its neighbours are not affected, the worker
  * runs its own image.Decode path for that message.  The streams live in blocks shared by the group: ipx_batcher_release hands a file's
@@ -680,7 +692,7 @@ typedef struct ipx_batcher ipx_batcher;
 typedef struct {
     int32_t max_batch;      /* files per job; 0 = 256 (a part of ipx_plan_run_jpeg_jpeg) */
     int32_t max_wait_us;    /* how long the first file of a group may wait for company WHILE other jobs of this batcher run; 0 = 2000 */
-    int32_t quality;        /* jpeg.Options.Quality of the outputs; 0 = 85 (domain.DefaultJPEGQuality, task.go:57) */
+    int32_t quality;        /* jpeg.Options.Quality of the JPEG outputs (a GIF's watermark among them); 0 = 85 (domain.DefaultJPEGQuality, task.go:57) */
 } ipx_batcher_config;
 typedef uint64_t ipx_batch_ticket;
 typedef struct {

@@ -2,7 +2,10 @@
 """The micro-batcher under load (ipx_batcher_*): S submitter threads, each with ONE file in flight at a time as a goroutine of the
 reference has (internal/worker/worker.go:112-149), 1080p 4:2:0 q85 uploads, resize 1024x576 + thumbnail 200 + watermark, three JPEG
 streams back.  Prints images/s and the p50 / p99 latency of a file (submit -> its objects), and how the batcher grouped the files.
-usage: tools/bench_batcher.py [files per submitter] [max_batch] [max_wait_us] [submitters ...]"""
+--format png | gif: photo-like 1024x768 uploads of that format instead (the corpora of tools/bench_png_decode.py and
+tools/bench_gif_decode.py: Pillow-written RGB PNGs, 256-colour GIFs), resize 512x384 + thumbnail 64 as those tools ask for; mixed: the
+JPEG, PNG and GIF uploads in turn, each with its own size and operators.
+usage: tools/bench_batcher.py [--format jpeg|png|gif|mixed] [files per submitter] [max_batch] [max_wait_us] [submitters ...]"""
 import io
 import os
 import sys
@@ -18,23 +21,57 @@ from PIL import Image  # noqa: E402
 import imageprocessor_amd as ipx  # noqa: E402
 from helpers import DEFAULT_COL, text_glyphs  # noqa: E402
 
-per = int(sys.argv[1]) if len(sys.argv) > 1 else 64
-max_batch = int(sys.argv[2]) if len(sys.argv) > 2 else 256
-max_wait = int(sys.argv[3]) if len(sys.argv) > 3 else 2000
-subs = [int(v) for v in sys.argv[4:]] or [3, 16, 64]
-sw, sh = 1920, 1080
-yy, xx = np.mgrid[0:sh, 0:sw]
-files = []
-for k in range(4):
-    base = np.stack([np.sin(xx / (40.0 + 7 * k)) * 90 + 128, np.cos(yy / (31.0 + 5 * k)) * 90 + 128, ((xx + 2 * yy) / 6.0 + 40 * k) % 256], -1)
-    img = (base + np.random.default_rng(k).normal(0, 6, (sh, sw, 3))).clip(0, 255).astype(np.uint8)
-    buf = io.BytesIO()
-    Image.fromarray(img).save(buf, "JPEG", quality=85)
-    files.append(buf.getvalue())
-glyphs = text_glyphs(sw, sh)
-ops = dict(resize=(1024, 768, True), thumbnail=(200, True), glyphs=glyphs, col=DEFAULT_COL)
+argv = sys.argv[1:]
+fmt = "jpeg"
+if "--format" in argv:
+    i = argv.index("--format")
+    fmt = argv[i + 1]
+    del argv[i:i + 2]
+if fmt not in ("jpeg", "png", "gif", "mixed"):
+    raise SystemExit("bench_batcher: --format jpeg|png|gif|mixed")
+per = int(argv[0]) if len(argv) > 0 else 64
+max_batch = int(argv[1]) if len(argv) > 1 else 256
+max_wait = int(argv[2]) if len(argv) > 2 else 2000
+subs = [int(v) for v in argv[3:]] or [3, 16, 64]
+
+
+def jpeg_uploads():
+    sw, sh = 1920, 1080
+    yy, xx = np.mgrid[0:sh, 0:sw]
+    out = []
+    for k in range(4):
+        base = np.stack([np.sin(xx / (40.0 + 7 * k)) * 90 + 128, np.cos(yy / (31.0 + 5 * k)) * 90 + 128, ((xx + 2 * yy) / 6.0 + 40 * k) % 256], -1)
+        img = (base + np.random.default_rng(k).normal(0, 6, (sh, sw, 3))).clip(0, 255).astype(np.uint8)
+        buf = io.BytesIO()
+        Image.fromarray(img).save(buf, "JPEG", quality=85)
+        out.append(buf.getvalue())
+    return [(f, sw, sh, dict(resize=(1024, 768, True), thumbnail=(200, True), glyphs=text_glyphs(sw, sh), col=DEFAULT_COL)) for f in out]
+
+
+def png_uploads(sw=1024, sh=768):
+    import png_corpus
+    out = []
+    for k in range(4):
+        buf = io.BytesIO()
+        Image.fromarray(png_corpus.photo(sh, sw, 3, 9000 + k).astype(np.uint8), "RGB").save(buf, "PNG")
+        out.append(buf.getvalue())
+    return [(f, sw, sh, dict(resize=(sw // 2, sh // 2, False), thumbnail=(64, True))) for f in out]
+
+
+def gif_uploads(sw=1024, sh=768):
+    import gif_corpus
+    return [(gif_corpus.make(sw, sh, 9000 + k, "photo", ncol=256, interlace=False), sw, sh, dict(resize=(sw // 2, sh // 2, False), thumbnail=(64, True)))
+            for k in range(4)]
+
+
+makers = {"jpeg": jpeg_uploads, "png": png_uploads, "gif": gif_uploads}
+if fmt == "mixed":
+    files = [u for trio in zip(jpeg_uploads(), png_uploads(), gif_uploads()) for u in trio]
+else:
+    files = makers[fmt]()
+nf = len(files)
 with ipx.Pool(devices=(0,)) as pool, ipx.Batcher(pool, max_batch=max_batch, max_wait_us=max_wait, quality=85) as b:
-    for t in [b.submit(files[i % 4], sw, sh, **ops) for i in range(32)]:      # plans, glyph set, lanes warm
+    for t in [b.submit(files[i % nf][0], *files[i % nf][1:3], **files[i % nf][3]) for i in range(32)]:      # plans, glyph set, lanes warm
         b.wait(t)
     for S in subs:
         lat = []
@@ -45,7 +82,8 @@ with ipx.Pool(devices=(0,)) as pool, ipx.Batcher(pool, max_batch=max_batch, max_
             mine = []
             for i in range(per):
                 t0 = time.perf_counter()
-                st, out = b.wait(b.submit(files[(k + i) % 4], sw, sh, **ops))
+                f = files[(k + i) % nf]
+                st, out = b.wait(b.submit(f[0], f[1], f[2], **f[3]))
                 mine.append(time.perf_counter() - t0)
                 assert st == 0 and out["resize"]
             with mu:
@@ -58,7 +96,7 @@ with ipx.Pool(devices=(0,)) as pool, ipx.Batcher(pool, max_batch=max_batch, max_
         lat.sort()
         st = b.stats()
         nb = st["batches"] - before["batches"]
-        print("%3d submitters x %d files: %7.0f images/s; latency p50 %.2f ms, p99 %.2f ms; %d batches (mean %.1f files; %d by size, %d by timer, %d when idle)"
-              % (S, per, S * per / dt, lat[len(lat) // 2] * 1e3, lat[min(len(lat) - 1, int(len(lat) * 0.99))] * 1e3, nb, S * per / max(1, nb),
+        print("%s %3d submitters x %d files: %7.0f images/s; latency p50 %.2f ms, p99 %.2f ms; %d batches (mean %.1f files; %d by size, %d by timer, %d when idle)"
+              % (fmt, S, per, S * per / dt, lat[len(lat) // 2] * 1e3, lat[min(len(lat) - 1, int(len(lat) * 0.99))] * 1e3, nb, S * per / max(1, nb),
                  st["flushed_by_size"] - before["flushed_by_size"], st["flushed_by_timer"] - before["flushed_by_timer"],
                  st["flushed_when_idle"] - before["flushed_when_idle"]), flush=True)
