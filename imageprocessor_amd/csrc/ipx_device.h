@@ -80,6 +80,47 @@ __device__ __forceinline__ uint32_t glyph_run(uint32_t d, int x, int y, const De
     return d;
 }
 
+// The text walk of the stand-alone composites (composite_kernel, ks_tail_kernel): the glyph table `tab` (LDS) four glyphs at a time on
+// a lane's pixels d[r][k] = (x + k, ybase + YSTEP * r): rectangle tests from the table, the mask bytes of the glyphs that hold a pixel
+// loaded together (the PX bytes of a row packed into a dword), then the composites in string order -- a step costs one global latency
+// instead of one per glyph.  A ballot skips steps no lane of the wave touches.
+template <int PX, int ROWS, int YSTEP>
+__device__ __forceinline__ void glyph_walk(const DevGlyph *tab, int n, int x, int ybase, Rect bbox, uint32_t (&d)[ROWS][PX], uint32_t sr,
+                                           uint32_t sg, uint32_t sb, uint32_t sa)
+{
+    static_assert(PX >= 1 && PX <= 4, "a row's mask bytes travel in one dword");
+    for (int g = 0; g < n; g += 4) {
+        uint32_t m[4][ROWS];
+        bool any = false;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const DevGlyph G = tab[min(g + j, n - 1)];
+#pragma unroll
+            for (int r = 0; r < ROWS; r++) {
+                const int y = ybase + YSTEP * r;
+                const bool iny = g + j < n && y >= G.y0 && y < G.y1 && y < bbox.y1;
+                uint32_t mm = 0u;
+#pragma unroll
+                for (int k = 0; k < PX; k++) {
+                    const bool in = iny && x + k >= G.x0 && x + k < G.x1;
+                    mm |= (in ? (uint32_t)G.mask[(size_t)(y - G.y0) * G.mstride + (x + k - G.x0)] : 0u) << (8 * k);
+                    any |= in;
+                }
+                m[j][r] = mm;
+            }
+        }
+        if (!__any(any)) continue;  // wave-uniform skip
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (int r = 0; r < ROWS; r++)
+#pragma unroll
+                for (int k = 0; k < PX; k++) {
+                    const uint32_t mk = (m[j][r] >> (8 * k)) & 0xffu;
+                    if (mk) d[r][k] = glyph_over(d[r][k], mk, sr, sg, sb, sa);
+                }
+    }
+}
 
 }  // namespace
 }  // namespace ipx

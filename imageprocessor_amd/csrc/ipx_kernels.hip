@@ -182,12 +182,11 @@ __global__ __launch_bounds__(256) void draw_ycbcr_kernel(uint8_t *dst, int dstri
     }
 }
 
-// Stand-alone composite over the bounding box of the clipped glyph rectangles (the text pass after every band kernel, and the
-// per-operation seam).  One wave covers a 64-pixel row segment.  The glyph table goes to LDS once per workgroup; the list is walked
-// four glyphs at a time: rectangle tests from LDS, the mask bytes of the glyphs that hold the pixel loaded together, then the composites
-// in string order -- a step costs one global latency instead of one per glyph (the first version loaded descriptor and mask per
-// glyph and pixel, each a full round trip: 156 us per 1024 frames for a 16-glyph text).  A ballot skips steps no lane of the segment
-// touches, and untouched pixels are never written.
+// Stand-alone composite over the bounding box of the clipped glyph rectangles (the per-operation seam and the batch path's fallbacks;
+// behind the one-pass kernel's float pass the text is part of ks_tail_kernel, ipx_ks_tail.hip).  One wave covers a 64-pixel row
+// segment.  The glyph table goes to LDS once per workgroup; the list is walked four glyphs at a time (glyph_walk, ipx_device.h; the
+// first version loaded descriptor and mask per glyph and pixel, each a full round trip: 156 us per 1024 frames for a 16-glyph text).
+// Untouched pixels are never written.
 constexpr int kCompositeRows = 4;   // pixels per thread (one column, 4 rows apart): the table load and the launch overhead of a block serve 16 rows
 __global__ __launch_bounds__(256) void composite_kernel(uint8_t *dst, int dstride, size_t frame_stride,
                                                         const DevGlyph *__restrict__ gl, int n,
@@ -200,40 +199,19 @@ __global__ __launch_bounds__(256) void composite_kernel(uint8_t *dst, int dstrid
     const int ybase = bbox.y0 + (int)(blockIdx.y * (4 * kCompositeRows) + threadIdx.y);
     uint8_t *frame = dst + blockIdx.z * frame_stride;
     // the pixels first (their loads fly while the table arrives): a thread takes kCompositeRows pixels of one column, 4 rows apart
-    uint32_t d[kCompositeRows], d0[kCompositeRows];
+    uint32_t d[kCompositeRows][1], d0[kCompositeRows];
 #pragma unroll
     for (int r = 0; r < kCompositeRows; r++) {
         const int y = ybase + 4 * r;
-        d0[r] = d[r] = x < bbox.x1 && y < bbox.y1 ? *(const uint32_t *)(frame + (size_t)y * dstride + (size_t)x * 4) : 0u;
+        d0[r] = d[r][0] = x < bbox.x1 && y < bbox.y1 ? *(const uint32_t *)(frame + (size_t)y * dstride + (size_t)x * 4) : 0u;
     }
     for (int g = lt; g < n; g += 256) tab[g] = gl[g];
     __syncthreads();
-    for (int g = 0; g < n; g += 4) {
-        uint32_t m[4][kCompositeRows];
-        bool any = false;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const DevGlyph G = tab[min(g + j, n - 1)];
-            const bool inx = g + j < n && x >= G.x0 && x < G.x1;
-#pragma unroll
-            for (int r = 0; r < kCompositeRows; r++) {
-                const int y = ybase + 4 * r;
-                const bool in = inx && y >= G.y0 && y < G.y1 && y < bbox.y1;
-                m[j][r] = in ? G.mask[(size_t)(y - G.y0) * G.mstride + (x - G.x0)] : 0u;
-                any |= in;
-            }
-        }
-        if (!__any(any)) continue;  // wave-uniform skip
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-#pragma unroll
-            for (int r = 0; r < kCompositeRows; r++)
-                if (m[j][r]) d[r] = glyph_over(d[r], m[j][r], sr, sg, sb, sa);
-    }
+    glyph_walk<1, kCompositeRows, 4>(tab, n, x, ybase, bbox, d, sr, sg, sb, sa);
 #pragma unroll
     for (int r = 0; r < kCompositeRows; r++) {
         const int y = ybase + 4 * r;
-        if (x < bbox.x1 && y < bbox.y1 && d[r] != d0[r]) *(uint32_t *)(frame + (size_t)y * dstride + (size_t)x * 4) = d[r];
+        if (x < bbox.x1 && y < bbox.y1 && d[r][0] != d0[r]) *(uint32_t *)(frame + (size_t)y * dstride + (size_t)x * 4) = d[r][0];
     }
 }
 

@@ -73,6 +73,7 @@ struct KsGenArgs {
     const uint8_t *src; int sstride; size_t src_fs;
     const uint8_t *cb, *cr; int cstride, ratio; size_t c_fs;
     int nframes;
+    int src_w;                            // pixels per source row where the caller lets the exact pass load taps 16 bytes at a time (ks_row_sum); 0: dword by dword
 };
 hipError_t launch_ks_generic(const KsGenArgs &a, hipStream_t s);
 
@@ -135,6 +136,8 @@ struct KsFusedArgs {
                                // list of (dy, dx) of the pixels it could not decide -- output k's at fix + frame * fix_stride + (k ? fix_cap[0] : 0),
                                // fix_cap[k] entries -- and how many were appended, fix_count[2 * frame + k]
 };
+// the text of a batch's watermark frames: the clipped glyphs in HBM, their bounding box, the colour as 16-bit values
+struct KsText { const DevGlyph *gl; int n; Rect bbox; uint32_t sr, sg, sb, sa; };
 // what the exact per-pixel pass after the float pass needs per output: the axes in HBM (NULL list: no float pass)
 struct KsFix { uint2 *list = nullptr; int *count = nullptr; int cap[2] = {0, 0}; KsAxisDev ax[2], ay[2]; };
 // one segmentation of the frame's rows and the row tables cut for it
@@ -167,9 +170,27 @@ bool ks_fused_plan(int sw, int sh, const KsFusedIn *sc0, const KsFusedIn *sc1, i
 void ks_fused_rebase(KsFusedPlan *p, const uint8_t *dev_blob);
 // *matched = false: nothing launched (shape, alignment or kind the kernel is not built for)
 // fix: lists for the float pass (RGBA with `redo`, YCbCr, Gray sources), or NULL: float64 throughout
-hipError_t launch_ks_fused(const KsFusedPlan &p, KsFusedArgs &a, const KsFix *fix, int cus, hipStream_t s, bool *matched);
+// text: the glyphs of the watermark frames (a.wm), or NULL.  *text_done = true: the text went out with the sequence (the tail launch,
+// below); false: the caller still has to composite it.
+hipError_t launch_ks_fused(const KsFusedPlan &p, KsFusedArgs &a, const KsFix *fix, const KsText *text, int cus, hipStream_t s, bool *matched, bool *text_done);
 // the exact pass over the float pass's lists: every listed pixel of one output (described by `g`, one frame per blockIdx.y) recomputed.
 // list / count: the output's list and counter of frame 0; frame f's are list + f * list_stride and count[f * count_stride]
 hipError_t launch_ks_fix(const KsGenArgs &g, const uint2 *list, size_t list_stride, const int *count, int count_stride, int cap, hipStream_t s);
+
+// The tail of a batch behind the float pass and the float64 redo pass (ipx_ks_tail.hip): ONE launch for the exact pass over both
+// outputs' lists and the text of the watermark frames -- three kinds of work that write disjoint bytes, interleaved frame by frame so
+// that they are in flight together.  g[k] / list[k] / count[k] / cap[k] as launch_ks_fix takes them (cap[k] = 0: no such output);
+// text.n = 0 or wm = NULL: no text.  The launcher fills R, chunks, tbx and tby.
+struct KsTailArgs {
+    KsGenArgs g[2];
+    const uint2 *list[2]; const int *count[2]; int cap[2];
+    size_t list_stride; int count_stride;
+    int nframes;
+    int R[2], chunks[2];       // lanes per pixel and blocks per frame of each output's exact part
+    uint8_t *wm; int wm_stride; size_t wm_fs;
+    KsText text;
+    int tbx, tby;              // text blocks per frame: 64 x 16 pixels each
+};
+hipError_t launch_ks_tail(KsTailArgs t, hipStream_t s);
 
 }  // namespace ipx

@@ -816,9 +816,9 @@ hipError_t launch_src(const KsFusedPlan &p, const KsFusedArgs &a, int nitems, hi
 
 }  // namespace
 
-hipError_t launch_ks_fused(const KsFusedPlan &p, KsFusedArgs &a, const KsFix *fix, int cus, hipStream_t s, bool *matched)
+hipError_t launch_ks_fused(const KsFusedPlan &p, KsFusedArgs &a, const KsFix *fix, const KsText *text, int cus, hipStream_t s, bool *matched, bool *text_done)
 {
-    *matched = false;
+    *matched = false; *text_done = false;
     if (!p.ok || a.nframes <= 0) return hipSuccess;
     // frames are addressed through buffer descriptors with aligned dword (chroma: word) loads
     if ((((uintptr_t)a.src) | (uintptr_t)a.sstride | a.src_fs) & 3) return hipSuccess;
@@ -902,20 +902,53 @@ hipError_t launch_ks_fused(const KsFusedPlan &p, KsFusedArgs &a, const KsFix *fi
     layout(false);
     a.fix = fast ? fix->list : nullptr; a.fix_count = fast ? fix->count : nullptr;
     a.fix_cap[0] = fast ? fix->cap[0] : 0; a.fix_cap[1] = fast ? fix->cap[1] : 0; a.fix_stride = a.fix_cap[0] + a.fix_cap[1];
+    auto exact_args = [&](const KsFusedOut &o) {
+        KsGenArgs g{};
+        g.dst = o.out; g.dstride = o.ostride; g.dst_fs = o.frame_stride;
+        g.adr_x1 = o.dw; g.adr_y1 = o.dh; g.sr_x0 = o.sr_x0; g.sr_y0 = o.sr_y0;
+        g.ax = fix->ax[o.pk]; g.ay = fix->ay[o.pk]; g.op = IPX_OP_SRC; g.kind = o.kind;
+        g.src = a.src; g.sstride = a.sstride; g.src_fs = a.src_fs;
+        g.cb = a.cb; g.cr = a.cr; g.cstride = a.cstride; g.ratio = a.ratio; g.c_fs = a.c_fs;
+        g.nframes = a.nframes;
+        return g;
+    };
     auto exact_listed = [&]() {
         hipError_t e = hipSuccess;
         for (int i = 0; i < a.nout && e == hipSuccess; i++) {
             const KsFusedOut &o = a.o[i];
-            KsGenArgs g{};
-            g.dst = o.out; g.dstride = o.ostride; g.dst_fs = o.frame_stride;
-            g.adr_x1 = o.dw; g.adr_y1 = o.dh; g.sr_x0 = o.sr_x0; g.sr_y0 = o.sr_y0;
-            g.ax = fix->ax[o.pk]; g.ay = fix->ay[o.pk]; g.op = IPX_OP_SRC; g.kind = o.kind;
-            g.src = a.src; g.sstride = a.sstride; g.src_fs = a.src_fs;
-            g.cb = a.cb; g.cr = a.cr; g.cstride = a.cstride; g.ratio = a.ratio; g.c_fs = a.c_fs;
-            g.nframes = a.nframes;
-            e = launch_ks_fix(g, fix->list + (o.pk ? fix->cap[0] : 0), (size_t)a.fix_stride, fix->count + o.pk, 2, fix->cap[o.pk], s);
+            e = launch_ks_fix(exact_args(o), fix->list + (o.pk ? fix->cap[0] : 0), (size_t)a.fix_stride, fix->count + o.pk, 2, fix->cap[o.pk], s);
         }
         return e;
+    };
+    // What follows the float pass.  By default: the float64 redo pass on the items the float pass gave up, then ONE tail launch
+    // (ipx_ks_tail.hip) with the exact pass over both outputs' lists and the text of the watermark frames in flight together.
+    //   * The redo pass rewrites whole items, watermark rows included, so the text has to come after it: the tail goes last.
+    //   * The exact pixels may be written after the redo pass as well as before it: both write the reference's bytes for the same pixel
+    //     (the exact pass uses the general 4-channel tap of its kind, also on frames that were not opaque), and a list that overflowed is
+    //     cut at its capacity either way.
+    //   * Inside the tail no two parts write the same byte: output 0's frames, output 1's frames, the watermark frames' text box.
+    // IPX_KS_TAIL=0 (read per call): the sequence as it was -- the exact launches, the redo pass, and the text left to the caller.
+    const char *tv = getenv("IPX_KS_TAIL");
+    const bool tail = !(tv && *tv && atoi(tv) == 0);
+    auto after_float = [&](auto redo_pass) {
+        if (!tail) {
+            hipError_t e = exact_listed();
+            return e == hipSuccess ? redo_pass() : e;
+        }
+        hipError_t e = redo_pass();
+        if (e != hipSuccess) return e;
+        KsTailArgs t{};
+        for (int i = 0; i < a.nout; i++) {
+            const KsFusedOut &o = a.o[i];
+            t.g[i] = exact_args(o);
+            t.g[i].src_w = a.sw;
+            t.list[i] = fix->list + (o.pk ? fix->cap[0] : 0); t.count[i] = fix->count + o.pk; t.cap[i] = fix->cap[o.pk];
+        }
+        t.list_stride = (size_t)a.fix_stride; t.count_stride = 2; t.nframes = a.nframes;
+        t.wm = a.wm; t.wm_stride = a.wm_stride; t.wm_fs = a.wm_fs;
+        if (text) t.text = *text;
+        *text_done = true;
+        return launch_ks_tail(t, s);
     };
     hipError_t e = hipSuccess;
     switch (src) {
@@ -924,32 +957,28 @@ hipError_t launch_ks_fused(const KsFusedPlan &p, KsFusedArgs &a, const KsFix *fi
         layout(true);
         e = p.nacc == 2 ? launch_one<KS_NRGBA, 4, 2, false, true>(p, a, n, s) : launch_one<KS_NRGBA, 4, 4, false, true>(p, a, n, s);
         layout(false);
-        if (e == hipSuccess) e = exact_listed();
-        if (e == hipSuccess) e = launch_src<KS_NRGBA, 4>(p, a, n, s);
+        if (e == hipSuccess) e = after_float([&]() { return launch_src<KS_NRGBA, 4>(p, a, n, s); });
         return e;
     case KS_TAP64:
         if (!fast) { a.redo = nullptr; return launch_src<KS_TAP64, 4>(p, a, n, s); }
         layout(true);
         e = p.nacc == 2 ? launch_one<KS_TAP64, 4, 2, false, true>(p, a, n, s) : launch_one<KS_TAP64, 4, 4, false, true>(p, a, n, s);
         layout(false);
-        if (e == hipSuccess) e = exact_listed();
-        if (e == hipSuccess) e = launch_src<KS_TAP64, 4>(p, a, n, s);
+        if (e == hipSuccess) e = after_float([&]() { return launch_src<KS_TAP64, 4>(p, a, n, s); });
         return e;
     case KS_YCC:
         if (!fast) { a.redo = nullptr; return launch_src<KS_YCC, 3>(p, a, n, s); }
         layout(true);
         e = p.nacc == 2 ? launch_one<KS_YCC, 3, 2, false, true>(p, a, n, s) : launch_one<KS_YCC, 3, 4, false, true>(p, a, n, s);
         layout(false);
-        if (e == hipSuccess) e = exact_listed();
-        if (e == hipSuccess) e = launch_src<KS_YCC, 3>(p, a, n, s);
+        if (e == hipSuccess) e = after_float([&]() { return launch_src<KS_YCC, 3>(p, a, n, s); });
         return e;
     case KS_GRAY:
         if (!fast) { a.redo = nullptr; return launch_src<KS_GRAY, 1>(p, a, n, s); }
         layout(true);
         e = p.nacc == 2 ? launch_one<KS_GRAY, 1, 2, false, true>(p, a, n, s) : launch_one<KS_GRAY, 1, 4, false, true>(p, a, n, s);
         layout(false);
-        if (e == hipSuccess) e = exact_listed();
-        if (e == hipSuccess) e = launch_src<KS_GRAY, 1>(p, a, n, s);
+        if (e == hipSuccess) e = after_float([&]() { return launch_src<KS_GRAY, 1>(p, a, n, s); });
         return e;
     default: break;
     }
@@ -959,8 +988,10 @@ hipError_t launch_ks_fused(const KsFusedPlan &p, KsFusedArgs &a, const KsFix *fi
         layout(true);
         e = p.nacc == 2 ? launch_one<KS_RGBA, 3, 2, true, true>(p, a, n, s) : launch_one<KS_RGBA, 3, 4, true, true>(p, a, n, s);
         layout(false);
-        if (e == hipSuccess) e = exact_listed();
-    } else e = p.nacc == 2 ? launch_one<KS_RGBA, 3, 2, true>(p, a, n, s) : launch_one<KS_RGBA, 3, 4, true>(p, a, n, s);
+        if (e == hipSuccess) e = after_float([&]() { return launch_src<KS_RGBA, 4>(p, a, n, s); });
+        return e;
+    }
+    e = p.nacc == 2 ? launch_one<KS_RGBA, 3, 2, true>(p, a, n, s) : launch_one<KS_RGBA, 3, 4, true>(p, a, n, s);
     if (e == hipSuccess) e = launch_src<KS_RGBA, 4>(p, a, n, s);
     return e;
 }

@@ -1219,7 +1219,7 @@ static int run_dev_any(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, int n, c
         KsFix fixv, *fix = nullptr;
         const int max_items = n * fp.nstrips * std::max(fp.whole.nseg, fp.split.nseg);
         const bool spec = src.kind == IPX_SRC_RGBA && env_int("IPX_KS_SPEC", 1);
-        // (three more launches and a memset; measured faster than float64 throughout at every size from one 640x360 frame to 8K frames)
+        // (two more launches and a memset; measured faster than float64 throughout at every size from one 640x360 frame to 8K frames)
         const bool fast = (spec || src.kind == IPX_SRC_YCBCR || src.kind == IPX_SRC_NRGBA || (src.kind == IPX_SRC_TAP64 && src.le_alpha)) &&
                           env_int("IPX_KS_FAST", 1) != 0;
         if (spec || fast) {
@@ -1247,8 +1247,15 @@ static int run_dev_any(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, int n, c
             a.stamps = stamp_buf;
         }
 #endif
-        bool matched = false;
-        hipError_t e = launch_ks_fused(fp, a, fix, ctx->cus, s, &matched);
+        // the text goes along: behind a float pass it is part of the tail launch (ipx_ks_tail.hip) instead of a launch of its own
+        KsText text{}, *txt = nullptr;
+        if (wm && pl->glyphs.n > 0 && pl->p.glyphs) {
+            const uint8_t *c = pl->p.glyphs->col;
+            text = KsText{pl->glyphs.dev, pl->glyphs.n, pl->glyphs.bbox, c[0] * 0x101u, c[1] * 0x101u, c[2] * 0x101u, c[3] * 0x101u};
+            txt = &text;
+        }
+        bool matched = false, text_done = false;
+        hipError_t e = launch_ks_fused(fp, a, fix, txt, ctx->cus, s, &matched, &text_done);
         if (fix && matched && e == hipSuccess && env_int("IPX_KS_STATS", 0)) {   // diagnostic: how full the float pass's lists got, how many items went to float64
             std::vector<int> cnt((size_t)n * 2), flags((size_t)max_items);
             (void)hipMemcpyAsync(cnt.data(), fixv.count, cnt.size() * sizeof(int), hipMemcpyDeviceToHost, s);
@@ -1277,7 +1284,7 @@ static int run_dev_any(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, int n, c
 #endif
         if (e != hipSuccess) { set_error("one-pass kernel launch failed: %s", hipGetErrorString(e)); return IPX_ERR_HIP; }
         if (matched) {
-            IPX_HIP(composite_text(pl, wm, wm_frame_stride, n, s));
+            if (!text_done) IPX_HIP(composite_text(pl, wm, wm_frame_stride, n, s));   // no float pass (no lists), or IPX_KS_TAIL=0
             return IPX_OK;
         }
     }
