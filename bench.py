@@ -9,8 +9,13 @@ the max-over-ranks of the timed region.
 
 A "step" is one pass of the hot path over the whole batch (one fused launch).  Prints ONE JSON
 line on rank 0: `value` is the HBM-resident rate; `roofline` comes from HIP events on the stream
-the kernel runs on; `cpu_baseline` is the CPU oracle on a time-bounded sample; `e2e` holds the
-PCIe-inclusive legs (pinned host memory in and out, JPEG in and out) -- reported, never `value`.
+the kernel runs on.  A plain run does no more than that line needs: set up, warm up, time the steps.
+
+--full adds everything else the benchmark measures or checks, after the timed steps: the check of
+what was timed against the CPU oracle (`checked`), the plain-copy ceiling beside the roofline
+(`roofline.copy_ceiling`), `cpu_baseline` (the CPU oracle on a time-bounded sample) and `e2e` (the
+PCIe-inclusive legs: pinned host memory in and out, JPEG in and out -- reported, never `value`).
+Without it `checked` is false and the other three are absent or null.
 
 --mixed N runs BASELINE config 5 instead (mixed 480p-8K sizes, pull scheduling).
 
@@ -41,12 +46,16 @@ def parse():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--pool", type=int, default=32, help="distinct seeded frames tiled over the batch")
-    ap.add_argument("--cpu-seconds", type=float, default=6.0, help="seconds per row of the CPU baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the headline figure does not need: the check against the CPU oracle, "
+                         "the plain-copy ceiling, the CPU baseline and the PCIe-inclusive legs (--cpu-seconds, --copy-gib, --e2e-frames "
+                         "and --e2e-reps size them)")
+    ap.add_argument("--cpu-seconds", type=float, default=6.0, help="with --full: seconds per row of the CPU baseline (0 = skip)")
     ap.add_argument("--sets", type=int, default=3, help="buffer sets the steps rotate over (the run time depends on where buffers land: DESIGN.md 4)")
-    ap.add_argument("--copy-gib", type=int, default=4, help="size of the plain-copy ceiling measurement beside the roofline (0 = skip; N = 1 only)")
-    ap.add_argument("--e2e-frames", type=int, default=256, help="frames per call of the PCIe-inclusive legs (0 = skip; N = 1 only)")
-    ap.add_argument("--e2e-reps", type=int, default=4)
-    ap.add_argument("--check", action="store_true", help="compare frame 0 with the oracle after the run")
+    ap.add_argument("--copy-gib", type=int, default=4, help="with --full: size of the plain-copy ceiling measurement beside the roofline (0 = skip; N = 1 only)")
+    ap.add_argument("--e2e-frames", type=int, default=256, help="with --full: frames per call of the PCIe-inclusive legs (0 = skip; N = 1 only)")
+    ap.add_argument("--e2e-reps", type=int, default=4, help="with --full: timed calls per PCIe-inclusive leg")
+    ap.add_argument("--check", action="store_true", help="check what was timed against the CPU oracle as --full does, on --pool more slots (also without --full)")
     ap.add_argument("--mixed", type=int, default=0, metavar="N",
                     help="BASELINE config 5 instead: N frames per GPU of mixed sizes (480p-8K, seed 0x51), full "
                          "pipeline, pull scheduling over a shared largest-first queue (work stealing across ranks)")
@@ -278,7 +287,7 @@ def run_mixed(args, ipx, shard, rank, local_rank, world):
                          "uniform_ms_per_frame": {"%dx%d" % sizes[si]: round(uniform_ms[si], 5) for si in range(len(sizes))},
                          "vs_byte_weighted_uniform": round(expect_ms / (wall_max * 1e3), 4)},
         }
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             import oracle
             pools = [mb.pool[si][0] for si in range(len(sizes))]
             glyphs = mb.glyphs
@@ -521,26 +530,28 @@ def main():
         L.ipx_event_destroy(ctx.handle, e1)
     frames_done, elapsed = shard.aggregate(F * K, elapsed)   # frames summed over ranks, time = max over ranks
 
-    # Every run checks what it timed: frames 0, P - 1 and F - 1 of the last buffer set (slot i holds pool frame i % P) against the CPU
-    # oracle, every byte of every output.  The oracle is the checker here, never the thing measured.  --check adds P more slots.
+    # --full (or --check) checks what was timed: frames 0, P - 1 and F - 1 of the last buffer set (slot i holds pool frame i % P) against
+    # the CPU oracle, every byte of every output.  The oracle is the checker here, never the thing measured.  --check adds P more slots.
     checked = None
     if rank == 0:
-        import oracle
         s_, r_, t_, w_ = sets[(turn[0] - 1) % nsets]
-        slots = sorted({0, min(P, F) - 1, F - 1} | (set(range(min(P, F), min(2 * P, F))) if args.check else set()))
         rstride, tstride = info.resize_bytes + pad, info.thumb_bytes + pad
-        for slot in slots:
-            want = oracle.process(pool[slot % P], resize=resize or (1, 1, False), thumb=thumb or (1, False), glyphs=glyphs, col=DEFAULT_COL,
-                                  want=[k for k, b in (("resize", r_), ("thumbnail", t_), ("watermark", w_)) if b])
-            for key, buf, stride, shape in (("resize", r_, rstride, (info.resize_h, info.resize_w, 4)), ("thumbnail", t_, tstride, (info.thumb_h, info.thumb_w, 4)),
-                                            ("watermark", w_, info.wm_bytes, (sh, sw, 4))):
-                if buf and not np.array_equal(buf.download(shape, offset=slot * stride), want[key]):
-                    raise SystemExit("bench.py: %s of slot %d differs from the oracle" % (key, slot))
-        checked = True
+        outputs = [(key, buf, stride, shape) for key, buf, stride, shape in (
+            ("resize", r_, rstride, (info.resize_h, info.resize_w, 4)), ("thumbnail", t_, tstride, (info.thumb_h, info.thumb_w, 4)),
+            ("watermark", w_, info.wm_bytes, (sh, sw, 4))) if buf]
+        checked = False
+        if args.full or args.check:
+            import oracle
+            slots = sorted({0, min(P, F) - 1, F - 1} | (set(range(min(P, F), min(2 * P, F))) if args.check else set()))
+            for slot in slots:
+                want = oracle.process(pool[slot % P], resize=resize or (1, 1, False), thumb=thumb or (1, False), glyphs=glyphs, col=DEFAULT_COL,
+                                      want=[key for key, _, _, _ in outputs])
+                for key, buf, stride, shape in outputs:
+                    if not np.array_equal(buf.download(shape, offset=slot * stride), want[key]):
+                        raise SystemExit("bench.py: %s of slot %d differs from the oracle" % (key, slot))
+            checked = True
         if args.dump_outputs:
-            dump_outputs(args.dump_outputs, F, [(key, buf, stride, shape) for key, buf, stride, shape in (
-                ("resize", r_, rstride, (info.resize_h, info.resize_w, 4)), ("thumbnail", t_, tstride, (info.thumb_h, info.thumb_w, 4)),
-                ("watermark", w_, info.wm_bytes, (sh, sw, 4))) if buf])
+            dump_outputs(args.dump_outputs, F, outputs)
 
     if rank == 0 and os.environ.get("IPX_BENCH_TRACE"):
         print("launch_ms:", " ".join("%.3f" % m for m in launch_ms), file=sys.stderr)
@@ -596,17 +607,17 @@ def main():
                          "frac_best_set": round(alg / (min(sum(launch_ms[i::nsets]) / len(launch_ms[i::nsets]) for i in range(nsets)) * 1e-3) / 1e9
                                                 / HBM_PEAK_GBS, 4)},
         }
-        if world == 1 and args.copy_gib > 0:
+        if args.full and world == 1 and args.copy_gib > 0:
             cc = copy_ceiling(ctx, args.copy_gib)
             out["roofline"]["copy_ceiling"] = cc
             out["roofline"]["frac_of_copy_ceiling"] = round(achieved / cc["best"], 4)
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(pool, glyphs, DEFAULT_COL, resize, thumb,
                                                [k for k, b in (("resize", res), ("thumbnail", th), ("watermark", wm)) if b],
                                                args.cpu_seconds)
         else:
             out["cpu_baseline"] = None
-        if world == 1 and args.e2e_frames > 0 and args.workload in ("full", "full-keepaspect"):
+        if args.full and world == 1 and args.e2e_frames > 0 and args.workload in ("full", "full-keepaspect"):
             for bs in sets:
                 for b in bs:
                     if b:
