@@ -260,12 +260,17 @@ int Batcher::release(uint64_t ticket, std::string *err)
         b = it->second.first;
         b->cv.wait(lk, [&] { return b->flushed; });     // releasing a file that is still waiting for company waits for its batch
         tickets_.erase(it);
-        last = --b->unreleased == 0 && !b->submit_failed && !b->job_released;
-        if (last) b->job_released = true;
     }
     // a file's bytes are read until its batch has run: whoever lets go of a ticket -- with or without having waited for it -- may free
     // the file once this returns
     if (!b->submit_failed) { (void)be_.wait(be_.self, b->job); job_seen_done(b); }
+    {
+        // counted off only AFTER the wait: counted before it, the batch's last file could hand the job back to the backend while
+        // another file's release was still on its way into be_.wait, which then asked about a job that no longer existed
+        std::lock_guard<std::mutex> lk(mu_);
+        last = --b->unreleased == 0 && !b->submit_failed && !b->job_released;
+        if (last) b->job_released = true;
+    }
     if (last) return be_.release(be_.self, b->job);     // the batch's output blocks are shared: they go back with its last file
     return IPX_OK;
 }

@@ -268,9 +268,11 @@ void jpeg_huff_packed(uint32_t out[1024]);
 hipError_t launch_jpeg_len(const int16_t *coefs, int nblk, int n, const uint32_t *tables, uint32_t *len, hipStream_t s);
 // len[b] += bits of block b's DC symbol (difference to the previous block of its component), from the dense DC array of the transform kernel
 hipError_t launch_jpeg_dclen(const int16_t *dcq, int nblk, int n, const uint32_t *tables, uint32_t *len, hipStream_t s);
-hipError_t launch_jpeg_bits(const int16_t *coefs, int nblk, int n, const uint32_t *tables, const uint32_t *off, const uint32_t *total_bits,
-                            const unsigned long long *ubase, uint8_t *ustream, hipStream_t s);
+hipError_t launch_jpeg_bits(const int16_t *coefs, int nblk, int n, const uint32_t *tables, const uint32_t *off,
+                            const unsigned long long *total_bits, const unsigned long long *ubase, uint8_t *ustream, hipStream_t s);
 hipError_t launch_scan(uint32_t *v, int per_frame, int n, uint32_t *total, hipStream_t s);
+// the same scan with the frame's sum in 64 bits (the offsets still wrap at 2^32: the caller refuses a frame whose sum reaches that)
+hipError_t launch_scan64(uint32_t *v, int per_frame, int n, unsigned long long *total, hipStream_t s);
 int jpeg_chunk_bytes();
 hipError_t launch_jpeg_ffcount(const uint8_t *ustream, const unsigned long long *ubase, const uint32_t *ubytes, int max_chunks, int n,
                                uint32_t *ffcount, hipStream_t s);

@@ -159,7 +159,7 @@ struct BitSink {
 
 // pass B: every block's bits to their place (off = exclusive scan of len); the last block pads with ones
 __global__ __launch_bounds__(256) void jpeg_bits_kernel(const int16_t *coefs, int nblk, const uint32_t *tables, const uint32_t *off,
-                                                        const uint32_t *total_bits, const unsigned long long *ubase, uint8_t *ustream)
+                                                        const unsigned long long *total_bits, const unsigned long long *ubase, uint8_t *ustream)
 {
     __shared__ HuffLds h;
     __shared__ uint32_t lds[256 * kBlkWords];
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256) void jpeg_bits_kernel(const int16_t *coefs, in
     BitSink s((uint32_t *)(ustream + ubase[f]), off[(size_t)f * nblk + b]);
     code_block(lds + threadIdx.x * kBlkWords, prev_dc_of(fc, b), (b % 6) < 4 ? 0 : 1, h, s);
     if (b == nblk - 1) {
-        const uint32_t pad = (8 - (total_bits[f] & 7)) & 7;   // emit(0x7f, 7): only the bits that complete a byte get out
+        const uint32_t pad = (8 - (uint32_t)(total_bits[f] & 7)) & 7;   // emit(0x7f, 7): only the bits that complete a byte get out
         if (pad) s((1u << pad) - 1, pad);
     }
     s.flush();
@@ -184,7 +184,11 @@ __global__ __launch_bounds__(256) void jpeg_bits_kernel(const int16_t *coefs, in
 // Tiles of 4096 values, four consecutive ones per thread: wave scan by shuffles, the sixteen wave sums through LDS, the next tile's
 // loads in flight while this one is scanned.  (The first form gave every thread n / 1024 CONSECUTIVE values and walked them twice, one
 // dependent strided load after the other: 78 us for the 48 600 blocks of one 1080p frame -- a sixth of a small call's encode.)
-__global__ __launch_bounds__(1024) void scan_kernel(uint32_t *v, int n, uint32_t *total)
+// Total = unsigned long long for the encoder's bit lengths: the offsets stay 32-bit (and wrap past 2^32), the frame's sum does not, so
+// the host can refuse such a frame before anything uses its offsets.  A tile's own sum fits 32 bits (4096 values of at most a block's
+// ~2600 bits, or a chunk's 64 bytes).
+template <class Total>
+__global__ __launch_bounds__(1024) void scan_kernel(uint32_t *v, int n, Total *total)
 {
     __shared__ uint32_t wsum[2][16];
     uint32_t *a = v + (size_t)blockIdx.x * n;
@@ -193,6 +197,7 @@ __global__ __launch_bounds__(1024) void scan_kernel(uint32_t *v, int n, uint32_t
         for (int k = 0; k < 4; k++) x[k] = i + k < n ? a[i + k] : 0u;
     };
     uint32_t carry = 0, nxt[4];
+    Total sum = 0;
     load(4 * t, nxt);
     int flip = 0;
     for (int base = 0; base < n; base += 4096, flip ^= 1) {
@@ -215,8 +220,9 @@ __global__ __launch_bounds__(1024) void scan_kernel(uint32_t *v, int n, uint32_t
         run += x1; if (i + 2 < n) a[i + 2] = run;
         run += x2; if (i + 3 < n) a[i + 3] = run;
         carry += all;
+        sum += all;
     }
-    if (t == 0) total[blockIdx.x] = carry;
+    if (t == 0) total[blockIdx.x] = sum;
 }
 
 constexpr int kChunk = 64;    // unstuffed bytes per thread in the stuffing passes
@@ -306,15 +312,20 @@ hipError_t launch_jpeg_len(const int16_t *coefs, int nblk, int n, const uint32_t
     hipLaunchKernelGGL(jpeg_len_kernel, dim3((nblk + 255) / 256, n), dim3(256), 0, s, coefs, nblk, tables, len);
     return hipGetLastError();
 }
-hipError_t launch_jpeg_bits(const int16_t *coefs, int nblk, int n, const uint32_t *tables, const uint32_t *off, const uint32_t *total_bits,
-                            const unsigned long long *ubase, uint8_t *ustream, hipStream_t s)
+hipError_t launch_jpeg_bits(const int16_t *coefs, int nblk, int n, const uint32_t *tables, const uint32_t *off,
+                            const unsigned long long *total_bits, const unsigned long long *ubase, uint8_t *ustream, hipStream_t s)
 {
     hipLaunchKernelGGL(jpeg_bits_kernel, dim3((nblk + 255) / 256, n), dim3(256), 0, s, coefs, nblk, tables, off, total_bits, ubase, ustream);
     return hipGetLastError();
 }
 hipError_t launch_scan(uint32_t *v, int per_frame, int n, uint32_t *total, hipStream_t s)
 {
-    hipLaunchKernelGGL(scan_kernel, dim3(n), dim3(1024), 0, s, v, per_frame, total);
+    hipLaunchKernelGGL(scan_kernel<uint32_t>, dim3(n), dim3(1024), 0, s, v, per_frame, total);
+    return hipGetLastError();
+}
+hipError_t launch_scan64(uint32_t *v, int per_frame, int n, unsigned long long *total, hipStream_t s)
+{
+    hipLaunchKernelGGL(scan_kernel<unsigned long long>, dim3(n), dim3(1024), 0, s, v, per_frame, total);
     return hipGetLastError();
 }
 int jpeg_chunk_bytes() { return kChunk; }

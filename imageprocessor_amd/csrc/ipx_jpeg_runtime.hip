@@ -142,15 +142,16 @@ int jpeg_encode_sets(ipx_ctx *ctx, hipStream_t s, const JpegEncSet *sets, int K,
         unsigned long long *d_ubase = nullptr, *d_obase = nullptr;
         uint8_t *d_hdr = nullptr;
     } dv[3];
-    std::vector<uint32_t> tot((size_t)K * n), ubytes((size_t)K * n), ff((size_t)K * n);
-    std::vector<unsigned long long> ubase((size_t)K * n), obase((size_t)K * n);
+    std::vector<uint32_t> ubytes((size_t)K * n), ff((size_t)K * n);
+    std::vector<unsigned long long> tot((size_t)K * n), ubase((size_t)K * n), obase((size_t)K * n);
     StreamSync sync{s};                           // after the host buffers above: the queued copies read and write them
     AsyncFree mem{s, {}};
     uint32_t *d_tab;
     IPX_HIP(mem.get(&d_tab, sizeof packed));
     IPX_HIP(hipMemcpyAsync(d_tab, packed, sizeof packed, hipMemcpyHostToDevice, s));
-    uint32_t *d_tot, *d_fftot;                    // [K][n]
-    IPX_HIP(mem.get(&d_tot, (size_t)K * n * 4));
+    unsigned long long *d_tot;                    // [K][n]: bits of every frame's scan, in 64 bits (the block offsets are 32-bit)
+    uint32_t *d_fftot;                            // [K][n]
+    IPX_HIP(mem.get(&d_tot, (size_t)K * n * 8));
     IPX_HIP(mem.get(&d_fftot, (size_t)K * n * 4));
     if (trace) fprintf(stderr, "[ipx]   tables queued at %.2f ms\n", ems());
     for (int k = 0; k < K; k++) {
@@ -176,13 +177,27 @@ int jpeg_encode_sets(ipx_ctx *ctx, hipStream_t s, const JpegEncSet *sets, int K,
             if (rc) return rc;
             IPX_HIP(launch_jpeg_len(o.dcoefs, d.nblk, n, d_tab, d.d_len, s));     // the earlier separate pass over the coefficients
         }
-        IPX_HIP(launch_scan(d.d_len, d.nblk, n, d_tot + (size_t)k * n, s));
+        IPX_HIP(launch_scan64(d.d_len, d.nblk, n, d_tot + (size_t)k * n, s));
         if (trace) fprintf(stderr, "[ipx]   set %d (%dx%d) transform and sizes queued at %.2f ms\n", k, o.w, o.h, ems());
     }
-    IPX_HIP(hipMemcpyAsync(tot.data(), d_tot, (size_t)K * n * 4, hipMemcpyDeviceToHost, s));
+    IPX_HIP(hipMemcpyAsync(tot.data(), d_tot, (size_t)K * n * 8, hipMemcpyDeviceToHost, s));
     t_q1 = ems();
     IPX_HIP(hipStreamSynchronize(s));
     t_s1 = ems();
+    // The block offsets (d_len after the scan) and ubytes are 32-bit: a frame whose scan reaches 2^32 - 1 bits (some 200 M pixels of
+    // binary noise at quality 100) would wrap them, and the bit packer would then write beyond d_ustream.  Refused here, before
+    // anything reads the offsets or is sized from them; IPX_JPEG_MAX_SCAN_BITS can only lower the limit (for the tests).
+    {
+        const unsigned long long top = 0xffffffffull;
+        const int knob = env_int("IPX_JPEG_MAX_SCAN_BITS", 0);
+        const unsigned long long limit = knob > 0 ? std::min<unsigned long long>((unsigned long long)knob, top) : top;
+        for (size_t j = 0; j < (size_t)K * n; j++)
+            if (tot[j] >= limit) {
+                set_error("jpeg: scan too long for the GPU entropy coder (%llu bits in frame %d of output %d; the limit is %llu)", tot[j],
+                          (int)(j % n), (int)(j / n), limit);
+                return IPX_ERR_UNSUPPORTED;        // (AsyncFree and StreamSync release and wait on the way out)
+            }
+    }
     unsigned long long utotal = 0;
     const int chunk = jpeg_chunk_bytes();
     size_t ff_words = 0;
@@ -190,7 +205,7 @@ int jpeg_encode_sets(ipx_ctx *ctx, hipStream_t s, const JpegEncSet *sets, int K,
         uint32_t umax = 0;
         for (int i = 0; i < n; i++) {
             const size_t j = (size_t)k * n + i;
-            ubytes[j] = (tot[j] + 7) / 8;
+            ubytes[j] = (uint32_t)((tot[j] + 7) / 8);
             ubase[j] = utotal;
             utotal += align256((size_t)ubytes[j] + 8);
             umax = std::max(umax, ubytes[j]);
@@ -410,6 +425,7 @@ static int run_host_jpeg_impl(const char *who, ipx_ctx *ctx, const ipx_plan *pl,
     }
     ctx->cv.notify_all();
     if (status != IPX_OK) {
+        ipx_jpeg_result_free(ctx, res.release());   // the chunks that did finish: freed BEFORE the text is set (ipx_host_free clears it)
         set_error("%s", err_text.c_str());
         return status;
     }

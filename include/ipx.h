@@ -423,7 +423,11 @@ int ipx_processor_process(ipx_ctx *ctx, const ipx_task *task, const ipx_image *d
  * Y0 Y1 Y2 Y3 Cb Cr); the Huffman coder sizes every block while it still sits in LDS, places the bits, stuffs 0xff bytes and
  * prepends SOI / DQT / SOF0 / DHT / SOS in further kernels (ipx_jpeg_encode_batch_dev and the ipx_plan_run_*_jpeg entries), so only
  * finished streams cross the link.  ipx_jpeg_entropy_encode is the same coder on the host, for coefficients a caller has downloaded.
- * The byte stream is the one Go's encoder writes (no JFIF segment, both DQT tables, 4:2:0, Annex K Huffman tables). */
+ * The byte stream is the one Go's encoder writes (no JFIF segment, both DQT tables, 4:2:0, Annex K Huffman tables).
+ * Limit of the GPU entropy coder: the bit offsets inside a frame's scan are 32-bit, so a batch holding a frame whose entropy-coded scan
+ * reaches 2^32 - 1 bits (512 MiB; some 200 M pixels of noise at quality 100) is refused as a whole by ipx_jpeg_encode_batch_dev and the
+ * ipx_plan_run_*_jpeg entries with IPX_ERR_UNSUPPORTED, "jpeg: scan too long for the GPU entropy coder", before anything is
+ * written; the worker keeps its CPU path for it.  ipx_jpeg_encode_rgba8 and ipx_jpeg_entropy_encode (host coder) have no such limit. */
 size_t ipx_jpeg_coef_count(int w, int h);                 /* int16 elements per frame                 */
 int ipx_jpeg_quant_tables(int quality, uint8_t out[128]); /* the two DQT tables, zig-zag order         */
 /* n frames resident in HBM -> coefficients in HBM (n * ipx_jpeg_coef_count int16).  Asynchronous. */

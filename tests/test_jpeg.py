@@ -6,7 +6,11 @@ csrc/ipx_jpeg_host.cpp).  PARITY UNPINNED against Go itself (no toolchain); what
   * libjpeg (through Pillow) writes the SAME scan bytes as the Gray path of the oracle for every image and
     quality tried, and the same DQT / DHT payloads: that covers fdct, the quantiser's rounding, the Huffman
     tables, run lengths, bit packing, 0xff stuffing, edge replication and the final padding;
-  * colour conversion: known answers of color.RGBToYCbCr (primaries, greys) and a decode through Pillow.
+  * colour conversion: known answers of color.RGBToYCbCr (primaries, greys) and a decode through Pillow;
+  * the whole colour path -- color.RGBToYCbCr against the real JFIF matrix over all 2^24 triples, edge replication into partial MCUs,
+    the (s + 2) >> 2 chroma box, the Y0 Y1 Y2 Y3 Cb Cr block order, the chroma quantiser, the rounding rule on exact ties -- against
+    the float64 reference of tests/jpeg_encode_reference.py (written from T.81, not from the oracle): tests/test_jpeg_reference.py,
+    and for the GPU encoder tests/test_jpeg_reference_gpu.py.
 The product is then held to the oracle byte for byte (host half here; the GPU half in the gpu-marked tests).
 """
 import io
