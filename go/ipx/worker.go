@@ -60,7 +60,7 @@ func (o *Objects) Release() {
 // It blocks until the file's batch has run.  What falls back -- IsUnsupported(err), or an Invalid status Go's decoder will confirm:
 // run the reference's own image.Decode path for this message; its neighbours in the batch are not affected --
 //   - JPEG: CMYK and other four-component files, 4:1:1 and other samplings, damaged files;
-//   - PNG: Adam7, another chunk order, bytes after the zlib stream, sub-byte gray with tRNS, frames beyond the addressable span;
+//   - PNG: Adam7 unless IPX_PNG_ADAM7=1, another chunk order, bytes after the zlib stream, sub-byte gray with tRNS, frames beyond the addressable span;
 //   - GIF: a first image away from (0, 0), an empty one, or one of another size than the logical screen (DecodeConfig reports the
 //     screen, the GPU leg decodes the first image: such a file falls back alone);
 //   - anything that is none of the three (a WebP, a BMP): it goes the JPEG way and that decoder refuses it.

@@ -1,4 +1,4 @@
-// ipx_png_dec.h -- png.Decode (non-interlaced files) on the GPU: what the kernels (ipx_png_dec.hip) and the host half
+// ipx_png_dec.h -- png.Decode (non-interlaced files, and Adam7 ones under IPX_PNG_ADAM7=1) on the GPU: what the kernels (ipx_png_dec.hip) and the host half
 // (ipx_png_dec_host.cpp) share.  Not part of the ABI.  The restatement of Go's reader is in DESIGN.md section 4.10;
 // tests/png_decode_model.py is the model it is held to.
 #pragma once
@@ -20,7 +20,7 @@ inline int png_kind_bpp(int kind) { return src_bpp(src_of_png(kind)); }
 // ---- host parse ----------------------------------------------------------------------------------------------------------------
 // What the host reads of one file: the chunk headers up to IEND (never the image data).  status: IPX_OK (the chunks' CRCs and the zlib
 // stream still have to be checked), IPX_ERR_INVALID (Go's reader fails on the container) or IPX_ERR_UNSUPPORTED (outside the GPU
-// path: Adam7, another chunk order, sub-byte gray with tRNS, ...).
+// path: Adam7 unless the caller passes adam7, another chunk order, sub-byte gray with tRNS, ...).
 struct PngSpan { uint32_t off, len; };   // bytes of the file
 struct PngFileInfo {
     int status = 0;
@@ -28,7 +28,8 @@ struct PngFileInfo {
     int depth = 0, ctype = 0;
     int bpp = 1;                  // the filters' bytes per pixel: max(1, bits per pixel / 8)
     uint32_t rowbytes = 0;        // 1 + (bits per pixel * w + 7) / 8
-    uint64_t raw_len = 0;         // h * rowbytes
+    uint64_t raw_len = 0;         // h * rowbytes; Adam7: the sum over the non-empty passes of ph * (1 + (bits per pixel * pw + 7) / 8)
+    bool interlace = false;       // Adam7 (only with adam7 set; otherwise such a file is UNSUPPORTED)
     uint32_t file_len = 0;        // through IEND's CRC
     uint32_t idat_len = 0;        // the zlib stream: every IDAT payload
     uint32_t idat_last = 0;       // where the last IDAT's payload starts in that stream
@@ -38,7 +39,17 @@ struct PngFileInfo {
     std::vector<PngSpan> idat;    // IDAT payloads in file order
     uint8_t pal[1024];            // palette kinds: 256 x (R, G, B, A), tRNS applied, entries past PLTE opaque black
 };
-int png_parse(const uint8_t *p, size_t n, PngFileInfo *info);
+int png_parse(const uint8_t *p, size_t n, bool adam7, PngFileInfo *info);
+
+// Adam7's pass p (0 .. 6): pixel (px, py) of the pass is pixel (xo + px * xf, yo + py * yf) of the frame.  One hex digit per pass.
+struct PngPass { uint32_t xf, yf, xo, yo; };
+__host__ __device__ inline PngPass png_pass(int p)
+{
+    const int s = 4 * p;
+    return PngPass{(0x1224488u >> s) & 15, (0x2244888u >> s) & 15, (0x0102040u >> s) & 15, (0x1020400u >> s) & 15};
+}
+// the pass's width or height in a frame of n columns or rows (0: the pass is skipped, filter bytes and all)
+__host__ __device__ inline uint32_t png_pass_dim(uint32_t n, uint32_t off, uint32_t f) { return n > off ? (n - off + f - 1) / f : 0; }
 
 // ---- device side ---------------------------------------------------------------------------------------------------------------
 // One piece of a chunk's CRC (a workgroup of png_crc_kernel): the piece's bytes at blob + src, its chunk, the bytes of the chunk after
@@ -62,6 +73,7 @@ struct PngDecDesc {
     uint32_t w, h, rowbytes, slot;
     uint16_t ctype, depth, kind, trns;   // trns: 1 when tRNS samples are compared (gray / truecolour)
     uint16_t tv[3], bpp;
+    uint16_t interlace, pad;   // (pad: the size stays a multiple of 8 in the open)  interlace 1: the rows are Adam7's passes (png_unfilter_kernel<true>), 0: the frame's rows
 };
 // per-file status word, written by the kernels: 0 OK; bit 0 a chunk CRC differs; bit 1 the zlib stream breaks a rule of Go's reader;
 // bit 2 a row's filter type is above 4; bit 3 bytes or an IDAT chunk follow the Adler-32 (UNSUPPORTED unless another bit is set)
@@ -72,5 +84,6 @@ hipError_t launch_png_crc_check(const uint8_t *blob, const PngChunk *chunks, int
                                 hipStream_t s);
 hipError_t launch_png_inflate(const uint8_t *zlib, const PngDecDesc *desc, int n, uint8_t *raw, uint32_t *status, hipStream_t s);
 hipError_t launch_png_unfilter(const PngDecDesc *desc, int n, uint8_t *raw, uint8_t *frames, uint32_t *status, hipStream_t s);
+hipError_t launch_png_unfilter_adam7(const PngDecDesc *desc, int n, uint8_t *raw, uint8_t *frames, uint32_t *status, hipStream_t s);
 
 }  // namespace ipx

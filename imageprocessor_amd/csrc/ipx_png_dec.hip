@@ -1,8 +1,9 @@
-// ipx_png_dec.hip -- png.Decode (image/png reader.go, compress/zlib, compress/flate) of a batch of non-interlaced files on the GPU, and
+// ipx_png_dec.hip -- png.Decode (image/png reader.go, compress/zlib, compress/flate) of a batch of files on the GPU, and
 // the ABI entries built on it.  Kernels: the CRC of every chunk in pieces (combined with crc_shift) that also gathers the IDAT payloads
 // into one zlib stream per file, the per-chunk check, the inflate (one wave per file: input, Huffman tables and the 32 KiB window in
 // LDS, match copies spread over the lanes, coalesced flushes with the Adler-32) and the unfilter (a diagonal wavefront of 64 rows that
-// writes the frame layout of the type Go returns).  Host half: ipx_png_dec_host.cpp.  DESIGN.md section 4.10.
+// writes the frame layout of the type Go returns; for Adam7 files, taken under IPX_PNG_ADAM7=1, one such wave per pass that scatters
+// its pixels to where the pass puts them).  Host half: ipx_png_dec_host.cpp.  DESIGN.md section 4.10.
 #include <memory>
 #include <vector>
 
@@ -417,6 +418,9 @@ hipError_t launch_png_inflate(const uint8_t *zlib, const PngDecDesc *desc, int n
 // depths) t - i.  The unit above comes from lane i - 1's result of the step before by a cross-lane shift, the one above-left from the
 // step before that; lane 0 reads the band above's last row, which lane 63 wrote back in place (agent-scope loads after a release
 // fence: the bytes were stored in this launch).  Each unit is converted and written to the frame at once.
+// An Adam7 file is seven such images (png_unfilter_kernel<true>): a wave per pass runs the same wavefront over the pass's own rows,
+// from a zero row above, and its pixel (px, py) lands at (xo + px * xf, yo + py * yf) of the frame.  The waves of a file write
+// neighbouring frame bytes, so every frame store is a whole store of its own bytes, never a read-modify-write.
 __device__ inline uint32_t byte_of(uint32_t u0, uint32_t u1, int k) { return ((k < 4 ? u0 : u1) >> (8 * (k & 3))) & 0xFF; }
 
 __device__ inline void unit_load(const uint8_t *p, int bpp, uint32_t &u0, uint32_t &u1)
@@ -434,19 +438,22 @@ __device__ inline uint32_t load_above_byte(const uint8_t *p)
     return (wd >> (8 * (a & 3))) & 0xFF;
 }
 
-// the unit's pixels in the frame layout of the file's kind
-__device__ inline void emit(const PngDecDesc &d, uint8_t *fr, uint32_t r, uint32_t x, uint32_t u0, uint32_t u1)
+// the unit's pixels in the frame layout of the file's kind: unit ux of a row of pw pixels, into frame row r.  kAdam7: pixel px of that
+// row is the frame's column ps.xo + px * ps.xf; otherwise the row is the frame's own (pw = d.w, ps unused).
+template <bool kAdam7>
+__device__ inline void emit(const PngDecDesc &d, uint8_t *fr, uint32_t r, uint32_t ux, uint32_t u0, uint32_t u1, uint32_t pw, const PngPass &ps)
 {
     const uint32_t w = d.w;
     if (d.depth < 8) {
         const uint32_t dep = d.depth, ppb = 8 / dep, mask = (1u << dep) - 1, scale = d.ctype == 0 ? 255 / mask : 1;
         uint8_t *o = fr + (size_t)r * w;
         for (uint32_t j = 0; j < ppb; j++) {
-            const uint32_t px = x * ppb + j;
-            if (px < w) o[px] = (uint8_t)(((u0 >> (8 - dep * (j + 1))) & mask) * scale);
+            const uint32_t px = ux * ppb + j;
+            if (px < pw) o[kAdam7 ? ps.xo + px * ps.xf : px] = (uint8_t)(((u0 >> (8 - dep * (j + 1))) & mask) * scale);
         }
         return;
     }
+    const uint32_t x = kAdam7 ? ps.xo + ux * ps.xf : ux;
     const bool t = d.trns != 0;
     if (d.depth == 8) {
         switch (d.ctype) {
@@ -497,19 +504,40 @@ __device__ inline void emit(const PngDecDesc &d, uint8_t *fr, uint32_t r, uint32
     }
 }
 
+// kAdam7: a workgroup of one wave per (file, pass) runs the same wavefront over the pass's rows, which start behind those of the passes
+// before it.  The passes of a file share nothing (each starts from a zero row above), so they run side by side; an empty pass has no
+// bytes and its wave leaves at once.  Not kAdam7: the file's rows are the frame's; being a template, not a shared function, keeps that
+// instantiation's instructions those of a kernel without the passes (the inliner's order otherwise changes its registers).
+template <bool kAdam7>
 __global__ __launch_bounds__(64) void png_unfilter_kernel(const PngDecDesc *__restrict__ desc, uint8_t *__restrict__ raw,
                                                           uint8_t *__restrict__ frames, uint32_t *__restrict__ status)
 {
-    const PngDecDesc d = desc[blockIdx.x];
+    const PngDecDesc d = desc[kAdam7 ? blockIdx.x / 7 : blockIdx.x];
     if (status[d.slot] & (kPngBadZlib | kPngBadCrc)) return;
     const int lane = threadIdx.x;
     uint8_t *base = raw + d.roff, *fr = frames + d.foff;
     const int bpp = d.bpp;
-    const uint32_t rb = d.rowbytes, units = (rb - 1) / bpp;
+    uint32_t rb = d.rowbytes, h = d.h, pw = d.w;
+    PngPass ps = PngPass{1, 1, 0, 0};
+    if constexpr (kAdam7) {
+        const uint32_t bits = d.depth < 8 ? d.depth : bpp * 8u;          // per pixel
+        uint32_t off = 0;
+        rb = h = 0;
+        for (uint32_t k = 0; k <= blockIdx.x % 7; k++) {
+            off += h * rb;                                               // (an empty pass: rb is 0)
+            ps = png_pass((int)k);
+            pw = png_pass_dim(d.w, ps.xo, ps.xf);
+            h = png_pass_dim(d.h, ps.yo, ps.yf);
+            rb = pw && h ? 1 + (bits * pw + 7) / 8 : 0;
+        }
+        if (rb == 0) return;
+        base += off;
+    }
+    const uint32_t units = (rb - 1) / bpp;
     bool bad = false;
-    for (uint32_t r0 = 0; r0 < d.h; r0 += 64) {
+    for (uint32_t r0 = 0; r0 < h; r0 += 64) {
         const uint32_t r = r0 + lane;
-        const bool act = r < d.h;
+        const bool act = r < h;
         uint8_t *row = base + (size_t)(act ? r : 0) * rb;
         uint32_t ft = act ? row[0] : 0;
         if (ft > 4) { bad = true; ft = 0; }
@@ -557,7 +585,7 @@ __global__ __launch_bounds__(64) void png_unfilter_kernel(const PngDecDesc *__re
                 }
                 c0 = n0;
                 c1 = n1;
-                emit(d, fr, r, (uint32_t)x, n0, n1);
+                emit<kAdam7>(d, fr, kAdam7 ? ps.yo + r * ps.yf : r, (uint32_t)x, n0, n1, pw, ps);
             }
         }
         __threadfence();
@@ -569,7 +597,14 @@ __global__ __launch_bounds__(64) void png_unfilter_kernel(const PngDecDesc *__re
 hipError_t launch_png_unfilter(const PngDecDesc *desc, int n, uint8_t *raw, uint8_t *frames, uint32_t *status, hipStream_t s)
 {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(png_unfilter_kernel, dim3(n), dim3(64), 0, s, desc, raw, frames, status);
+    hipLaunchKernelGGL(png_unfilter_kernel<false>, dim3(n), dim3(64), 0, s, desc, raw, frames, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_png_unfilter_adam7(const PngDecDesc *desc, int n, uint8_t *raw, uint8_t *frames, uint32_t *status, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(png_unfilter_kernel<true>, dim3(7 * (unsigned)n), dim3(64), 0, s, desc, raw, frames, status);
     return hipGetLastError();
 }
 
@@ -580,12 +615,14 @@ hipError_t launch_png_unfilter(const PngDecDesc *desc, int n, uint8_t *raw, uint
 namespace {
 constexpr uint32_t kCrcPiece = 16384;
 
-// parse n files (a thread per eight of them); status[i] from the container
+// parse n files (a thread per eight of them); status[i] from the container.  IPX_PNG_ADAM7=1 in the environment, read on every call,
+// lets Adam7 files through to the GPU; anything else keeps them UNSUPPORTED.
 int png_parse_all(const ipx_bytes *files, int n, std::vector<PngFileInfo> &info, int *status)
 {
+    const bool adam7 = env_int("IPX_PNG_ADAM7", 0) == 1;
     std::atomic<int> failed{IPX_OK};
     HostPool::instance().parallel_for(n, std::max(1, std::min(n / 8, 16)), [&](int i) {
-        const int rc = guarded_status([&] { status[i] = png_parse(files[i].data, files[i].data ? files[i].len : 0, &info[i]); }, nullptr);
+        const int rc = guarded_status([&] { status[i] = png_parse(files[i].data, files[i].data ? files[i].len : 0, adam7, &info[i]); }, nullptr);
         if (rc) failed = rc;
     });
     if (failed) { set_error("png decode: host parse failed"); return failed; }
@@ -668,6 +705,7 @@ static int png_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
             d.trns = f.trns ? 1 : 0;
             for (int k = 0; k < 3; k++) d.tv[k] = f.trns_v[k];
             d.bpp = (uint16_t)f.bpp;
+            d.interlace = f.interlace ? 1 : 0;
             // the chunks' CRC pieces; IDAT payloads land back to back at zoff
             size_t zat = zbytes;
             uint32_t ii = 0;
@@ -699,6 +737,8 @@ static int png_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
             const int i = idx[group[g]];
             memcpy(hblob + foff[g], files[i].data, info[i].file_len);
         });
+        // the Adam7 files' descriptors go behind the others: each unfilter kernel takes its own run of the table
+        const int m0 = (int)(std::stable_partition(desc.begin(), desc.end(), [](const PngDecDesc &d) { return !d.interlace; }) - desc.begin());
         uint8_t *dblob, *dz, *draw;
         uint32_t *dacc;
         PngCrcPiece *dpieces;
@@ -719,7 +759,8 @@ static int png_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
         IPX_HIP(launch_png_crc(dblob, dpieces, (int)pieces.size(), dacc, dz, s));
         IPX_HIP(launch_png_crc_check(dblob, dchunks, (int)chunks.size(), dacc, dstate, s));
         IPX_HIP(launch_png_inflate(dz, ddesc, m, draw, dstate, s));
-        IPX_HIP(launch_png_unfilter(ddesc, m, draw, frames, dstate, s));
+        IPX_HIP(launch_png_unfilter(ddesc, m0, draw, frames, dstate, s));
+        IPX_HIP(launch_png_unfilter_adam7(ddesc + m0, m - m0, draw, frames, dstate, s));
         // the host vectors must outlive the copies: wait before they go
         IPX_HIP(hipStreamSynchronize(s));
         group.clear();

@@ -28,13 +28,14 @@ int channels(int ctype) { return ctype == 0 || ctype == 3 ? 1 : ctype == 4 ? 2 :
 
 }  // namespace
 
-int png_parse(const uint8_t *p, size_t n, PngFileInfo *info)
+int png_parse(const uint8_t *p, size_t n, bool adam7, PngFileInfo *info)
 {
     PngFileInfo &f = *info;
     f.status = 0;
     f.w = f.h = 0;
     f.kind = -1;
     f.trns = false;
+    f.interlace = false;
     f.crc.clear();
     f.idat.clear();
     f.idat_len = 0;
@@ -62,7 +63,8 @@ int png_parse(const uint8_t *p, size_t n, PngFileInfo *info)
             f.depth = d[8];
             f.ctype = d[9];
             if (d[10] != 0 || d[11] != 0 || d[12] > 1 || w <= 0 || h <= 0 || !legal(f.ctype, f.depth)) return f.status = IPX_ERR_INVALID;
-            if (d[12] == 1) return f.status = IPX_ERR_UNSUPPORTED;          // Adam7
+            if (d[12] == 1 && !adam7) return f.status = IPX_ERR_UNSUPPORTED;   // Adam7 without the caller's switch
+            f.interlace = d[12] == 1;
             f.w = w;
             f.h = h;
             stage = kIHDR;
@@ -120,6 +122,15 @@ int png_parse(const uint8_t *p, size_t n, PngFileInfo *info)
     f.bpp = bits >= 8 ? bits / 8 : 1;
     f.rowbytes = (uint32_t)(1 + ((uint64_t)bits * f.w + 7) / 8);
     f.raw_len = (uint64_t)f.h * f.rowbytes;
+    if (f.interlace) {
+        // each non-empty pass is an image of its own: ph rows of a filter byte and pw pixels; an empty pass has no bytes at all
+        f.raw_len = 0;
+        for (int k = 0; k < 7; k++) {
+            const PngPass ps = png_pass(k);
+            const uint64_t pw = png_pass_dim((uint32_t)f.w, ps.xo, ps.xf), ph = png_pass_dim((uint32_t)f.h, ps.yo, ps.yf);
+            if (pw && ph) f.raw_len += ph * (1 + ((uint64_t)bits * pw + 7) / 8);
+        }
+    }
     switch (f.ctype) {
     case 0: f.kind = f.depth == 16 ? (f.trns ? IPX_PNG_NRGBA64 : IPX_PNG_GRAY16) : (f.trns ? IPX_PNG_NRGBA : IPX_PNG_GRAY); break;
     case 2: f.kind = f.depth == 16 ? (f.trns ? IPX_PNG_NRGBA64 : IPX_PNG_RGBA64) : (f.trns ? IPX_PNG_NRGBA : IPX_PNG_RGBA); break;

@@ -561,7 +561,9 @@ int ipx_plan_run_gif_gif(ipx_ctx *ctx, const ipx_plan *plan, int n, const ipx_by
  * For a PNG upload image.Decode is png.Decode.  The host walks the chunk headers only (signature, IHDR, PLTE, tRNS, IDAT, IEND); the
  * whole files go up, and on the GPU the CRC of every chunk is checked in parallel pieces, the IDAT payloads are gathered into one zlib
  * stream per file, one wave per file inflates it with its Huffman tables, input and 32 KiB window in LDS, and a diagonal wavefront of
- * rows unfilters it and writes the frame layout of the type Go returns (IPX_PNG_*):
+ * rows unfilters it and writes the frame layout of the type Go returns (IPX_PNG_*).  Adam7-interlaced files are taken only when
+ * IPX_PNG_ADAM7=1 is set in the environment (read on every call; unset or anything else: IPX_ERR_UNSUPPORTED as before): then a wave per
+ * pass unfilters the pass and puts its pixels where they belong, and the file decodes to the frame of its non-interlaced twin.
  *   IPX_PNG_GRAY     *image.Gray     1 byte per pixel     gray 1/2/4/8 without tRNS             -> ipx_plan_run_dev_gray
  *   IPX_PNG_NRGBA    *image.NRGBA    4                    gray 8 + tRNS, gray-alpha 8, RGB 8 + tRNS, RGBA 8 -> ipx_plan_run_dev_nrgba
  *   IPX_PNG_RGBA     *image.RGBA     4 (A = 0xff)         RGB 8 without tRNS                    -> ipx_plan_run_dev
@@ -573,7 +575,7 @@ int ipx_plan_run_gif_gif(ipx_ctx *ctx, const ipx_plan *plan, int n, const ipx_by
  * palettes + i * 1024 (256 x (R, G, B, A), non-premultiplied: tRNS entries as color.NRGBA, entries past PLTE opaque black, as Go pads
  * them), else palettes == NULL.  *w, *h: 0, or the size the batch must have; *kind: -1, or the kind it must have; on return the batch's
  * size and kind (the first decodable file's).  status[i]: IPX_OK, IPX_ERR_INVALID (Go's decoder fails on the file too) or
- * IPX_ERR_UNSUPPORTED (Adam7, another chunk order, bytes after the zlib stream, sub-byte gray with tRNS, another size or kind than the
+ * IPX_ERR_UNSUPPORTED (Adam7 unless IPX_PNG_ADAM7=1, another chunk order, bytes after the zlib stream, sub-byte gray with tRNS, another size or kind than the
  * batch's, frames beyond ipx_frame_supported, ...: the worker decodes those with Go as before; the full list is in DESIGN.md section
  * 4.10).  The frames of non-OK files are undefined; pix == NULL when no file was decodable.  Free the frames with ipx_png_frames_free:
  * stream-ordered allocations of `stream` (NULL: the context's default stream). */
@@ -588,7 +590,8 @@ void ipx_png_frames_free(ipx_ctx *ctx, ipx_png_frames *owner);
  * (the plan's frame size is the batch's size) and png.Encode of all three outputs (a PNG watermark stays PNG), all on the GPU; only
  * compressed bytes cross the link.  Files of any kind may be mixed: they are grouped by kind on the host, decoded in large groups
  * (IPX_HOST_CHUNK_PNG_DEC files, bounded by memory) and fed to the operators and the encoder in chunks of IPX_HOST_CHUNK_PNG.
- * status[i] as for ipx_png_decode_batch; outputs of non-OK files are {NULL, 0}.  Streams as for ipx_plan_run_host_png
+ * status[i] as for ipx_png_decode_batch (Adam7 files: IPX_ERR_UNSUPPORTED unless IPX_PNG_ADAM7=1; the pool's IPX_JOB_PNG and the
+ * micro-batcher go through this entry and answer alike); outputs of non-OK files are {NULL, 0}.  Streams as for ipx_plan_run_host_png
  * (ipx_jpeg_result_free). */
 int ipx_plan_run_png_png(ipx_ctx *ctx, const ipx_plan *plan, int n, const ipx_bytes *files, ipx_bytes *resize_out, ipx_bytes *thumb_out,
                          ipx_bytes *wm_out, int *status, ipx_jpeg_result **result);

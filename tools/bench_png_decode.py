@@ -9,6 +9,8 @@ corpora written by Pillow at its defaults (photo-like RGB, photo-like RGBA, flat
   python tools/bench_png_decode.py               # the table, one JSON line per case
   python tools/bench_png_decode.py --profile     # a short run meant for rocprofv3 --kernel-trace --stats (kernel times per launch)
   python tools/bench_png_decode.py --quick       # 200x200 only, batches 1 and 64
+  python tools/bench_png_decode.py --adam7       # the same corpora as Adam7 files (IPX_PNG_ADAM7=1 is set for the run): each file's
+                                                 # samples re-wrapped by tests/png_adam7_corpus.py (Paeth rows, zlib level 6)
 
 Files: 16 distinct seeded files per corpus, repeated through the batch."""
 import argparse
@@ -48,6 +50,16 @@ def pillow_png(a, corpus):
     return b.getvalue()
 
 
+def adam7_of(data):
+    """the Adam7 file of a file's samples (Pillow cannot write one)"""
+    import png_adam7_corpus
+    im = pillow_decode(data)
+    a = np.asarray(im)
+    if im.mode == "P":
+        return png_adam7_corpus.write(a[..., None], 3, 8, plte=np.asarray(im.getpalette(), np.uint8).reshape(-1, 3), filters=(4,))
+    return png_adam7_corpus.write(a, {"RGB": 2, "RGBA": 6}[im.mode], 8, filters=(4,))
+
+
 def pillow_decode(data):
     from PIL import Image
     im = Image.open(io.BytesIO(data))
@@ -70,7 +82,10 @@ def main():
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--adam7", action="store_true")
     a = ap.parse_args()
+    if a.adam7:
+        os.environ["IPX_PNG_ADAM7"] = "1"
     import imageprocessor_amd as ipx
     import png_decode_model as dm
     if ipx.device_count() < 1:
@@ -90,6 +105,8 @@ def main():
                                 for s in range(16)]
                 else:
                     distinct = [pillow_png(frames(w, h, corpus, 9000 + s), corpus) for s in range(16)]
+                if a.adam7:
+                    distinct = [adam7_of(f) for f in distinct]
                 t0 = time.perf_counter()
                 for f in distinct:
                     pillow_decode(f)
@@ -106,7 +123,7 @@ def main():
                         assert st.count(0) == n, st[:8]
 
                     td = timed(decode_only, a.reps)
-                    row = {"bench": "png_decode", "corpus": corpus, "kind": kind, "w": w, "h": h, "batch": n,
+                    row = {"bench": "png_decode", "adam7": a.adam7, "corpus": corpus, "kind": kind, "w": w, "h": h, "batch": n,
                            "bytes_per_file": sum(len(f) for f in distinct) // len(distinct),
                            "decode_ms": round(td * 1e3, 3), "decode_files_per_s": round(n / td, 1),
                            "pillow_one_thread_decode_ms_per_file_not_go": round(pil_one * 1e3, 3)}
