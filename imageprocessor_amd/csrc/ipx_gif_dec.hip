@@ -3,12 +3,10 @@
 // first bytes in LDS and checks every rule of the reader, O(1) work per code) and the expansion (every lane of a grid takes one code and
 // writes its string backwards along the entry -> code-ordinal map of its segment, straight into the de-interlaced row).  Host half:
 // ipx_gif_dec_host.cpp.  DESIGN.md section 4.8 has the restatement and the numbers.
-#include <memory>
 #include <vector>
 
 #include "ipx_gif_dec.h"
-#include "ipx_runtime_internal.h"
-#include "ipx_threads.h"
+#include "ipx_decode_common.h"
 
 namespace ipx {
 
@@ -185,12 +183,8 @@ hipError_t launch_gif_expand(const GifDecDesc *desc, int n, const GifCode *codes
 // file's when *w == 0 (files of another size: IPX_ERR_UNSUPPORTED)
 static int gif_parse_batch(const ipx_bytes *files, int n, int *w, int *h, std::vector<GifFileInfo> &info, int *status)
 {
-    std::atomic<int> failed{IPX_OK};
-    HostPool::instance().parallel_for(n, std::max(1, std::min(n / 8, 16)), [&](int i) {
-        const int rc = guarded_status([&] { status[i] = gif_parse(files[i].data, files[i].data ? files[i].len : 0, &info[i]); }, nullptr);
-        if (rc) failed = rc;
-    });
-    if (failed) { set_error("gif decode: host parse failed"); return failed; }
+    const int rc = parallel_light(n, [&](int i) { status[i] = gif_parse(files[i].data, files[i].data ? files[i].len : 0, &info[i]); }, "gif decode: host parse failed");
+    if (rc) return rc;
     for (int i = 0; i < n; i++) {
         if (status[i] != IPX_OK) continue;
         if (*w <= 0) { *w = info[i].w; *h = info[i].h; }
@@ -205,28 +199,21 @@ static int gif_parse_batch(const ipx_bytes *files, int n, int *w, int *h, std::v
 static int gif_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files, int n, const std::vector<GifFileInfo> &info,
                             uint8_t *frames, size_t frame_stride, uint8_t *palettes, int *status)
 {
-    std::vector<uint8_t *> pinned;
-    struct Release {    // the pinned blocks go back once the stream is past the copies that read them
-        ipx_ctx *ctx; hipStream_t s; std::vector<uint8_t *> &p;
-        ~Release() { (void)hipStreamSynchronize(s); for (uint8_t *q : p) (void)ipx_host_free(ctx, q); }
-    } release{ctx, s, pinned};
+    PinnedBlocks pinned(ctx, s);
     AsyncFree mem{s, {}};
     uint32_t *dstate;
     IPX_HIP(mem.get(&dstate, (size_t)n * kGifStateWords * 4));
     // palettes: one upload of every slot
-    uint8_t *hpal = (uint8_t *)ipx_host_alloc(ctx, (size_t)n * 1024);
+    uint8_t *hpal = pinned.get((size_t)n * 1024);
     if (!hpal) return IPX_ERR_NOMEM;
-    pinned.push_back(hpal);
     for (int i = 0; i < n; i++) {
         if (status[i] == IPX_OK) memcpy(hpal + (size_t)i * 1024, info[i].pal, 1024);
         else memset(hpal + (size_t)i * 1024, 0, 1024);
     }
     IPX_HIP(hipMemcpyAsync(palettes, hpal, (size_t)n * 1024, hipMemcpyHostToDevice, s));
     const size_t budget = (size_t)env_int("IPX_GIF_DEC_SCRATCH_MB", 4096) << 20;
-    std::vector<int> group;
-    auto run_group = [&]() -> int {
+    auto run_group = [&](const std::vector<int> &group) -> int {
         const int m = (int)group.size();
-        if (m == 0) return IPX_OK;
         size_t data_bytes = 0, codes = 0;
         uint32_t max_cap = 0;
         std::vector<GifDecDesc> desc(m);
@@ -250,14 +237,14 @@ static int gif_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
             max_cap = std::max(max_cap, d.code_cap);
         }
         const size_t desc_bytes = align256(sizeof(GifDecDesc) * m);
-        uint8_t *hblob = (uint8_t *)ipx_host_alloc(ctx, desc_bytes + data_bytes);
+        uint8_t *hblob = pinned.get(desc_bytes + data_bytes);
         if (!hblob) return IPX_ERR_NOMEM;
-        pinned.push_back(hblob);
         memcpy(hblob, desc.data(), sizeof(GifDecDesc) * m);
-        HostPool::instance().parallel_for(m, std::max(1, std::min(m / 8, 16)), [&](int g) {
+        const int rc = parallel_light(m, [&](int g) {
             const int i = group[g];
             gif_gather(files[i].data, files[i].len, info[i], hblob + desc_bytes + desc[g].data_off);
-        });
+        }, "gif decode: host gather failed");
+        if (rc) return rc;
         uint8_t *dblob;
         GifCode *dcodes;
         IPX_HIP(mem.get(&dblob, desc_bytes + data_bytes));
@@ -267,22 +254,11 @@ static int gif_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
         IPX_HIP(launch_gif_walk(dblob + desc_bytes, ddesc, m, dcodes, dstate, s));
         const int bpf = (int)std::max<uint32_t>(1, std::min<uint32_t>((max_cap + 255) / 256, (uint32_t)std::max(1, 16384 / m)));
         IPX_HIP(launch_gif_expand(ddesc, m, dcodes, dstate, frames, frame_stride, bpf, s));
-        group.clear();
         return IPX_OK;
     };
-    size_t group_bytes = 0;
-    for (int i = 0; i < n; i++) {
-        if (status[i] != IPX_OK) continue;
-        const size_t need = (size_t)gif_code_cap(info[i]) * sizeof(GifCode) + info[i].data_len;
-        if (!group.empty() && group_bytes + need > budget) {
-            const int rc = run_group();
-            if (rc) return rc;
-            group_bytes = 0;
-        }
-        group.push_back(i);
-        group_bytes += need;
-    }
-    int rc = run_group();
+    std::vector<int> ok;
+    for (int i = 0; i < n; i++) if (status[i] == IPX_OK) ok.push_back(i);
+    const int rc = for_groups_under(ok, budget, [&](int i) { return (size_t)gif_code_cap(info[i]) * sizeof(GifCode) + info[i].data_len; }, run_group);
     if (rc) return rc;
     std::vector<uint32_t> st((size_t)n * kGifStateWords);
     IPX_HIP(hipMemcpyAsync(st.data(), dstate, st.size() * 4, hipMemcpyDeviceToHost, s));
@@ -296,17 +272,9 @@ static int gif_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
 }
 
 // ---- the entries -----------------------------------------------------------------------------------------------------------------
-struct ipx_gif_frames { std::vector<void *> dev; hipStream_t stream = nullptr; };   // stream-ordered allocations of `stream`
-
 extern "C" {
 
-void ipx_gif_frames_free(ipx_ctx *ctx, ipx_gif_frames *o)
-{
-    if (!o) return;
-    if (ctx) (void)hipSetDevice(ctx->device);
-    for (void *p : o->dev) (void)hipFreeAsync(p, o->stream);
-    delete o;
-}
+void ipx_gif_frames_free(ipx_ctx *ctx, ipx_gif_frames *o) { dev_blocks_free(ctx, o); }
 
 int ipx_gif_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *gifs, int n, int *w, int *h, ipx_paletted_batch *frames,
                          int *status, ipx_gif_frames **owner) try
@@ -325,29 +293,22 @@ int ipx_gif_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *gifs, int 
     int bw = *w, bh = *h;
     int rc = gif_parse_batch(gifs, n, &bw, &bh, info, status);
     if (rc) return rc;
-    bool any = false;
-    for (int i = 0; i < n; i++) any |= status[i] == IPX_OK;
-    if (!any) return IPX_OK;
-    std::unique_ptr<ipx_gif_frames> o(new ipx_gif_frames);
-    o->stream = s;
+    if (!any_ok(status, n)) return IPX_OK;
+    OwnedBlocks<ipx_gif_frames> o(ctx, s);
     const size_t fs = align256((size_t)bw * bh);
     uint8_t *dframes = nullptr, *dpal = nullptr;
-    hipError_t e = hipMallocAsync((void **)&dframes, fs * n, s);
-    if (e == hipSuccess) { o->dev.push_back(dframes); e = hipMallocAsync((void **)&dpal, (size_t)n * 1024, s); }
-    if (e == hipSuccess) o->dev.push_back(dpal);
+    hipError_t e = o.alloc(&dframes, fs * n);
+    if (e == hipSuccess) e = o.alloc(&dpal, (size_t)n * 1024);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        ipx_gif_frames_free(ctx, o.release());
         set_error("ipx_gif_decode_batch: device allocation failed: %s", hipGetErrorString(e));
         return IPX_ERR_NOMEM;
     }
     rc = gif_decode_files(ctx, s, gifs, n, info, dframes, fs, dpal, status);
-    if (rc) { ipx_gif_frames_free(ctx, o.release()); return rc; }
+    if (rc) return rc;
     *w = bw;
     *h = bh;
-    any = false;
-    for (int i = 0; i < n; i++) any |= status[i] == IPX_OK;
-    if (!any) { ipx_gif_frames_free(ctx, o.release()); return IPX_OK; }     // every image failed in its data: no frames
+    if (!any_ok(status, n)) return IPX_OK;     // every image failed in its data: no frames
     frames->index = dframes;
     frames->stride = bw;
     frames->frame_stride = fs;
@@ -390,9 +351,7 @@ int ipx_plan_run_gif_gif(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_byte
         int bw = sw, bh = sh;
         rc = gif_parse_batch(files + i0, m, &bw, &bh, info, status + i0);
         if (rc) return rc;
-        bool any = false;
-        for (int i = 0; i < m; i++) any |= status[i0 + i] == IPX_OK;
-        if (!any) continue;
+        if (!any_ok(status + i0, m)) continue;
         StreamSync sync{s};
         AsyncFree mem{s, {}};
         uint8_t *didx, *dpal, *dout = nullptr;
@@ -401,9 +360,7 @@ int ipx_plan_run_gif_gif(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_byte
         if (outs.frame_bytes()) IPX_HIP(mem.get(&dout, outs.frame_bytes() * m));
         rc = gif_decode_files(ctx, s, files + i0, m, info, didx, fsrc, dpal, status + i0);
         if (rc) return rc;
-        any = false;
-        for (int i = 0; i < m; i++) any |= status[i0 + i] == IPX_OK;
-        if (!any) continue;
+        if (!any_ok(status + i0, m)) continue;
         const PlanOutputs::Frames f = outs.place(dout, m);
         rc = run_dev_src(ctx, s, pl, m, packed_src(kSrcPaletted, didx, sw, fsrc, dpal), f.dev[0], outs.o[0].fs, f.dev[1], outs.o[1].fs, f.dev[2], outs.o[2].fs);
         if (!rc) rc = encode_outputs(ctx, s, outs, f, m, i0, quality, status, res);

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <map>
 #include <mutex>
+#include <vector>
 
 #include "../../include/ipx.h"
 
@@ -245,11 +246,30 @@ hipError_t launch_par_sync(const JpegParArgs &a, int round, hipStream_t s);
 hipError_t launch_par_write(const JpegParArgs &a, hipStream_t s);
 hipError_t launch_par_dc(const JpegParArgs &a, hipStream_t s);
 int jpeg_parse(const uint8_t *d, size_t len, JpegDecInfo *info, JpegDecTables *tab);
-}  // namespace ipx
-#include <vector>
-namespace ipx {
 int jpeg_host_decode(const uint8_t *d, size_t len, JpegDecInfo *info, int16_t *coefs, int16_t *dcs, size_t nblk, uint16_t qnat[3][64],
                      bool *progressive);
+// The host plan of a batch decode (jpeg_plan_batch in ipx_jpeg_dec_host.cpp; no device call): the files parsed, the batch's geometry
+// chosen, the baseline scans cut into pieces (grouped by table class) and parallel images, all placed in one blob.
+struct JpegPlanOptions {
+    int want_w, want_h;        // the size asked for; want_w <= 0: the first parsed file's
+    bool use_par;              // IPX_JPEG_PAR: long scans without restart markers go to the parallel decoder
+    int forced_sub, max_sub;   // IPX_JPEG_PAR_SUB: 128 .. 1024 fixes the sub-sequence size, else the batch chooses; jpeg_par_sub_bytes()
+};
+struct JpegBatchPlan {
+    std::vector<JpegDecInfo> info;
+    std::vector<JpegDecTables> tabs;
+    std::vector<uint8_t> valid;       // per file: bit 0 decodable (final only once the host-decoded files are through), bit 1 progressive
+    std::vector<size_t> blob_off;     // where a GPU-decoded file's scan lies in the blob
+    std::vector<int> hslot;           // host-decoded files (info.host_scans) numbered in file order, -1 for the others
+    std::vector<JpegDecImage> items;  // pieces by table class, every class but the last padded to whole groups of 64 (padding: valid == 0)
+    std::vector<JpegParImage> par;
+    int ref = -1, par_sub = 0, nhost = 0;   // ref: the file that sets the batch's geometry; -1: nothing decodable
+    size_t blob_bytes = 0, piece_ubytes = 0;
+    double parse_ms = 0;              // for the IPX_DEBUG timing line
+};
+// status[i]: the parser's verdict, UNSUPPORTED outside the batch's geometry.  Returns the status of an exception on a preparation thread.
+int jpeg_plan_batch(const ipx_bytes *files, int n, const JpegPlanOptions &opt, int *status, JpegBatchPlan *plan);
+bool jpeg_same_tables(const JpegDecTables &x, const JpegDecTables &y);     // the Huffman tables (not the quantisers)
 hipError_t launch_jpeg_huff(const JpegDecArgs &a, hipStream_t s);
 // the same pieces through the word-wise reader of the parallel decoder: unstuff each piece into ublob (+ its length into ulen), then one
 // decode pass -- the state at the start of a piece is known, so nothing is speculative.  The 64 pieces of a workgroup share one set
@@ -257,10 +277,6 @@ hipError_t launch_jpeg_huff(const JpegDecArgs &a, hipStream_t s);
 hipError_t launch_jpeg_pieces(const JpegDecArgs &a, uint8_t *ublob, uint32_t *ulen, hipStream_t s);
 hipError_t launch_jpeg_idct(const JpegDecArgs &a, const JpegPlanes &pl, hipStream_t s);
 
-}  // namespace ipx
-
-#include <vector>
-namespace ipx {
 void jpeg_write_stream(const int16_t *coefs, int w, int h, const JpegTables &t, std::vector<uint8_t> *out);
 void jpeg_write_header(int w, int h, const JpegTables &t, std::vector<uint8_t> *out);
 void jpeg_huff_packed(uint32_t out[1024]);

@@ -10,9 +10,11 @@
 // 12-bit samples.  Progressive files, files coded in several scans and Huffman table ids above 1 are marked host_scans: their
 // scans are decoded on the host (ipx_jpeg_dec_prog.cpp) and only the transform onwards runs on the GPU.  A file has to end the way
 // Go's marker loop wants it to (EOI after the last scan), or it is malformed here as it is there.
+#include <algorithm>
+#include <chrono>
 #include <cstring>
 
-#include "ipx_internal.h"
+#include "ipx_decode_common.h"
 
 namespace ipx {
 
@@ -223,6 +225,154 @@ int jpeg_parse(const uint8_t *d, size_t len, JpegDecInfo *info, JpegDecTables *t
         }
         i += n;
     }
+}
+
+// ---- the host plan of a batch (JpegBatchPlan, ipx_internal.h) -----------------------------------------------------------------------------
+
+bool jpeg_same_tables(const JpegDecTables &x, const JpegDecTables &y)
+{
+    return !memcmp(x.lut, y.lut, sizeof x.lut) && !memcmp(x.maxcode, y.maxcode, sizeof x.maxcode) &&
+           !memcmp(x.valoff, y.valoff, sizeof x.valoff) && !memcmp(x.vals, y.vals, sizeof x.vals);
+}
+
+namespace {
+
+inline int mcus_of(const JpegDecInfo &I) { return ((I.w + 8 * I.h0 - 1) / (8 * I.h0)) * ((I.h + 8 * I.v0 - 1) / (8 * I.v0)); }
+
+// The RSTn markers of a baseline scan, as offsets into it.  Inside entropy-coded data 0xff is followed by 0x00 or by a marker, so every
+// 0xff 0xd0..0xd7 pair is an RSTn.  IPX_ERR_UNSUPPORTED for markers out of sequence or not one per restart interval.
+int find_restarts(const uint8_t *sd, const JpegDecInfo &I, std::vector<uint32_t> *marks)
+{
+    const int nmcu = mcus_of(I);
+    if (I.ri <= 0 || nmcu <= I.ri) return IPX_OK;
+    int expected = 0;
+    for (size_t k = 0; k + 1 < I.scan_len;) {
+        const uint8_t *q = (const uint8_t *)memchr(sd + k, 0xff, I.scan_len - 1 - k);
+        if (!q) break;
+        k = (size_t)(q - sd);
+        const uint8_t m2 = sd[k + 1];
+        if (m2 == 0x00) { k += 2; continue; }
+        if (m2 < 0xd0 || m2 > 0xd7) break;                        // EOI or another marker: the scan ends here
+        if (m2 != 0xd0 + expected) return IPX_ERR_UNSUPPORTED;
+        marks->push_back((uint32_t)k);
+        expected = (expected + 1) & 7;
+        k += 2;
+    }
+    return (int)marks->size() != (nmcu + I.ri - 1) / I.ri - 1 ? IPX_ERR_UNSUPPORTED : IPX_OK;   // Go would try to resynchronise
+}
+
+// table classes: tab_of[i] = the first image of the batch whose Huffman tables equal image i's (most batches have one class, the
+// Annex K tables every encoder defaults to); the piece kernels share one set per workgroup, so pieces are grouped by class
+std::vector<int> table_classes(const JpegBatchPlan &P, const int *status)
+{
+    const int n = (int)P.info.size();
+    std::vector<int> tab_of(n, -1), reps;
+    for (int i = 0; i < n; i++) {
+        if (status[i] != IPX_OK || P.info[i].host_scans) continue;
+        for (size_t k = reps.size(); k-- > 0 && tab_of[i] < 0;)     // newest first: neighbours tend to match
+            if (jpeg_same_tables(P.tabs[i], P.tabs[reps[k]])) tab_of[i] = reps[k];
+        if (tab_of[i] < 0) { tab_of[i] = i; reps.push_back(i); }
+        if (reps.size() > 64) break;                                   // a batch of hand-optimised tables: not worth the quadratic search
+    }
+    for (int i = 0; i < n; i++) if (status[i] == IPX_OK && tab_of[i] < 0) tab_of[i] = i;
+    return tab_of;
+}
+
+// group the pieces by table class (stable: image order inside a class), each group padded to whole workgroups of 64
+void group_by_class(std::vector<JpegDecImage> &items)
+{
+    bool one_class = true;
+    for (auto &it : items) one_class = one_class && it.tab_img == items[0].tab_img;
+    if (one_class) return;
+    std::stable_sort(items.begin(), items.end(), [](const JpegDecImage &x, const JpegDecImage &y) { return x.tab_img < y.tab_img; });
+    std::vector<JpegDecImage> grouped;
+    JpegDecImage pad;
+    memset(&pad, 0, sizeof pad);
+    for (size_t k = 0; k < items.size(); k++) {
+        if (k && items[k].tab_img != items[k - 1].tab_img)
+            while (grouped.size() & 63) { pad.tab_img = items[k - 1].tab_img; grouped.push_back(pad); }
+        grouped.push_back(items[k]);
+    }
+    items.swap(grouped);
+}
+
+}  // namespace
+
+int jpeg_plan_batch(const ipx_bytes *files, int n, const JpegPlanOptions &opt, int *status, JpegBatchPlan *plan)
+{
+    JpegBatchPlan &P = *plan;
+    P.info.resize(n); P.tabs.resize(n);
+    P.valid.assign(n, 0); P.blob_off.assign(n, 0); P.hslot.assign(n, -1);
+    const auto t0 = std::chrono::steady_clock::now();
+    // pieces of a scan: the whole scan, or one per restart interval
+    std::vector<std::vector<uint32_t>> marks(n);
+    // host preparation runs on a few threads: parsing is trivial, but finding the RSTn markers walks every compressed byte (0.3 GB for
+    // a thousand 1080p files).  Files whose scans are walked on the host (progressive, several scans) only have their frame header
+    // read here; their scans wait for the batch's geometry.
+    const int rc = parallel_light(n, [&](int i) {
+        status[i] = !files[i].data ? IPX_ERR_INVALID : (files[i].len >= ((size_t)1 << 30) ? IPX_ERR_UNSUPPORTED : jpeg_parse(files[i].data, files[i].len, &P.info[i], &P.tabs[i]));
+        if (status[i] == IPX_OK && !P.info[i].host_scans) status[i] = find_restarts(files[i].data + P.info[i].scan_off, P.info[i], &marks[i]);
+    }, "jpeg decode: host preparation failed");
+    P.parse_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rc) return rc;
+    const std::vector<int> tab_of = table_classes(P, status);
+    // Sub-sequences of the scans that are decoded in parallel (ipx_jpeg_dec_par.hip): 1 KiB each for a large batch.  A lane walks its
+    // sub-sequence symbol by symbol, so a pass over a small batch takes as long as ONE sub-sequence takes while the chip idles (8
+    // files: 44 waves, 1.3 ms per pass, three passes); shorter ones until the batch fills about eight waves per CU.
+    P.par_sub = opt.max_sub;
+    if (opt.forced_sub == 128 || opt.forced_sub == 256 || opt.forced_sub == 512 || opt.forced_sub == 1024) P.par_sub = opt.forced_sub;
+    else {
+        size_t total = 0;
+        for (int i = 0; i < n; i++) if (status[i] == IPX_OK && !P.info[i].host_scans) total += P.info[i].scan_len;
+        while (P.par_sub > 256 && total / (size_t)P.par_sub < (size_t)131072) P.par_sub >>= 1;     // (128 measured no better: 3.0 against 3.1 ms for 8 files, worse for 64)
+    }
+    const std::vector<JpegDecInfo> &info = P.info;
+    for (int i = 0; i < n; i++) {
+        if (status[i] == IPX_OK) {
+            if (P.ref < 0 && (opt.want_w <= 0 || (info[i].w == opt.want_w && info[i].h == opt.want_h))) P.ref = i;
+            if (P.ref >= 0 && (info[i].w != info[P.ref].w || info[i].h != info[P.ref].h || info[i].h0 != info[P.ref].h0 || info[i].v0 != info[P.ref].v0 ||
+                               info[i].ncomp != info[P.ref].ncomp))
+                status[i] = IPX_ERR_UNSUPPORTED;
+            else if (P.ref < 0) status[i] = IPX_ERR_UNSUPPORTED;   // a size other than the one asked for
+        }
+        if (status[i] != IPX_OK) continue;
+        // coefficients come from the host, straight into a pinned block in the IDCT kernel's layout (slot hslot[i]); bit 1: progressive
+        if (info[i].host_scans) { P.valid[i] = info[i].progressive ? 3 : 1; P.hslot[i] = P.nhost++; continue; }
+        const JpegDecInfo &I = info[i];
+        const int nmcu = mcus_of(I);
+        auto push = [&](size_t a0, size_t a1, int m0, int cnt) {
+            JpegDecImage it;
+            memset(&it, 0, sizeof it);
+            it.scan_off = P.blob_bytes + (a0 & ~(size_t)15); it.scan_len = (uint32_t)(a1 - (a0 & ~(size_t)15));
+            it.img = (uint32_t)i; it.first_mcu = (uint32_t)m0; it.n_mcu = (uint32_t)cnt;
+            memcpy(it.td, I.td, 3); memcpy(it.ta, I.ta, 3);
+            it.valid = 1;
+            it.pad = (uint8_t)(a0 & 15);           // bytes to skip: pieces start 16-byte aligned for the kernel's chunk loads
+            it.uoff = P.piece_ubytes;              // its unstuffed copy (launch_jpeg_pieces): a region of its own
+            it.tab_img = (uint32_t)tab_of[i];
+            P.piece_ubytes += ((a1 - a0) + 15 + 16) & ~(size_t)15;
+            P.items.push_back(it);
+        };
+        size_t start = 0;
+        int mcu = 0;
+        for (uint32_t k : marks[i]) { push(start, k, mcu, I.ri); P.items.back().strict_end = 1; mcu += I.ri; start = (size_t)k + 2; }
+        if (marks[i].empty() && opt.use_par && I.scan_len >= (size_t)4 * opt.max_sub && I.scan_len < ((size_t)1 << 28)) {   // (the same files whatever par_sub is)
+            // a long scan without restart markers: decoded in parallel inside the scan (ipx_jpeg_dec_par.hip)
+            JpegParImage pi;
+            memset(&pi, 0, sizeof pi);
+            pi.scan_off = P.blob_bytes; pi.scan_len = (uint32_t)I.scan_len; pi.img = (uint32_t)i;
+            pi.nsub = (uint32_t)((I.scan_len + P.par_sub - 1) / P.par_sub);
+            memcpy(pi.td, I.td, 3); memcpy(pi.ta, I.ta, 3);
+            P.par.push_back(pi);
+        } else {
+            push(start, I.scan_len, mcu, nmcu - mcu);
+        }
+        P.valid[i] = 1;
+        P.blob_off[i] = P.blob_bytes;
+        P.blob_bytes += (I.scan_len + 15 + 16) & ~(size_t)15;
+    }
+    if (P.ref >= 0) group_by_class(P.items);
+    return IPX_OK;
 }
 
 }  // namespace ipx

@@ -1,0 +1,339 @@
+// ipx_jpeg_dec_runtime.hip -- the driver of image.Decode for JPEG batches: the host plan (ipx_jpeg_dec_host.cpp), then the device
+// blocks, the upload, the Huffman passes and the reconstruction as stages of jpeg_decode_files.  Kernels: ipx_jpeg_dec.hip,
+// ipx_jpeg_dec_par.hip; the host scan decoder of progressive files: ipx_jpeg_dec_prog.cpp.
+#include <chrono>
+
+#include "ipx_decode_common.h"
+
+namespace {
+
+// the one conversion of a HIP result of the driver into a status
+int hip_status(hipError_t e, const char *what)
+{
+    if (e != hipSuccess) set_error("%s: %s", what, hipGetErrorString(e));
+    return e == hipSuccess ? IPX_OK : IPX_ERR_HIP;
+}
+#define DEC_HIP(what, call) do { const int rc_ = hip_status((call), what); if (rc_) return rc_; } while (0)
+
+struct Events { hipEvent_t ev[2] = {nullptr, nullptr}; ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); } };   // of the two pinned halves
+
+// What the stages of one call share.  The members go in reverse order: the wait for the stream first, then the pinned blocks, the
+// scratch, and only then the host vectors that copies queued on the stream read (the plan) or write (dev_status).
+struct DecRun {
+    ipx_ctx *ctx; hipStream_t s; const ipx_bytes *jpegs; int n; int *status;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    double t_alloc = 0, t_pin = 0, t_pack = 0, t_launch = 0;
+    JpegBatchPlan plan;
+    std::vector<int> dev_status;
+    JpegDecArgs a{};
+    JpegPlanes pl{};
+    uint8_t *d_blob = nullptr, *d_valid = nullptr; JpegDecImage *d_img = nullptr; JpegDecTables *d_tab = nullptr;
+    AsyncFree mem;                     // scratch of this call: stream-ordered, or bumped out of the lane's decode buffer
+    PinnedBlocks pinned;
+    StreamSync sync;
+    DecRun(ipx_ctx *c, hipStream_t st, const ipx_bytes *f, int n_, int *status_)
+        : ctx(c), s(st), jpegs(f), n(n_), status(status_), mem{st, {}}, pinned(c, st), sync{st} {}
+    double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
+// Stage 2: the batch's geometry, the planes and the scratch.  lane != NULL: everything is bumped out of the lane's decode buffer, grown
+// once to an estimate of the whole call.
+int dec_blocks(DecRun &r, Lane *lane, bool planes_in_lane, OwnedBlocks<ipx_jpeg_planes> &own)
+{
+    const JpegBatchPlan &P = r.plan;
+    const JpegDecInfo &R = P.info[P.ref];
+    const int n = r.n;
+    JpegDecArgs &a = r.a;
+    JpegPlanes &pl = r.pl;
+    a.n = n; a.h0 = R.h0; a.v0 = R.v0; a.w = R.w; a.h = R.h;
+    a.mxx = (R.w + 8 * R.h0 - 1) / (8 * R.h0); a.myy = (R.h + 8 * R.v0 - 1) / (8 * R.v0);
+    const bool gray = R.ncomp == 1;                        // *image.Gray: one block per MCU, no chroma planes
+    a.ybl = R.h0 * R.v0; a.bpm = gray ? 1 : a.ybl + 2;
+    a.nblk = a.mxx * a.myy * a.bpm;
+    a.nitems = (int)P.items.size();
+    pl.ystride = 8 * R.h0 * a.mxx; pl.cstride = 8 * a.mxx;
+    pl.y_fs = align256((size_t)pl.ystride * 8 * R.v0 * a.myy); pl.c_fs = gray ? 0 : align256((size_t)pl.cstride * 8 * a.myy);
+    if (lane) {
+        size_t subs = 0;
+        for (auto &pi : P.par) subs = std::max(subs, (size_t)pi.nsub);
+        subs *= P.par.size();
+        const size_t est = (pl.y_fs + 2 * pl.c_fs) * n + (size_t)n * a.nblk * 130 + 3 * (P.blob_bytes + 1024) + P.piece_ubytes +
+                           P.items.size() * (sizeof(JpegDecImage) + 8) + (size_t)n * (sizeof(JpegDecTables) + 64) + P.par.size() * (sizeof(JpegParImage) + 64) +
+                           subs * 96 + ((size_t)4 << 20);
+        const int rr = lane_reserve_dec(*lane, est);
+        if (rr) return rr;
+        r.mem.arena = lane->dec; r.mem.cap = lane->dec_bytes;
+    }
+    auto plane = [&](uint8_t **p, size_t bytes) {
+        if (lane && planes_in_lane) return r.mem.get(p, bytes);   // first requests of the call and counted in est: they always fit
+        return own.alloc(p, bytes);
+    };
+    DEC_HIP("plane allocation", plane(&pl.y, pl.y_fs * n));
+    if (!gray) DEC_HIP("plane allocation", plane(&pl.cb, pl.c_fs * n));
+    if (!gray) DEC_HIP("plane allocation", plane(&pl.cr, pl.c_fs * n));
+    DEC_HIP("scratch allocation", r.mem.get(&r.d_blob, P.blob_bytes + 16));
+    DEC_HIP("scratch allocation", r.mem.get(&r.d_img, sizeof(JpegDecImage) * P.items.size()));
+    DEC_HIP("scratch allocation", r.mem.get(&r.d_valid, (size_t)n));
+    DEC_HIP("scratch allocation", r.mem.get(&r.d_tab, sizeof(JpegDecTables) * n));
+    DEC_HIP("scratch allocation", r.mem.get(&a.coefs, (size_t)n * a.nblk * 128));
+    DEC_HIP("scratch allocation", r.mem.get(&a.status, sizeof(int) * n));
+    DEC_HIP("scratch allocation", r.mem.get(&a.dcs, (size_t)n * a.nblk * 2 + 16));
+    a.blob = r.d_blob; a.img = r.d_img; a.tab = r.d_tab; pl.valid = r.d_valid;
+    r.t_alloc = r.ms();
+    return IPX_OK;
+}
+
+// Stage 3: the blob, the items and the memsets; then the host-decoded files of the batch (progressive, several scans) group by group:
+// their scans are walked on the pool's threads, in groups of IPX_JPEG_HOST_GROUP files, into one half of a pinned block of two groups,
+// and the coefficients are copied into their slots (after the memsets, same stream) while the next group decodes into the other half.
+// (One block for all of them was 6.3 MB per 1080p file, 1.6 GB for a part of 256 progressive files, per part and per feeder of a pool;
+// uploading from pageable vectors took a quarter of such a call.)
+int dec_upload(DecRun &r)
+{
+    JpegBatchPlan &P = r.plan;
+    const JpegDecArgs &a = r.a;
+    const int n = r.n;
+    hipStream_t s = r.s;
+    static const char *const kPrep = "jpeg decode: host preparation failed";
+    uint8_t *hblob = r.pinned.get(P.blob_bytes + 16);
+    if (!hblob) return IPX_ERR_NOMEM;
+    const size_t hcoef_words = (size_t)a.nblk * 64, hslot_words = hcoef_words + a.nblk;
+    const int group = std::max(1, env_int("IPX_JPEG_HOST_GROUP", 16));
+    std::vector<int> hfiles;
+    for (int i = 0; i < n; i++) if (P.hslot[i] >= 0) hfiles.push_back(i);
+    int16_t *hpin = nullptr;
+    if (P.nhost) {
+        hpin = (int16_t *)r.pinned.get((size_t)2 * std::min(P.nhost, group) * hslot_words * sizeof(int16_t));
+        if (!hpin) {   // no pinned memory for them: these files stay on the caller's CPU path, the rest of the batch goes on
+            for (int i : hfiles) { r.status[i] = IPX_ERR_UNSUPPORTED; P.valid[i] = 0; }
+            hfiles.clear();
+            clear_error();
+        }
+    }
+    r.t_pin = r.ms();
+    // packing the scans walks every compressed byte
+    int rc = parallel_light(n, [&](int i) { if (P.valid[i] && !P.info[i].host_scans) memcpy(hblob + P.blob_off[i], r.jpegs[i].data + P.info[i].scan_off, P.info[i].scan_len); }, kPrep);
+    if (rc) return rc;
+    r.t_pack = r.ms();
+    DEC_HIP("jpeg decode", hipMemcpyAsync(r.d_blob, hblob, P.blob_bytes, hipMemcpyHostToDevice, s));
+    DEC_HIP("jpeg decode", hipMemcpyAsync(r.d_img, P.items.data(), sizeof(JpegDecImage) * P.items.size(), hipMemcpyHostToDevice, s));
+    DEC_HIP("jpeg decode", hipMemsetAsync(a.coefs, 0, (size_t)n * a.nblk * 128, s));
+    DEC_HIP("jpeg decode", hipMemsetAsync(a.status, 0, sizeof(int) * n, s));
+    DEC_HIP("jpeg decode", hipMemsetAsync(a.dcs, 0, (size_t)n * a.nblk * 2, s));
+    Events ev;
+    for (int g0 = 0, gi = 0; g0 < (int)hfiles.size(); g0 += group, gi++) {
+        const int half = gi & 1, cnt = std::min(group, (int)hfiles.size() - g0);
+        int16_t *base = hpin + (size_t)half * std::min(P.nhost, group) * hslot_words;
+        if (gi >= 2) DEC_HIP("jpeg decode", hipEventSynchronize(ev.ev[half]));          // the copies of two groups ago have left this half
+        rc = parallel_heavy(cnt, [&](int j) {
+            const int i = hfiles[g0 + j];
+            bool prog = false;
+            JpegDecInfo full;
+            const int st = jpeg_host_decode(r.jpegs[i].data, r.jpegs[i].len, &full, base + (size_t)j * hslot_words, base + (size_t)j * hslot_words + hcoef_words,
+                                            (size_t)a.nblk, P.tabs[i].qnat, &prog);
+            if (st != IPX_OK) { r.status[i] = st; P.valid[i] = 0; }
+        }, kPrep);
+        if (rc) return rc;
+        for (int j = 0; j < cnt; j++) {
+            const int i = hfiles[g0 + j];
+            if (!P.valid[i]) continue;
+            DEC_HIP("jpeg decode", hipMemcpyAsync(a.coefs + (size_t)i * hcoef_words, base + (size_t)j * hslot_words, hcoef_words * 2, hipMemcpyHostToDevice, s));
+            DEC_HIP("jpeg decode", hipMemcpyAsync(a.dcs + (size_t)i * a.nblk, base + (size_t)j * hslot_words + hcoef_words, (size_t)a.nblk * 2, hipMemcpyHostToDevice, s));
+        }
+        if (!ev.ev[half]) DEC_HIP("jpeg decode", hipEventCreateWithFlags(&ev.ev[half], hipEventDisableTiming));
+        DEC_HIP("jpeg decode", hipEventRecord(ev.ev[half], s));
+    }
+    // (which files are decodable is final only now: a host-decoded file may have failed in its scans; and the host decoder fills the
+    // quantisation tables of its files)
+    DEC_HIP("jpeg decode", hipMemcpyAsync(r.d_valid, P.valid.data(), (size_t)n, hipMemcpyHostToDevice, s));
+    DEC_HIP("jpeg decode", hipMemcpyAsync(r.d_tab, P.tabs.data(), sizeof(JpegDecTables) * n, hipMemcpyHostToDevice, s));
+    return IPX_OK;
+}
+
+// the blocks and the launch arguments of the passes that are parallel inside a scan
+int par_setup(DecRun &r, JpegParArgs &P, uint32_t **d_tot)
+{
+    std::vector<JpegParImage> &par = r.plan.par;
+    const JpegDecArgs &a = r.a;
+    hipStream_t s = r.s;
+    const size_t blob_bytes = r.plan.blob_bytes;
+    P.blob = r.d_blob; P.tab = r.d_tab; P.nimg = (int)par.size(); P.bpm = a.bpm; P.ybl = a.ybl; P.nblk = a.nblk;
+    P.coefs = a.coefs; P.status = a.status; P.dcs = a.dcs;
+    P.sub = r.plan.par_sub;
+    for (auto &pi : par) P.max_nsub = std::max(P.max_nsub, (int)pi.nsub);
+    for (size_t k = 0; k < par.size(); k++) par[k].sub_off = k * (size_t)P.max_nsub;
+    const size_t nsubs = par.size() * (size_t)P.max_nsub, cks = (size_t)jpeg_par_checkpoints();
+    // The scan bytes of a wave's 64 sub-sequences staged in LDS (small batches: a SIMD has one wave, which would wait for a global load
+    // nearly every symbol), or read through L1 / L2 (big ones lose more to the occupancy the rows cost): DESIGN.md section 4.6
+    P.stage_rows = env_int("IPX_JPEG_PAR_STAGE", -1);
+    if (P.stage_rows < 0) P.stage_rows = nsubs <= (size_t)env_int("IPX_JPEG_PAR_STAGE_SUBS", 98304) ? 1 : 0;
+    JpegParImage *d_par = nullptr;
+    DEC_HIP("jpeg decode", r.mem.get(&d_par, sizeof(JpegParImage) * par.size()));
+    DEC_HIP("jpeg decode", r.mem.get(&P.stuffed, nsubs * 4));
+    DEC_HIP("jpeg decode", r.mem.get(&P.entry, nsubs * 8));
+    DEC_HIP("jpeg decode", r.mem.get(&P.exit_a, nsubs * 8));
+    DEC_HIP("jpeg decode", r.mem.get(&P.exit_b, nsubs * 8));
+    DEC_HIP("jpeg decode", r.mem.get(&P.ends, nsubs * 4));
+    DEC_HIP("jpeg decode", r.mem.get(&P.ck_state, nsubs * 8 * cks));
+    DEC_HIP("jpeg decode", r.mem.get(&P.ck_ends, nsubs * 4 * cks));
+    DEC_HIP("jpeg decode", r.mem.get(&P.total_ends, par.size() * 4));
+    DEC_HIP("jpeg decode", r.mem.get(d_tot, par.size() * 4));
+    DEC_HIP("jpeg decode", r.mem.get(&P.changed, 4));
+    P.img = d_par;
+    DEC_HIP("jpeg decode", hipMemcpyAsync(d_par, par.data(), sizeof(JpegParImage) * par.size(), hipMemcpyHostToDevice, s));
+    DEC_HIP("jpeg decode", hipMemsetAsync(P.stuffed, 0, nsubs * 4, s));
+    DEC_HIP("jpeg decode", hipMemsetAsync(P.entry, 0xff, nsubs * 8, s));
+    DEC_HIP("jpeg decode", hipMemsetAsync(P.ends, 0, nsubs * 4, s));
+    DEC_HIP("jpeg decode", hipMemsetAsync(P.ck_state, 0xff, nsubs * 8 * cks, s));
+    DEC_HIP("jpeg decode", hipMemsetAsync(P.ck_ends, 0, nsubs * 4 * cks, s));
+    DEC_HIP("jpeg decode", r.mem.get(&P.ublob, blob_bytes + 64));
+    DEC_HIP("jpeg decode", r.mem.get(&P.scan_end, par.size() * 4));
+    DEC_HIP("jpeg decode", r.mem.get(&P.ulen, par.size() * 4));
+    DEC_HIP("jpeg decode", hipMemsetAsync(P.ublob, 0, blob_bytes + 64, s));
+    DEC_HIP("jpeg decode", hipMemsetAsync(P.scan_end, 0xff, par.size() * 4, s));
+    DEC_HIP("jpeg decode", hipMemsetAsync(P.ulen, 0, par.size() * 4, s));
+    return IPX_OK;
+}
+
+// a scan that never settled (it would take a pathological file): its image goes whole to the serial kernel
+int par_fallback(DecRun &r)
+{
+    const JpegDecArgs &a = r.a;
+    std::vector<JpegDecImage> serial;
+    for (auto &pi : r.plan.par) {
+        JpegDecImage it;
+        memset(&it, 0, sizeof it);
+        it.scan_off = pi.scan_off; it.scan_len = pi.scan_len; it.img = pi.img; it.first_mcu = 0; it.n_mcu = (uint32_t)(a.mxx * a.myy);
+        memcpy(it.td, pi.td, 3); memcpy(it.ta, pi.ta, 3);
+        it.valid = 1;
+        serial.push_back(it);
+    }
+    StreamSync wait{r.s};               // `serial` must outlive the copy
+    JpegDecImage *d_serial;
+    DEC_HIP("jpeg decode", r.mem.get(&d_serial, sizeof(JpegDecImage) * serial.size()));
+    DEC_HIP("jpeg decode", hipMemcpyAsync(d_serial, serial.data(), sizeof(JpegDecImage) * serial.size(), hipMemcpyHostToDevice, r.s));
+    JpegDecArgs a2 = a;
+    a2.img = d_serial; a2.nitems = (int)serial.size();
+    DEC_HIP("jpeg decode", launch_jpeg_huff(a2, r.s));
+    return IPX_OK;
+}
+
+// the passes that are parallel inside a scan: count and unstuff, the speculative pass, rounds until no entry state changes (the host reads
+// one counter per round), then the write and DC passes -- or the serial kernel
+int dec_parallel(DecRun &r)
+{
+    hipStream_t s = r.s;
+    JpegParArgs P{};
+    uint32_t *d_tot = nullptr;
+    const int rc = par_setup(r, P, &d_tot);
+    if (rc) return rc;
+    DEC_HIP("jpeg decode", launch_par_count(P, s));
+    DEC_HIP("jpeg decode", launch_scan(P.stuffed, P.max_nsub, P.nimg, d_tot, s));
+    DEC_HIP("jpeg decode", launch_par_unstuff(P, s));
+    DEC_HIP("jpeg decode", launch_par_sync(P, 0, s));
+    bool converged = false;
+    const int max_rounds = env_int("IPX_JPEG_PAR_ROUNDS", 96);
+    for (int round = 1; !converged && round <= max_rounds; round++) {
+        uint32_t changed = 0;
+        DEC_HIP("jpeg decode", hipMemsetAsync(P.changed, 0, 4, s));
+        DEC_HIP("jpeg decode", launch_par_sync(P, round, s));
+        DEC_HIP("jpeg decode", hipMemcpyAsync(&changed, P.changed, 4, hipMemcpyDeviceToHost, s));
+        const hipError_t e = hipStreamSynchronize(s);
+        if (getenv("IPX_DEBUG")) fprintf(stderr, "[ipx] jpeg par sync round %d: %u entries changed\n", round, changed);
+        DEC_HIP("jpeg decode", e);
+        converged = changed == 0;
+    }
+    if (!converged) return par_fallback(r);
+    DEC_HIP("jpeg decode", launch_scan(P.ends, P.max_nsub, P.nimg, P.total_ends, s));
+    DEC_HIP("jpeg decode", launch_par_write(P, s));
+    DEC_HIP("jpeg decode", launch_par_dc(P, s));
+    return IPX_OK;
+}
+
+// Stage 4: the pieces (or the byte-wise kernel), then the scans that are decoded in parallel
+int dec_huffman(DecRun &r)
+{
+    const JpegBatchPlan &P = r.plan;
+    JpegDecArgs &a = r.a;
+    int ref_gpu = -1;                                        // the first image the Huffman kernels decode: the one whose tables a shared-table launch carries
+    for (int i = 0; i < r.n && ref_gpu < 0; i++) if (P.valid[i] && !P.info[i].host_scans) ref_gpu = i;
+    a.first_valid = ref_gpu >= 0 ? ref_gpu : P.ref;
+    a.shared_tables = env_int("IPX_JPEG_SHARED_TABLES", 1);
+    for (int i = 0; i < r.n && a.shared_tables && ref_gpu >= 0; i++)
+        if (P.valid[i] && !P.info[i].host_scans && !jpeg_same_tables(P.tabs[i], P.tabs[ref_gpu])) a.shared_tables = 0;
+    if (a.nitems > 0) {
+        if (env_int("IPX_JPEG_PIECE", 1)) {
+            uint8_t *d_upieces; uint32_t *d_ulen;
+            DEC_HIP("jpeg decode", r.mem.get(&d_upieces, P.piece_ubytes + 64));
+            DEC_HIP("jpeg decode", r.mem.get(&d_ulen, sizeof(uint32_t) * P.items.size()));
+            DEC_HIP("jpeg decode", launch_jpeg_pieces(a, d_upieces, d_ulen, r.s));
+        } else {
+            DEC_HIP("jpeg decode", launch_jpeg_huff(a, r.s));     // the earlier kernel: byte-wise reader, per-lane tables when the files of the batch carry different ones
+        }
+    }
+    return P.par.empty() ? IPX_OK : dec_parallel(r);
+}
+
+// Stage 5: the reconstruction, the kernels' verdicts, and the planes handed out
+int dec_finish(DecRun &r, ipx_ycbcr_batch *planes)
+{
+    DEC_HIP("jpeg decode", launch_jpeg_idct(r.a, r.pl, r.s));
+    r.t_launch = r.ms();
+    r.dev_status.assign(r.n, 0);
+    DEC_HIP("jpeg decode", hipMemcpyAsync(r.dev_status.data(), r.a.status, sizeof(int) * r.n, hipMemcpyDeviceToHost, r.s));
+    DEC_HIP("jpeg decode", hipStreamSynchronize(r.s));
+    if ((getenv("IPX_DEBUG") && r.ms() > 200.0) || env_int("IPX_DEBUG_J2J", 0))
+        fprintf(stderr, "[ipx] decode of %d files: parsed at %.1f ms, device scratch at %.1f, pinned block at %.1f, packed at %.1f, launched at %.1f, finished at %.1f\n", r.n, r.plan.parse_ms, r.t_alloc, r.t_pin, r.t_pack, r.t_launch, r.ms());
+    for (int i = 0; i < r.n; i++)
+        if (r.status[i] == IPX_OK && r.dev_status[i]) r.status[i] = jpeg_status_of(r.dev_status[i]);
+    planes->y = r.pl.y; planes->cb = r.pl.cb; planes->cr = r.pl.cr;
+    planes->ystride = r.pl.ystride; planes->cstride = r.pl.cstride;
+    planes->y_frame_stride = r.pl.y_fs; planes->c_frame_stride = r.pl.c_fs;
+    planes->ratio = r.plan.info[r.plan.ref].ratio;
+    return IPX_OK;
+}
+
+}  // namespace
+
+// lane != NULL: scratch is bumped out of the lane's decode buffer (no allocation in the steady state); planes_in_lane: the planes too --
+// the caller then holds the lane for as long as it uses them and *owner has nothing to free
+int jpeg_decode_files(ipx_ctx *ctx, hipStream_t s, Lane *lane, bool planes_in_lane, const ipx_bytes *jpegs, int n, int *w, int *h,
+                      ipx_ycbcr_batch *planes, int *status, ipx_jpeg_planes **owner)
+{
+    OwnedBlocks<ipx_jpeg_planes> own(ctx, s);
+    DecRun r(ctx, s, jpegs, n, status);
+    const JpegPlanOptions opt{*w, *h, env_int("IPX_JPEG_PAR", 1) != 0, env_int("IPX_JPEG_PAR_SUB", 0), jpeg_par_sub_bytes()};
+    int rc = jpeg_plan_batch(jpegs, n, opt, status, &r.plan);
+    if (rc) return rc;
+    if (r.plan.ref < 0) return IPX_OK;
+    *w = r.plan.info[r.plan.ref].w; *h = r.plan.info[r.plan.ref].h;
+    rc = dec_blocks(r, lane, planes_in_lane, own);
+    if (!rc) rc = dec_upload(r);
+    if (!rc) rc = dec_huffman(r);
+    if (!rc) rc = dec_finish(r, planes);
+    if (rc) return rc;
+    *owner = own.release();
+    return IPX_OK;
+}
+
+extern "C" {
+
+void ipx_jpeg_planes_free(ipx_ctx *ctx, ipx_jpeg_planes *o) { dev_blocks_free(ctx, o); }
+
+int ipx_jpeg_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *jpegs, int n, int *w, int *h, ipx_ycbcr_batch *planes,
+                          int *status, ipx_jpeg_planes **owner) try
+{
+    IPX_ENTER(ctx);
+    if (!jpegs || n < 0 || !w || !h || !planes || !status || !owner) { set_error("ipx_jpeg_decode_batch: bad argument"); return IPX_ERR_INVALID; }
+    *owner = nullptr;
+    memset(planes, 0, sizeof *planes);
+    if (n == 0) return IPX_OK;
+    if (n > 65535) { set_error("ipx_jpeg_decode_batch: at most 65535 files per call"); return IPX_ERR_UNSUPPORTED; }
+    // the scratch comes out of a lane's decode buffer for the duration of the call; the planes are the caller's (stream-ordered allocations)
+    LaneLease lane(ctx);
+    return jpeg_decode_files(ctx, stream ? (hipStream_t)stream : ctx->stream, env_int("IPX_JPEG_LANE_ARENA", 1) ? &lane.get() : nullptr, false, jpegs, n, w, h,
+                             planes, status, owner);
+}
+IPX_CATCH_STATUS
+
+}  // extern "C"

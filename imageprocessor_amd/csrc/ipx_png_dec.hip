@@ -4,13 +4,12 @@
 // LDS, match copies spread over the lanes, coalesced flushes with the Adler-32) and the unfilter (a diagonal wavefront of 64 rows that
 // writes the frame layout of the type Go returns; for Adam7 files, taken under IPX_PNG_ADAM7=1, one such wave per pass that scatters
 // its pixels to where the pass puts them).  Host half: ipx_png_dec_host.cpp.  DESIGN.md section 4.10.
-#include <memory>
+#include <numeric>
 #include <vector>
 
 #include "ipx_png.h"
 #include "ipx_png_dec.h"
-#include "ipx_runtime_internal.h"
-#include "ipx_threads.h"
+#include "ipx_decode_common.h"
 
 namespace ipx {
 
@@ -620,13 +619,7 @@ constexpr uint32_t kCrcPiece = 16384;
 int png_parse_all(const ipx_bytes *files, int n, std::vector<PngFileInfo> &info, int *status)
 {
     const bool adam7 = env_int("IPX_PNG_ADAM7", 0) == 1;
-    std::atomic<int> failed{IPX_OK};
-    HostPool::instance().parallel_for(n, std::max(1, std::min(n / 8, 16)), [&](int i) {
-        const int rc = guarded_status([&] { status[i] = png_parse(files[i].data, files[i].data ? files[i].len : 0, adam7, &info[i]); }, nullptr);
-        if (rc) failed = rc;
-    });
-    if (failed) { set_error("png decode: host parse failed"); return failed; }
-    return IPX_OK;
+    return parallel_light(n, [&](int i) { status[i] = png_parse(files[i].data, files[i].data ? files[i].len : 0, adam7, &info[i]); }, "png decode: host parse failed");
 }
 
 // the batch's size and kind: *w x *h (or the first parsed file's when *w == 0) and *kind (or the first's when -1); others UNSUPPORTED
@@ -652,32 +645,24 @@ static int png_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
 {
     const int n = (int)idx.size();
     if (n == 0) return IPX_OK;
-    std::vector<uint8_t *> pinned;
-    struct Release {
-        ipx_ctx *ctx; hipStream_t s; std::vector<uint8_t *> &p;
-        ~Release() { (void)hipStreamSynchronize(s); for (uint8_t *q : p) (void)ipx_host_free(ctx, q); }
-    } release{ctx, s, pinned};
+    PinnedBlocks pinned(ctx, s);
     AsyncFree mem{s, {}};
     uint32_t *dstate;
     IPX_HIP(mem.get(&dstate, (size_t)n * 4));
     IPX_HIP(hipMemsetAsync(dstate, 0, (size_t)n * 4, s));
     if (palettes) {     // one upload of every slot up to the last (zero for slots not decoded here)
         const int nslot = *std::max_element(slot.begin(), slot.end()) + 1;
-        uint8_t *hpal = (uint8_t *)ipx_host_alloc(ctx, (size_t)nslot * 1024);
+        uint8_t *hpal = pinned.get((size_t)nslot * 1024);
         if (!hpal) return IPX_ERR_NOMEM;
-        pinned.push_back(hpal);
         memset(hpal, 0, (size_t)nslot * 1024);
         for (int g = 0; g < n; g++) memcpy(hpal + (size_t)slot[g] * 1024, info[idx[g]].pal, 1024);
         IPX_HIP(hipMemcpyAsync(palettes, hpal, (size_t)nslot * 1024, hipMemcpyHostToDevice, s));
     }
     const size_t budget = (size_t)env_int("IPX_PNG_DEC_SCRATCH_MB", 8192) << 20;
-    std::vector<int> group;     // positions in idx
-    auto run_group = [&]() -> int {
+    auto run_group = [&](const std::vector<int> &group) -> int {     // positions in idx
         const int m = (int)group.size();
-        if (m == 0) return IPX_OK;
         // this group's scratch: the device blocks go back (stream-ordered) first, then the pinned block once the stream is past its copy
-        std::vector<uint8_t *> gpinned;
-        Release grelease{ctx, s, gpinned};
+        PinnedBlocks gpinned(ctx, s);
         AsyncFree gmem{s, {}};
         std::vector<PngDecDesc> desc(m);
         std::vector<PngCrcPiece> pieces;
@@ -730,13 +715,13 @@ static int png_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
             zbytes += align256((size_t)f.idat_len + 32);
             rbytes += align256(f.raw_len);
         }
-        uint8_t *hblob = (uint8_t *)ipx_host_alloc(ctx, fbytes);
+        uint8_t *hblob = gpinned.get(fbytes);
         if (!hblob) return IPX_ERR_NOMEM;
-        gpinned.push_back(hblob);
-        HostPool::instance().parallel_for(m, std::max(1, std::min(m / 8, 16)), [&](int g) {
+        const int rc = parallel_light(m, [&](int g) {
             const int i = idx[group[g]];
             memcpy(hblob + foff[g], files[i].data, info[i].file_len);
-        });
+        }, "png decode: host gather failed");
+        if (rc) return rc;
         // the Adam7 files' descriptors go behind the others: each unfilter kernel takes its own run of the table
         const int m0 = (int)(std::stable_partition(desc.begin(), desc.end(), [](const PngDecDesc &d) { return !d.interlace; }) - desc.begin());
         uint8_t *dblob, *dz, *draw;
@@ -763,21 +748,11 @@ static int png_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
         IPX_HIP(launch_png_unfilter_adam7(ddesc + m0, m - m0, draw, frames, dstate, s));
         // the host vectors must outlive the copies: wait before they go
         IPX_HIP(hipStreamSynchronize(s));
-        group.clear();
         return IPX_OK;
     };
-    size_t group_bytes = 0;
-    for (int g = 0; g < n; g++) {
-        const size_t need = png_group_bytes(info[idx[g]]);
-        if (!group.empty() && group_bytes + need > budget) {
-            const int rc = run_group();
-            if (rc) return rc;
-            group_bytes = 0;
-        }
-        group.push_back(g);
-        group_bytes += need;
-    }
-    int rc = run_group();
+    std::vector<int> all(n);
+    std::iota(all.begin(), all.end(), 0);
+    const int rc = for_groups_under(all, budget, [&](int g) { return png_group_bytes(info[idx[g]]); }, run_group);
     if (rc) return rc;
     std::vector<uint32_t> st(n);
     IPX_HIP(hipMemcpyAsync(st.data(), dstate, (size_t)n * 4, hipMemcpyDeviceToHost, s));
@@ -790,17 +765,9 @@ static int png_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
 }
 
 // ---- the entries -----------------------------------------------------------------------------------------------------------------
-struct ipx_png_frames { std::vector<void *> dev; hipStream_t stream = nullptr; };   // stream-ordered allocations of `stream`
-
 extern "C" {
 
-void ipx_png_frames_free(ipx_ctx *ctx, ipx_png_frames *o)
-{
-    if (!o) return;
-    if (ctx) (void)hipSetDevice(ctx->device);
-    for (void *p : o->dev) (void)hipFreeAsync(p, o->stream);
-    delete o;
-}
+void ipx_png_frames_free(ipx_ctx *ctx, ipx_png_frames *o) { dev_blocks_free(ctx, o); }
 
 int ipx_png_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *files, int n, int *w, int *h, int *kind, ipx_png_batch *frames,
                          int *status, ipx_png_frames **owner) try
@@ -824,32 +791,24 @@ int ipx_png_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *files, int
     for (int i = 0; i < n; i++)
         if (status[i] == IPX_OK) idx.push_back(i);
     if (idx.empty()) return IPX_OK;
-    std::unique_ptr<ipx_png_frames> o(new ipx_png_frames);
-    o->stream = s;
+    OwnedBlocks<ipx_png_frames> o(ctx, s);
     const int kb = png_kind_bpp(bk);
     const size_t fs = align256((size_t)bw * bh * kb);
     uint8_t *dframes = nullptr, *dpal = nullptr;
-    hipError_t e = hipMallocAsync((void **)&dframes, fs * n, s);
-    if (e == hipSuccess) o->dev.push_back(dframes);
-    if (e == hipSuccess && bk == IPX_PNG_PALETTED) {
-        e = hipMallocAsync((void **)&dpal, (size_t)n * 1024, s);
-        if (e == hipSuccess) o->dev.push_back(dpal);
-    }
+    hipError_t e = o.alloc(&dframes, fs * n);
+    if (e == hipSuccess && bk == IPX_PNG_PALETTED) e = o.alloc(&dpal, (size_t)n * 1024);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        ipx_png_frames_free(ctx, o.release());
         set_error("ipx_png_decode_batch: device allocation failed: %s", hipGetErrorString(e));
         return IPX_ERR_NOMEM;
     }
     if (dpal) IPX_HIP(hipMemsetAsync(dpal, 0, (size_t)n * 1024, s));
     rc = png_decode_files(ctx, s, files, idx, idx, info, dframes, fs, dpal, status);     // frame i of file i
-    if (rc) { ipx_png_frames_free(ctx, o.release()); return rc; }
+    if (rc) return rc;
     *w = bw;
     *h = bh;
     *kind = bk;
-    bool any = false;
-    for (int i = 0; i < n; i++) any |= status[i] == IPX_OK;
-    if (!any) { ipx_png_frames_free(ctx, o.release()); return IPX_OK; }
+    if (!any_ok(status, n)) return IPX_OK;
     frames->pix = dframes;
     frames->stride = bw * kb;
     frames->frame_stride = fs;

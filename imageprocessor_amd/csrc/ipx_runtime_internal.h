@@ -1,5 +1,6 @@
 // ipx_runtime_internal.h -- the runtime's own types (context, lanes, glyph sets, plans) and the small helpers every
-// translation unit that implements ABI entries needs (ipx_runtime.hip, ipx_jpeg_runtime.hip).  Not part of the ABI.
+// translation unit that implements ABI entries needs (ipx_runtime.hip, ipx_jpeg_runtime.hip, ipx_jpeg_dec_runtime.hip, the GIF and PNG
+// halves).  What only the decode drivers share sits on top of it in ipx_decode_common.h.  Not part of the ABI.
 #pragma once
 
 #include <sched.h>
@@ -357,6 +358,10 @@ int jpeg_encode_sets(ipx_ctx *ctx, hipStream_t s, const JpegEncSet *sets, int K,
 // gif.Encode of n frames in HBM into one pinned block *blob (ipx_gif.hip)
 int gif_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w, int h, int stride, size_t frame_stride, int n,
                     uint8_t **blob, size_t *offs, size_t *lens);
+
+// image.Decode of n JPEG files into planes in HBM (ipx_jpeg_dec_runtime.hip); *w x *h: the size asked for, or 0 for the first parsed file's
+int jpeg_decode_files(ipx_ctx *ctx, hipStream_t s, Lane *lane, bool planes_in_lane, const ipx_bytes *jpegs, int n, int *w, int *h,
+                      ipx_ycbcr_batch *planes, int *status, ipx_jpeg_planes **owner);
 
 // the pinned blocks the streams of the compressed-out batch entries live in (ipx_jpeg_result_free)
 struct ipx_jpeg_result { std::vector<uint8_t *> blobs; };

@@ -1,6 +1,9 @@
 // CPU-side sanitizer run of the parsers that read bytes from outside: the JPEG marker parser (ipx_jpeg_dec_host.cpp, fed with
 // every upload), the host scan decoder of progressive / multi-scan files (ipx_jpeg_dec_prog.cpp) and the TrueType loader / rasteriser (ipx_font.cpp).  Built with -fsanitize=address,undefined by tools/sanitize/run.sh;
 // inputs: seed files given on the command line (*.jpg, *.ttf), mutated with a fixed-seed generator.  Any report aborts the run.
+// The JPEG seeds and their mutations then go, in mixed batches of 1, 5 and 70 files, through the host plan of a batch decode
+// (jpeg_plan_batch), whose invariants -- what the kernels rely on when they index the blob and the scratch -- are asserted.
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -12,6 +15,7 @@
 
 namespace ipx {
 void set_error(const char *, ...) {}
+int status_of_exception() noexcept { return IPX_ERR_NOMEM; }
 }
 
 static uint64_t rng_state = 0x9e3779b97f4a7c15ull;
@@ -45,14 +49,78 @@ static void mutate(std::vector<uint8_t> &v, size_t lo, size_t hi)
     }
 }
 
+#define PLAN_CHECK(cond) do { if (!(cond)) { fprintf(stderr, "batch plan: %s does not hold (batch of %d)\n", #cond, n); abort(); } } while (0)
+
+static long plan_pieces = 0, plan_padding = 0, plan_par = 0;
+
+// one batch through jpeg_plan_batch
+static void check_plan(const std::vector<std::vector<uint8_t>> &batch, const ipx::JpegPlanOptions &opt)
+{
+    const int n = (int)batch.size();
+    std::vector<uint8_t *> heap(n);          // exact-size copies: a read past a file's end is an ASan report
+    std::vector<ipx_bytes> files(n);
+    for (int i = 0; i < n; i++) {
+        heap[i] = (uint8_t *)malloc(batch[i].size() ? batch[i].size() : 1);
+        memcpy(heap[i], batch[i].data(), batch[i].size());
+        files[i].data = heap[i]; files[i].len = batch[i].size();
+    }
+    std::vector<int> status(n, 0);
+    ipx::JpegBatchPlan P;
+    PLAN_CHECK(ipx::jpeg_plan_batch(files.data(), n, opt, status.data(), &P) == IPX_OK);
+    const size_t end = P.blob_bytes + 16;
+    std::vector<std::pair<size_t, size_t>> regions;                 // the pieces' unstuffed copies
+    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> mcus(n); // per image: (first_mcu, n_mcu) of its pieces
+    for (size_t k = 0; k < P.items.size(); k++) {
+        const ipx::JpegDecImage &it = P.items[k];
+        const bool last_class = it.tab_img == P.items.back().tab_img;
+        if (k && it.tab_img != P.items[k - 1].tab_img) PLAN_CHECK(k % 64 == 0);          // every class run but the last: whole groups of 64
+        if (!it.valid) { PLAN_CHECK(!last_class); plan_padding++; continue; }            // padding
+        PLAN_CHECK((int)it.img < n && status[it.img] == IPX_OK && P.valid[it.img] == 1 && !P.info[it.img].host_scans);
+        PLAN_CHECK(it.scan_off % 16 == 0 && it.pad < 16 && it.pad <= it.scan_len && it.scan_off + it.scan_len <= end);
+        PLAN_CHECK(it.scan_off >= P.blob_off[it.img] && it.scan_off + it.scan_len <= P.blob_off[it.img] + P.info[it.img].scan_len);
+        PLAN_CHECK(it.uoff % 16 == 0 && it.uoff + (it.scan_len - it.pad) + 16 <= P.piece_ubytes);
+        regions.push_back({(size_t)it.uoff, (size_t)it.uoff + (it.scan_len - it.pad) + 16});
+        mcus[it.img].push_back({it.first_mcu, it.n_mcu});
+        PLAN_CHECK((int)it.tab_img < n && status[it.tab_img] == IPX_OK && ipx::jpeg_same_tables(P.tabs[it.img], P.tabs[it.tab_img]));
+    }
+    std::sort(regions.begin(), regions.end());
+    for (size_t k = 1; k < regions.size(); k++) PLAN_CHECK(regions[k - 1].second <= regions[k].first);
+    for (const ipx::JpegParImage &pi : P.par) {
+        PLAN_CHECK((int)pi.img < n && status[pi.img] == IPX_OK && P.valid[pi.img] == 1 && mcus[pi.img].empty());
+        PLAN_CHECK(pi.scan_off == P.blob_off[pi.img] && pi.scan_len == P.info[pi.img].scan_len && pi.scan_off + pi.scan_len <= end);
+        PLAN_CHECK(P.par_sub >= 128 && pi.nsub == (pi.scan_len + P.par_sub - 1) / P.par_sub);
+        mcus[pi.img].push_back({0u, ~0u});
+    }
+    int nhost = 0;
+    for (int i = 0; i < n; i++) {
+        const ipx::JpegDecInfo &I = P.info[i];
+        if (status[i] != IPX_OK) { PLAN_CHECK(!P.valid[i] && mcus[i].empty() && P.hslot[i] < 0); continue; }
+        PLAN_CHECK(P.ref >= 0 && I.w == P.info[P.ref].w && I.h == P.info[P.ref].h && I.h0 == P.info[P.ref].h0 && I.v0 == P.info[P.ref].v0 && I.ncomp == P.info[P.ref].ncomp);
+        if (I.host_scans) { PLAN_CHECK(P.hslot[i] == nhost++ && mcus[i].empty() && (P.valid[i] & 1)); continue; }
+        PLAN_CHECK(P.hslot[i] < 0 && !mcus[i].empty());
+        if (mcus[i][0].second == ~0u) continue;                                          // a parallel image: the whole scan
+        const uint32_t nmcu = (uint32_t)(((I.w + 8 * I.h0 - 1) / (8 * I.h0)) * ((I.h + 8 * I.v0 - 1) / (8 * I.v0)));
+        std::sort(mcus[i].begin(), mcus[i].end());
+        uint32_t at = 0;
+        for (auto &m : mcus[i]) { PLAN_CHECK(m.first == at && m.second > 0); at += m.second; }   // the pieces tile [0, nmcu) exactly
+        PLAN_CHECK(at == nmcu);
+    }
+    PLAN_CHECK(nhost == P.nhost);
+    for (uint8_t *h : heap) free(h);
+    plan_pieces += (long)P.items.size();
+    plan_par += (long)P.par.size();
+}
+
 int main(int argc, char **argv)
 {
     const int cases = argc > 1 ? atoi(argv[1]) : 2000;
+    std::vector<std::vector<uint8_t>> jpeg_seeds;
     long jpeg_ok = 0, jpeg_bad = 0, font_ok = 0, font_bad = 0, host_ok = 0, host_bad = 0;
     for (int a = 2; a < argc; a++) {
         const std::string path = argv[a];
         const std::vector<uint8_t> seed = slurp(argv[a]);
         const bool is_font = path.size() > 4 && path.substr(path.size() - 4) == ".ttf";
+        if (!is_font) jpeg_seeds.push_back(seed);
         for (int t = 0; t < cases; t++) {
             std::vector<uint8_t> v = seed;
             if (is_font) {
@@ -107,7 +175,20 @@ int main(int argc, char **argv)
             }
         }
     }
-    printf("jpeg headers: %ld parsed, %ld refused; host scan decodes: %ld done, %ld refused; fonts: %ld loaded, %ld refused; no sanitizer report\n",
-           jpeg_ok, jpeg_bad, host_ok, host_bad, font_ok, font_bad);
+    long plans = 0;
+    for (int t = 0; !jpeg_seeds.empty() && t < std::max(30, cases / 10); t++) {
+        const int n = t % 3 == 0 ? 1 : (t % 3 == 1 ? 5 : 70);
+        std::vector<std::vector<uint8_t>> batch(n);
+        for (auto &v : batch) {
+            v = jpeg_seeds[rnd() % jpeg_seeds.size()];
+            if (rnd() % 3 == 0) mutate(v, 2, v.size());
+        }
+        static const int subs[] = {0, 0, 128, 256, 512, 1024};
+        const ipx::JpegPlanOptions opt{t % 5 == 4 ? 160 : 0, t % 5 == 4 ? 120 : 0, t % 7 != 6, subs[t % 6], 1024};
+        check_plan(batch, opt);
+        plans++;
+    }
+    printf("jpeg headers: %ld parsed, %ld refused; host scan decodes: %ld done, %ld refused; batch plans: %ld checked, %ld pieces (%ld of them padding), %ld parallel images; fonts: %ld loaded, %ld refused; no sanitizer report\n",
+           jpeg_ok, jpeg_bad, host_ok, host_bad, plans, plan_pieces, plan_padding, plan_par, font_ok, font_bad);
     return 0;
 }
