@@ -46,11 +46,31 @@ def _bytes_array(files):
     return arr
 
 
+def _rows(a):
+    """-> (uint8 array, row stride in bytes): `a` itself when its rows are contiguous and strides[0] covers a row -- a window of a
+    larger array, which is what an image's SubImage is --, a packed copy otherwise"""
+    a = np.asarray(a, dtype=np.uint8)
+    row = int(np.prod(a.shape[1:]))
+    if a.ndim < 2 or not a[:1].flags.c_contiguous or (a.shape[0] > 1 and a.strides[0] < row):
+        a = np.ascontiguousarray(a)
+    return a, (a.strides[0] if a.shape[0] > 1 else row)
+
+
 def _frame(a):
-    a = np.ascontiguousarray(a, dtype=np.uint8)
+    """an RGBA8 source frame -> (array, row stride)"""
+    a, stride = _rows(a)
     if a.ndim != 3 or a.shape[2] != 4:
         raise ValueError("RGBA8 frame must be H x W x 4")
-    return a
+    return a, stride
+
+
+def _dst(dst, shape=None):
+    """a destination frame is written in place: H x W x 4 uint8 with contiguous rows -> its row stride"""
+    assert isinstance(dst, np.ndarray) and dst.dtype == np.uint8 and dst.ndim == 3 and dst.shape[2] == 4 and dst.flags.writeable
+    assert shape is None or dst.shape == shape
+    d, stride = _rows(dst)
+    assert d is dst, "the destination's rows must be contiguous and strides[0] at least a row"
+    return stride
 
 
 # ---- host-only rules (no GPU needed) ------------------------------------------------------------
@@ -93,12 +113,12 @@ def _glyph_array(glyphs):
     keep = []
     arr = (Glyph * max(1, len(glyphs)))()
     for i, g in enumerate(glyphs):
-        m = np.ascontiguousarray(g["mask"], dtype=np.uint8)
+        m, mstride = _rows(g["mask"])
         if m.ndim != 2:
             raise ValueError("glyph mask must be mh x mw")
         keep.append(m)
         mp = g.get("mp", (0, 0))
-        arr[i] = Glyph(m.ctypes.data, m.shape[1], m.shape[0], m.shape[1], _rect(g["dr"]), int(mp[0]),
+        arr[i] = Glyph(m.ctypes.data, m.shape[1], m.shape[0], mstride, _rect(g["dr"]), int(mp[0]),
                        int(mp[1]))
     return arr, keep
 
@@ -209,9 +229,9 @@ class Plan:
     def run_dev(self, n, src_ptr, resize_ptr=None, thumb_ptr=None, wm_ptr=None, stream=None,
                 sstride=None, src_frame_stride=None, resize_frame_stride=None,
                 thumb_frame_stride=None, wm_frame_stride=None):
+        sstride = self._sw * 4 if sstride is None else sstride
         self._run(lib().ipx_plan_run_dev, (stream,), n,
-                  (src_ptr, sstride if sstride is not None else self._sw * 4,
-                   src_frame_stride if src_frame_stride is not None else self._sw * self._sh * 4),
+                  (src_ptr, sstride, sstride * self._sh if src_frame_stride is None else src_frame_stride),
                   (resize_ptr, thumb_ptr, wm_ptr), (resize_frame_stride, thumb_frame_stride, wm_frame_stride))
 
     def run_host(self, frames, want=("resize", "thumbnail", "watermark"), out=None):
@@ -313,26 +333,39 @@ class Plan:
         every output on the GPU."""
         return self._run_files(lib().ipx_plan_run_png_png, files, want, copy)
 
-    def run_dev_nrgba(self, n, src_ptr, resize_ptr=None, thumb_ptr=None, wm_ptr=None, stream=None):
-        """*image.NRGBA frames (tightly packed) resident in HBM (ipx_plan_run_dev_nrgba)"""
-        self._run(lib().ipx_plan_run_dev_nrgba, (stream,), n, (src_ptr, self._sw * 4, self._sw * self._sh * 4), (resize_ptr, thumb_ptr, wm_ptr))
+    def run_dev_nrgba(self, n, src_ptr, resize_ptr=None, thumb_ptr=None, wm_ptr=None, stream=None,
+                      sstride=None, src_frame_stride=None, resize_frame_stride=None,
+                      thumb_frame_stride=None, wm_frame_stride=None):
+        """*image.NRGBA frames resident in HBM, tightly packed unless the strides say otherwise (ipx_plan_run_dev_nrgba)"""
+        sstride = self._sw * 4 if sstride is None else sstride
+        self._run(lib().ipx_plan_run_dev_nrgba, (stream,), n,
+                  (src_ptr, sstride, sstride * self._sh if src_frame_stride is None else src_frame_stride),
+                  (resize_ptr, thumb_ptr, wm_ptr), (resize_frame_stride, thumb_frame_stride, wm_frame_stride))
 
-    def run_dev_deep(self, n, kind, src_ptr, stride, frame_stride, resize_ptr=None, thumb_ptr=None, wm_ptr=None, stream=None):
+    def run_dev_deep(self, n, kind, src_ptr, stride, frame_stride, resize_ptr=None, thumb_ptr=None, wm_ptr=None, stream=None,
+                     resize_frame_stride=None, thumb_frame_stride=None, wm_frame_stride=None):
         """*image.NRGBA64 / RGBA64 / Gray16 / CMYK frames (Go's Pix) resident in HBM (ipx_plan_run_dev_deep)"""
-        self._run(lib().ipx_plan_run_dev_deep, (stream,), n, (kind, src_ptr, stride, frame_stride), (resize_ptr, thumb_ptr, wm_ptr))
+        self._run(lib().ipx_plan_run_dev_deep, (stream,), n, (kind, src_ptr, stride, frame_stride), (resize_ptr, thumb_ptr, wm_ptr),
+                  (resize_frame_stride, thumb_frame_stride, wm_frame_stride))
 
-    def run_dev_gray(self, n, gray_ptr, stride, frame_stride, resize_ptr=None, thumb_ptr=None, wm_ptr=None, stream=None):
+    def run_dev_gray(self, n, gray_ptr, stride, frame_stride, resize_ptr=None, thumb_ptr=None, wm_ptr=None, stream=None,
+                     resize_frame_stride=None, thumb_frame_stride=None, wm_frame_stride=None):
         """*image.Gray frames resident in HBM (ipx_plan_run_dev_gray)"""
-        self._run(lib().ipx_plan_run_dev_gray, (stream,), n, (gray_ptr, stride, frame_stride), (resize_ptr, thumb_ptr, wm_ptr))
+        self._run(lib().ipx_plan_run_dev_gray, (stream,), n, (gray_ptr, stride, frame_stride), (resize_ptr, thumb_ptr, wm_ptr),
+                  (resize_frame_stride, thumb_frame_stride, wm_frame_stride))
 
-    def run_dev_paletted(self, n, index_ptr, stride, frame_stride, palettes_ptr, resize_ptr=None, thumb_ptr=None, wm_ptr=None, stream=None):
+    def run_dev_paletted(self, n, index_ptr, stride, frame_stride, palettes_ptr, resize_ptr=None, thumb_ptr=None, wm_ptr=None, stream=None,
+                         resize_frame_stride=None, thumb_frame_stride=None, wm_frame_stride=None):
         """*image.Paletted frames resident in HBM: index bytes plus 256 x (R, G, B, A) per frame (ipx_plan_run_dev_paletted)"""
-        self._run(lib().ipx_plan_run_dev_paletted, (stream,), n, (index_ptr, stride, frame_stride, palettes_ptr), (resize_ptr, thumb_ptr, wm_ptr))
+        self._run(lib().ipx_plan_run_dev_paletted, (stream,), n, (index_ptr, stride, frame_stride, palettes_ptr), (resize_ptr, thumb_ptr, wm_ptr),
+                  (resize_frame_stride, thumb_frame_stride, wm_frame_stride))
 
     def run_dev_ycbcr(self, n, y_ptr, cb_ptr, cr_ptr, ratio, ystride, cstride, y_frame_stride, c_frame_stride,
-                      resize_ptr=None, thumb_ptr=None, wm_ptr=None, stream=None):
+                      resize_ptr=None, thumb_ptr=None, wm_ptr=None, stream=None,
+                      resize_frame_stride=None, thumb_frame_stride=None, wm_frame_stride=None):
         b = _lib.YCbCrBatch(y_ptr, cb_ptr, cr_ptr, ystride, cstride, y_frame_stride, c_frame_stride, int(ratio))
-        self._run(lib().ipx_plan_run_dev_ycbcr, (stream,), n, (C.byref(b),), (resize_ptr, thumb_ptr, wm_ptr))
+        self._run(lib().ipx_plan_run_dev_ycbcr, (stream,), n, (C.byref(b),), (resize_ptr, thumb_ptr, wm_ptr),
+                  (resize_frame_stride, thumb_frame_stride, wm_frame_stride))
 
     def run_host_ycbcr(self, y, cb, cr, ratio, want=("resize", "thumbnail", "watermark")):
         """A batch of decoded JPEG frames: y n x H x W, cb / cr n x CH x CW uint8 (image.YCbCr planes)."""
@@ -444,92 +477,110 @@ class Context:
     def plan(self, sw, sh, **kw):
         return Plan(self, sw, sh, **kw)
 
+    # ---- per-operation seam on frames in HBM (asynchronous on `stream`; null: the context's) ----------
+    def dev_scale_bilinear(self, dst_ptr, dw, dh, dstride, dr, src_ptr, sw, sh, sstride, sr, op=OP_OVER, stream=None):
+        """xdraw.BiLinear.Scale on RGBA8 frames resident in HBM (ipx_dev_scale_bilinear_rgba8)"""
+        _check(lib().ipx_dev_scale_bilinear_rgba8(self.handle, stream, dst_ptr, dw, dh, dstride, _rect(dr), src_ptr, sw, sh, sstride,
+                                                  _rect(sr), op))
+
+    def dev_draw(self, dst_ptr, dw, dh, dstride, r, src_ptr, sw, sh, sstride, sp=(0, 0), op=OP_SRC, stream=None):
+        """draw.Draw on RGBA8 frames resident in HBM (ipx_dev_draw_rgba8)"""
+        _check(lib().ipx_dev_draw_rgba8(self.handle, stream, dst_ptr, dw, dh, dstride, _rect(r), src_ptr, sw, sh, sstride,
+                                        int(sp[0]), int(sp[1]), op))
+
+    def dev_composite_glyphs(self, dst_ptr, dw, dh, dstride, glyphset, stream=None):
+        """the text of a GlyphSet onto one RGBA8 frame resident in HBM (ipx_dev_composite_glyphs_rgba8)"""
+        _check(lib().ipx_dev_composite_glyphs_rgba8(self.handle, stream, dst_ptr, dw, dh, dstride, glyphset.handle))
+
     # ---- per-operation seam on host arrays (synchronous) ----------------------------------------
     def scale_bilinear(self, src, dw, dh, sr=None, dr=None, op=OP_OVER, dst=None):
         """xdraw.BiLinear.Scale(dst, dr, src, sr, op, nil); dst defaults to a zeroed frame."""
-        src = _frame(src)
+        src, sstride = _frame(src)
         sh, sw = src.shape[:2]
         if dst is None:
             dst = np.zeros((dh, dw, 4), np.uint8)
-        assert dst.dtype == np.uint8 and dst.flags.c_contiguous and dst.shape == (dh, dw, 4)
+        dstride = _dst(dst, (dh, dw, 4))
         _check(lib().ipx_scale_bilinear_rgba8(
-            self.handle, dst.ctypes.data, dw, dh, dw * 4, _rect(dr if dr is not None else (0, 0, dw, dh)),
-            src.ctypes.data, sw, sh, sw * 4, _rect(sr if sr is not None else (0, 0, sw, sh)), op))
+            self.handle, dst.ctypes.data, dw, dh, dstride, _rect(dr if dr is not None else (0, 0, dw, dh)),
+            src.ctypes.data, sw, sh, sstride, _rect(sr if sr is not None else (0, 0, sw, sh)), op))
         return dst
 
     def draw(self, dst, r, src, sp=(0, 0), op=OP_SRC):
-        src = _frame(src)
-        assert dst.dtype == np.uint8 and dst.flags.c_contiguous
+        src, sstride = _frame(src)
+        dstride = _dst(dst)
         dh, dw = dst.shape[:2]
         sh, sw = src.shape[:2]
-        _check(lib().ipx_draw_rgba8(self.handle, dst.ctypes.data, dw, dh, dw * 4, _rect(r),
-                                    src.ctypes.data, sw, sh, sw * 4, int(sp[0]), int(sp[1]), op))
+        _check(lib().ipx_draw_rgba8(self.handle, dst.ctypes.data, dw, dh, dstride, _rect(r),
+                                    src.ctypes.data, sw, sh, sstride, int(sp[0]), int(sp[1]), op))
         return dst
 
     # ---- the deep source types: Go's Pix rows (H x W*bpp uint8) of *image.NRGBA64 / RGBA64 / Gray16 / CMYK frames ----------
     def scale_bilinear_deep(self, pix, kind, dw, dh, sr=None, dr=None, op=OP_OVER, dst=None):
-        pix = np.ascontiguousarray(pix, np.uint8)
+        pix, pstride = _rows(pix)
         sh, row = pix.shape
         sw = row // {DEEP_GRAY16: 2, DEEP_CMYK: 4}.get(kind, 8)
         if dst is None:
             dst = np.zeros((dh, dw, 4), np.uint8)
-        assert dst.dtype == np.uint8 and dst.flags.c_contiguous and dst.shape == (dh, dw, 4)
-        _check(lib().ipx_scale_bilinear_deep(self.handle, dst.ctypes.data, dw, dh, dw * 4, _rect(dr if dr is not None else (0, 0, dw, dh)),
-                                             pix.ctypes.data, sw, sh, row, kind, _rect(sr if sr is not None else (0, 0, sw, sh)), op))
+        dstride = _dst(dst, (dh, dw, 4))
+        _check(lib().ipx_scale_bilinear_deep(self.handle, dst.ctypes.data, dw, dh, dstride, _rect(dr if dr is not None else (0, 0, dw, dh)),
+                                             pix.ctypes.data, sw, sh, pstride, kind, _rect(sr if sr is not None else (0, 0, sw, sh)), op))
         return dst
 
     def draw_deep(self, dst, r, pix, kind, sp=(0, 0), op=OP_SRC):
-        pix = np.ascontiguousarray(pix, np.uint8)
-        assert dst.dtype == np.uint8 and dst.flags.c_contiguous
+        pix, pstride = _rows(pix)
+        dstride = _dst(dst)
         dh, dw = dst.shape[:2]
         sh, row = pix.shape
         sw = row // {DEEP_GRAY16: 2, DEEP_CMYK: 4}.get(kind, 8)
-        _check(lib().ipx_draw_deep(self.handle, dst.ctypes.data, dw, dh, dw * 4, _rect(r), pix.ctypes.data, sw, sh, row, kind,
+        _check(lib().ipx_draw_deep(self.handle, dst.ctypes.data, dw, dh, dstride, _rect(r), pix.ctypes.data, sw, sh, pstride, kind,
                                    int(sp[0]), int(sp[1]), op))
         return dst
 
     # ---- source-type variants: *image.NRGBA and *image.YCbCr sources (SURVEY.md 8(f) N2) -------------
     def scale_bilinear_nrgba(self, src, dw, dh, sr=None, dr=None, op=OP_OVER, dst=None):
-        src = _frame(src)
+        src, sstride = _frame(src)
         sh, sw = src.shape[:2]
         if dst is None:
             dst = np.zeros((dh, dw, 4), np.uint8)
-        assert dst.dtype == np.uint8 and dst.flags.c_contiguous and dst.shape == (dh, dw, 4)
+        dstride = _dst(dst, (dh, dw, 4))
         _check(lib().ipx_scale_bilinear_nrgba8(
-            self.handle, dst.ctypes.data, dw, dh, dw * 4, _rect(dr if dr is not None else (0, 0, dw, dh)),
-            src.ctypes.data, sw, sh, sw * 4, _rect(sr if sr is not None else (0, 0, sw, sh)), op))
+            self.handle, dst.ctypes.data, dw, dh, dstride, _rect(dr if dr is not None else (0, 0, dw, dh)),
+            src.ctypes.data, sw, sh, sstride, _rect(sr if sr is not None else (0, 0, sw, sh)), op))
         return dst
 
     def draw_nrgba(self, dst, r, src, sp=(0, 0), op=OP_SRC):
-        src = _frame(src)
-        assert dst.dtype == np.uint8 and dst.flags.c_contiguous
+        src, sstride = _frame(src)
+        dstride = _dst(dst)
         dh, dw = dst.shape[:2]
         sh, sw = src.shape[:2]
-        _check(lib().ipx_draw_nrgba8(self.handle, dst.ctypes.data, dw, dh, dw * 4, _rect(r), src.ctypes.data, sw, sh,
-                                     sw * 4, int(sp[0]), int(sp[1]), op))
+        _check(lib().ipx_draw_nrgba8(self.handle, dst.ctypes.data, dw, dh, dstride, _rect(r), src.ctypes.data, sw, sh,
+                                     sstride, int(sp[0]), int(sp[1]), op))
         return dst
 
     @staticmethod
     def _ycbcr(y, cb, cr, ratio):
-        y, cb, cr = (np.ascontiguousarray(a, dtype=np.uint8) for a in (y, cb, cr))
+        (y, ystride), (cb, cstride), (cr, rstride) = (_rows(a) for a in (y, cb, cr))
+        if rstride != cstride:          # (one stride serves both chroma planes)
+            cb, cr = np.ascontiguousarray(cb), np.ascontiguousarray(cr)
+            cstride = cb.shape[1]
         h, w = y.shape
-        return _lib.YCbCr(y.ctypes.data, cb.ctypes.data, cr.ctypes.data, w, cb.shape[1], w, h, int(ratio)), (y, cb, cr)
+        return _lib.YCbCr(y.ctypes.data, cb.ctypes.data, cr.ctypes.data, ystride, cstride, w, h, int(ratio)), (y, cb, cr)
 
     def scale_bilinear_ycbcr(self, y, cb, cr, ratio, dw, dh, sr=None, dr=None, dst=None):
         st, keep = self._ycbcr(y, cb, cr, ratio)
         if dst is None:
             dst = np.zeros((dh, dw, 4), np.uint8)
-        assert dst.dtype == np.uint8 and dst.flags.c_contiguous and dst.shape == (dh, dw, 4)
-        _check(lib().ipx_scale_bilinear_ycbcr(self.handle, dst.ctypes.data, dw, dh, dw * 4,
+        dstride = _dst(dst, (dh, dw, 4))
+        _check(lib().ipx_scale_bilinear_ycbcr(self.handle, dst.ctypes.data, dw, dh, dstride,
                                               _rect(dr if dr is not None else (0, 0, dw, dh)), C.byref(st),
                                               _rect(sr if sr is not None else (0, 0, st.w, st.h))))
         return dst
 
     def draw_ycbcr(self, dst, r, y, cb, cr, ratio, sp=(0, 0)):
         st, keep = self._ycbcr(y, cb, cr, ratio)
-        assert dst.dtype == np.uint8 and dst.flags.c_contiguous
+        dstride = _dst(dst)
         dh, dw = dst.shape[:2]
-        _check(lib().ipx_draw_ycbcr(self.handle, dst.ctypes.data, dw, dh, dw * 4, _rect(r), C.byref(st), int(sp[0]),
+        _check(lib().ipx_draw_ycbcr(self.handle, dst.ctypes.data, dw, dh, dstride, _rect(r), C.byref(st), int(sp[0]),
                                     int(sp[1])))
         return dst
 
@@ -711,11 +762,11 @@ class Context:
         return info, st
 
     def composite_glyphs(self, dst, glyphs, col):
-        assert dst.dtype == np.uint8 and dst.flags.c_contiguous
+        dstride = _dst(dst)
         dh, dw = dst.shape[:2]
         arr, keep = _glyph_array(list(glyphs))
         c = (C.c_uint8 * 4)(*[int(v) for v in col])
-        _check(lib().ipx_composite_glyphs_rgba8(self.handle, dst.ctypes.data, dw, dh, dw * 4, arr,
+        _check(lib().ipx_composite_glyphs_rgba8(self.handle, dst.ctypes.data, dw, dh, dstride, arr,
                                                 len(glyphs), c))
         return dst
 

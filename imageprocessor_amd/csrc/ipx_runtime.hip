@@ -618,6 +618,7 @@ int ipx_dev_scale_bilinear_rgba8(ipx_ctx *ctx, void *stream, uint8_t *dst, int d
 {
     IPX_ENTER(ctx);
     IPX_FRAME("ipx_dev_scale_bilinear_rgba8", "destination", dst, dw, dh, dstride);
+    IPX_DEV_OUT("ipx_dev_scale_bilinear_rgba8", "destination", dst, (unsigned)dstride);
     IPX_FRAME("ipx_dev_scale_bilinear_rgba8", "source", src, sw, sh, sstride);
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     AsyncFree mem{s, {}};
@@ -633,6 +634,7 @@ int ipx_dev_draw_rgba8(ipx_ctx *ctx, void *stream, uint8_t *dst, int dw, int dh,
 {
     IPX_ENTER(ctx);
     IPX_FRAME("ipx_dev_draw_rgba8", "destination", dst, dw, dh, dstride);
+    IPX_DEV_OUT("ipx_dev_draw_rgba8", "destination", dst, (unsigned)dstride);
     IPX_FRAME("ipx_dev_draw_rgba8", "source", src, sw, sh, sstride);
     return dev_draw(stream ? (hipStream_t)stream : ctx->stream, dst, dw, dh, dstride, to_rect(r), src,
                     sw, sh, sstride, spx, spy, op);
@@ -694,6 +696,7 @@ int ipx_dev_composite_glyphs_rgba8(ipx_ctx *ctx, void *stream, uint8_t *dst, int
     IPX_ENTER(ctx);
     if (!gs) { set_error("ipx_dev_composite_glyphs_rgba8: bad argument"); return IPX_ERR_INVALID; }
     IPX_FRAME("ipx_dev_composite_glyphs_rgba8", "destination", dst, dw, dh, dstride);
+    IPX_DEV_OUT("ipx_dev_composite_glyphs_rgba8", "destination", dst, (unsigned)dstride);
     return dev_composite(stream ? (hipStream_t)stream : ctx->stream, dst, dw, dh, dstride, 0, 1, gs);
 }
 IPX_CATCH_STATUS
@@ -1423,7 +1426,11 @@ static int run_dev_entry(const char *who, ipx_ctx *ctx, void *stream, const ipx_
                          size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out, size_t wm_frame_stride)
 {
     const int rc = src_check(who, pl, b, n, true);
-    if (rc || n == 0) return rc;
+    if (rc) return rc;
+    IPX_DEV_OUT(who, "resize", resize_out, 0, resize_frame_stride);
+    IPX_DEV_OUT(who, "thumbnail", thumb_out, 0, thumb_frame_stride);
+    IPX_DEV_OUT(who, "watermark", wm_out, 0, wm_frame_stride);
+    if (n == 0) return rc;
     return run_dev_src(ctx, stream ? (hipStream_t)stream : ctx->stream, pl, n, b, resize_out, resize_frame_stride, thumb_out, thumb_frame_stride,
                        wm_out, wm_frame_stride);
 }
@@ -1513,7 +1520,7 @@ static int run_host_packed(const char *who, ipx_ctx *ctx, const ipx_plan *pl, in
     auto d2h = [&](uint8_t *host, size_t host_stride, const uint8_t *dev, size_t dev_stride, size_t bytes, int i0, int m,
                    hipStream_t st) {
         if (!dev || !bytes) return hipSuccess;
-        if (host_stride == dev_stride)  // tight on both sides: the chunk as one run of bytes
+        if (host_stride == dev_stride && (bytes == dev_stride || m == 1))  // tight on both sides: the chunk as one run of bytes (equal strides with a gap: the gap is the caller's)
             return copy_pieces(host + (size_t)i0 * host_stride, dev, dev_stride * (m - 1) + bytes, hipMemcpyDeviceToHost, st);
         hipError_t r = hipSuccess;
         for (int i = 0; i < m && r == hipSuccess; i++)
@@ -1531,6 +1538,7 @@ static int run_host_packed(const char *who, ipx_ctx *ctx, const ipx_plan *pl, in
     if (direct && resize_out) direct = (vres = pinned_device_view(resize_out, resize_frame_stride * (n - 1) + pl->info.resize_bytes)) != nullptr;
     if (direct && thumb_out) direct = (vth = pinned_device_view(thumb_out, thumb_frame_stride * (n - 1) + pl->info.thumb_bytes)) != nullptr;
     if (direct && wm_out) direct = (vwm = pinned_device_view(wm_out, wm_frame_stride * (n - 1) + pl->info.wm_bytes)) != nullptr;
+    if (getenv("IPX_KS_DEBUG")) fprintf(stderr, "[ipx host] outputs %s\n", direct ? "stored by the kernels" : "copied from scratch");
     const size_t S = lanes.size();
     const hipStream_t s_up = lanes[0]->stream, s_down = lanes[S > 1 ? 1 : 0]->stream, s_run = lanes[S > 2 ? 2 : 0]->stream;
     const bool staged = S > 1 && env_int("IPX_HOST_STAGED", 1) != 0;

@@ -201,6 +201,18 @@ inline int frame_status(const char *who, const char *what, const void *p, int w,
 }
 #define IPX_FRAME(who, what, p, w, h, stride) do { const int rc_ = frame_status(who, what, p, w, h, stride); if (rc_) return rc_; } while (0)
 
+// A frame the kernels WRITE in HBM: every store is a whole pixel (a dword; the one-pass kernel's watermark copy: four) at its natural
+// alignment, so the frame's address, row stride and frame stride are multiples of 4.  Anything else is refused before a launch.
+inline int dev_out_status(const char *who, const char *what, const void *p, unsigned long long stride, unsigned long long frame_stride = 0)
+{
+    if (p && (((uintptr_t)p | stride | frame_stride) & 3)) {
+        set_error("%s: the %s frames' address and strides must be multiples of 4", who, what);
+        return IPX_ERR_INVALID;
+    }
+    return IPX_OK;
+}
+#define IPX_DEV_OUT(who, what, p, ...) do { const int rc_ = dev_out_status(who, what, p, __VA_ARGS__); if (rc_) return rc_; } while (0)
+
 // The body of a worker thread: an exception must not leave the thread (std::terminate would take the Go / Python worker down);
 // it becomes the status and text the spawning call reports.
 template <class F> inline int guarded_status(F &&fn, std::string *text) noexcept

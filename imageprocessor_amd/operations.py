@@ -50,7 +50,7 @@ def _params(d):
 
 
 def _image(a):
-    a = _frame(a)
+    a = np.ascontiguousarray(_frame(a)[0])
     return Image(a.ctypes.data, a.shape[1], a.shape[0], a.shape[1] * 4), a
 
 

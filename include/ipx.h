@@ -174,7 +174,18 @@ int ipx_draw_ycbcr(ipx_ctx *ctx, uint8_t *dst, int dw, int dh, int dstride, ipx_
                    const ipx_ycbcr *src, int spx, int spy);
 
 /* ---- same operations on frames already resident in HBM, asynchronous on `stream` -------------
- * `stream` is a hipStream_t (NULL = the context's own stream).  Pointers are device pointers. */
+ * `stream` is a hipStream_t (NULL = the context's own stream).  Pointers are device pointers.
+ *
+ * Layout.  Row strides may exceed the rows, and a frame may be a window of a larger one (dst / src point at the window's first pixel).
+ *   dst, dstride   REQUIRED multiples of 4: the kernels store whole pixels at their natural alignment.  Anything else is
+ *                  IPX_ERR_INVALID, decided on the host before any launch; nothing is written.
+ *   src, sstride   any value.  When dst, dstride, src and sstride are all multiples of 16 and the width drawn is a multiple of 4,
+ *                  ipx_dev_draw_rgba8 with IPX_OP_SRC copies 16 bytes per lane; everything else, including a source off a 4-byte
+ *                  boundary, is read a pixel at a time: the same bytes, slower.  (Each pixel is then one dword load from an
+ *                  address that is no multiple of 4: this rests on the device serving unaligned global dword loads, which
+ *                  tests/test_layouts_gpu.py pins by the bytes.  A load can only return wrong bytes, which a test sees; a store
+ *                  could write outside the frame, which is why destinations are refused instead.)
+ * Bytes of the destination outside the rectangle drawn into, padding included, are never written. */
 
 int ipx_dev_scale_bilinear_rgba8(ipx_ctx *ctx, void *stream, uint8_t *dst, int dw, int dh,
                                  int dstride, ipx_rect dr, const uint8_t *src, int sw, int sh,
@@ -220,7 +231,30 @@ int ipx_plan_query(const ipx_plan *plan, ipx_plan_info *info);
 
 /* n frames resident in HBM at src + i*src_frame_stride (row stride sstride); outputs tightly
  * packed rows at out + i*out_frame_stride.  An output pointer may be NULL to skip it even when
- * the plan has the operator.  Asynchronous on `stream`. */
+ * the plan has the operator.  Asynchronous on `stream`.
+ *
+ * Layout of the ipx_plan_run_dev* entries (tests/test_layouts_gpu.py holds every line):
+ *   outputs        each output pointer and its frame stride are REQUIRED multiples of 4 (rows are tight, so every row then is): the
+ *                  kernels store whole pixels -- the one-pass kernel four at a time into the watermark frames -- through buffer
+ *                  descriptors built at that address.  Anything else is IPX_ERR_INVALID, decided on the host before any launch;
+ *                  nothing is written.  No more than 4 is needed: frame strides larger than the frames, and frames at 4, 8 or 12
+ *                  bytes past a 16-byte boundary, run on the same kernels, and no byte between or around the frames is written.
+ *   RGBA8, NRGBA8  src, sstride and src_frame_stride multiples of 4: the one-pass kernel (ks_fused_kernel), any width (rows whose
+ *                  width is no multiple of 4 have a variant of their own).  Otherwise the batch is served by one kernel per
+ *                  output, which reads a pixel at a time (an unaligned dword load each, as for the ipx_dev_* sources above): the
+ *                  same bytes, slower.
+ *   Gray, Y        pointer, row stride and frame stride multiples of 4 AND a width that is a multiple of 4: the one-pass kernel;
+ *                  otherwise one kernel per output (byte loads), slower.
+ *   Cb, Cr         as Y, but multiples of 2 are enough for 4:2:2 and 4:2:0 (4:4:4 and 4:4:0: 4).
+ *   index planes   any layout; multiples of 4 (and a width that is one) take the expansion's vector path.  The expanded frames are
+ *                  the library's own, so the one-pass kernel runs whatever the index planes' layout.
+ *   palettes       REQUIRED 4-byte aligned (IPX_ERR_INVALID otherwise).
+ *   deep types     src, sstride and src_frame_stride REQUIRED multiples of 2 (CMYK: 4), IPX_ERR_INVALID otherwise; the expanded taps
+ *                  are the library's own: the one-pass kernel when the width is a multiple of 4, one kernel per output otherwise.
+ * A plan whose resize enlarges by more than about two (a source row feeding more than four output rows) has no one-pass kernel at all.
+ * The host variants (ipx_plan_run_host*) take any layout of sources and outputs: frames are copied row by row where they are not
+ * tight; pinned outputs whose pointers and frame strides are all multiples of 16 are stored by the kernels directly, others are
+ * copied a frame at a time, and bytes between the frames are never written either way. */
 int ipx_plan_run_dev(ipx_ctx *ctx, void *stream, const ipx_plan *plan, int n, const uint8_t *src,
                      int sstride, size_t src_frame_stride, uint8_t *resize_out,
                      size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride,
@@ -250,8 +284,9 @@ int ipx_plan_run_dev_ycbcr(ipx_ctx *ctx, void *stream, const ipx_plan *plan, int
                            size_t thumb_frame_stride, uint8_t *wm_out, size_t wm_frame_stride);
 /* A batch of *image.NRGBA frames (PNGs with alpha): like the YCbCr batch, per operator as the reference's helpers treat the
  * type -- resize and the non-crop thumbnail weight 16-bit premultiplied taps (scaleX_NRGBA), the crop thumbnail scales its 8-bit
- * crop copy and the watermark premultiplies to RGBA8 (drawNRGBASrc).  One pass (ks_fused_kernel) for
- * 16-byte aligned frames whose width is a multiple of 4, three kernels otherwise; the same bytes either way. */
+ * crop copy and the watermark premultiplies to RGBA8 (drawNRGBASrc).  One pass (ks_fused_kernel) for frames whose pointer, row stride
+ * and frame stride are multiples of 4 -- at any width: rows that are no multiple of 4 pixels wide have a variant of the kernel --,
+ * one kernel per output otherwise; the same bytes either way (the layout rules above ipx_plan_run_dev). */
 int ipx_plan_run_dev_nrgba(ipx_ctx *ctx, void *stream, const ipx_plan *plan, int n, const uint8_t *src, int sstride,
                            size_t src_frame_stride, uint8_t *resize_out, size_t resize_frame_stride, uint8_t *thumb_out,
                            size_t thumb_frame_stride, uint8_t *wm_out, size_t wm_frame_stride);

@@ -6,6 +6,8 @@ CPU, tests/test_jpeg_reference_gpu.py on the GPU).  Everything is built from see
 test_jpeg_reference.py::test_stream_length_edges_are_present asserts every property on the committed list."""
 import numpy as np
 
+from layout_cases import lay_out  # noqa: F401  (n x H x W x 4 -> (allocation, offset, stride, frame stride); the padding is 0xA5)
+
 KINDS = ["noise", "binary", "smooth", "photo", "checker", "translucent", "edge"]
 EXTRA_KINDS = ["flat", "basis"]
 
@@ -81,19 +83,6 @@ LAYOUTS = [("stride 4w+4", 4, 0, 0), ("stride 4w+12", 12, 0, 0), ("stride 4w+16"
 # (w, h, n): whole workgroups (128 x 16 pixels) that take the aligned 16-byte loads when the layout allows, next to partial ones; the
 # widths are multiples of 4, so that the tightly packed call itself is the aligned one (stride and frame stride multiples of 16)
 LAYOUT_SHAPES = [(128, 16, 3), (260, 33, 2), (144, 17, 2), (132, 48, 1), (512, 64, 2)]
-
-
-def lay_out(frames, extra_stride, extra_frame, offset):
-    """n x H x W x 4 -> (bytes of the allocation, offset of frame 0, stride, frame stride); the padding is filled with 0xA5 so that a
-    kernel reading it would show"""
-    n, h, w, _ = frames.shape
-    stride = 4 * w + extra_stride
-    fs = h * stride + extra_frame
-    buf = np.full(offset + n * fs + 64, 0xA5, np.uint8)
-    for i in range(n):
-        rows = np.lib.stride_tricks.as_strided(buf[offset + i * fs:], (h, 4 * w), (stride, 1))
-        rows[...] = frames[i].reshape(h, 4 * w)
-    return buf, offset, stride, fs
 
 
 # ---- stream-length edges ----------------------------------------------------------------------------------------------------
