@@ -210,3 +210,36 @@ func (p *Plan) RunJPEGJPEG(files [][]byte, quality int) (*Streams, error) {
 	}
 	return s, nil
 }
+
+// JPEGRoute is the decoder a JPEG file's scans reach.
+type JPEGRoute int
+
+const (
+	JPEGRoutePar       JPEGRoute = C.IPX_JPEG_ROUTE_PAR        // one baseline scan: the parallel Huffman kernels
+	JPEGRouteHostScans JPEGRoute = C.IPX_JPEG_ROUTE_HOST_SCANS // progressive, multi-scan: the library's host threads
+	JPEGRouteGPUScans  JPEGRoute = C.IPX_JPEG_ROUTE_GPU_SCANS  // progressive with a clean marker pre-pass, under IPX_JPEG_PROG_GPU=1
+)
+
+// JPEGScanRoute reports the route file would take now (the environment switch is read); host only, needs no Context.  The error is the
+// marker parser's verdict on the file.
+func JPEGScanRoute(file []byte) (JPEGRoute, error) {
+	if len(file) == 0 {
+		return JPEGRoutePar, &Error{Status: Invalid, Text: "empty file"}
+	}
+	var route C.int
+	err := call(func() C.int {
+		return C.ipx_jpeg_scan_route((*C.uint8_t)(unsafe.Pointer(&file[0])), C.size_t(len(file)), &route)
+	})
+	return JPEGRoute(route), err
+}
+
+// JPEGDecodeCounts: since the Context was made, the files that reached the decoder of each JPEGRoute, and in [3] the files the GPU scan
+// walk ended with a status other than OK.
+func (x *Context) JPEGDecodeCounts() (counts [4]int64, err error) {
+	var c [4]C.longlong
+	err = call(func() C.int { return C.ipx_jpeg_decode_counts(x.c, &c[0]) })
+	for i := range c {
+		counts[i] = int64(c[i])
+	}
+	return counts, err
+}

@@ -702,6 +702,24 @@ class Context:
             info.update(batch=b, free=lambda: lib().ipx_jpeg_planes_free(self.handle, owner))
         return info, st
 
+    JPEG_ROUTE_PAR, JPEG_ROUTE_HOST_SCANS, JPEG_ROUTE_GPU_SCANS = 0, 1, 2
+
+    @staticmethod
+    def jpeg_scan_route(data):
+        """Which decoder the scans of this JPEG would reach now (IPX_JPEG_PROG_GPU is read): -> (parse status, JPEG_ROUTE_*).  Host
+        only: needs no device."""
+        buf = bytes(data)
+        route = C.c_int(-1)
+        st = lib().ipx_jpeg_scan_route(buf, len(buf), C.byref(route))
+        return st, route.value
+
+    def jpeg_decode_counts(self):
+        """Since the context was made: files that reached the decoder of route [0..2], and [3] files the GPU scan walk ended with a
+        status other than IPX_OK."""
+        counts = (C.c_longlong * 4)()
+        _check(lib().ipx_jpeg_decode_counts(self.handle, counts))
+        return list(counts)
+
     def gif_decode_batch(self, files, w=0, h=0, download=True):
         """image.Decode of a batch of GIF byte strings on the GPU (the first image of each).  -> (info, status list); info = dict(w, h,
         stride, index, palettes) with index as n x h x w and palettes as n x 256 x 4 uint8 arrays (download=True), or the device

@@ -180,6 +180,8 @@ struct JpegDecInfo {
     int host_scans;            // 1: not one baseline scan the GPU's Huffman kernels take (progressive, several scans, table ids above 1):
                                // jpeg_host_decode walks the scans on the host, the coefficients go up, the GPU does the rest
     int progressive;           // SOF2 (reconstructProgressiveImage's rule for blocks outside the image applies)
+    int gpu_scans;             // host_scans files only, under IPX_JPEG_PROG_GPU=1: the marker pre-pass was clean (jpeg_prog_prepass), the
+                               // scans are walked by jpeg_prog_kernel instead of jpeg_host_decode
     uint8_t td[3], ta[3];      // kernel table slots of the three components: 0,1 = DC tables, 2,3 = AC tables
     size_t scan_off, scan_len; // entropy-coded data within the file
 };
@@ -248,19 +250,61 @@ hipError_t launch_par_dc(const JpegParArgs &a, hipStream_t s);
 int jpeg_parse(const uint8_t *d, size_t len, JpegDecInfo *info, JpegDecTables *tab);
 int jpeg_host_decode(const uint8_t *d, size_t len, JpegDecInfo *info, int16_t *coefs, int16_t *dcs, size_t nblk, uint16_t qnat[3][64],
                      bool *progressive);
+// ---- progressive scans walked on the GPU (IPX_JPEG_PROG_GPU=1): the scan program of a file (jpeg_prog_prepass in ipx_jpeg_dec_prog.cpp)
+// and the kernel that runs it (ipx_jpeg_dec_scans.hip) ----
+constexpr int IPX_JPEG_PROG_MAX_SCANS = 64;
+// one DHT definition in the device format: the 9-bit first level and the per-length bounds of the host decoder's Huff
+struct JpegProgHuff {
+    uint16_t look[512];                            // length << 8 | symbol, 0: no code of at most 9 bits
+    int32_t mincode[17], maxcode[17], valptr[17];  // by code length 1..16; maxcode -1: no code of that length
+    uint8_t vals[256];
+    int32_t ncodes;
+};
+static_assert(sizeof(JpegProgHuff) % 16 == 0, "copied to LDS in 16-byte units");
+struct JpegProgScan {
+    uint32_t off, len;           // the READABLE entropy data within the file: up to the first 0xff that 0x00 does not follow
+    uint8_t ns, ss, se, ah, al;
+    uint8_t comp[3];             // component index per slot
+    uint16_t dc_def[3], ac_def[3];   // the table definitions in effect (indices into the file's definitions, of which there are at most
+                                     // IPX_JPEG_PROG_MAX_SCANS * 3: one per table a scan decodes with); 0xffff: not used by this scan
+    uint32_t rsv;
+};
+struct JpegProgFile { unsigned long long blob_off; uint32_t img, nscans, scan0, def0; };   // scan0 / def0: first entry in the batch's arrays
+struct JpegProgPlan {            // what the pre-pass leaves for one file
+    std::vector<JpegProgScan> scans;
+    std::vector<JpegProgHuff> defs;
+};
+struct JpegProgArgs {
+    const uint8_t *blob; const JpegProgFile *files; const JpegProgScan *scans; const JpegProgHuff *defs;
+    int16_t *coefs, *dcs; int *status;
+    int nfiles, mxx, myy, h0, v0, nblk, w, h, bpm, ybl;
+};
+// the status word of a file whose walk met a coefficient that int16 truncates to zero: the host decoder's non-zero mask and the
+// coefficients disagree from there on, so the driver asks jpeg_host_decode for this (damaged) file's verdict
+constexpr uint32_t kJpegProgHostVerdict = 0x3fffffeu;
+// 1: SOF2, and Decoder::run's marker loop with the entropy data skipped reaches EOI with every SOS header valid, every table a scan
+// decodes with defined, no restart interval and at most IPX_JPEG_PROG_MAX_SCANS scans; then *plan and qnat (the FINAL tables) are filled
+bool jpeg_prog_prepass(const uint8_t *d, size_t len, const JpegDecInfo &info, JpegProgPlan *plan, uint16_t qnat[3][64]);
+hipError_t launch_jpeg_prog(const JpegProgArgs &a, hipStream_t s);
+int jpeg_prog_lds_bytes();
+
 // The host plan of a batch decode (jpeg_plan_batch in ipx_jpeg_dec_host.cpp; no device call): the files parsed, the batch's geometry
 // chosen, the baseline scans cut into pieces (grouped by table class) and parallel images, all placed in one blob.
 struct JpegPlanOptions {
     int want_w, want_h;        // the size asked for; want_w <= 0: the first parsed file's
     bool use_par;              // IPX_JPEG_PAR: long scans without restart markers go to the parallel decoder
     int forced_sub, max_sub;   // IPX_JPEG_PAR_SUB: 128 .. 1024 fixes the sub-sequence size, else the batch chooses; jpeg_par_sub_bytes()
+    bool prog_gpu = false;     // IPX_JPEG_PROG_GPU=1: progressive files with a clean pre-pass are walked on the GPU
 };
 struct JpegBatchPlan {
     std::vector<JpegDecInfo> info;
     std::vector<JpegDecTables> tabs;
     std::vector<uint8_t> valid;       // per file: bit 0 decodable (final only once the host-decoded files are through), bit 1 progressive
     std::vector<size_t> blob_off;     // where a GPU-decoded file's scan lies in the blob
-    std::vector<int> hslot;           // host-decoded files (info.host_scans) numbered in file order, -1 for the others
+    std::vector<int> hslot;           // host-decoded files (info.host_scans without gpu_scans) numbered in file order, -1 for the others
+    std::vector<int> gfiles;          // files whose scans jpeg_prog_kernel walks (info.gpu_scans), their whole bytes in the blob at blob_off
+    std::vector<JpegProgPlan> prog;   // per file; filled for gfiles only
+    std::vector<uint8_t> route;       // per file: the IPX_JPEG_ROUTE_* its decoder is reached by; 0xff: refused before (ipx_jpeg_decode_counts)
     std::vector<JpegDecImage> items;  // pieces by table class, every class but the last padded to whole groups of 64 (padding: valid == 0)
     std::vector<JpegParImage> par;
     int ref = -1, par_sub = 0, nhost = 0;   // ref: the file that sets the batch's geometry; -1: nothing decodable

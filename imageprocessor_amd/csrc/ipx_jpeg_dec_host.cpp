@@ -303,6 +303,7 @@ int jpeg_plan_batch(const ipx_bytes *files, int n, const JpegPlanOptions &opt, i
     JpegBatchPlan &P = *plan;
     P.info.resize(n); P.tabs.resize(n);
     P.valid.assign(n, 0); P.blob_off.assign(n, 0); P.hslot.assign(n, -1);
+    P.prog.resize(n); P.route.assign(n, 0xff);
     const auto t0 = std::chrono::steady_clock::now();
     // pieces of a scan: the whole scan, or one per restart interval
     std::vector<std::vector<uint32_t>> marks(n);
@@ -312,6 +313,10 @@ int jpeg_plan_batch(const ipx_bytes *files, int n, const JpegPlanOptions &opt, i
     const int rc = parallel_light(n, [&](int i) {
         status[i] = !files[i].data ? IPX_ERR_INVALID : (files[i].len >= ((size_t)1 << 30) ? IPX_ERR_UNSUPPORTED : jpeg_parse(files[i].data, files[i].len, &P.info[i], &P.tabs[i]));
         if (status[i] == IPX_OK && !P.info[i].host_scans) status[i] = find_restarts(files[i].data + P.info[i].scan_off, P.info[i], &marks[i]);
+        // a progressive file whose marker pre-pass is wholly clean has its scans walked by jpeg_prog_kernel (opt-in); every other one
+        // keeps the host route, which gives the verdict as before
+        if (status[i] == IPX_OK && opt.prog_gpu && P.info[i].progressive)
+            P.info[i].gpu_scans = jpeg_prog_prepass(files[i].data, files[i].len, P.info[i], &P.prog[i], P.tabs[i].qnat) ? 1 : 0;
     }, "jpeg decode: host preparation failed");
     P.parse_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (rc) return rc;
@@ -337,7 +342,16 @@ int jpeg_plan_batch(const ipx_bytes *files, int n, const JpegPlanOptions &opt, i
         }
         if (status[i] != IPX_OK) continue;
         // coefficients come from the host, straight into a pinned block in the IDCT kernel's layout (slot hslot[i]); bit 1: progressive
-        if (info[i].host_scans) { P.valid[i] = info[i].progressive ? 3 : 1; P.hslot[i] = P.nhost++; continue; }
+        P.route[i] = (uint8_t)(!info[i].host_scans ? IPX_JPEG_ROUTE_PAR : info[i].gpu_scans ? IPX_JPEG_ROUTE_GPU_SCANS : IPX_JPEG_ROUTE_HOST_SCANS);
+        if (info[i].host_scans && !info[i].gpu_scans) { P.valid[i] = info[i].progressive ? 3 : 1; P.hslot[i] = P.nhost++; continue; }
+        if (info[i].gpu_scans) {
+            // the file's bytes go into the blob whole (16-byte aligned: the kernel stages scan data with aligned 16-byte loads); no hslot
+            P.valid[i] = 3;
+            P.blob_off[i] = P.blob_bytes;
+            P.blob_bytes += (files[i].len + 15 + 16) & ~(size_t)15;
+            P.gfiles.push_back(i);
+            continue;
+        }
         const JpegDecInfo &I = info[i];
         const int nmcu = mcus_of(I);
         auto push = [&](size_t a0, size_t a1, int m0, int cnt) {

@@ -226,33 +226,102 @@ struct Decoder {
         }
     }
 
-    // processSOS: the header at s (sn bytes), the entropy-coded data from *pos on; *pos ends where the marker loop continues
-    void scan(const uint8_t *s, size_t sn, size_t *pos)
+    // the checks at the top of processSOS on the header at s (sn bytes); false: status is set
+    struct ScanHeader { int ns, ci[3], td[3], ta[3]; int32_t zs, ze; uint32_t ah, al; };
+    bool scan_header(const uint8_t *s, size_t sn, ScanHeader *H)
     {
-        if (!ncomp) return fail(IPX_ERR_INVALID);
-        if (sn < 6 || (size_t)(4 + 2 * ncomp) < sn || sn % 2) return fail(IPX_ERR_INVALID);
-        const int ns = s[0];
-        if (sn != (size_t)(4 + 2 * ns)) return fail(IPX_ERR_INVALID);
-        int ci[3] = {0, 0, 0}, td[3] = {0, 0, 0}, ta[3] = {0, 0, 0}, total_hv = 0;
+        if (!ncomp) return fail(IPX_ERR_INVALID), false;
+        if (sn < 6 || (size_t)(4 + 2 * ncomp) < sn || sn % 2) return fail(IPX_ERR_INVALID), false;
+        const int ns = H->ns = s[0];
+        if (sn != (size_t)(4 + 2 * ns)) return fail(IPX_ERR_INVALID), false;
+        int *ci = H->ci, *td = H->td, *ta = H->ta, total_hv = 0;
+        for (int i = 0; i < 3; i++) ci[i] = td[i] = ta[i] = 0;
         for (int i = 0; i < ns; i++) {
             int k = -1;
             for (int j = 0; j < ncomp; j++) if (s[1 + 2 * i] == cid[j]) k = j;
-            if (k < 0) return fail(IPX_ERR_INVALID);
-            for (int j = 0; j < i; j++) if (ci[j] == k) return fail(IPX_ERR_INVALID);
+            if (k < 0) return fail(IPX_ERR_INVALID), false;
+            for (int j = 0; j < i; j++) if (ci[j] == k) return fail(IPX_ERR_INVALID), false;
             ci[i] = k;
             total_hv += ch[k] * cv[k];
             td[i] = s[2 + 2 * i] >> 4; ta[i] = s[2 + 2 * i] & 15;
-            if (td[i] > 3 || ta[i] > 3 || (baseline && (td[i] > 1 || ta[i] > 1))) return fail(IPX_ERR_INVALID);
+            if (td[i] > 3 || ta[i] > 3 || (baseline && (td[i] > 1 || ta[i] > 1))) return fail(IPX_ERR_INVALID), false;
         }
-        if (ncomp > 1 && total_hv > 10) return fail(IPX_ERR_INVALID);
-        int32_t zs = 0, ze = 63;
-        uint32_t ah = 0, al = 0;
+        if (ncomp > 1 && total_hv > 10) return fail(IPX_ERR_INVALID), false;
+        H->zs = 0; H->ze = 63; H->ah = H->al = 0;
         if (progressive) {
-            zs = s[1 + 2 * ns]; ze = s[2 + 2 * ns]; ah = s[3 + 2 * ns] >> 4; al = s[3 + 2 * ns] & 15;
-            if ((zs == 0 && ze != 0) || zs > ze || ze >= 64) return fail(IPX_ERR_INVALID);
-            if (zs != 0 && ns != 1) return fail(IPX_ERR_INVALID);
-            if (ah != 0 && ah != al + 1) return fail(IPX_ERR_INVALID);
+            const int32_t zs = H->zs = s[1 + 2 * ns], ze = H->ze = s[2 + 2 * ns];
+            const uint32_t ah = H->ah = s[3 + 2 * ns] >> 4, al = H->al = s[3 + 2 * ns] & 15;
+            if ((zs == 0 && ze != 0) || zs > ze || ze >= 64) return fail(IPX_ERR_INVALID), false;
+            if (zs != 0 && ns != 1) return fail(IPX_ERR_INVALID), false;
+            if (ah != 0 && ah != al + 1) return fail(IPX_ERR_INVALID), false;
         }
+        return true;
+    }
+
+    // The marker pre-pass of the GPU scan walk (jpeg_prog_prepass): with `pre` set, run() is the same marker loop, but a scan's entropy
+    // data is not decoded.  *pos stays at the data's start: the marker loop skips forward from wherever the reader stopped to the first
+    // real marker, over data bytes, 0xff 0x00, fill bytes and stray RSTn alike -- and the reader (Bits::fill) never passes an 0xff that
+    // 0x00 does not follow, so from the data's start the loop arrives at the same segment as it does behind a decoded scan.
+    JpegProgPlan *pre = nullptr;
+    bool pre_clean = true;                // false: something the GPU walk does not take; the host route gives the verdict
+    // Table definitions are put into the device format only when a scan decodes with them, once per definition: a DHT that redefines
+    // an id only forgets the index (def_of = -1).  So a file holds at most three per scan, IPX_JPEG_PROG_MAX_SCANS * 3 in all,
+    // however many DHT segments it carries -- a file of a hundred thousand unused tables costs nothing here, as on the host route.
+    int def_of[2][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}};   // the materialised definition in effect per table class and id; -1: none yet
+    int use(int tc, int th)               // the index of the definition in effect, materialised now if it was not; -1: never defined
+    {
+        const Huff &h = hf[tc][th];
+        if (!h.ncodes) return -1;
+        if (def_of[tc][th] >= 0) return def_of[tc][th];
+        JpegProgHuff t;
+        memset(&t, 0, sizeof t);
+        memcpy(t.look, h.look, sizeof t.look);
+        for (int l = 1; l <= 16; l++) { t.mincode[l] = h.mincode[l]; t.maxcode[l] = h.maxcode[l]; t.valptr[l] = h.valptr[l]; }
+        t.maxcode[0] = -1;
+        memcpy(t.vals, h.vals, (size_t)h.ncodes);
+        t.ncodes = h.ncodes;
+        def_of[tc][th] = (int)pre->defs.size();
+        pre->defs.push_back(t);
+        return def_of[tc][th];
+    }
+    void prescan(const uint8_t *s, size_t sn, size_t pos)
+    {
+        ScanHeader H;
+        if (!scan_header(s, sn, &H)) return;
+        scans++;
+        if (!pre_clean || !progressive || ri != 0 || scans > IPX_JPEG_PROG_MAX_SCANS) { pre_clean = false; return; }
+        JpegProgScan P;
+        memset(&P, 0, sizeof P);
+        P.ns = (uint8_t)H.ns; P.ss = (uint8_t)H.zs; P.se = (uint8_t)H.ze; P.ah = (uint8_t)H.ah; P.al = (uint8_t)H.al;
+        for (int i = 0; i < 3; i++) {
+            P.comp[i] = (uint8_t)H.ci[i];
+            P.dc_def[i] = P.ac_def[i] = 0xffff;
+            if (i >= H.ns) continue;
+            // the tables Decoder::scan decodes with: DC in a first scan that starts at 0, AC in every scan of a band (a DC refinement
+            // scan reads plain bits)
+            if (H.zs == 0 && H.ah == 0) { const int k = use(0, H.td[i]); if (k < 0) { pre_clean = false; return; } P.dc_def[i] = (uint16_t)k; }
+            if (H.zs > 0) { const int k = use(1, H.ta[i]); if (k < 0) { pre_clean = false; return; } P.ac_def[i] = (uint16_t)k; }
+        }
+        size_t end = pos;                 // Bits::fill's end: the first 0xff that 0x00 does not follow, or the end of the file
+        while (end < len) {
+            const uint8_t *q = (const uint8_t *)memchr(d + end, 0xff, len - end);
+            if (!q) { end = len; break; }
+            end = (size_t)(q - d);
+            if (end + 1 >= len || d[end + 1] != 0) break;
+            end += 2;
+        }
+        P.off = (uint32_t)pos; P.len = (uint32_t)(end - pos);
+        pre->scans.push_back(P);
+    }
+
+    // processSOS: the header at s (sn bytes), the entropy-coded data from *pos on; *pos ends where the marker loop continues
+    void scan(const uint8_t *s, size_t sn, size_t *pos)
+    {
+        ScanHeader H;
+        if (!scan_header(s, sn, &H)) return;
+        const int ns = H.ns, *ci = H.ci, *td = H.td, *ta = H.ta;
+        const int32_t zs = H.zs, ze = H.ze;
+        const uint32_t ah = H.ah, al = H.al;
         if (!out_ready) {
             ybl = ch[0] * cv[0];
             bpm = ncomp == 1 ? 1 : ybl + 2;
@@ -414,6 +483,7 @@ struct Decoder {
                     for (int b = 0; b < 16; b++) total += s[k + 1 + b];
                     if (total == 0 || total > 256 || k + 17 + (size_t)total > sn) return fail(IPX_ERR_INVALID);
                     huff_build(hf[tc][th], s + k + 1, s + k + 17, total);
+                    if (pre) def_of[tc][th] = -1;          // redefined: materialised again if a scan decodes with it
                     k += 17 + (size_t)total;
                 }
                 break;
@@ -437,7 +507,7 @@ struct Decoder {
                 break;
             case 0xe0: if (sn >= 5 && !memcmp(s, "JFIF\0", 5)) jfif = true; break;
             case 0xee: if (sn >= 12 && !memcmp(s, "Adobe", 5)) { adobe = true; adobe_transform = s[11]; } break;
-            case 0xda: scan(s, sn, &pos); break;
+            case 0xda: if (pre) prescan(s, sn, pos); else scan(s, sn, &pos); break;
             default:
                 if ((m >= 0xe0 && m <= 0xef) || m == 0xfe) break;         // APPn, COM
                 return fail(m < 0xc0 ? IPX_ERR_INVALID : IPX_ERR_UNSUPPORTED);
@@ -478,6 +548,25 @@ int jpeg_host_decode(const uint8_t *d, size_t len, JpegDecInfo *info, int16_t *c
     for (int c = 0; c < 3; c++)
         for (int zig = 0; zig < 64; zig++) qnat[c][kUnzig[zig]] = c < D.ncomp ? D.quant[D.ctq[c]][zig] : 0;
     return IPX_OK;
+}
+
+// The marker pre-pass of a progressive file for the GPU scan walk (ipx_internal.h).  len < 2^30 (jpeg_plan_batch refuses larger files).
+bool jpeg_prog_prepass(const uint8_t *d, size_t len, const JpegDecInfo &info, JpegProgPlan *plan, uint16_t qnat[3][64])
+{
+    if (!info.progressive) return false;
+    Decoder D;
+    memset(D.quant, 0, sizeof D.quant);
+    memset(D.cid, 0, sizeof D.cid); memset(D.ch, 0, sizeof D.ch); memset(D.cv, 0, sizeof D.cv); memset(D.ctq, 0, sizeof D.ctq);
+    D.d = d; D.len = len;
+    plan->scans.clear(); plan->defs.clear();
+    D.pre = plan;
+    D.run();
+    if (D.status != IPX_OK || !D.pre_clean || !D.progressive) return false;
+    // the frame the header parser saw (both take the file's first SOF)
+    if (D.w != info.w || D.h != info.h || D.ch[0] != info.h0 || D.cv[0] != info.v0 || D.ncomp != info.ncomp) return false;
+    for (int c = 0; c < 3; c++)
+        for (int zig = 0; zig < 64; zig++) qnat[c][kUnzig[zig]] = c < D.ncomp ? D.quant[D.ctq[c]][zig] : 0;
+    return true;
 }
 
 }  // namespace ipx

@@ -1,6 +1,7 @@
 // ipx_jpeg_dec_runtime.hip -- the driver of image.Decode for JPEG batches: the host plan (ipx_jpeg_dec_host.cpp), then the device
-// blocks, the upload, the Huffman passes and the reconstruction as stages of jpeg_decode_files.  Kernels: ipx_jpeg_dec.hip,
-// ipx_jpeg_dec_par.hip; the host scan decoder of progressive files: ipx_jpeg_dec_prog.cpp.
+// blocks, the upload, the scan walk of progressive files (opt-in), the Huffman passes and the reconstruction as stages of
+// jpeg_decode_files.  Kernels: ipx_jpeg_dec.hip, ipx_jpeg_dec_par.hip, ipx_jpeg_dec_scans.hip; the host scan decoder of progressive
+// files, and the marker pre-pass of the GPU scan walk: ipx_jpeg_dec_prog.cpp.
 #include <chrono>
 
 #include "ipx_decode_common.h"
@@ -25,6 +26,7 @@ struct DecRun {
     double t_alloc = 0, t_pin = 0, t_pack = 0, t_launch = 0;
     JpegBatchPlan plan;
     std::vector<int> dev_status;
+    std::vector<uint8_t> prog_block;   // the scan programs of the GPU-walked files as uploaded (dec_scans)
     JpegDecArgs a{};
     JpegPlanes pl{};
     uint8_t *d_blob = nullptr, *d_valid = nullptr; JpegDecImage *d_img = nullptr; JpegDecTables *d_tab = nullptr;
@@ -57,9 +59,11 @@ int dec_blocks(DecRun &r, Lane *lane, bool planes_in_lane, OwnedBlocks<ipx_jpeg_
         size_t subs = 0;
         for (auto &pi : P.par) subs = std::max(subs, (size_t)pi.nsub);
         subs *= P.par.size();
+        size_t prog_bytes = 0;                   // the scan programs as dec_scans uploads them
+        for (int i : P.gfiles) prog_bytes += sizeof(JpegProgFile) + P.prog[i].scans.size() * sizeof(JpegProgScan) + P.prog[i].defs.size() * sizeof(JpegProgHuff) + 64;
         const size_t est = (pl.y_fs + 2 * pl.c_fs) * n + (size_t)n * a.nblk * 130 + 3 * (P.blob_bytes + 1024) + P.piece_ubytes +
                            P.items.size() * (sizeof(JpegDecImage) + 8) + (size_t)n * (sizeof(JpegDecTables) + 64) + P.par.size() * (sizeof(JpegParImage) + 64) +
-                           subs * 96 + ((size_t)4 << 20);
+                           subs * 96 + ((size_t)4 << 20) + prog_bytes;
         const int rr = lane_reserve_dec(*lane, est);
         if (rr) return rr;
         r.mem.arena = lane->dec; r.mem.cap = lane->dec_bytes;
@@ -112,7 +116,10 @@ int dec_upload(DecRun &r)
     }
     r.t_pin = r.ms();
     // packing the scans walks every compressed byte
-    int rc = parallel_light(n, [&](int i) { if (P.valid[i] && !P.info[i].host_scans) memcpy(hblob + P.blob_off[i], r.jpegs[i].data + P.info[i].scan_off, P.info[i].scan_len); }, kPrep);
+    int rc = parallel_light(n, [&](int i) {
+        if (P.valid[i] && !P.info[i].host_scans) memcpy(hblob + P.blob_off[i], r.jpegs[i].data + P.info[i].scan_off, P.info[i].scan_len);
+        if (P.valid[i] && P.info[i].gpu_scans) memcpy(hblob + P.blob_off[i], r.jpegs[i].data, r.jpegs[i].len);   // the whole file: its scans lie between its segments
+    }, kPrep);
     if (rc) return rc;
     r.t_pack = r.ms();
     DEC_HIP("jpeg decode", hipMemcpyAsync(r.d_blob, hblob, P.blob_bytes, hipMemcpyHostToDevice, s));
@@ -147,6 +154,42 @@ int dec_upload(DecRun &r)
     // quantisation tables of its files)
     DEC_HIP("jpeg decode", hipMemcpyAsync(r.d_valid, P.valid.data(), (size_t)n, hipMemcpyHostToDevice, s));
     DEC_HIP("jpeg decode", hipMemcpyAsync(r.d_tab, P.tabs.data(), sizeof(JpegDecTables) * n, hipMemcpyHostToDevice, s));
+    return IPX_OK;
+}
+
+// Stage 3b: the progressive files whose scans the GPU walks (IPX_JPEG_PROG_GPU=1, a clean marker pre-pass): their programs -- files,
+// scans, table definitions -- go up in one block, one wave per file walks the scans in file order into the coefficient slots that
+// dec_upload zeroed.  The files' bytes are in the blob already.
+int dec_scans(DecRun &r)
+{
+    const JpegBatchPlan &P = r.plan;
+    if (P.gfiles.empty()) return IPX_OK;
+    const JpegDecArgs &a = r.a;
+    size_t nscans = 0, ndefs = 0;
+    for (int i : P.gfiles) { nscans += P.prog[i].scans.size(); ndefs += P.prog[i].defs.size(); }
+    const size_t nf = P.gfiles.size();
+    const size_t off_scans = (nf * sizeof(JpegProgFile) + 15) & ~(size_t)15, off_defs = (off_scans + nscans * sizeof(JpegProgScan) + 15) & ~(size_t)15;
+    r.prog_block.assign(off_defs + ndefs * sizeof(JpegProgHuff) + 16, 0);
+    JpegProgFile *hf = (JpegProgFile *)r.prog_block.data();
+    JpegProgScan *hs = (JpegProgScan *)(r.prog_block.data() + off_scans);
+    JpegProgHuff *hd = (JpegProgHuff *)(r.prog_block.data() + off_defs);
+    uint32_t s0 = 0, d0 = 0;
+    for (size_t k = 0; k < nf; k++) {
+        const int i = P.gfiles[k];
+        const JpegProgPlan &G = P.prog[i];
+        hf[k] = JpegProgFile{(unsigned long long)P.blob_off[i], (uint32_t)i, (uint32_t)G.scans.size(), s0, d0};
+        if (!G.scans.empty()) memcpy(hs + s0, G.scans.data(), G.scans.size() * sizeof(JpegProgScan));
+        if (!G.defs.empty()) memcpy(hd + d0, G.defs.data(), G.defs.size() * sizeof(JpegProgHuff));
+        s0 += (uint32_t)G.scans.size(); d0 += (uint32_t)G.defs.size();
+    }
+    uint8_t *d_prog = nullptr;
+    DEC_HIP("jpeg decode", r.mem.get(&d_prog, r.prog_block.size()));
+    DEC_HIP("jpeg decode", hipMemcpyAsync(d_prog, r.prog_block.data(), r.prog_block.size(), hipMemcpyHostToDevice, r.s));
+    JpegProgArgs g{};
+    g.blob = r.d_blob; g.files = (const JpegProgFile *)d_prog; g.scans = (const JpegProgScan *)(d_prog + off_scans); g.defs = (const JpegProgHuff *)(d_prog + off_defs);
+    g.coefs = a.coefs; g.dcs = a.dcs; g.status = a.status;
+    g.nfiles = (int)nf; g.mxx = a.mxx; g.myy = a.myy; g.h0 = a.h0; g.v0 = a.v0; g.nblk = a.nblk; g.w = a.w; g.h = a.h; g.bpm = a.bpm; g.ybl = a.ybl;
+    DEC_HIP("jpeg decode", launch_jpeg_prog(g, r.s));
     return IPX_OK;
 }
 
@@ -284,8 +327,24 @@ int dec_finish(DecRun &r, ipx_ycbcr_batch *planes)
     DEC_HIP("jpeg decode", hipStreamSynchronize(r.s));
     if ((getenv("IPX_DEBUG") && r.ms() > 200.0) || env_int("IPX_DEBUG_J2J", 0))
         fprintf(stderr, "[ipx] decode of %d files: parsed at %.1f ms, device scratch at %.1f, pinned block at %.1f, packed at %.1f, launched at %.1f, finished at %.1f\n", r.n, r.plan.parse_ms, r.t_alloc, r.t_pin, r.t_pack, r.t_launch, r.ms());
-    for (int i = 0; i < r.n; i++)
+    const JpegBatchPlan &P = r.plan;
+    for (int i = 0; i < r.n; i++) {
+        const bool walked = P.route[i] == IPX_JPEG_ROUTE_GPU_SCANS;
         if (r.status[i] == IPX_OK && r.dev_status[i]) r.status[i] = jpeg_status_of(r.dev_status[i]);
+        if (walked && r.dev_status[i] == jpeg_status_key(kJpegProgHostVerdict, IPX_ERR_UNSUPPORTED)) {
+            // a coefficient of this (damaged) file truncated to zero in int16: the host decoder, whose walk differs from there on, says
+            // which way it fails -- it has no planes either way
+            std::vector<int16_t> scratch((size_t)r.a.nblk * 65);
+            JpegDecInfo full;
+            uint16_t q[3][64];
+            bool prog = false;
+            const int st = jpeg_host_decode(r.jpegs[i].data, r.jpegs[i].len, &full, scratch.data(), scratch.data() + (size_t)r.a.nblk * 64, (size_t)r.a.nblk, q, &prog);
+            r.status[i] = st != IPX_OK ? st : IPX_ERR_UNSUPPORTED;
+        }
+        // by route: every file that reached its decoder, whatever came of it
+        if (P.route[i] <= IPX_JPEG_ROUTE_GPU_SCANS) r.ctx->jpeg_counts[P.route[i]]++;
+        if (walked && r.status[i] != IPX_OK) r.ctx->jpeg_counts[3]++;
+    }
     planes->y = r.pl.y; planes->cb = r.pl.cb; planes->cr = r.pl.cr;
     planes->ystride = r.pl.ystride; planes->cstride = r.pl.cstride;
     planes->y_frame_stride = r.pl.y_fs; planes->c_frame_stride = r.pl.c_fs;
@@ -302,13 +361,14 @@ int jpeg_decode_files(ipx_ctx *ctx, hipStream_t s, Lane *lane, bool planes_in_la
 {
     OwnedBlocks<ipx_jpeg_planes> own(ctx, s);
     DecRun r(ctx, s, jpegs, n, status);
-    const JpegPlanOptions opt{*w, *h, env_int("IPX_JPEG_PAR", 1) != 0, env_int("IPX_JPEG_PAR_SUB", 0), jpeg_par_sub_bytes()};
+    const JpegPlanOptions opt{*w, *h, env_int("IPX_JPEG_PAR", 1) != 0, env_int("IPX_JPEG_PAR_SUB", 0), jpeg_par_sub_bytes(), env_int("IPX_JPEG_PROG_GPU", 0) == 1};
     int rc = jpeg_plan_batch(jpegs, n, opt, status, &r.plan);
     if (rc) return rc;
     if (r.plan.ref < 0) return IPX_OK;
     *w = r.plan.info[r.plan.ref].w; *h = r.plan.info[r.plan.ref].h;
     rc = dec_blocks(r, lane, planes_in_lane, own);
     if (!rc) rc = dec_upload(r);
+    if (!rc) rc = dec_scans(r);
     if (!rc) rc = dec_huffman(r);
     if (!rc) rc = dec_finish(r, planes);
     if (rc) return rc;
@@ -335,5 +395,32 @@ int ipx_jpeg_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *jpegs, in
                              planes, status, owner);
 }
 IPX_CATCH_STATUS
+
+int ipx_jpeg_scan_route(const uint8_t *file, size_t len, int *route) try
+{
+    clear_error();
+    if (!file || !route) { set_error("ipx_jpeg_scan_route: bad argument"); return IPX_ERR_INVALID; }
+    *route = IPX_JPEG_ROUTE_PAR;
+    if (len >= ((size_t)1 << 30)) return IPX_ERR_UNSUPPORTED;
+    JpegDecInfo info;
+    JpegDecTables tab;
+    const int st = jpeg_parse(file, len, &info, &tab);
+    if (st != IPX_OK) return st;
+    if (info.host_scans) {
+        JpegProgPlan plan;
+        const bool gpu = env_int("IPX_JPEG_PROG_GPU", 0) == 1 && info.progressive && jpeg_prog_prepass(file, len, info, &plan, tab.qnat);
+        *route = gpu ? IPX_JPEG_ROUTE_GPU_SCANS : IPX_JPEG_ROUTE_HOST_SCANS;
+    }
+    return IPX_OK;
+}
+IPX_CATCH_STATUS
+
+int ipx_jpeg_decode_counts(ipx_ctx *ctx, long long counts[4])
+{
+    clear_error();
+    if (!ctx || !counts) { set_error("ipx_jpeg_decode_counts: bad argument"); return IPX_ERR_INVALID; }
+    for (int k = 0; k < 4; k++) counts[k] = ctx->jpeg_counts[k].load();
+    return IPX_OK;
+}
 
 }  // extern "C"

@@ -3,6 +3,7 @@
 // halves).  What only the decode drivers share sits on top of it in ipx_decode_common.h.  Not part of the ABI.
 #pragma once
 
+#include <atomic>
 #include <sched.h>
 
 #include <algorithm>
@@ -66,6 +67,8 @@ struct ipx_ctx {
     // axes of the kernel scaler in HBM by (destination extent, source extent), for the per-operation seam (ks_axis_get)
     std::mutex ks_mu;
     std::map<std::pair<int, int>, std::pair<uint8_t *, KsAxisDev>> ks_axes;
+    // ipx_jpeg_decode_counts: files decoded by route (IPX_JPEG_ROUTE_*) since ipx_create; [3]: files the GPU scan walk ended with a status
+    std::atomic<long long> jpeg_counts[4] = {{0}, {0}, {0}, {0}};
     static constexpr size_t kFlatChromaBytes = (size_t)64 << 10;
 };
 

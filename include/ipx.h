@@ -548,7 +548,11 @@ int ipx_plan_run_host_png(ipx_ctx *ctx, const ipx_plan *plan, int n, const uint8
  * files of one size and one kind (three components at 4:4:4 / 4:2:2 / 4:2:0 / 4:4:0, or one component) is decoded here.  Baseline files:
  * the compressed bytes go up, Huffman decoding runs in parallel inside each scan (or per restart interval), the integer IDCT of idct.go runs
  * block-parallel.  Progressive (SOF2), multi-scan and extended-sequential files: their scans are decoded by the host threads that parse
- * the batch (the scans refine each other), the coefficients go up, IDCT onwards is the same GPU path.  Either way the *image.YCbCr planes
+ * the batch (the scans refine each other), the coefficients go up, IDCT onwards is the same GPU path.  With IPX_JPEG_PROG_GPU=1 in the
+ * environment (read on every call; unset or anything else: as before) a progressive file whose marker pre-pass is wholly clean -- it
+ * reaches EOI, every SOS header is valid, every Huffman table a scan decodes with is defined, no restart interval, at most 64 scans -- goes
+ * up as compressed bytes instead and one GPU wave per file walks its scans in file order; every other file keeps the host route, and the
+ * planes and statuses are the same on both.  Either way the *image.YCbCr planes
  * (MCU-padded strides, as image.NewYCbCr lays them out) stay in
  * HBM, ready for ipx_plan_run_dev_ycbcr (ratio IPX_GRAY: only y is set; ipx_plan_run_dev_gray).  status[i]: IPX_OK, IPX_ERR_INVALID (malformed:
  * Go's decoder fails on the file too, including a file that ends without EOI) or
@@ -568,6 +572,15 @@ int ipx_plan_run_jpeg_jpeg(ipx_ctx *ctx, const ipx_plan *plan, int n, const ipx_
 int ipx_jpeg_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *jpegs, int n, int *w, int *h,
                           ipx_ycbcr_batch *planes, int *status, ipx_jpeg_planes **owner);
 void ipx_jpeg_planes_free(ipx_ctx *ctx, ipx_jpeg_planes *owner);
+/* Which decoder a JPEG file's scans reach: the parallel Huffman kernels (one baseline scan), the host threads, or the GPU scan walk. */
+enum { IPX_JPEG_ROUTE_PAR = 0, IPX_JPEG_ROUTE_HOST_SCANS = 1, IPX_JPEG_ROUTE_GPU_SCANS = 2 };
+/* host only, no context: the route this file would take now (IPX_JPEG_PROG_GPU is read); returns the parse status, *route is
+ * meaningful when that is IPX_OK */
+int ipx_jpeg_scan_route(const uint8_t *file, size_t len, int *route);
+/* since ipx_create: the files that reached the decoder of route [0..2] in any decode entry of this context (whatever status they ended
+ * with; files refused by the marker parser or for their geometry reach none), and [3] the files the GPU scan walk ended with a status
+ * other than IPX_OK */
+int ipx_jpeg_decode_counts(ipx_ctx *ctx, long long counts[4]);
 
 /* ---- image.Decode for GIFs (decoder side) ---------------------------------------------
  * For a GIF upload image.Decode is gif.Decode: the FIRST image of the file as an *image.Paletted.  The host reads the container

@@ -96,6 +96,24 @@ static void check_plan(const std::vector<std::vector<uint8_t>> &batch, const ipx
         const ipx::JpegDecInfo &I = P.info[i];
         if (status[i] != IPX_OK) { PLAN_CHECK(!P.valid[i] && mcus[i].empty() && P.hslot[i] < 0); continue; }
         PLAN_CHECK(P.ref >= 0 && I.w == P.info[P.ref].w && I.h == P.info[P.ref].h && I.h0 == P.info[P.ref].h0 && I.v0 == P.info[P.ref].v0 && I.ncomp == P.info[P.ref].ncomp);
+        if (I.gpu_scans) {
+            // a progressive file the GPU walks (opt.prog_gpu): its whole bytes in the blob, 16-byte aligned; every scan's readable data
+            // inside the file; every table a scan decodes with among the file's definitions
+            PLAN_CHECK(opt.prog_gpu && I.host_scans && I.progressive && P.hslot[i] < 0 && mcus[i].empty() && P.valid[i] == 3);
+            PLAN_CHECK(std::count(P.gfiles.begin(), P.gfiles.end(), i) == 1 && P.route[i] == IPX_JPEG_ROUTE_GPU_SCANS);
+            PLAN_CHECK(P.blob_off[i] % 16 == 0 && P.blob_off[i] + ((files[i].len + 15) & ~(size_t)15) <= end);
+            const ipx::JpegProgPlan &G = P.prog[i];
+            PLAN_CHECK(!G.scans.empty() && G.scans.size() <= (size_t)ipx::IPX_JPEG_PROG_MAX_SCANS && G.defs.size() <= 3 * G.scans.size());
+            for (const ipx::JpegProgScan &s : G.scans) {
+                PLAN_CHECK((size_t)s.off + s.len <= files[i].len && s.ns >= 1 && s.ns <= I.ncomp && s.ss <= s.se && s.se < 64 && (s.ss == 0 || s.ns == 1));
+                for (int c = 0; c < s.ns; c++) {
+                    PLAN_CHECK(s.comp[c] < I.ncomp);
+                    if (s.ss == 0 && s.ah == 0) PLAN_CHECK(s.dc_def[c] < G.defs.size());
+                    if (s.ss > 0) PLAN_CHECK(s.ac_def[c] < G.defs.size());
+                }
+            }
+            continue;
+        }
         if (I.host_scans) { PLAN_CHECK(P.hslot[i] == nhost++ && mcus[i].empty() && (P.valid[i] & 1)); continue; }
         PLAN_CHECK(P.hslot[i] < 0 && !mcus[i].empty());
         if (mcus[i][0].second == ~0u) continue;                                          // a parallel image: the whole scan
@@ -184,7 +202,7 @@ int main(int argc, char **argv)
             if (rnd() % 3 == 0) mutate(v, 2, v.size());
         }
         static const int subs[] = {0, 0, 128, 256, 512, 1024};
-        const ipx::JpegPlanOptions opt{t % 5 == 4 ? 160 : 0, t % 5 == 4 ? 120 : 0, t % 7 != 6, subs[t % 6], 1024};
+        const ipx::JpegPlanOptions opt{t % 5 == 4 ? 160 : 0, t % 5 == 4 ? 120 : 0, t % 7 != 6, subs[t % 6], 1024, t % 3 != 2};
         check_plan(batch, opt);
         plans++;
     }
