@@ -148,6 +148,11 @@ func (p *Pool) SubmitJPEG(w, h int, o Ops, files [][]byte, quality int) (*Job, e
 // thumbnail.go:70-74, watermark.go:66-79): a JPEG job three JPEGs, a PNG job three PNGs, a GIF job a GIF, a GIF and a JPEG for the
 // watermark.  quality is jpeg.Options.Quality (a PNG job ignores it).  FileStatus(i) != OK marks the files Go processes itself.
 func (p *Pool) SubmitFiles(format FileFormat, w, h int, o Ops, files [][]byte, quality int) (*Job, error) {
+	return p.submitFiles(format, w, h, o, files, quality, nil)
+}
+
+// texts: nil, or one ipx_text per file (SubmitFilesTexts); ipx_job_submit copies them
+func (p *Pool) submitFiles(format FileFormat, w, h int, o Ops, files [][]byte, quality int, texts *C.ipx_text) (*Job, error) {
 	n := len(files)
 	ops, free := p.ops(w, h, o)
 	defer free()
@@ -168,7 +173,7 @@ func (p *Pool) SubmitFiles(format FileFormat, w, h int, o Ops, files [][]byte, q
 	job.cmem = append(job.cmem, unsafe.Pointer(ro), unsafe.Pointer(to), unsafe.Pointer(wo))
 	job.resize, job.thumb, job.wm = unsafe.Slice(ro, n), unsafe.Slice(to, n), unsafe.Slice(wo, n)
 	j := C.ipx_job{kind: C.int32_t(format), ops: ops, n: C.int32_t(n), files: &cf[0], quality: C.int32_t(quality),
-		resize_jpeg: ro, thumb_jpeg: to, wm_jpeg: wo, status: &job.cstatus[0]}
+		resize_jpeg: ro, thumb_jpeg: to, wm_jpeg: wo, status: &job.cstatus[0], texts: texts}
 	if !o.Watermark {
 		j.wm_jpeg = nil
 	}

@@ -123,6 +123,21 @@ def _glyph_array(glyphs):
     return arr, keep
 
 
+def _text_array(texts):
+    """texts: one (glyphs, col) pair per file or frame -> (ipx_text array, what it points into)"""
+    keep = []
+    arr = (_lib.Text * max(1, len(texts)))()
+    for i, (glyphs, col) in enumerate(texts):
+        glyphs = list(glyphs)
+        ga, gk = _glyph_array(glyphs)
+        keep.append((ga, gk))
+        arr[i].glyphs = ga if glyphs else None
+        arr[i].n_glyphs = len(glyphs)
+        for c in range(4):
+            arr[i].col[c] = int(col[c])
+    return arr, keep
+
+
 # ---- GPU objects -------------------------------------------------------------------------------------
 
 class DevBuffer:
@@ -172,6 +187,29 @@ class GlyphSet:
     def close(self):
         if self.handle:
             lib().ipx_glyphset_destroy(self.ctx.handle, self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TextSet:
+    """One text per frame of a batch, clipped for w x h frames and resident in HBM (ipx_textset_*).  texts: (glyphs, col) pairs."""
+
+    def __init__(self, ctx, texts, w, h, stream=None):
+        self.ctx = ctx
+        texts = list(texts)
+        arr, keep = _text_array(texts)
+        hd = C.c_void_p()
+        _check(lib().ipx_textset_create(ctx.handle, stream, arr, len(texts), int(w), int(h), C.byref(hd)))
+        self.handle, self.n, self.w, self.h = hd.value, len(texts), int(w), int(h)
+
+    def close(self):
+        if self.handle:
+            lib().ipx_textset_destroy(self.ctx.handle, self.handle)
             self.handle = None
 
     def __del__(self):
@@ -319,18 +357,36 @@ class Plan:
         b = _lib.YCbCrBatch(y.ctypes.data, cb.ctypes.data, cr.ctypes.data, w, cb.shape[2], h * w, cb.shape[1] * cb.shape[2], int(ratio))
         return self._run_streams(lib().ipx_plan_run_host_ycbcr_jpeg, n, want, copy, (C.byref(b), int(quality)))
 
-    def run_jpeg_jpeg(self, files, quality=85, want=("resize", "thumbnail", "watermark"), copy=True):
-        """JPEG byte strings in -> ({operator: [jpeg bytes | None] * n}, status list): decode, operators, encode on the GPU."""
+    def _run_files_texts(self, entry, files, texts, want, copy, args=()):
+        """A file-in entry with texts[i] = (glyphs, col) drawn on file i's watermark (the plan must be copy-only: watermark=True)."""
+        texts = list(texts)
+        if len(texts) != len(files):
+            raise ValueError("one text per file")
+        arr, keep = _text_array(texts)
+        n = len(files)
+        status = (C.c_int * max(n, 1))()
+        out = self._run_streams(entry, n, want, copy, (_bytes_array(files), arr) + args, status)
+        return out, list(status)[:n]
+
+    def run_jpeg_jpeg(self, files, quality=85, want=("resize", "thumbnail", "watermark"), copy=True, texts=None):
+        """JPEG byte strings in -> ({operator: [jpeg bytes | None] * n}, status list): decode, operators, encode on the GPU.
+        texts: None, or one (glyphs, col) per file (ipx_plan_run_jpeg_jpeg_texts)."""
+        if texts is not None:
+            return self._run_files_texts(lib().ipx_plan_run_jpeg_jpeg_texts, files, texts, want, copy, (int(quality),))
         return self._run_files(lib().ipx_plan_run_jpeg_jpeg, files, want, copy, (int(quality),))
 
-    def run_gif_gif(self, files, quality=85, want=("resize", "thumbnail", "watermark"), copy=True):
+    def run_gif_gif(self, files, quality=85, want=("resize", "thumbnail", "watermark"), copy=True, texts=None):
         """GIF byte strings in -> ({operator: [bytes | None] * n}, status list): gif.Decode, operators, gif.Encode of resize / thumbnail
-        and jpeg.Encode (at `quality`) of the watermark on the GPU."""
+        and jpeg.Encode (at `quality`) of the watermark on the GPU.  texts: None, or one (glyphs, col) per file."""
+        if texts is not None:
+            return self._run_files_texts(lib().ipx_plan_run_gif_gif_texts, files, texts, want, copy, (int(quality),))
         return self._run_files(lib().ipx_plan_run_gif_gif, files, want, copy, (int(quality),))
 
-    def run_png_png(self, files, want=("resize", "thumbnail", "watermark"), copy=True):
+    def run_png_png(self, files, want=("resize", "thumbnail", "watermark"), copy=True, texts=None):
         """PNG byte strings of any kind in -> ({operator: [png bytes | None] * n}, status list): png.Decode, operators and png.Encode of
-        every output on the GPU."""
+        every output on the GPU.  texts: None, or one (glyphs, col) per file."""
+        if texts is not None:
+            return self._run_files_texts(lib().ipx_plan_run_png_png_texts, files, texts, want, copy)
         return self._run_files(lib().ipx_plan_run_png_png, files, want, copy)
 
     def run_dev_nrgba(self, n, src_ptr, resize_ptr=None, thumb_ptr=None, wm_ptr=None, stream=None,
@@ -474,6 +530,9 @@ class Context:
     def glyphset(self, glyphs, col):
         return GlyphSet(self, glyphs, col)
 
+    def textset(self, texts, w, h, stream=None):
+        return TextSet(self, texts, w, h, stream)
+
     def plan(self, sw, sh, **kw):
         return Plan(self, sw, sh, **kw)
 
@@ -491,6 +550,13 @@ class Context:
     def dev_composite_glyphs(self, dst_ptr, dw, dh, dstride, glyphset, stream=None):
         """the text of a GlyphSet onto one RGBA8 frame resident in HBM (ipx_dev_composite_glyphs_rgba8)"""
         _check(lib().ipx_dev_composite_glyphs_rgba8(self.handle, stream, dst_ptr, dw, dh, dstride, glyphset.handle))
+
+    def dev_composite_texts(self, dst_ptr, w, h, dstride, frame_stride, n_frames, textset, first=0, map=None, stream=None):
+        """frame z of n_frames RGBA8 frames in HBM gets text map[z] (first + z without a map) of a TextSet, in one launch
+        (ipx_dev_composite_texts_rgba8)"""
+        m = None if map is None else (C.c_int32 * max(1, len(map)))(*[int(v) for v in map])
+        _check(lib().ipx_dev_composite_texts_rgba8(self.handle, stream, dst_ptr, w, h, dstride, frame_stride, n_frames, textset.handle,
+                                                   int(first), m))
 
     # ---- per-operation seam on host arrays (synchronous) ----------------------------------------
     def scale_bilinear(self, src, dw, dh, sr=None, dr=None, op=OP_OVER, dst=None):
@@ -927,17 +993,26 @@ class Pool:
         return self.submit_files(files, sw, sh, "jpeg", quality, resize, thumbnail, glyphs, col, watermark)
 
     def submit_files(self, files, sw, sh, format="jpeg", quality=85, resize=(1024, 768, True), thumbnail=(200, True), glyphs=None,
-                     col=(0, 0, 0, 0), watermark=False, want=("resize", "thumbnail", "watermark")):
+                     col=(0, 0, 0, 0), watermark=False, want=("resize", "thumbnail", "watermark"), texts=None):
         """Uploaded files of one format ("jpeg", "png", "gif") and of sw x sh images in -> PoolJob; wait() gives ({operator: [bytes |
         None]}, status list) with streams of the job's format (PNG: three PNGs; GIF: GIF, GIF and a JPEG at `quality` for the
-        watermark).  An operator not in `want` gets no output array and is left out."""
+        watermark).  An operator not in `want` gets no output array and is left out.  texts: None, or one (glyphs, col) per file
+        (ipx_job.texts; `glyphs` must then be left out)."""
         n = len(files)
-        ops, keep = self._ops(sw, sh, resize, thumbnail, glyphs, col, watermark)
+        ops, keep = self._ops(sw, sh, resize, thumbnail, glyphs, col, watermark or texts is not None)
+        tarr = None
+        if texts is not None:
+            texts = list(texts)
+            if len(texts) != n:
+                raise ValueError("one text per file")
+            tarr = _text_array(texts)
         arr = _bytes_array(files)
         status = (C.c_int32 * max(1, n))()
         outs = {}
         j = _lib.Job()
         j.kind, j.ops, j.n, j.files, j.quality, j.status = self.FILE_KINDS[format], ops, n, arr, int(quality), status
+        if tarr is not None:
+            j.texts = tarr[0]
         if resize and "resize" in want:
             outs["resize"] = (_lib.Bytes * max(1, n))()
             j.resize_jpeg = outs["resize"]
@@ -947,7 +1022,7 @@ class Pool:
         if ops.do_watermark and "watermark" in want:
             outs["watermark"] = (_lib.Bytes * max(1, n))()
             j.wm_jpeg = outs["watermark"]
-        return PoolJob(self, j, {"files": arr, "status": status, "glyphs": keep}, outs, n)
+        return PoolJob(self, j, {"files": arr, "status": status, "glyphs": keep, "texts": tarr}, outs, n)
 
 
 def jpeg_entropy_encode(coefs, w, h, quality=85):

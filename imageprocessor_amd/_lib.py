@@ -17,6 +17,10 @@ class Glyph(C.Structure):
                 ("dr", Rect), ("mpx", C.c_int32), ("mpy", C.c_int32)]
 
 
+class Text(C.Structure):
+    _fields_ = [("glyphs", C.POINTER(Glyph)), ("n_glyphs", C.c_int32), ("col", C.c_uint8 * 4)]
+
+
 class Config(C.Structure):
     _fields_ = [("device", C.c_int32), ("lanes", C.c_int32), ("lane_bytes", C.c_size_t)]
 
@@ -112,7 +116,7 @@ class Job(C.Structure):
                 ("wm_out", C.c_void_p), ("wm_frame_stride", C.c_size_t),
                 ("files", C.POINTER(Bytes)), ("quality", C.c_int32),
                 ("resize_jpeg", C.POINTER(Bytes)), ("thumb_jpeg", C.POINTER(Bytes)), ("wm_jpeg", C.POINTER(Bytes)),
-                ("status", C.POINTER(C.c_int32))]
+                ("status", C.POINTER(C.c_int32)), ("texts", C.POINTER(Text))]
 
 
 class BatcherConfig(C.Structure):
@@ -170,6 +174,9 @@ SIGNATURES = {
     "ipx_glyphset_create": (_I, [_P, C.POINTER(Glyph), _I, _P, C.POINTER(_P)]),
     "ipx_glyphset_destroy": (None, [_P, _P]),
     "ipx_dev_composite_glyphs_rgba8": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "ipx_textset_create": (_I, [_P, _P, C.POINTER(Text), _I, _I, _I, C.POINTER(_P)]),
+    "ipx_textset_destroy": (None, [_P, _P]),
+    "ipx_dev_composite_texts_rgba8": (_I, [_P, _P, _P, _I, _I, _I, _Z, _I, _P, _I, C.POINTER(C.c_int32)]),
     "ipx_plan_create": (_I, [_P, C.POINTER(PlanParams), C.POINTER(_P)]),
     "ipx_plan_destroy": (None, [_P, _P]),
     "ipx_plan_query": (_I, [_P, C.POINTER(PlanInfo)]),
@@ -232,6 +239,12 @@ SIGNATURES = {
     "ipx_png_frames_free": (None, [_P, _P]),
     "ipx_plan_run_png_png": (_I, [_P, _P, _I, C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(_I),
                                   C.POINTER(_P)]),
+    "ipx_plan_run_jpeg_jpeg_texts": (_I, [_P, _P, _I, C.POINTER(Bytes), C.POINTER(Text), _I, C.POINTER(Bytes), C.POINTER(Bytes),
+                                          C.POINTER(Bytes), C.POINTER(_I), C.POINTER(_P)]),
+    "ipx_plan_run_png_png_texts": (_I, [_P, _P, _I, C.POINTER(Bytes), C.POINTER(Text), C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(Bytes),
+                                        C.POINTER(_I), C.POINTER(_P)]),
+    "ipx_plan_run_gif_gif_texts": (_I, [_P, _P, _I, C.POINTER(Bytes), C.POINTER(Text), _I, C.POINTER(Bytes), C.POINTER(Bytes),
+                                        C.POINTER(Bytes), C.POINTER(_I), C.POINTER(_P)]),
     "ipx_font_create": (_I, [_P, _Z, C.POINTER(_P)]),
     "ipx_font_destroy": (None, [_P]),
     "ipx_font_glyph_index": (_I, [_P, C.c_uint32]),

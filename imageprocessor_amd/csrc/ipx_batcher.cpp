@@ -9,8 +9,9 @@
 
 namespace ipx {
 
-Batcher::Batcher(const BatchBackend &be, int max_batch, int max_wait_us, int quality, int idle_jobs)
-    : be_(be), max_batch_(std::max(1, max_batch)), quality_(quality), max_wait_(std::max(0, max_wait_us)), idle_jobs_(std::max(0, idle_jobs))
+Batcher::Batcher(const BatchBackend &be, int max_batch, int max_wait_us, int quality, int idle_jobs, bool per_file_texts)
+    : be_(be), max_batch_(std::max(1, max_batch)), quality_(quality), texts_(per_file_texts), max_wait_(std::max(0, max_wait_us)),
+      idle_jobs_(std::max(0, idle_jobs))
 {
     if (const char *e = getenv("IPX_BATCHER_IDLE_FLUSH")) idle_jobs_ = std::max(0, atoi(e));
     timer_ = std::thread([this] { timer_loop(); });
@@ -48,26 +49,29 @@ Batcher::~Batcher()
     }
 }
 
-// deep copy + the grouping key: frame size, operator parameters, colour, every glyph's geometry and mask bytes
-int Batcher::copy_ops(const ipx_pool_ops &in, OpsCopy *out, std::string *key, std::string *err)
+// deep copy + the grouping key: frame size, operator parameters, colour, every glyph's geometry and mask bytes (key_text false: the key
+// stops before the colour)
+int Batcher::copy_ops(const ipx_pool_ops &in, OpsCopy *out, std::string *key, std::string *err, bool key_text)
 {
     if (in.sw <= 0 || in.sh <= 0) { *err = "ipx_batcher_submit: the frame size of the file (ops.sw, ops.sh) is required"; return IPX_ERR_INVALID; }
     if (in.n_glyphs < 0 || (in.n_glyphs && !in.glyphs)) { *err = "ipx_batcher_submit: bad glyph list"; return IPX_ERR_INVALID; }
     out->p = in;
     key->assign((const char *)&in, offsetof(ipx_pool_ops, glyphs));
-    key->append((const char *)in.col, 4);
+    if (key_text) key->append((const char *)in.col, 4);
     out->glyphs.assign(in.glyphs, in.glyphs + in.n_glyphs);
     out->masks.resize((size_t)in.n_glyphs);
     for (int i = 0; i < in.n_glyphs; i++) {
         const ipx_glyph &g = in.glyphs[i];
         if (g.mw < 0 || g.mh < 0 || (g.mw && g.mh && (!g.mask || g.mstride < g.mw))) { *err = "ipx_batcher_submit: a glyph has a bad mask"; return IPX_ERR_INVALID; }
-        key->append((const char *)&g.mw, sizeof(int32_t) * 2);
-        key->append((const char *)&g.dr, sizeof g.dr);
-        key->append((const char *)&g.mpx, sizeof(int32_t) * 2);
+        if (key_text) {
+            key->append((const char *)&g.mw, sizeof(int32_t) * 2);
+            key->append((const char *)&g.dr, sizeof g.dr);
+            key->append((const char *)&g.mpx, sizeof(int32_t) * 2);
+        }
         out->masks[i].resize((size_t)g.mw * g.mh);
         for (int y = 0; y < g.mh; y++) {
             memcpy(out->masks[i].data() + (size_t)y * g.mw, g.mask + (size_t)y * g.mstride, (size_t)g.mw);
-            key->append((const char *)g.mask + (size_t)y * g.mstride, (size_t)g.mw);
+            if (key_text) key->append((const char *)g.mask + (size_t)y * g.mstride, (size_t)g.mw);
         }
         out->glyphs[i].mask = out->masks[i].data();
         out->glyphs[i].mstride = g.mw;
@@ -116,9 +120,11 @@ static int sniff_kind(const ipx_bytes &f)
 int Batcher::submit(const ipx_bytes &file, const ipx_pool_ops &ops, uint64_t *ticket, std::string *err)
 {
     if (!ticket || !file.data || !file.len) { *err = "ipx_batcher_submit: bad argument"; return IPX_ERR_INVALID; }
+    // a text per file: one that no text set takes (kMaxGlyphs of the kernels) is refused here, alone, before it can join a group
+    if (texts_ && ops.n_glyphs > 256) { *err = "ipx_batcher_submit: the text has more than 256 glyphs"; return IPX_ERR_UNSUPPORTED; }
     OpsCopy oc;
     std::string key;
-    const int rc = copy_ops(ops, &oc, &key, err);
+    const int rc = copy_ops(ops, &oc, &key, err, !texts_);
     if (rc) return rc;
     // four more key bytes: for a JPEG the shape (three bytes, zeros otherwise), then the format (the job kind).  PNG files are NOT split by colour type or depth: ipx_plan_run_png_png groups kinds itself,
     // and splitting here would only make every group wait longer for company.
@@ -136,7 +142,11 @@ int Batcher::submit(const ipx_bytes &file, const ipx_pool_ops &ops, uint64_t *ti
             auto b = std::make_shared<Batch>();
             b->key = key;
             b->kind = kind;
-            b->ops = std::move(oc);
+            if (texts_) {                                       // the group's own operators carry no text: the plan only copies the frame
+                b->ops.p = oc.p;
+                b->ops.p.glyphs = nullptr; b->ops.p.n_glyphs = 0;
+                memset(b->ops.p.col, 0, 4);
+            } else b->ops = std::move(oc);
             if (!b->ops.glyphs.empty()) {                       // the moved vectors kept their buffers; the pointers into them stay good
                 for (size_t i = 0; i < b->ops.glyphs.size(); i++) b->ops.glyphs[i].mask = b->ops.masks[i].data();
                 b->ops.p.glyphs = b->ops.glyphs.data();
@@ -147,6 +157,7 @@ int Batcher::submit(const ipx_bytes &file, const ipx_pool_ops &ops, uint64_t *ti
         }
         Batch &b = *it->second;
         b.files.push_back(file);
+        if (texts_) b.file_ops.push_back(std::move(oc));
         *ticket = next_ticket_++;
         tickets_[*ticket] = {it->second, (int)b.files.size() - 1};
         b.unreleased++;
@@ -178,6 +189,18 @@ void Batcher::flush(const std::shared_ptr<Batch> &b, Why why)
     j.thumb_jpeg = b->ops.p.do_thumbnail ? b->th.data() : nullptr;
     j.wm_jpeg = b->ops.p.do_watermark ? b->wm.data() : nullptr;
     j.status = b->status.data();
+    if (texts_) {                                               // (the moved copies kept their buffers; the pointers are set here, once)
+        b->texts.resize((size_t)n);
+        for (int i = 0; i < n; i++) {
+            OpsCopy &o = b->file_ops[i];
+            for (size_t g = 0; g < o.glyphs.size(); g++) o.glyphs[g].mask = o.masks[g].data();
+            ipx_text &x = b->texts[i];
+            x.glyphs = o.glyphs.empty() ? nullptr : o.glyphs.data();
+            x.n_glyphs = (int32_t)o.glyphs.size();
+            memcpy(x.col, o.p.col, 4);
+        }
+        j.texts = b->texts.data();
+    }
     ipx_ticket t = 0;
     const int rc = be_.submit(be_.self, &j, &t);
     std::string text = rc && be_.last_error ? be_.last_error() : "";
@@ -326,7 +349,8 @@ int ipx_batcher_create(ipx_pool *pool, const ipx_batcher_config *cfg, ipx_batche
     b->pool = pool;
     b->b = new ipx::Batcher(be, cfg && cfg->max_batch > 0 ? cfg->max_batch : 256, cfg && cfg->max_wait_us > 0 ? cfg->max_wait_us : 2000,
                             cfg && cfg->quality > 0 ? cfg->quality : 85,
-                            4 * std::max(1, ipx_pool_slots(pool)));   // (the pool's default: four feeders per device)
+                            4 * std::max(1, ipx_pool_slots(pool)),    // (the pool's default: four feeders per device)
+                            [] { const char *e = getenv("IPX_BATCH_TEXTS"); return e && !strcmp(e, "1"); }());
     *out = b;
     return IPX_OK;
 }

@@ -8,6 +8,11 @@
 // first file has waited max_wait_us, and every file gets its own status -- a file the GPU path cannot decode does not fail its
 // neighbours (the worker runs its own image.Decode path for it).
 //
+// per_file_texts (the ABI: IPX_BATCH_TEXTS=1, read once at ipx_batcher_create): the grouping key stops before the colour and the glyphs
+// -- format, frame size, JPEG shape and operator parameters stay in it -- so files that differ only in their watermark text share a group.
+// Each file keeps its own deep-copied text; the group goes out as one file job with ops.glyphs = NULL and ipx_job::texts set, and one
+// launch per chunk draws every file's own text (composite_texts_kernel).  A text of more than 256 glyphs is refused at submit, alone.
+//
 // All of it is host logic over three calls of a backend (submit / wait / release of a job), so it builds and runs without a GPU: the
 // product binds the backend to ipx_job_* of a pool, tools/sanitize/batcher_host_test.cpp and batcher_formats_host_test.cpp bind it to a fake and run under ThreadSanitizer.
 #pragma once
@@ -39,7 +44,7 @@ class Batcher {
 public:
     // idle_jobs: a group leaves at once while fewer jobs than this are running (what the backend can run side by side: the pool's
     // feeders); 0 = size and timer only
-    Batcher(const BatchBackend &be, int max_batch, int max_wait_us, int quality, int idle_jobs = 1);
+    Batcher(const BatchBackend &be, int max_batch, int max_wait_us, int quality, int idle_jobs = 1, bool per_file_texts = false);
     ~Batcher();                                     // flushes what is pending, waits for every job, releases them
     int submit(const ipx_bytes &file, const ipx_pool_ops &ops, uint64_t *ticket, std::string *err);
     int wait(uint64_t ticket, ipx_batch_result *res, std::string *err);
@@ -58,6 +63,8 @@ private:
         OpsCopy ops;
         std::chrono::steady_clock::time_point deadline;
         std::vector<ipx_bytes> files;
+        std::vector<OpsCopy> file_ops;              // per_file_texts: file i's own glyphs and colour; `texts` is made of them at flush
+        std::vector<ipx_text> texts;
         std::vector<ipx_bytes> res, th, wm;
         std::vector<int32_t> status;
         // guarded by Batcher::mu_
@@ -68,7 +75,7 @@ private:
         int unreleased = 0;
         std::condition_variable cv;                 // flushed
     };
-    static int copy_ops(const ipx_pool_ops &in, OpsCopy *out, std::string *key, std::string *err);
+    static int copy_ops(const ipx_pool_ops &in, OpsCopy *out, std::string *key, std::string *err, bool key_text = true);
     enum Why { BySize, ByTimer, WhenIdle };
     void flush(const std::shared_ptr<Batch> &b, Why why);
     void job_seen_done(const std::shared_ptr<Batch> &b);   // the first waiter back from the backend: perhaps nothing runs any more
@@ -76,6 +83,7 @@ private:
 
     BatchBackend be_;
     int max_batch_, quality_;
+    bool texts_ = false;                            // per_file_texts
     std::chrono::microseconds max_wait_;
     std::mutex mu_;
     std::condition_variable cv_timer_;

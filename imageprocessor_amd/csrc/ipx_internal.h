@@ -115,6 +115,15 @@ hipError_t launch_stream_copy(void *dst, const void *src, size_t bytes, hipStrea
 hipError_t launch_composite(uint8_t *dst, int dstride, size_t frame_stride, int nframes,
                             const DevGlyph *glyphs_dev, int n, Rect bbox, uint32_t sr, uint32_t sg,
                             uint32_t sb, uint32_t sa, hipStream_t s);
+// one text of a text set (ipx_textset): its clipped glyphs glyphs[first .. first + n) of the set's one table, their bounding box (empty:
+// nothing to draw) and the colour as launch_composite takes it (c * 0x101)
+struct DevText {
+    int first, n;
+    Rect bbox;
+    uint16_t col[4];
+};
+hipError_t launch_composite_texts(uint8_t *dst, int dstride, size_t frame_stride, int nframes, const DevText *texts_dev,
+                                  const DevGlyph *glyphs_dev, const int *map_dev, int first, int bw, int bh, hipStream_t s);
 
 hipError_t launch_gray_expand(uint8_t *dst, size_t dst_fs, const uint8_t *src, int sstride, size_t src_fs, int w, int h, int n, hipStream_t s);
 hipError_t launch_palette_expand(uint8_t *dst, size_t dst_fs, const uint8_t *src, int sstride, size_t src_fs, const uint8_t *palettes, int w,

@@ -479,8 +479,9 @@ IPX_CATCH_STATUS
 // ---- compressed in, compressed out: image.Decode, the operators and jpeg.Encode without leaving the GPU ------
 extern "C" {
 
-static int run_jpeg_jpeg_one(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, int quality, ipx_bytes *resize_out,
-                             ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result)
+// texts: null, or this part's own n texts (texts[i] for files[i])
+static int run_jpeg_jpeg_one(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, const ipx_text *texts, int quality,
+                             ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result)
 {
     IPX_ENTER(ctx);
     *result = nullptr;
@@ -525,6 +526,10 @@ static int run_jpeg_jpeg_one(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_
     if (rc) return rc;
     const double t_res = ms_since(t0);
     ResultOwner res(ctx);
+    // a text per file: the set is uploaded once per part, chunk i0 draws texts i0 .. i0 + m behind the plan's copy of the frame
+    ipx_textset ts;
+    const bool draw = texts && pl->p.do_watermark && outs.o[2].fs;
+    if (draw && (rc = textset_build(s, who, texts, n, outs.o[2].w, outs.o[2].h, &ts))) return rc;
     for (int i0 = 0; i0 < n && !rc; i0 += chunk) {
         const int m = std::min(chunk, n - i0);
         const PlanOutputs::Frames f = outs.place((uint8_t *)(((uintptr_t)lane->dev + 255) & ~(uintptr_t)255), chunk);
@@ -533,6 +538,7 @@ static int run_jpeg_jpeg_one(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_
         d.plane[0] += d.frame_stride[0] * i0;
         if (d.plane[1]) { d.plane[1] += d.frame_stride[1] * i0; d.plane[2] += d.frame_stride[1] * i0; }
         rc = run_dev_src(ctx, s, pl, m, d, f.dev[0], outs.o[0].fs, f.dev[1], outs.o[1].fs, f.dev[2], outs.o[2].fs);
+        if (!rc && draw) rc = dev_composite_texts(s, nullptr, f.dev[2], outs.o[2].w * 4, outs.o[2].fs, m, ts, i0, nullptr);
         if (!rc) rc = encode_outputs(ctx, s, outs, f, m, i0, quality, status, res);
     }
     (void)hipStreamSynchronize(s);
@@ -543,11 +549,10 @@ static int run_jpeg_jpeg_one(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_
 }
 
 
-int ipx_plan_run_jpeg_jpeg(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, int quality, ipx_bytes *resize_out,
-                           ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result) try
+// the body of ipx_plan_run_jpeg_jpeg (texts == NULL: no text launch) and ipx_plan_run_jpeg_jpeg_texts
+static int run_jpeg_jpeg(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, const ipx_text *texts, int quality,
+                         ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result)
 {
-    IPX_ENTER(ctx);
-    if (!pl || n < 0 || !files || !status || !result) { set_error("ipx_plan_run_jpeg_jpeg: bad argument"); return IPX_ERR_INVALID; }
     *result = nullptr;
     // a large batch is cut into parts that run on lanes of their own, one host thread each: while one part is in its (host-paced)
     // encode read-backs another decodes.  Two callers with 1024 files each measured 15 k images/s against 11.7 k for one.
@@ -555,14 +560,14 @@ int ipx_plan_run_jpeg_jpeg(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_by
     // than four gain nothing.  One lane stays free for a per-operator call that arrives while the batch runs.
     const int nl = (int)ctx->lanes.size();
     const int parts = std::max(1, std::min({nl >= 3 ? nl - 1 : nl, n / std::max(1, env_int("IPX_JPEG_JPEG_PART", 256)), env_int("IPX_JPEG_JPEG_MAXPARTS", 4)}));
-    if (parts == 1) return run_jpeg_jpeg_one(ctx, pl, n, files, quality, resize_out, thumb_out, wm_out, status, result);
+    if (parts == 1) return run_jpeg_jpeg_one(who, ctx, pl, n, files, texts, quality, resize_out, thumb_out, wm_out, status, result);
     std::vector<ipx_jpeg_result *> res(parts, nullptr);
     std::vector<int> rcs(parts, IPX_OK);
     std::vector<std::string> errs(parts);
     auto work = [&](int k) {
         const int i0 = (int)((long long)n * k / parts), i1 = (int)((long long)n * (k + 1) / parts);
-        rcs[k] = run_jpeg_jpeg_one(ctx, pl, i1 - i0, files + i0, quality, resize_out ? resize_out + i0 : nullptr, thumb_out ? thumb_out + i0 : nullptr,
-                                   wm_out ? wm_out + i0 : nullptr, status + i0, &res[k]);
+        rcs[k] = run_jpeg_jpeg_one(who, ctx, pl, i1 - i0, files + i0, texts ? texts + i0 : nullptr, quality, resize_out ? resize_out + i0 : nullptr,
+                                   thumb_out ? thumb_out + i0 : nullptr, wm_out ? wm_out + i0 : nullptr, status + i0, &res[k]);
         if (rcs[k]) errs[k] = ipx_last_error();
     };
     auto guarded = [&](int k) { const int rc = guarded_status([&] { work(k); }, &errs[k]); if (rc) rcs[k] = rc; };
@@ -576,6 +581,26 @@ int ipx_plan_run_jpeg_jpeg(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_by
     if (rc) return rc;
     *result = all.release();
     return IPX_OK;
+}
+
+int ipx_plan_run_jpeg_jpeg(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, int quality, ipx_bytes *resize_out,
+                           ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result) try
+{
+    IPX_ENTER(ctx);
+    if (!pl || n < 0 || !files || !status || !result) { set_error("ipx_plan_run_jpeg_jpeg: bad argument"); return IPX_ERR_INVALID; }
+    return run_jpeg_jpeg("ipx_plan_run_jpeg_jpeg", ctx, pl, n, files, nullptr, quality, resize_out, thumb_out, wm_out, status, result);
+}
+IPX_CATCH_STATUS
+
+int ipx_plan_run_jpeg_jpeg_texts(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, const ipx_text *texts, int quality,
+                                 ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result) try
+{
+    IPX_ENTER(ctx);
+    if (!pl || n < 0 || !files || !status || !result) { set_error("ipx_plan_run_jpeg_jpeg_texts: bad argument"); return IPX_ERR_INVALID; }
+    *result = nullptr;
+    const int rc = leg_texts_check("ipx_plan_run_jpeg_jpeg_texts", pl, texts, n);
+    if (rc) return rc;
+    return run_jpeg_jpeg("ipx_plan_run_jpeg_jpeg_texts", ctx, pl, n, files, texts, quality, resize_out, thumb_out, wm_out, status, result);
 }
 IPX_CATCH_STATUS
 

@@ -215,6 +215,41 @@ __global__ __launch_bounds__(256) void composite_kernel(uint8_t *dst, int dstrid
     }
 }
 
+// composite_kernel with everything that is per batch there made per frame: frame z of the launch draws text map[z] (first + z without a
+// map) of one text set -- a descriptor table and ONE glyph table all texts share (ipx_textset, ipx_runtime.hip).  The grid spans the
+// largest clipped box of the chunk; a block outside its own frame's box leaves before it loads anything (blockIdx and the descriptor
+// are uniform over the block, so no barrier is skipped by part of a wave), and a text with an empty box costs nothing.
+__global__ __launch_bounds__(256) void composite_texts_kernel(uint8_t *dst, int dstride, size_t frame_stride,
+                                                              const DevText *__restrict__ texts, const DevGlyph *__restrict__ glyphs,
+                                                              const int *__restrict__ map, int first)
+{
+    __shared__ DevGlyph tab[kMaxGlyphs];
+    const DevText T = texts[map ? map[blockIdx.z] : first + (int)blockIdx.z];
+    const Rect bbox = T.bbox;
+    if ((int)(blockIdx.x * 64) >= bbox.x1 - bbox.x0 || (int)(blockIdx.y * (4 * kCompositeRows)) >= bbox.y1 - bbox.y0) return;
+    const DevGlyph *gl = glyphs + T.first;
+    const int n = T.n;
+    const uint32_t sr = T.col[0], sg = T.col[1], sb = T.col[2], sa = T.col[3];
+    const int lt = (int)(threadIdx.y * 64 + threadIdx.x);
+    const int x = bbox.x0 + (int)(blockIdx.x * 64 + threadIdx.x);
+    const int ybase = bbox.y0 + (int)(blockIdx.y * (4 * kCompositeRows) + threadIdx.y);
+    uint8_t *frame = dst + blockIdx.z * frame_stride;
+    uint32_t d[kCompositeRows][1], d0[kCompositeRows];
+#pragma unroll
+    for (int r = 0; r < kCompositeRows; r++) {
+        const int y = ybase + 4 * r;
+        d0[r] = d[r][0] = x < bbox.x1 && y < bbox.y1 ? *(const uint32_t *)(frame + (size_t)y * dstride + (size_t)x * 4) : 0u;
+    }
+    for (int g = lt; g < n; g += 256) tab[g] = gl[g];
+    __syncthreads();
+    glyph_walk<1, kCompositeRows, 4>(tab, n, x, ybase, bbox, d, sr, sg, sb, sa);
+#pragma unroll
+    for (int r = 0; r < kCompositeRows; r++) {
+        const int y = ybase + 4 * r;
+        if (x < bbox.x1 && y < bbox.y1 && d[r][0] != d0[r]) *(uint32_t *)(frame + (size_t)y * dstride + (size_t)x * 4) = d[r][0];
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -385,6 +420,16 @@ hipError_t launch_composite(uint8_t *dst, int dstride, size_t frame_stride, int 
     dim3 block(64, 4), grid((bbox.dx() + 63) / 64, (bbox.dy() + 4 * kCompositeRows - 1) / (4 * kCompositeRows), nframes);
     hipLaunchKernelGGL(composite_kernel, grid, block, 0, s, dst, dstride, frame_stride, glyphs_dev, n,
                        bbox, sr, sg, sb, sa);
+    return hipGetLastError();
+}
+
+// one launch for nframes frames and any number of texts; (bw, bh): the largest clipped box among the frames' texts, known to the host
+hipError_t launch_composite_texts(uint8_t *dst, int dstride, size_t frame_stride, int nframes, const DevText *texts_dev,
+                                  const DevGlyph *glyphs_dev, const int *map_dev, int first, int bw, int bh, hipStream_t s)
+{
+    if (nframes <= 0 || bw <= 0 || bh <= 0) return hipSuccess;
+    dim3 block(64, 4), grid((bw + 63) / 64, (bh + 4 * kCompositeRows - 1) / (4 * kCompositeRows), nframes);
+    hipLaunchKernelGGL(composite_texts_kernel, grid, block, 0, s, dst, dstride, frame_stride, texts_dev, glyphs_dev, map_dev, first);
     return hipGetLastError();
 }
 

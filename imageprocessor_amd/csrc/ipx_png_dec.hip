@@ -828,11 +828,12 @@ extern "C" {
 // files, at most ~4 GiB of frames): upload, CRC, inflate and unfilter into HBM; then per chunk of IPX_HOST_CHUNK_PNG frames the
 // operators on frames of that kind (run_dev_src) and png.Encode of all three outputs.  The operators run on every slot of a chunk (a failed file's slot
 // holds whatever its frame holds); only OK files' streams are handed out.
-int ipx_plan_run_png_png(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, ipx_bytes *resize_out, ipx_bytes *thumb_out,
-                         ipx_bytes *wm_out, int *status, ipx_jpeg_result **result) try
+// (the body of ipx_plan_run_png_png -- texts == NULL: no text launch -- and of ipx_plan_run_png_png_texts, where texts[i] is drawn on
+// file i's watermark frame between the operators and the encoder: one text set per call; the files are sorted by kind here, so the
+// frames of a chunk take their texts through the chunk's own slice of idx)
+static int run_png_png(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, const ipx_text *texts,
+                       ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result)
 {
-    IPX_ENTER(ctx);
-    if (!pl || n < 0 || !files || !status || !result) { set_error("ipx_plan_run_png_png: bad argument"); return IPX_ERR_INVALID; }
     *result = nullptr;
     const int sw = pl->p.sw, sh = pl->p.sh;
     const PlanOutputs outs(pl, resize_out, thumb_out, wm_out, Codec::Png, Codec::Png, Codec::Png);
@@ -848,6 +849,9 @@ int ipx_plan_run_png_png(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_byte
     ResultOwner res(ctx);
     LaneLease lane(ctx);
     hipStream_t s = lane->stream;
+    ipx_textset ts;
+    const bool draw = texts && pl->p.do_watermark && outs.o[2].fs;
+    if (draw && (rc = textset_build(s, who, texts, n, outs.o[2].w, outs.o[2].h, &ts))) return rc;
     for (int kind = 0; kind < kPngKinds; kind++) {
         std::vector<int> of_kind;
         for (int i = 0; i < n; i++)
@@ -879,6 +883,8 @@ int ipx_plan_run_png_png(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_byte
                 const PlanOutputs::Frames f = outs.place(dout, cm);
                 const BatchSrc d = packed_src(src_of_png(kind), dfr + fs * c0, sw * kb, fs, dpal ? dpal + (size_t)1024 * c0 : nullptr);
                 rc = run_dev_src(ctx, s, pl, cm, d, f.dev[0], outs.o[0].fs, f.dev[1], outs.o[1].fs, f.dev[2], outs.o[2].fs);
+                // (idx outlives the group's wait for the stream, and with it the copy of this slice)
+                if (!rc && draw) rc = dev_composite_texts(s, &omem, f.dev[2], outs.o[2].w * 4, outs.o[2].fs, cm, ts, 0, idx.data() + c0);
                 if (!rc) rc = encode_outputs(ctx, s, outs, f, cm, 0, 0, status, res, idx.data() + c0);
                 if (rc) return rc;
             }
@@ -886,6 +892,26 @@ int ipx_plan_run_png_png(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_byte
     }
     *result = res.release();
     return IPX_OK;
+}
+
+int ipx_plan_run_png_png(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, ipx_bytes *resize_out, ipx_bytes *thumb_out,
+                         ipx_bytes *wm_out, int *status, ipx_jpeg_result **result) try
+{
+    IPX_ENTER(ctx);
+    if (!pl || n < 0 || !files || !status || !result) { set_error("ipx_plan_run_png_png: bad argument"); return IPX_ERR_INVALID; }
+    return run_png_png("ipx_plan_run_png_png", ctx, pl, n, files, nullptr, resize_out, thumb_out, wm_out, status, result);
+}
+IPX_CATCH_STATUS
+
+int ipx_plan_run_png_png_texts(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, const ipx_text *texts, ipx_bytes *resize_out,
+                               ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result) try
+{
+    IPX_ENTER(ctx);
+    if (!pl || n < 0 || !files || !status || !result) { set_error("ipx_plan_run_png_png_texts: bad argument"); return IPX_ERR_INVALID; }
+    *result = nullptr;
+    const int rc = leg_texts_check("ipx_plan_run_png_png_texts", pl, texts, n);
+    if (rc) return rc;
+    return run_png_png("ipx_plan_run_png_png_texts", ctx, pl, n, files, texts, resize_out, thumb_out, wm_out, status, result);
 }
 IPX_CATCH_STATUS
 

@@ -41,6 +41,10 @@ struct PoolOps {                 // a deep copy of ipx_pool_ops: the caller may 
 struct JobState {
     ipx_job job{};
     PoolOps ops;
+    // ipx_job::texts, deep-copied like the glyphs of ops: text i's glyphs and their masks (rows tight); job.texts points at `texts`
+    std::vector<ipx_text> texts;
+    std::vector<std::vector<ipx_glyph>> text_glyphs;
+    std::vector<std::vector<std::vector<uint8_t>>> text_masks;
     std::vector<ipx_jpeg_result *> results;   // file jobs: pinned blocks the output streams live in, per slot that produced them
     std::vector<ipx_ctx *> result_ctx;        // (chunks append under the job's State::mu)
 };
@@ -116,6 +120,29 @@ int copy_ops(const ipx_pool_ops &in, PoolOps *out)
     out->p.glyphs = out->glyphs.data();
     out->key = std::move(key);
     return IPX_OK;
+}
+
+// (texts_check has seen the list)
+void copy_texts(const ipx_text *in, int n, JobState *j)
+{
+    j->texts.assign(in, in + n);
+    j->text_glyphs.resize(n);
+    j->text_masks.resize(n);
+    for (int t = 0; t < n; t++) {
+        std::vector<ipx_glyph> &gl = j->text_glyphs[t];
+        gl.assign(in[t].glyphs, in[t].glyphs + in[t].n_glyphs);
+        j->text_masks[t].resize(gl.size());
+        for (size_t i = 0; i < gl.size(); i++) {
+            ipx_glyph &g = gl[i];
+            std::vector<uint8_t> &m = j->text_masks[t][i];
+            m.resize((size_t)g.mw * g.mh);
+            for (int y = 0; y < g.mh; y++) memcpy(m.data() + (size_t)y * g.mw, g.mask + (size_t)y * g.mstride, g.mw);
+            g.mask = m.data();
+            g.mstride = g.mw;
+        }
+        j->texts[t].glyphs = gl.empty() ? nullptr : gl.data();
+    }
+    j->job.texts = j->texts.data();
 }
 
 struct Feeder {                     // what one feeder thread owns; made and destroyed on that thread
@@ -205,10 +232,20 @@ int run_chunk(Slot &s, Feeder &f, JobState &j, int i0, int m, ipx_jpeg_result **
         const ipx_job &q = j.job;
         ipx_bytes *ores = q.resize_jpeg ? q.resize_jpeg + i0 : nullptr, *oth = q.thumb_jpeg ? q.thumb_jpeg + i0 : nullptr;
         ipx_bytes *owm = q.wm_jpeg ? q.wm_jpeg + i0 : nullptr;
+        const ipx_text *tx = q.texts ? q.texts + i0 : nullptr;      // a text per file: the legs' _texts entries on the chunk's own slice
         switch (q.kind) {     // (every one returns with the chunk's GPU work finished)
-        case IPX_JOB_JPEG: rc = ipx_plan_run_jpeg_jpeg(s.ctx, plan, m, q.files + i0, q.quality, ores, oth, owm, q.status + i0, res); break;
-        case IPX_JOB_PNG: rc = ipx_plan_run_png_png(s.ctx, plan, m, q.files + i0, ores, oth, owm, q.status + i0, res); break;
-        case IPX_JOB_GIF: rc = ipx_plan_run_gif_gif(s.ctx, plan, m, q.files + i0, q.quality, ores, oth, owm, q.status + i0, res); break;
+        case IPX_JOB_JPEG:
+            rc = tx ? ipx_plan_run_jpeg_jpeg_texts(s.ctx, plan, m, q.files + i0, tx, q.quality, ores, oth, owm, q.status + i0, res)
+                    : ipx_plan_run_jpeg_jpeg(s.ctx, plan, m, q.files + i0, q.quality, ores, oth, owm, q.status + i0, res);
+            break;
+        case IPX_JOB_PNG:
+            rc = tx ? ipx_plan_run_png_png_texts(s.ctx, plan, m, q.files + i0, tx, ores, oth, owm, q.status + i0, res)
+                    : ipx_plan_run_png_png(s.ctx, plan, m, q.files + i0, ores, oth, owm, q.status + i0, res);
+            break;
+        case IPX_JOB_GIF:
+            rc = tx ? ipx_plan_run_gif_gif_texts(s.ctx, plan, m, q.files + i0, tx, q.quality, ores, oth, owm, q.status + i0, res)
+                    : ipx_plan_run_gif_gif(s.ctx, plan, m, q.files + i0, q.quality, ores, oth, owm, q.status + i0, res);
+            break;
         default: rc = run_pixel_chunk(s, f, j, plan, i0, m);
         }
         if (!cached) {
@@ -253,6 +290,12 @@ int job_check(const ipx_job *job)
     if (!job || job->n < 0) { set_error("ipx_job_submit: bad job"); return IPX_ERR_INVALID; }
     const ipx_pool_ops &o = job->ops;
     if (o.sw <= 0 || o.sh <= 0) { set_error("ipx_job_submit: frame size %dx%d", o.sw, o.sh); return IPX_ERR_INVALID; }
+    if (job->texts) {
+        if (!is_file_job(job->kind)) { set_error("ipx_job_submit: texts go with file jobs only (a text per decoded frame is not offered)"); return IPX_ERR_INVALID; }
+        if (o.glyphs || o.n_glyphs) { set_error("ipx_job_submit: a job with texts must have ops.glyphs == NULL (the plan only copies the watermark frame)"); return IPX_ERR_INVALID; }
+        const int rc = texts_check("ipx_job_submit", job->texts, job->n);
+        if (rc) return rc;
+    }
     if (const int bpp = pixel_job_bpp(job->kind)) {
         if (job->n && (!job->src || (long long)job->sstride < (long long)o.sw * bpp)) { set_error("ipx_job_submit: bad source frames"); return IPX_ERR_INVALID; }
         if (!frame_span_ok(o.sw, o.sh, job->sstride, bpp) || (bpp != 1 && !frame_span_ok(o.sw, o.sh, (long long)o.sw * std::max(bpp, 4), std::max(bpp, 4)))) {
@@ -356,6 +399,7 @@ int ipx_job_submit(ipx_pool *pool, const ipx_job *job, ipx_ticket *ticket) try
     j->job = *job;
     rc = copy_ops(job->ops, &j->ops);
     if (rc) return rc;
+    if (job->texts) copy_texts(job->texts, job->n, j);
     const bool of_files = is_file_job(job->kind);
     if (of_files)
         for (int i = 0; i < job->n; i++) job->status[i] = IPX_OK;

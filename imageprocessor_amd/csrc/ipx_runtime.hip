@@ -162,6 +162,41 @@ int dev_scale(ipx_ctx *ctx, hipStream_t s, int *flag, uint8_t *dst, int dw, int 
     return dev_scale_src(ctx, s, flag, dst, dw, dh, dstride, dr, rgba_src(src, sw, sh, sstride), sr, op);
 }
 
+// image/draw's clipping of each glyph's dr against a dw x dh frame and its mask, mp moved with it (draw_clip): the surviving glyphs
+// are appended to *tab with their masks at masks_dev + mask_off; returns their bounding box (all zeros when none survives).  The one
+// clipper of glyph sets (glyphs_for_frame) and text sets (textset_build).
+Rect clip_glyphs(const GlyphHost *g, size_t n, const uint8_t *masks_dev, int dw, int dh, std::vector<DevGlyph> *tab)
+{
+    Rect bb{0, 0, 0, 0};
+    const size_t before = tab->size();
+    for (size_t i = 0; i < n; i++) {
+        Rect r = g[i].dr;
+        int spx = 0, spy = 0, mpx = g[i].mpx, mpy = g[i].mpy;
+        if (!draw_clip(r, dw, dh, false, 0, 0, spx, spy, true, g[i].mw, g[i].mh, mpx, mpy)) continue;
+        DevGlyph d;
+        d.mask = masks_dev + g[i].mask_off + (size_t)mpy * g[i].mw + mpx;
+        d.mstride = g[i].mw;
+        d.x0 = r.x0; d.y0 = r.y0; d.x1 = r.x1; d.y1 = r.y1;
+        if (tab->size() == before) bb = r;
+        else {
+            bb.x0 = std::min(bb.x0, r.x0); bb.y0 = std::min(bb.y0, r.y0);
+            bb.x1 = std::max(bb.x1, r.x1); bb.y1 = std::max(bb.y1, r.y1);
+        }
+        tab->push_back(d);
+    }
+    return bb;
+}
+
+// one glyph of the ABI into the packed blob (rows tight): false for a bad mask
+bool pack_glyph(const ipx_glyph &g, std::vector<uint8_t> *blob, GlyphHost *h)
+{
+    if (g.mw < 0 || g.mh < 0 || (g.mw && g.mh && (!g.mask || g.mstride < g.mw))) return false;
+    h->mask_off = blob->size();
+    h->mw = g.mw; h->mh = g.mh; h->dr = to_rect(g.dr); h->mpx = g.mpx; h->mpy = g.mpy;
+    for (int y = 0; y < g.mh; y++) blob->insert(blob->end(), g.mask + (size_t)y * g.mstride, g.mask + (size_t)y * g.mstride + g.mw);
+    return true;
+}
+
 // clip every glyph against a dw x dh frame (image/draw.clip) and cache the device table
 int glyphs_for_frame(const ipx_glyphset *gs, int dw, int dh, ClippedGlyphs *out)
 {
@@ -169,22 +204,7 @@ int glyphs_for_frame(const ipx_glyphset *gs, int dw, int dh, ClippedGlyphs *out)
     auto it = gs->clipped.find({dw, dh});
     if (it != gs->clipped.end()) { *out = it->second; return IPX_OK; }
     std::vector<DevGlyph> tab;
-    Rect bb{0, 0, 0, 0};
-    for (const GlyphHost &g : gs->g) {
-        Rect r = g.dr;
-        int spx = 0, spy = 0, mpx = g.mpx, mpy = g.mpy;
-        if (!draw_clip(r, dw, dh, false, 0, 0, spx, spy, true, g.mw, g.mh, mpx, mpy)) continue;
-        DevGlyph d;
-        d.mask = gs->masks_dev + g.mask_off + (size_t)mpy * g.mw + mpx;
-        d.mstride = g.mw;
-        d.x0 = r.x0; d.y0 = r.y0; d.x1 = r.x1; d.y1 = r.y1;
-        if (tab.empty()) bb = r;
-        else {
-            bb.x0 = std::min(bb.x0, r.x0); bb.y0 = std::min(bb.y0, r.y0);
-            bb.x1 = std::max(bb.x1, r.x1); bb.y1 = std::max(bb.y1, r.y1);
-        }
-        tab.push_back(d);
-    }
+    const Rect bb = clip_glyphs(gs->g.data(), gs->g.size(), gs->masks_dev, dw, dh, &tab);
     ClippedGlyphs c;
     c.n = (int)tab.size();
     c.bbox = bb;
@@ -210,6 +230,100 @@ int dev_composite(hipStream_t s, uint8_t *dst, int dw, int dh, int dstride, size
 }
 
 }  // namespace
+
+// ---- text sets: one text per frame of a batch -------------------------------------------------------------
+int texts_check(const char *who, const ipx_text *texts, int n)
+{
+    if (n < 0 || (n && !texts)) { set_error("%s: bad text list", who); return IPX_ERR_INVALID; }
+    for (int t = 0; t < n; t++) {
+        const ipx_text &x = texts[t];
+        if (x.n_glyphs < 0 || (x.n_glyphs && !x.glyphs)) { set_error("%s: text %d has a bad glyph list", who, t); return IPX_ERR_INVALID; }
+        if (x.n_glyphs > kMaxGlyphs) { set_error("%s: text %d has %d glyphs, the limit is %d", who, t, x.n_glyphs, kMaxGlyphs); return IPX_ERR_UNSUPPORTED; }
+        for (int i = 0; i < x.n_glyphs; i++) {
+            const ipx_glyph &g = x.glyphs[i];
+            if (g.mw < 0 || g.mh < 0 || (g.mw && g.mh && (!g.mask || g.mstride < g.mw))) { set_error("%s: glyph %d of text %d has a bad mask", who, i, t); return IPX_ERR_INVALID; }
+        }
+    }
+    return IPX_OK;
+}
+
+int textset_build(hipStream_t s, const char *who, const ipx_text *texts, int n, int w, int h, ipx_textset *ts)
+{
+    int rc = texts_check(who, texts, n);
+    if (rc) return rc;
+    if (w < 0 || h < 0) { set_error("%s: bad frame size", who); return IPX_ERR_INVALID; }
+    std::vector<uint8_t> blob;
+    std::vector<GlyphHost> gh;
+    std::vector<int> start(n + 1, 0);
+    for (int t = 0; t < n; t++) {
+        for (int i = 0; i < texts[t].n_glyphs; i++) {
+            GlyphHost g;
+            (void)pack_glyph(texts[t].glyphs[i], &blob, &g);      // (texts_check has seen the masks)
+            gh.push_back(g);
+        }
+        start[t + 1] = (int)gh.size();
+    }
+    ts->mem.s = s;
+    ts->w = w; ts->h = h; ts->n = n;
+    uint8_t *masks_dev = nullptr;
+    IPX_HIP(ts->mem.get(&masks_dev, blob.size()));
+    std::vector<DevGlyph> tab;
+    std::vector<DevText> desc(n);
+    ts->bbox.assign(n, Rect{0, 0, 0, 0});
+    for (int t = 0; t < n; t++) {
+        DevText &d = desc[t];
+        d.first = (int)tab.size();
+        d.bbox = ts->bbox[t] = clip_glyphs(gh.data() + start[t], (size_t)(start[t + 1] - start[t]), masks_dev, w, h, &tab);
+        d.n = (int)tab.size() - d.first;
+        for (int c = 0; c < 4; c++) d.col[c] = (uint16_t)(texts[t].col[c] * 0x101u);
+    }
+    IPX_HIP(ts->mem.get(&ts->glyphs_dev, tab.size() * sizeof(DevGlyph)));
+    IPX_HIP(ts->mem.get(&ts->texts_dev, desc.size() * sizeof(DevText)));
+    if (!blob.empty()) IPX_HIP(hipMemcpyAsync(masks_dev, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
+    if (!tab.empty()) IPX_HIP(hipMemcpyAsync(ts->glyphs_dev, tab.data(), tab.size() * sizeof(DevGlyph), hipMemcpyHostToDevice, s));
+    if (!desc.empty()) IPX_HIP(hipMemcpyAsync(ts->texts_dev, desc.data(), desc.size() * sizeof(DevText), hipMemcpyHostToDevice, s));
+    IPX_HIP(hipStreamSynchronize(s));
+    return IPX_OK;
+}
+
+int dev_composite_texts(hipStream_t s, AsyncFree *mem, uint8_t *dst, int dstride, size_t frame_stride, int n_frames, const ipx_textset &ts,
+                        int first, const int *map)
+{
+    if (n_frames <= 0) return IPX_OK;
+    if (!map && (first < 0 || (long long)first + n_frames > ts.n)) {
+        set_error("composite texts: frames %d .. %lld of a set of %d texts", first, (long long)first + n_frames, ts.n);
+        return IPX_ERR_INVALID;
+    }
+    int bw = 0, bh = 0;
+    for (int z = 0; z < n_frames; z++) {
+        const int t = map ? map[z] : first + z;
+        if (t < 0 || t >= ts.n) { set_error("composite texts: frame %d names text %d of %d", z, t, ts.n); return IPX_ERR_INVALID; }
+        const Rect &b = ts.bbox[t];
+        if (b.empty()) continue;
+        bw = std::max(bw, b.dx()); bh = std::max(bh, b.dy());
+    }
+    if (!bw || !bh) return IPX_OK;
+    int *map_dev = nullptr;
+    if (map) {
+        if (!mem) { set_error("composite texts: a frame-to-text map needs scratch"); return IPX_ERR_INVALID; }
+        IPX_HIP(mem->get(&map_dev, (size_t)n_frames * sizeof(int)));
+        IPX_HIP(hipMemcpyAsync(map_dev, map, (size_t)n_frames * sizeof(int), hipMemcpyHostToDevice, s));
+    }
+    for (int z0 = 0; z0 < n_frames; z0 += 65535)       // (the grid's z)
+        IPX_HIP(launch_composite_texts(dst + (size_t)z0 * frame_stride, dstride, frame_stride, std::min(65535, n_frames - z0), ts.texts_dev,
+                                       ts.glyphs_dev, map_dev ? map_dev + z0 : nullptr, first + z0, bw, bh, s));
+    return IPX_OK;
+}
+
+int leg_texts_check(const char *who, const ipx_plan *pl, const ipx_text *texts, int n)
+{
+    if (!texts) { set_error("%s: bad argument", who); return IPX_ERR_INVALID; }
+    if (pl->p.glyphs) {
+        set_error("%s: the plan carries a glyph set of its own; per-file texts need a plan created with glyphs == NULL (copy only)", who);
+        return IPX_ERR_INVALID;
+    }
+    return texts_check(who, texts, n);
+}
 
 // =============================================================================================
 extern "C" {
@@ -655,15 +769,12 @@ int ipx_glyphset_create(ipx_ctx *ctx, const ipx_glyph *glyphs, int n, const uint
     std::vector<uint8_t> blob;
     for (int i = 0; i < n; i++) {
         const ipx_glyph &g = glyphs[i];
-        if (g.mw < 0 || g.mh < 0 || (g.mw && g.mh && (!g.mask || g.mstride < g.mw))) {
+        GlyphHost h;
+        if (!pack_glyph(g, &blob, &h)) {
             set_error("ipx_glyphset_create: glyph %d has a bad mask", i);
             delete gs;
             return IPX_ERR_INVALID;
         }
-        GlyphHost h;
-        h.mask_off = blob.size();
-        h.mw = g.mw; h.mh = g.mh; h.dr = to_rect(g.dr); h.mpx = g.mpx; h.mpy = g.mpy;
-        for (int y = 0; y < g.mh; y++) blob.insert(blob.end(), g.mask + (size_t)y * g.mstride, g.mask + (size_t)y * g.mstride + g.mw);
         gs->g.push_back(h);
     }
     gs->masks_bytes = blob.size();
@@ -698,6 +809,44 @@ int ipx_dev_composite_glyphs_rgba8(ipx_ctx *ctx, void *stream, uint8_t *dst, int
     IPX_FRAME("ipx_dev_composite_glyphs_rgba8", "destination", dst, dw, dh, dstride);
     IPX_DEV_OUT("ipx_dev_composite_glyphs_rgba8", "destination", dst, (unsigned)dstride);
     return dev_composite(stream ? (hipStream_t)stream : ctx->stream, dst, dw, dh, dstride, 0, 1, gs);
+}
+IPX_CATCH_STATUS
+
+int ipx_textset_create(ipx_ctx *ctx, void *stream, const ipx_text *texts, int n, int w, int h, ipx_textset **out) try
+{
+    IPX_ENTER(ctx);
+    if (!out) { set_error("ipx_textset_create: bad argument"); return IPX_ERR_INVALID; }
+    *out = nullptr;
+    ipx_textset *ts = new (std::nothrow) ipx_textset;
+    if (!ts) { set_error("out of memory"); return IPX_ERR_NOMEM; }
+    ts->device = ctx->device;
+    const int rc = textset_build(stream ? (hipStream_t)stream : ctx->stream, "ipx_textset_create", texts, n, w, h, ts);
+    if (rc) { delete ts; return rc; }
+    *out = ts;
+    return IPX_OK;
+}
+IPX_CATCH_STATUS
+
+void ipx_textset_destroy(ipx_ctx *ctx, ipx_textset *ts)
+{
+    if (!ts) return;
+    (void)hipSetDevice(ctx ? ctx->device : ts->device);
+    delete ts;       // (its memory is freed in the order of the stream it was created on)
+}
+
+int ipx_dev_composite_texts_rgba8(ipx_ctx *ctx, void *stream, uint8_t *dst, int w, int h, int dstride, size_t frame_stride, int n_frames,
+                                  const ipx_textset *ts, int first, const int32_t *map) try
+{
+    IPX_ENTER(ctx);
+    if (!ts || n_frames < 0) { set_error("ipx_dev_composite_texts_rgba8: bad argument"); return IPX_ERR_INVALID; }
+    if (w != ts->w || h != ts->h) { set_error("ipx_dev_composite_texts_rgba8: the text set was clipped for %dx%d frames, not %dx%d", ts->w, ts->h, w, h); return IPX_ERR_INVALID; }
+    IPX_FRAME("ipx_dev_composite_texts_rgba8", "destination", dst, w, h, dstride);
+    IPX_DEV_OUT("ipx_dev_composite_texts_rgba8", "destination", dst, (unsigned)dstride, frame_stride);
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    AsyncFree mem{s, {}};
+    const int rc = dev_composite_texts(s, &mem, dst, dstride, frame_stride, n_frames, *ts, first, (const int *)map);
+    if (map) (void)hipStreamSynchronize(s);     // the caller's map is read by a copy on the stream: done with it on return
+    return rc;
 }
 IPX_CATCH_STATUS
 

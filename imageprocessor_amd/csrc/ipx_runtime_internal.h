@@ -296,6 +296,27 @@ struct AsyncFree {
     }
 };
 
+// n texts clipped against one frame size (ipx_textset_create; the compressed-in / compressed-out legs build one per call on their own
+// stream): every text's clipped glyphs in ONE table, every mask in one blob, one descriptor per text.  The device memory is
+// stream-ordered and goes, in stream order, with the object.
+struct ipx_textset {
+    int device = 0, w = 0, h = 0, n = 0;
+    std::vector<Rect> bbox;             // per text, as in its descriptor: the host sizes the grid by the largest of a launch
+    DevText *texts_dev = nullptr;
+    DevGlyph *glyphs_dev = nullptr;
+    AsyncFree mem{nullptr, {}};
+};
+// host only: IPX_ERR_INVALID for a bad list or mask, IPX_ERR_UNSUPPORTED for a text of more than kMaxGlyphs glyphs
+int texts_check(const char *who, const ipx_text *texts, int n);
+// texts_check, then clip, pack and upload on `s`; returns with the uploads finished (the host staging is the call's own)
+int textset_build(hipStream_t s, const char *who, const ipx_text *texts, int n, int w, int h, ipx_textset *ts);
+// ONE launch (per 65535 frames) of composite_texts_kernel: frame z takes text map[z], or first + z.  `map` is host memory, uploaded into
+// *mem and read by that copy until `s` has been waited for; indices are checked here, before the launch.
+int dev_composite_texts(hipStream_t s, AsyncFree *mem, uint8_t *dst, int dstride, size_t frame_stride, int n_frames, const ipx_textset &ts,
+                        int first, const int *map);
+// what a _texts leg checks before it does anything: the plan is copy-only (no glyph set of its own) and the texts are well-formed
+int leg_texts_check(const char *who, const ipx_plan *pl, const ipx_text *texts, int n);
+
 // Waits for its stream on every way out of the scope.  Declare it AFTER every host buffer that copies queued on the stream read or write:
 // locals go in reverse order, so the wait then comes before those buffers are destroyed.
 struct StreamSync {

@@ -200,6 +200,26 @@ void ipx_glyphset_destroy(ipx_ctx *ctx, ipx_glyphset *gs);
 int ipx_dev_composite_glyphs_rgba8(ipx_ctx *ctx, void *stream, uint8_t *dst, int dw, int dh,
                                    int dstride, const ipx_glyphset *gs);
 
+/* ---- one text per frame ------------------------------------------------------------------------
+ * The upload form takes the watermark text from the user (watermark_text, internal/http-server/handler/image/image.go:249-251), so
+ * the text is a property of each upload like the frame size.  A text set holds n texts -- each one file's DrawString (its DrawMask
+ * calls) and parseColor -- clipped against w x h exactly as a glyph set is clipped per frame size (image/draw's clipping of dr against
+ * the frame and the mask, mp moved with it), all masks in one block and all descriptors in one table in HBM, uploaded on `stream`
+ * (NULL: the context's stream; the call returns when the uploads are done; the stream has to outlive the set).  A text of more than 256
+ * glyphs refuses the whole set with IPX_ERR_UNSUPPORTED, as ipx_glyphset_create does; a bad mask (mstride < mw, a null mask with
+ * area) is IPX_ERR_INVALID; n_glyphs == 0 is a valid text that draws nothing.
+ * ipx_dev_composite_texts_rgba8: n_frames frames of w x h (the set's size) at dst + z * frame_stride; frame z takes text map[z], or
+ * text first + z when map is NULL -- ONE launch however many different texts there are; a frame whose text has nothing left inside the
+ * frame costs no loads and no stores.  dst, dstride and frame_stride REQUIRED multiples of 4 (the layout rule above: IPX_ERR_INVALID
+ * before any launch); no byte outside the frames, and no pixel the text does not change, is written.  `map` is host memory (n_frames
+ * entries, each below the set's n, checked before the launch); with a map the call waits for the stream before it returns. */
+typedef struct { const ipx_glyph *glyphs; int32_t n_glyphs; uint8_t col[4]; } ipx_text;   /* one file's DrawString + parseColor */
+typedef struct ipx_textset ipx_textset;
+int ipx_textset_create(ipx_ctx *ctx, void *stream, const ipx_text *texts, int n, int w, int h, ipx_textset **out);
+void ipx_textset_destroy(ipx_ctx *ctx, ipx_textset *ts);
+int ipx_dev_composite_texts_rgba8(ipx_ctx *ctx, void *stream, uint8_t *dst, int w, int h, int dstride, size_t frame_stride,
+                                  int n_frames, const ipx_textset *ts, int first, const int32_t *map /* host, may be NULL */);
+
 /* ---- the batched worker path -------------------------------------------------------------------
  * Replaces (*ImageProcessor).Process (image_processor.go:39-102) between image.Decode (:47) and
  * the encoders (resize.go:78-91, thumbnail.go:68-81, watermark.go:66-79) for a batch of decoded
@@ -644,6 +664,20 @@ void ipx_png_frames_free(ipx_ctx *ctx, ipx_png_frames *owner);
 int ipx_plan_run_png_png(ipx_ctx *ctx, const ipx_plan *plan, int n, const ipx_bytes *files, ipx_bytes *resize_out, ipx_bytes *thumb_out,
                          ipx_bytes *wm_out, int *status, ipx_jpeg_result **result);
 
+/* ---- the three compressed-in / compressed-out legs with a text per file ----------------------------------
+ * As ipx_plan_run_jpeg_jpeg / _png_png / _gif_gif, with texts[i] drawn on files[i]'s watermark frame: the plan copies the frame
+ * (it must have been created with glyphs == NULL; a plan that carries a glyph set is refused with IPX_ERR_INVALID) and one launch per
+ * chunk of the leg draws every file's own text behind it (ipx_dev_composite_texts_rgba8), however many different texts the chunk
+ * holds.  The texts are checked first (the rules of ipx_textset_create) and uploaded once per call (the JPEG leg: once per part).  A
+ * plan without the watermark operator, or a null wm_out, checks the texts and draws nothing.  The resize and thumbnail streams are
+ * those of the plain legs. */
+int ipx_plan_run_jpeg_jpeg_texts(ipx_ctx *ctx, const ipx_plan *plan, int n, const ipx_bytes *files, const ipx_text *texts, int quality,
+                                 ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result);
+int ipx_plan_run_png_png_texts(ipx_ctx *ctx, const ipx_plan *plan, int n, const ipx_bytes *files, const ipx_text *texts,
+                               ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result);
+int ipx_plan_run_gif_gif_texts(ipx_ctx *ctx, const ipx_plan *plan, int n, const ipx_bytes *files, const ipx_text *texts, int quality,
+                               ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result);
+
 /* ---- one process, several GPUs, asynchronous jobs ----------------------------------------------------------
  * The reference worker is ONE process whose goroutines pull independent messages (worker.go:88-96, 112-149); it scales by
  * running more consumers, nothing is exchanged (kafka/consumer.go:23).  A pool is that shape behind the C ABI: one context per
@@ -715,6 +749,11 @@ typedef struct {
     const ipx_bytes *files; int32_t quality;
     ipx_bytes *resize_jpeg, *thumb_jpeg, *wm_jpeg;
     int32_t *status;
+    /* file jobs only: NULL, or n texts, texts[i] drawn on files[i]'s watermark frame (the job's chunks run the legs' _texts entries
+     * with texts + i0).  Then ops.glyphs must be NULL (IPX_ERR_INVALID otherwise, as for a pixel job with texts: a text per decoded
+     * frame is not offered); a text of more than 256 glyphs refuses the job (IPX_ERR_UNSUPPORTED).  Deep-copied at submit, like the
+     * glyphs of ops.  NULL: the job as it always was. */
+    const ipx_text *texts;
 } ipx_job;
 typedef uint64_t ipx_ticket;
 int ipx_job_submit(ipx_pool *pool, const ipx_job *job, ipx_ticket *ticket);     /* returns at once */
@@ -742,7 +781,12 @@ int ipx_pool_run_host(ipx_pool *pool, const ipx_job *jobs, int n_jobs);
  * share back (call it after fileRepo.SaveProcessed, image_processor.go:76), the blocks go with the group's last file.  At-least-once
  * delivery is unchanged: a goroutine commits its message only after its own ticket came back and its objects were saved.
  * cgo rule: the file bytes must stay valid (C-allocated for Go) until ipx_batcher_wait or ipx_batcher_release has returned for the
- * ticket; the operator description and its glyph masks are copied at submit.  Every entry is thread-safe. */
+ * ticket; the operator description and its glyph masks are copied at submit.  Every entry is thread-safe.
+ * IPX_BATCH_TEXTS=1 in the environment (read once, at ipx_batcher_create; unset or anything else: everything above, unchanged): the
+ * grouping key stops before the colour and the glyphs -- format, frame size, JPEG shape and operator parameters stay in it -- so files
+ * that differ only in their watermark text share a batch; each file keeps its own deep-copied text and the group goes out as one file
+ * job with ops.glyphs = NULL and ipx_job.texts set.  A file whose text has more than 256 glyphs is then refused at ipx_batcher_submit
+ * (IPX_ERR_UNSUPPORTED), alone, and never joins a group. */
 typedef struct ipx_batcher ipx_batcher;
 typedef struct {
     int32_t max_batch;      /* files per job; 0 = 256 (a part of ipx_plan_run_jpeg_jpeg) */

@@ -5,7 +5,9 @@ streams back.  Prints images/s and the p50 / p99 latency of a file (submit -> it
 --format png | gif: photo-like 1024x768 uploads of that format instead (the corpora of tools/bench_png_decode.py and
 tools/bench_gif_decode.py: Pillow-written RGB PNGs, 256-colour GIFs), resize 512x384 + thumbnail 64 as those tools ask for; mixed: the
 JPEG, PNG and GIF uploads in turn, each with its own size and operators.
-usage: tools/bench_batcher.py [--format jpeg|png|gif|mixed] [files per submitter] [max_batch] [max_wait_us] [submitters ...]"""
+--texts: every submitter watermarks with a text of its own (watermark_text of the upload form: 16 glyphs, its own seed), on every format.
+Without IPX_BATCH_TEXTS=1 in the environment such files never share a batch; with it they do (ipx_job.texts).
+usage: tools/bench_batcher.py [--format jpeg|png|gif|mixed] [--texts] [files per submitter] [max_batch] [max_wait_us] [submitters ...]"""
 import io
 import os
 import sys
@@ -27,6 +29,9 @@ if "--format" in argv:
     i = argv.index("--format")
     fmt = argv[i + 1]
     del argv[i:i + 2]
+own_texts = "--texts" in argv
+if own_texts:
+    argv.remove("--texts")
 if fmt not in ("jpeg", "png", "gif", "mixed"):
     raise SystemExit("bench_batcher: --format jpeg|png|gif|mixed")
 per = int(argv[0]) if len(argv) > 0 else 64
@@ -70,8 +75,20 @@ if fmt == "mixed":
 else:
     files = makers[fmt]()
 nf = len(files)
+_texts = {}
+
+
+def ops_of(f, k):
+    """the operators of upload f for submitter k: as they are, or with submitter k's own text on the watermark"""
+    if not own_texts:
+        return f[3]
+    if (k, f[1], f[2]) not in _texts:
+        _texts[(k, f[1], f[2])] = text_glyphs(f[1], f[2], seed=0xA8 + 1 + k)
+    return dict(f[3], glyphs=_texts[(k, f[1], f[2])], col=DEFAULT_COL)
+
+
 with ipx.Pool(devices=(0,)) as pool, ipx.Batcher(pool, max_batch=max_batch, max_wait_us=max_wait, quality=85) as b:
-    for t in [b.submit(files[i % nf][0], *files[i % nf][1:3], **files[i % nf][3]) for i in range(32)]:      # plans, glyph set, lanes warm
+    for t in [b.submit(files[i % nf][0], *files[i % nf][1:3], **ops_of(files[i % nf], i % max(subs))) for i in range(32)]:      # plans, glyph set, lanes warm
         b.wait(t)
     for S in subs:
         lat = []
@@ -83,7 +100,7 @@ with ipx.Pool(devices=(0,)) as pool, ipx.Batcher(pool, max_batch=max_batch, max_
             for i in range(per):
                 t0 = time.perf_counter()
                 f = files[(k + i) % nf]
-                st, out = b.wait(b.submit(f[0], f[1], f[2], **f[3]))
+                st, out = b.wait(b.submit(f[0], f[1], f[2], **ops_of(f, k)))
                 mine.append(time.perf_counter() - t0)
                 assert st == 0 and out["resize"]
             with mu:
@@ -96,7 +113,7 @@ with ipx.Pool(devices=(0,)) as pool, ipx.Batcher(pool, max_batch=max_batch, max_
         lat.sort()
         st = b.stats()
         nb = st["batches"] - before["batches"]
-        print("%s %3d submitters x %d files: %7.0f images/s; latency p50 %.2f ms, p99 %.2f ms; %d batches (mean %.1f files; %d by size, %d by timer, %d when idle)"
-              % (fmt, S, per, S * per / dt, lat[len(lat) // 2] * 1e3, lat[min(len(lat) - 1, int(len(lat) * 0.99))] * 1e3, nb, S * per / max(1, nb),
+        print("%s%s %3d submitters x %d files: %7.0f images/s; latency p50 %.2f ms, p99 %.2f ms; %d batches (mean %.1f files; %d by size, %d by timer, %d when idle)"
+              % (fmt, (" own texts, IPX_BATCH_TEXTS=%s" % os.environ.get("IPX_BATCH_TEXTS", "unset")) if own_texts else "", S, per, S * per / dt, lat[len(lat) // 2] * 1e3, lat[min(len(lat) - 1, int(len(lat) * 0.99))] * 1e3, nb, S * per / max(1, nb),
                  st["flushed_by_size"] - before["flushed_by_size"], st["flushed_by_timer"] - before["flushed_by_timer"],
                  st["flushed_when_idle"] - before["flushed_when_idle"]), flush=True)
