@@ -891,9 +891,9 @@ hipError_t launch_ks_fused(const KsFusedPlan &p, KsFusedArgs &a, const KsFix *fi
     *matched = true;
     const int n = (int)nitems;
     if (getenv("IPX_KS_DEBUG"))
-        fprintf(stderr, "[ipx ks] src %d nacc %d frames %d strips %d segs %d threads %d pitch %d dbuf %d lds %d (float pass: dbuf %d lds %d) | out0 ntap %d waves %d cpl %d wcols %d | out1 ntap %d waves %d cpl %d wcols %d\n", src, p.nacc,
+        fprintf(stderr, "[ipx ks] src %d nacc %d frames %d strips %d segs %d threads %d pitch %d dbuf %d lds %d (float pass: dbuf %d lds %d) | out0 ntap %d waves %d cpl %d wcols %d | out1 ntap %d waves %d cpl %d wcols %d | float pass: open_per_wave %d split %d %d\n", src, p.nacc,
                 a.nframes, a.nstrips, a.nseg, a.nthreads, a.pitch, p.dbuf, p.lds_bytes, p.fast.dbuf, p.fast.lds_bytes, a.o[0].ntap, a.o[0].waves, a.o[0].cpl, a.o[0].wcols, a.nout > 1 ? a.o[1].ntap : 0,
-                a.nout > 1 ? a.o[1].waves : 0, a.nout > 1 ? a.o[1].cpl : 0, a.nout > 1 ? a.o[1].wcols : 0);
+                a.nout > 1 ? a.o[1].waves : 0, a.nout > 1 ? a.o[1].cpl : 0, a.nout > 1 ? a.o[1].wcols : 0, p.fast.open_per_wave, a.o[0].split, a.nout > 1 ? a.o[1].split : 0);
     // the float pass where the source type has one and the caller brought lists: float kernel, the listed pixels in float64, then the
     // float64 kernel on the items the float kernel gave up
     bool fast = fix && fix->list && a.redo && (src == KS_RGBA || src == KS_YCC || src == KS_GRAY || src == KS_NRGBA || (src == KS_TAP64 && a.taps_le_alpha));
