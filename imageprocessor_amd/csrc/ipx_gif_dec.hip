@@ -365,7 +365,7 @@ static int run_gif_gif(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n,
         if (rc) return rc;
         if (!any_ok(status + i0, m)) continue;
         const PlanOutputs::Frames f = outs.place(dout, m);
-        rc = run_dev_src(ctx, s, pl, m, packed_src(kSrcPaletted, didx, sw, fsrc, dpal), f.dev[0], outs.o[0].fs, f.dev[1], outs.o[1].fs, f.dev[2], outs.o[2].fs);
+        rc = run_dev_src(ctx, s, pl, m, packed_src(kSrcPaletted, didx, sw, fsrc, dpal), outs.dst(f));
         if (!rc && draw) rc = dev_composite_texts(s, nullptr, f.dev[2], outs.o[2].w * 4, outs.o[2].fs, m, ts, i0, nullptr);
         if (!rc) rc = encode_outputs(ctx, s, outs, f, m, i0, quality, status, res);
         if (rc) return rc;

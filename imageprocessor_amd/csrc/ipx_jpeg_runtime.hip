@@ -288,10 +288,12 @@ void ResultOwner::adopt(ipx_jpeg_result *o)
 
 PlanOutputs::PlanOutputs(const ipx_plan *pl, ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, Codec res, Codec thumb, Codec wm)
 {
-    const ipx_plan_info &in = pl->info;
-    o[0] = {resize_out, in.resize_w, in.resize_h, resize_out ? align256(in.resize_bytes) : 0, 0, res};
-    o[1] = {thumb_out, in.thumb_w, in.thumb_h, thumb_out ? align256(in.thumb_bytes) : 0, 0, thumb};
-    o[2] = {wm_out, in.wm_w, in.wm_h, wm_out ? align256(in.wm_bytes) : 0, 0, wm};
+    ipx_bytes *const dst[kOuts] = {resize_out, thumb_out, wm_out};
+    const Codec codec[kOuts] = {res, thumb, wm};
+    for (int k = 0; k < kOuts; k++) {
+        const OutShape sh = out_shape(pl->info, k);
+        o[k] = {dst[k], sh.w, sh.h, dst[k] ? align256(sh.bytes) : 0, 0, codec[k]};
+    }
     for (Output &x : o)
         if (x.fs && x.codec == Codec::Jpeg) x.coef = align256(ipx_jpeg_coef_count(x.w, x.h) * 2);
 }
@@ -396,7 +398,7 @@ static int run_host_jpeg_impl(const char *who, ipx_ctx *ctx, const ipx_plan *pl,
             BatchSrc d;
             const hipError_t e = src_upload(host, L, i0, m, dsrc, chunk, l->stream, kCopyWholePlanes, &d);
             if (e != hipSuccess) { set_error("upload failed: %s", hipGetErrorString(e)); rc = IPX_ERR_HIP; break; }
-            rc = run_dev_src(ctx, l->stream, pl, m, d, f.dev[0], outs.o[0].fs, f.dev[1], outs.o[1].fs, f.dev[2], outs.o[2].fs);
+            rc = run_dev_src(ctx, l->stream, pl, m, d, outs.dst(f));
             if (!rc) rc = encode_outputs(ctx, l->stream, outs, f, m, i0, quality, nullptr, mine);
         }
         {
@@ -537,7 +539,7 @@ static int run_jpeg_jpeg_one(const char *who, ipx_ctx *ctx, const ipx_plan *pl, 
         if (planes.ratio == IPX_GRAY) d.type = kSrcGray;
         d.plane[0] += d.frame_stride[0] * i0;
         if (d.plane[1]) { d.plane[1] += d.frame_stride[1] * i0; d.plane[2] += d.frame_stride[1] * i0; }
-        rc = run_dev_src(ctx, s, pl, m, d, f.dev[0], outs.o[0].fs, f.dev[1], outs.o[1].fs, f.dev[2], outs.o[2].fs);
+        rc = run_dev_src(ctx, s, pl, m, d, outs.dst(f));
         if (!rc && draw) rc = dev_composite_texts(s, nullptr, f.dev[2], outs.o[2].w * 4, outs.o[2].fs, m, ts, i0, nullptr);
         if (!rc) rc = encode_outputs(ctx, s, outs, f, m, i0, quality, status, res);
     }

@@ -824,7 +824,7 @@ int ipx_plan_run_host_png(ipx_ctx *ctx, const ipx_plan *pl, int n, const uint8_t
         BatchSrc d;
         IPX_HIP(src_upload(host, L, i0, m, dsrc, m, s, kCopyFrameRows, &d));
         const PlanOutputs::Frames f = outs.place(dout, m);
-        int rc = run_dev_src(ctx, s, pl, m, d, f.dev[0], outs.o[0].fs, f.dev[1], outs.o[1].fs, f.dev[2], outs.o[2].fs);
+        int rc = run_dev_src(ctx, s, pl, m, d, outs.dst(f));
         if (!rc) rc = encode_outputs(ctx, s, outs, f, m, i0, 0, nullptr, res);
         if (rc) return rc;
     }

@@ -882,7 +882,7 @@ static int run_png_png(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n,
                 if (per_out) IPX_HIP(omem.get(&dout, per_out * cm));
                 const PlanOutputs::Frames f = outs.place(dout, cm);
                 const BatchSrc d = packed_src(src_of_png(kind), dfr + fs * c0, sw * kb, fs, dpal ? dpal + (size_t)1024 * c0 : nullptr);
-                rc = run_dev_src(ctx, s, pl, cm, d, f.dev[0], outs.o[0].fs, f.dev[1], outs.o[1].fs, f.dev[2], outs.o[2].fs);
+                rc = run_dev_src(ctx, s, pl, cm, d, outs.dst(f));
                 // (idx outlives the group's wait for the stream, and with it the copy of this slice)
                 if (!rc && draw) rc = dev_composite_texts(s, &omem, f.dev[2], outs.o[2].w * 4, outs.o[2].fs, cm, ts, 0, idx.data() + c0);
                 if (!rc) rc = encode_outputs(ctx, s, outs, f, cm, 0, 0, status, res, idx.data() + c0);

@@ -171,32 +171,18 @@ int feeder_reserve(Feeder &f, size_t bytes)
 int run_pixel_chunk(Slot &s, Feeder &f, const JobState &j, ipx_plan *plan, int i0, int m)
 {
     const ipx_job &q = j.job;
-    ipx_plan_info info;
-    int rc = ipx_plan_query(plan, &info);
-    if (rc) return rc;
     const BatchSrc host = packed_src(src_of_job(q.kind), q.src, q.sstride, q.src_frame_stride);      // (job_check has seen the arguments)
+    const BatchDst dst = job_dst(q).from(i0);
     const SrcLayout L = src_layout(plan, host);
+    const DstLayout D(plan, dst);
     const size_t fsrc = L.frame_bytes();
-    const size_t fres = q.resize_out ? align256(info.resize_bytes) : 0, fth = q.thumb_out ? align256(info.thumb_bytes) : 0;
-    const size_t fwm = q.wm_out ? align256(info.wm_bytes) : 0;
-    // outputs in pinned memory are written by the kernels themselves, over the link (run_host_packed in ipx_runtime.hip has the why)
-    uint8_t *vres = nullptr, *vth = nullptr, *vwm = nullptr;
-    bool direct = env_int("IPX_HOST_DIRECT", 1) != 0;
-    if (((uintptr_t)q.resize_out | (uintptr_t)q.thumb_out | (uintptr_t)q.wm_out | (fres ? q.resize_frame_stride : 0) | (fth ? q.thumb_frame_stride : 0) |
-         (fwm ? q.wm_frame_stride : 0)) & 15) direct = false;      // (16-byte stores: other strides go through the feeder's scratch)
-    if (direct && fres) direct = (vres = pinned_device_view(q.resize_out + (size_t)i0 * q.resize_frame_stride, q.resize_frame_stride * (m - 1) + info.resize_bytes)) != nullptr;
-    if (direct && fth) direct = (vth = pinned_device_view(q.thumb_out + (size_t)i0 * q.thumb_frame_stride, q.thumb_frame_stride * (m - 1) + info.thumb_bytes)) != nullptr;
-    if (direct && fwm) direct = (vwm = pinned_device_view(q.wm_out + (size_t)i0 * q.wm_frame_stride, q.wm_frame_stride * (m - 1) + info.wm_bytes)) != nullptr;
-    rc = feeder_reserve(f, (fsrc + (direct ? 0 : fres + fth + fwm)) * (size_t)m + 256);
+    // outputs in pinned memory are written by the kernels themselves, over the link (dst_direct in ipx_runtime.hip has the why)
+    BatchDst dout;
+    const bool direct = dst_direct(D, dst, m, &dout);
+    int rc = feeder_reserve(f, (fsrc + (direct ? 0 : D.frame_bytes())) * (size_t)m + 256);
     if (rc) return rc;
-    uint8_t *dsrc = f.dev, *dres = fres ? dsrc + fsrc * m : nullptr, *dth = fth ? dsrc + (fsrc + fres) * m : nullptr;
-    uint8_t *dwm = fwm ? dsrc + (fsrc + fres + fth) * m : nullptr;
-    size_t sres = fres, sth = fth, swm = fwm;
-    if (direct) {
-        dres = vres; sres = q.resize_frame_stride;
-        dth = vth; sth = q.thumb_frame_stride;
-        dwm = vwm; swm = q.wm_frame_stride;
-    }
+    uint8_t *dsrc = f.dev;
+    if (!direct) dout = D.place(dsrc + fsrc * m, m);
     // direct outputs: the upload goes on the slot's shared stream and the feeder's own stream (kernels) waits for it
     const hipStream_t up = direct && s.up_stream && f.uploaded ? s.up_stream : f.stream;
     BatchSrc d;
@@ -207,13 +193,9 @@ int run_pixel_chunk(Slot &s, Feeder &f, const JobState &j, ipx_plan *plan, int i
     }
     if (e != hipSuccess && up != f.stream) (void)hipStreamSynchronize(up);
     if (e != hipSuccess) { (void)hipStreamSynchronize(f.stream); set_error("pool: upload failed: %s", hipGetErrorString(e)); return IPX_ERR_HIP; }
-    rc = run_dev_src(s.ctx, f.stream, plan, m, d, dres, sres, dth, sth, dwm, swm);
+    rc = run_dev_src(s.ctx, f.stream, plan, m, d, dout);
     if (rc) { (void)hipStreamSynchronize(f.stream); return rc; }
-    for (int i = 0; i < m && e == hipSuccess && !direct; i++) {
-        if (dres && info.resize_bytes) e = hipMemcpyAsync(q.resize_out + (size_t)(i0 + i) * q.resize_frame_stride, dres + fres * i, info.resize_bytes, hipMemcpyDeviceToHost, f.stream);
-        if (e == hipSuccess && dth && info.thumb_bytes) e = hipMemcpyAsync(q.thumb_out + (size_t)(i0 + i) * q.thumb_frame_stride, dth + fth * i, info.thumb_bytes, hipMemcpyDeviceToHost, f.stream);
-        if (e == hipSuccess && dwm && info.wm_bytes) e = hipMemcpyAsync(q.wm_out + (size_t)(i0 + i) * q.wm_frame_stride, dwm + fwm * i, info.wm_bytes, hipMemcpyDeviceToHost, f.stream);
-    }
+    if (!direct) e = dst_download(dst, dout, D, 0, m, f.stream, kCopyFrames);
     const hipError_t e2 = hipStreamSynchronize(f.stream);
     if (e == hipSuccess) e = e2;
     if (e != hipSuccess) { set_error("pool: download failed: %s", hipGetErrorString(e)); return IPX_ERR_HIP; }

@@ -605,7 +605,8 @@ int ipx_link_probe(ipx_ctx *ctx, size_t up_bytes, size_t down_bytes, int reps, d
     if (e == hipSuccess) e = hipEventCreate(&e0);
     if (e == hipSuccess) e = hipEventCreate(&e1);
     if (e == hipSuccess) { memset(hu, 1, up_bytes); e = hipMemset(dd, 2, down_bytes); }
-    uint8_t *hd_dev = e == hipSuccess ? pinned_device_view(hd, down_bytes) : nullptr;
+    uint8_t *hd_dev = nullptr;       // the device's view of the pinned block (ipx_host_alloc maps what it pins)
+    if (e == hipSuccess && hipHostGetDevicePointer((void **)&hd_dev, hd, 0) != hipSuccess) { (void)hipGetLastError(); hd_dev = nullptr; }
     const size_t piece = (size_t)std::max(1, env_int("IPX_PROBE_CHUNK_MB", 32)) << 20;
     // down_by_kernel: the download as a kernel's stores into the pinned block (how run_host_packed delivers outputs) instead of a copy
     auto timed = [&](bool up, bool down, bool down_by_kernel, double *gb_up, double *gb_down) {
@@ -1332,13 +1333,13 @@ static hipError_t composite_text(const ipx_plan *pl, uint8_t *wm, size_t wm_fram
                             c[2] * 0x101u, c[3] * 0x101u, s);
 }
 
-static int run_dev_any(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, int n, const DevSrc &src, uint8_t *resize_out, size_t resize_frame_stride,
-                       uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out, size_t wm_frame_stride)
+static int run_dev_any(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, int n, const DevSrc &src, const BatchDst &dst)
 {
     const int sw = pl->p.sw, sh = pl->p.sh;
-    uint8_t *outs[2] = {pl->sc[0].on ? resize_out : nullptr, pl->sc[1].on ? thumb_out : nullptr};
-    const size_t ostr[2] = {resize_frame_stride, thumb_frame_stride};
-    uint8_t *wm = pl->p.do_watermark ? wm_out : nullptr;
+    uint8_t *outs[2] = {pl->sc[0].on ? dst.out[kOutResize] : nullptr, pl->sc[1].on ? dst.out[kOutThumb] : nullptr};
+    const size_t *ostr = dst.frame_stride;      // ([kOutResize], [kOutThumb]: the indices of pl->sc)
+    uint8_t *wm = pl->p.do_watermark ? dst.out[kOutWm] : nullptr;
+    const size_t wm_frame_stride = dst.frame_stride[kOutWm];
     for (int k = 0; k < 2; k++)
         if (pl->sc[k].dw <= 0 || pl->sc[k].dh <= 0) outs[k] = nullptr;
     if (!wm && !outs[0] && !outs[1]) return IPX_OK;
@@ -1523,8 +1524,7 @@ hipError_t src_upload(const BatchSrc &host, const SrcLayout &L, int i0, int m, u
     return e;
 }
 
-int run_dev_src(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, int m, const BatchSrc &b, uint8_t *resize_out, size_t resize_frame_stride,
-                uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out, size_t wm_frame_stride)
+int run_dev_src(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, int m, const BatchSrc &b, const BatchDst &dst)
 {
     // (a leg's chunk size may come from an environment knob: the limit of one launch is held here too)
     if (m > 65535) { set_error("at most 65535 frames per device call"); return IPX_ERR_UNSUPPORTED; }
@@ -1567,21 +1567,61 @@ int run_dev_src(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, int m, const Ba
         break;
     }
     }
-    return run_dev_any(ctx, s, pl, m, d, resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
+    return run_dev_any(ctx, s, pl, m, d, dst);
 }
 
 // an entry on frames in HBM: the check, then the operators on the caller's stream (null: the context's)
-static int run_dev_entry(const char *who, ipx_ctx *ctx, void *stream, const ipx_plan *pl, int n, const BatchSrc &b, uint8_t *resize_out,
-                         size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out, size_t wm_frame_stride)
+static int run_dev_entry(const char *who, ipx_ctx *ctx, void *stream, const ipx_plan *pl, int n, const BatchSrc &b, const BatchDst &dst)
 {
     const int rc = src_check(who, pl, b, n, true);
     if (rc) return rc;
-    IPX_DEV_OUT(who, "resize", resize_out, 0, resize_frame_stride);
-    IPX_DEV_OUT(who, "thumbnail", thumb_out, 0, thumb_frame_stride);
-    IPX_DEV_OUT(who, "watermark", wm_out, 0, wm_frame_stride);
+    for (int k = 0; k < kOuts; k++) IPX_DEV_OUT(who, out_shape(pl->info, k).name, dst.out[k], 0, dst.frame_stride[k]);
     if (n == 0) return rc;
-    return run_dev_src(ctx, stream ? (hipStream_t)stream : ctx->stream, pl, n, b, resize_out, resize_frame_stride, thumb_out, thumb_frame_stride,
-                       wm_out, wm_frame_stride);
+    return run_dev_src(ctx, stream ? (hipStream_t)stream : ctx->stream, pl, n, b, dst);
+}
+
+// ---- the output side of the pixel-out host legs: one description of a batch's outputs (BatchDst), laid out in scratch, stored into by
+// the kernels themselves where they can (dst_direct), downloaded where they cannot ----
+
+bool dst_direct(const DstLayout &L, const BatchDst &host, int m, BatchDst *view)
+{
+    *view = BatchDst{};
+    bool direct = env_int("IPX_HOST_DIRECT", 1) != 0;
+    for (int k = 0; k < kOuts; k++)
+        if (L.bytes[k] && (((uintptr_t)host.out[k] | host.frame_stride[k]) & 15)) direct = false;
+    for (int k = 0; k < kOuts && direct; k++) {
+        if (!L.bytes[k]) continue;
+        view->out[k] = pinned_device_view(host.out[k], host.frame_stride[k] * (m - 1) + L.bytes[k]);
+        view->frame_stride[k] = host.frame_stride[k];
+        direct = view->out[k] != nullptr;
+    }
+    return direct;
+}
+
+hipError_t dst_download(const BatchDst &host, const BatchDst &dev, const DstLayout &L, int i0, int m, hipStream_t s, const CopyPolicy &cp)
+{
+    hipError_t e = hipSuccess;
+    auto frame = [&](int k, int i) {
+        return hipMemcpyAsync(host.out[k] + (size_t)(i0 + i) * host.frame_stride[k], dev.out[k] + dev.frame_stride[k] * i, L.bytes[k], hipMemcpyDeviceToHost, s);
+    };
+    if (!cp.join_frames) {
+        for (int i = 0; i < m; i++)
+            for (int k = 0; k < kOuts && e == hipSuccess; k++)
+                if (L.bytes[k]) e = frame(k, i);
+        return e;
+    }
+    for (int k = 0; k < kOuts && e == hipSuccess; k++) {
+        const size_t hs = host.frame_stride[k], ds = dev.frame_stride[k];
+        if (!L.bytes[k]) continue;
+        if (hs == ds && (L.bytes[k] == ds || m == 1)) {   // tight on both sides: the chunk as one run of bytes (equal strides with a gap: the gap is the caller's)
+            const size_t bytes = ds * (m - 1) + L.bytes[k], piece = cp.piece ? cp.piece : bytes;
+            for (size_t o = 0; o < bytes && e == hipSuccess; o += piece)
+                e = hipMemcpyAsync(host.out[k] + (size_t)i0 * hs + o, dev.out[k] + o, std::min(piece, bytes - o), hipMemcpyDeviceToHost, s);
+        } else {
+            for (int i = 0; i < m && e == hipSuccess; i++) e = frame(k, i);
+        }
+    }
+    return e;
 }
 
 // device-side frame strides of run_host_packed: tight when that keeps rows 16-byte aligned (then a whole chunk moves with one copy per
@@ -1590,18 +1630,14 @@ static size_t tight16_or_align256(size_t bytes) { return (bytes & 15) == 0 ? byt
 
 // Frames in host memory, any single-plane source type: chunks over the lanes so that H2D of one chunk, the kernel of another and D2H of
 // a third overlap.
-static int run_host_packed(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n, const BatchSrc &host, uint8_t *resize_out,
-                           size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out, size_t wm_frame_stride)
+static int run_host_packed(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n, const BatchSrc &host, const BatchDst &dst)
 {
     int rc = src_check(who, pl, host, n, false);
     if (rc || n == 0) return rc;
-    const auto dstride = tight16_or_align256;
-    const SrcLayout L = src_layout(pl, host, dstride);
+    const SrcLayout L = src_layout(pl, host, tight16_or_align256);
+    const DstLayout D(pl, dst, tight16_or_align256);
     const size_t fsrc = L.frame_bytes();       // (the palette included)
-    const size_t fres = resize_out ? dstride(pl->info.resize_bytes) : 0;
-    const size_t fth = thumb_out ? dstride(pl->info.thumb_bytes) : 0;
-    const size_t fwm = wm_out ? dstride(pl->info.wm_bytes) : 0;
-    const size_t per_frame = fsrc + fres + fth + fwm;
+    const size_t per_frame = fsrc + D.frame_bytes();
     // chunk the batch so that H2D of one chunk, the kernel of another and D2H of a third overlap on
     // different lanes (one stream each); several chunks per lane keep all three engines busy
     const int nl = (int)ctx->lanes.size();
@@ -1660,33 +1696,11 @@ static int run_host_packed(const char *who, ipx_ctx *ctx, const ipx_plan *pl, in
     // pipeline over the lanes it took: every upload on the first lane's stream, every kernel on the third's, every download on the
     // second's, the lanes' scratch buffers as the slots chunks rotate through, events between the stages.
     const size_t piece = (size_t)std::max(1, env_int("IPX_COPY_PIECE_MB", 32)) << 20;
-    const CopyPolicy up_policy{true, false, piece};
-    auto copy_pieces = [&](uint8_t *dst, const uint8_t *from, size_t bytes, hipMemcpyKind k, hipStream_t st) {
-        hipError_t r = hipSuccess;
-        for (size_t o = 0; o < bytes && r == hipSuccess; o += piece) r = hipMemcpyAsync(dst + o, from + o, std::min(piece, bytes - o), k, st);
-        return r;
-    };
-    auto d2h = [&](uint8_t *host, size_t host_stride, const uint8_t *dev, size_t dev_stride, size_t bytes, int i0, int m,
-                   hipStream_t st) {
-        if (!dev || !bytes) return hipSuccess;
-        if (host_stride == dev_stride && (bytes == dev_stride || m == 1))  // tight on both sides: the chunk as one run of bytes (equal strides with a gap: the gap is the caller's)
-            return copy_pieces(host + (size_t)i0 * host_stride, dev, dev_stride * (m - 1) + bytes, hipMemcpyDeviceToHost, st);
-        hipError_t r = hipSuccess;
-        for (int i = 0; i < m && r == hipSuccess; i++)
-            r = hipMemcpyAsync(host + (size_t)(i0 + i) * host_stride, dev + dev_stride * i, bytes, hipMemcpyDeviceToHost, st);
-        return r;
-    };
-    // Outputs in pinned memory (hipHostMalloc / hipHostRegister: mapped into the device's address space) are written by the kernels
-    // themselves, over the link, instead of into the lane's scratch and from there by a copy engine: uploads are then the only copies
-    // in flight, so the two directions cannot land on one engine, and a chunk has two stages instead of three.
-    uint8_t *vres = nullptr, *vth = nullptr, *vwm = nullptr;
-    bool direct = !bounce && env_int("IPX_HOST_DIRECT", 1) != 0;
-    // (the kernels store 16 bytes per lane: frames whose stride would break that alignment go through the lane's scratch, which pads)
-    if (((uintptr_t)resize_out | (uintptr_t)thumb_out | (uintptr_t)wm_out | (resize_out ? resize_frame_stride : 0) | (thumb_out ? thumb_frame_stride : 0) |
-         (wm_out ? wm_frame_stride : 0)) & 15) direct = false;
-    if (direct && resize_out) direct = (vres = pinned_device_view(resize_out, resize_frame_stride * (n - 1) + pl->info.resize_bytes)) != nullptr;
-    if (direct && thumb_out) direct = (vth = pinned_device_view(thumb_out, thumb_frame_stride * (n - 1) + pl->info.thumb_bytes)) != nullptr;
-    if (direct && wm_out) direct = (vwm = pinned_device_view(wm_out, wm_frame_stride * (n - 1) + pl->info.wm_bytes)) != nullptr;
+    const CopyPolicy join_policy{true, false, piece};
+    // Outputs in pinned memory are written by the kernels themselves (dst_direct): uploads are then the only copies in flight, so the
+    // two directions cannot land on one engine, and a chunk has two stages instead of three.
+    BatchDst view;
+    const bool direct = !bounce && dst_direct(D, dst, n, &view);
     if (getenv("IPX_KS_DEBUG")) fprintf(stderr, "[ipx host] outputs %s\n", direct ? "stored by the kernels" : "copied from scratch");
     const size_t S = lanes.size();
     const hipStream_t s_up = lanes[0]->stream, s_down = lanes[S > 1 ? 1 : 0]->stream, s_run = lanes[S > 2 ? 2 : 0]->stream;
@@ -1700,15 +1714,7 @@ static int run_host_packed(const char *who, ipx_ctx *ctx, const ipx_plan *pl, in
         const hipStream_t up = staged ? s_up : l.stream, run = staged ? s_run : l.stream, down = staged ? s_down : l.stream;
         const int m = std::min(chunk, n - i0);
         uint8_t *dsrc = (uint8_t *)(((uintptr_t)l.dev + 255) & ~(uintptr_t)255);
-        uint8_t *dres = fres ? dsrc + fsrc * chunk : nullptr;
-        uint8_t *dth = fth ? dsrc + (fsrc + fres) * chunk : nullptr;
-        uint8_t *dwm = fwm ? dsrc + (fsrc + fres + fth) * chunk : nullptr;
-        size_t sres = fres, sth = fth, swm = fwm;
-        if (direct) {
-            dres = fres ? vres + (size_t)i0 * resize_frame_stride : nullptr; sres = resize_frame_stride;
-            dth = fth ? vth + (size_t)i0 * thumb_frame_stride : nullptr; sth = thumb_frame_stride;
-            dwm = fwm ? vwm + (size_t)i0 * wm_frame_stride : nullptr; swm = wm_frame_stride;
-        }
+        const BatchDst dout = direct ? view.from(i0) : D.place(dsrc + fsrc * chunk, chunk);
         // reuse of a lane's scratch: chunk c waits until chunk c - S has been downloaded (stream order when one stream does it all)
         if (staged && c >= (int)S) e = hipStreamWaitEvent(up, l.ev[2], 0);
         if (e != hipSuccess) break;
@@ -1718,12 +1724,12 @@ static int run_host_packed(const char *who, ipx_ctx *ctx, const ipx_plan *pl, in
             e = hipMemcpyAsync(dsrc, l.pin, L.row[0] * L.h[0], hipMemcpyHostToDevice, up);
             d = packed_src(host.type, dsrc, (int)L.row[0], L.fs[0]);
         } else {
-            e = src_upload(host, L, i0, m, dsrc, chunk, up, up_policy, &d);
+            e = src_upload(host, L, i0, m, dsrc, chunk, up, join_policy, &d);
         }
         if (e == hipSuccess && staged) e = hipEventRecord(l.ev[0], up);
         if (e == hipSuccess && staged) e = hipStreamWaitEvent(run, l.ev[0], 0);
         if (e != hipSuccess) break;
-        rc = run_dev_src(ctx, run, pl, m, d, dres, sres, dth, sth, dwm, swm);
+        rc = run_dev_src(ctx, run, pl, m, d, dout);
         if (rc) break;
         if (direct) {          // the outputs are where they belong when the kernels have finished
             if (staged) e = hipEventRecord(l.ev[2], run);
@@ -1735,12 +1741,10 @@ static int run_host_packed(const char *who, ipx_ctx *ctx, const ipx_plan *pl, in
             if (e != hipSuccess) break;
         }
         if (bounce) {          // one copy of the three outputs (they follow the source in the lane's scratch), handed out after the sync below
-            if (fres + fth + fwm) e = hipMemcpyAsync(l.pin + fsrc, dsrc + fsrc, fres + fth + fwm, hipMemcpyDeviceToHost, down);
+            if (D.frame_bytes()) e = hipMemcpyAsync(l.pin + fsrc, dsrc + fsrc, D.frame_bytes(), hipMemcpyDeviceToHost, down);
             continue;
         }
-        e = d2h(resize_out, resize_frame_stride, dres, fres, pl->info.resize_bytes, i0, m, down);
-        if (e == hipSuccess) e = d2h(thumb_out, thumb_frame_stride, dth, fth, pl->info.thumb_bytes, i0, m, down);
-        if (e == hipSuccess) e = d2h(wm_out, wm_frame_stride, dwm, fwm, pl->info.wm_bytes, i0, m, down);
+        e = dst_download(dst, dout, D, i0, m, down, join_policy);
         if (e == hipSuccess && staged) e = hipEventRecord(l.ev[2], down);
     }
     const double t_enq = trace ? ms_since(t_in) : 0;
@@ -1749,10 +1753,9 @@ static int run_host_packed(const char *who, ipx_ctx *ctx, const ipx_plan *pl, in
         if (e == hipSuccess) e = e2;
     }
     if (bounce && !rc && e == hipSuccess) {
-        const uint8_t *p = lanes[0]->pin + fsrc;
-        if (resize_out) memcpy(resize_out, p, pl->info.resize_bytes);
-        if (thumb_out) memcpy(thumb_out, p + fres, pl->info.thumb_bytes);
-        if (wm_out) memcpy(wm_out, p + fres + fth, pl->info.wm_bytes);
+        const BatchDst p = D.place(lanes[0]->pin + fsrc, 1);
+        for (int k = 0; k < kOuts; k++)
+            if (p.out[k]) memcpy(dst.out[k], p.out[k], D.bytes[k]);
     }
     if (trace)
         fprintf(stderr, "[ipx seam] lane %d of %d: lock %.2f ms, reserve %.2f, enqueued %.2f, done %.2f\n", (int)(lanes[0] - &ctx->lanes[0]), nl, t_lock, t_res,
@@ -1768,9 +1771,10 @@ static int run_host_packed(const char *who, ipx_ctx *ctx, const ipx_plan *pl, in
 
 extern "C" {
 
-// The twelve pixel-out batch entries: each describes its source (BatchSrc) and hands it on -- frames in HBM to run_dev_entry, frames in
-// host memory to run_host_packed (YCbCr planes: the entry's own single-lane schedule), which check them by the one rule (src_check).  The alignment the kernels need of a deep type's pixels
-// and of palettes is asked of HBM sources only: host frames are re-packed into aligned scratch on their way up.
+// The twelve pixel-out batch entries: each describes its source (BatchSrc) and its outputs (BatchDst, abi_dst) and hands them on --
+// frames in HBM to run_dev_entry, frames in host memory to run_host_packed (YCbCr planes: the entry's own single-lane schedule), which
+// check them by the one rule (src_check).  The alignment the kernels need of a deep type's pixels and of palettes is asked of HBM
+// sources only: host frames are re-packed into aligned scratch on their way up.
 
 int ipx_plan_run_dev(ipx_ctx *ctx, void *stream, const ipx_plan *pl, int n, const uint8_t *src, int sstride, size_t src_frame_stride,
                      uint8_t *resize_out, size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out,
@@ -1778,7 +1782,7 @@ int ipx_plan_run_dev(ipx_ctx *ctx, void *stream, const ipx_plan *pl, int n, cons
 {
     IPX_ENTER(ctx);
     return run_dev_entry("ipx_plan_run_dev", ctx, stream, pl, n, packed_src(kSrcRGBA, src, sstride, src_frame_stride),
-                         resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
+                           abi_dst(resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride));
 }
 IPX_CATCH_STATUS
 
@@ -1788,7 +1792,7 @@ int ipx_plan_run_host(ipx_ctx *ctx, const ipx_plan *pl, int n, const uint8_t *sr
 {
     IPX_ENTER(ctx);
     return run_host_packed("ipx_plan_run_host", ctx, pl, n, packed_src(kSrcRGBA, src, sstride, src_frame_stride),
-                           resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
+                           abi_dst(resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride));
 }
 IPX_CATCH_STATUS
 
@@ -1798,7 +1802,7 @@ int ipx_plan_run_dev_nrgba(ipx_ctx *ctx, void *stream, const ipx_plan *pl, int n
 {
     IPX_ENTER(ctx);
     return run_dev_entry("ipx_plan_run_dev_nrgba", ctx, stream, pl, n, packed_src(kSrcNRGBA, src, sstride, src_frame_stride),
-                         resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
+                           abi_dst(resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride));
 }
 IPX_CATCH_STATUS
 
@@ -1808,7 +1812,7 @@ int ipx_plan_run_host_nrgba(ipx_ctx *ctx, const ipx_plan *pl, int n, const uint8
 {
     IPX_ENTER(ctx);
     return run_host_packed("ipx_plan_run_host_nrgba", ctx, pl, n, packed_src(kSrcNRGBA, src, sstride, src_frame_stride),
-                           resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
+                           abi_dst(resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride));
 }
 IPX_CATCH_STATUS
 
@@ -1818,7 +1822,7 @@ int ipx_plan_run_dev_gray(ipx_ctx *ctx, void *stream, const ipx_plan *pl, int n,
 {
     IPX_ENTER(ctx);
     return run_dev_entry("ipx_plan_run_dev_gray", ctx, stream, pl, n, packed_src(kSrcGray, gray, stride, frame_stride),
-                         resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
+                           abi_dst(resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride));
 }
 IPX_CATCH_STATUS
 
@@ -1828,7 +1832,7 @@ int ipx_plan_run_host_gray(ipx_ctx *ctx, const ipx_plan *pl, int n, const uint8_
 {
     IPX_ENTER(ctx);
     return run_host_packed("ipx_plan_run_host_gray", ctx, pl, n, packed_src(kSrcGray, gray, stride, frame_stride),
-                           resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
+                           abi_dst(resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride));
 }
 IPX_CATCH_STATUS
 
@@ -1839,7 +1843,7 @@ int ipx_plan_run_dev_paletted(ipx_ctx *ctx, void *stream, const ipx_plan *pl, in
 {
     IPX_ENTER(ctx);
     return run_dev_entry("ipx_plan_run_dev_paletted", ctx, stream, pl, n, packed_src(kSrcPaletted, index, stride, frame_stride, palettes),
-                         resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
+                           abi_dst(resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride));
 }
 IPX_CATCH_STATUS
 
@@ -1850,7 +1854,7 @@ int ipx_plan_run_host_paletted(ipx_ctx *ctx, const ipx_plan *pl, int n, const ui
 {
     IPX_ENTER(ctx);
     return run_host_packed("ipx_plan_run_host_paletted", ctx, pl, n, packed_src(kSrcPaletted, index, stride, frame_stride, palettes),
-                           resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
+                           abi_dst(resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride));
 }
 IPX_CATCH_STATUS
 
@@ -1860,7 +1864,7 @@ int ipx_plan_run_dev_deep(ipx_ctx *ctx, void *stream, const ipx_plan *pl, int n,
 {
     IPX_ENTER(ctx);
     return run_dev_entry("ipx_plan_run_dev_deep", ctx, stream, pl, n, packed_src(src_of_deep(kind), src, sstride, src_frame_stride),
-                         resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
+                           abi_dst(resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride));
 }
 IPX_CATCH_STATUS
 
@@ -1870,7 +1874,7 @@ int ipx_plan_run_host_deep(ipx_ctx *ctx, const ipx_plan *pl, int n, int kind, co
 {
     IPX_ENTER(ctx);
     return run_host_packed("ipx_plan_run_host_deep", ctx, pl, n, packed_src(src_of_deep(kind), src, sstride, src_frame_stride),
-                           resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
+                           abi_dst(resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride));
 }
 IPX_CATCH_STATUS
 
@@ -1885,7 +1889,7 @@ int ipx_plan_run_dev_ycbcr(ipx_ctx *ctx, void *stream, const ipx_plan *pl, int n
 {
     IPX_ENTER(ctx);
     return run_dev_entry("ipx_plan_run_dev_ycbcr", ctx, stream, pl, n, ycbcr_src(src),
-                         resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
+                           abi_dst(resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride));
 }
 IPX_CATCH_STATUS
 
@@ -1898,29 +1902,23 @@ int ipx_plan_run_host_ycbcr(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_y
     const BatchSrc host = ycbcr_src(src);
     int rc = src_check("ipx_plan_run_host_ycbcr", pl, host, n, false);
     if (rc || n == 0) return rc;
+    const BatchDst dst = abi_dst(resize_out, resize_frame_stride, thumb_out, thumb_frame_stride, wm_out, wm_frame_stride);
     const SrcLayout L = src_layout(pl, host);
-    const size_t fres = resize_out ? align256(pl->info.resize_bytes) : 0, fth = thumb_out ? align256(pl->info.thumb_bytes) : 0;
-    const size_t fwm = wm_out ? align256(pl->info.wm_bytes) : 0;
+    const DstLayout D(pl, dst);
     LaneLease lane(ctx);
-    rc = lane_reserve(lane.get(), (L.frame_bytes() + fres + fth + fwm) * n + 1024);
+    rc = lane_reserve(lane.get(), (L.frame_bytes() + D.frame_bytes()) * n + 1024);
     if (rc) return rc;
     hipStream_t s = lane->stream;
-    uint8_t *dres = fres ? lane->dev + L.frame_bytes() * n : nullptr, *dth = fth ? lane->dev + (L.frame_bytes() + fres) * n : nullptr;
-    uint8_t *dwm = fwm ? lane->dev + (L.frame_bytes() + fres + fth) * n : nullptr;
+    const BatchDst dout = D.place(lane->dev + L.frame_bytes() * n, n);
     BatchSrc d;
-    IPX_HIP(src_upload(host, L, 0, n, lane->dev, n, s, kCopyFrameRows, &d));
-    rc = run_dev_src(ctx, s, pl, n, d, dres, fres, dth, fth, dwm, fwm);
-    if (rc) { (void)hipStreamSynchronize(s); return rc; }
-    for (int i = 0; i < n; i++) {
-        if (dres && pl->info.resize_bytes)
-            IPX_HIP(hipMemcpyAsync(resize_out + resize_frame_stride * i, dres + fres * i, pl->info.resize_bytes, hipMemcpyDeviceToHost, s));
-        if (dth && pl->info.thumb_bytes)
-            IPX_HIP(hipMemcpyAsync(thumb_out + thumb_frame_stride * i, dth + fth * i, pl->info.thumb_bytes, hipMemcpyDeviceToHost, s));
-        if (dwm && pl->info.wm_bytes)
-            IPX_HIP(hipMemcpyAsync(wm_out + wm_frame_stride * i, dwm + fwm * i, pl->info.wm_bytes, hipMemcpyDeviceToHost, s));
-    }
-    IPX_HIP(hipStreamSynchronize(s));
-    return IPX_OK;
+    // (from the first queued copy on, no way out before the stream has been waited for: the copies read and write the caller's memory)
+    hipError_t e = src_upload(host, L, 0, n, lane->dev, n, s, kCopyFrameRows, &d);
+    if (e == hipSuccess) rc = run_dev_src(ctx, s, pl, n, d, dout);
+    if (e == hipSuccess && !rc) e = dst_download(dst, dout, D, 0, n, s, kCopyFrames);
+    const hipError_t e2 = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = e2;
+    if (!rc && e != hipSuccess) { set_error("ipx_plan_run_host_ycbcr: %s", hipGetErrorString(e)); rc = IPX_ERR_HIP; }
+    return rc;
 }
 IPX_CATCH_STATUS
 

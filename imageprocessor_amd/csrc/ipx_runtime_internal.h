@@ -262,7 +262,7 @@ inline void bind_near_device(int device)
 
 
 // The device's view of `span` bytes of host memory a kernel may write: non-null when the range is pinned and mapped (hipHostMalloc,
-// hipHostRegister), null for pageable memory.  Kernels then write outputs over the link themselves (run_host_packed, the pool's chunks).
+// hipHostRegister), null for pageable memory.  Kernels then write outputs over the link themselves: dst_direct, below, is its one caller.
 inline uint8_t *pinned_device_view(uint8_t *host, size_t span)
 {
     if (!host || !span) return nullptr;
@@ -381,10 +381,68 @@ constexpr CopyPolicy kCopyWholePlanes{true, false, 0}, kCopyFrames{false, true, 
 hipError_t src_upload(const BatchSrc &host, const SrcLayout &L, int i0, int m, uint8_t *scratch, int slots, hipStream_t s, const CopyPolicy &cp,
                       BatchSrc *in_hbm);
 
-// The plan's operators on m frames in HBM, outputs to device-addressable frames (null: not wanted).  The one place that knows what a
-// source type needs first: a palette or deep pixels are expanded (stream-ordered scratch), Gray gets the flat chroma row.
-int run_dev_src(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, int m, const BatchSrc &in_hbm, uint8_t *resize_out, size_t resize_frame_stride,
-                uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out, size_t wm_frame_stride);
+// ---- the output side of the plan entries (ipx_runtime.hip) --------------------------------------------------------------------------
+
+// The plan's three outputs for a batch, in host memory or device-addressable: rows tight, frame i of output k at out[k] + i * frame_stride[k]
+enum { kOutResize, kOutThumb, kOutWm, kOuts };
+struct BatchDst {
+    uint8_t *out[kOuts] = {nullptr, nullptr, nullptr};     // null: not wanted
+    size_t frame_stride[kOuts] = {0, 0, 0};
+    BatchDst from(int i0) const                            // the same from frame i0 on
+    {
+        BatchDst d = *this;
+        for (int k = 0; k < kOuts; k++) if (d.out[k]) d.out[k] += (size_t)i0 * frame_stride[k];
+        return d;
+    }
+};
+inline BatchDst abi_dst(uint8_t *resize_out, size_t resize_frame_stride, uint8_t *thumb_out, size_t thumb_frame_stride, uint8_t *wm_out,
+                        size_t wm_frame_stride)
+{
+    return BatchDst{{resize_out, thumb_out, wm_out}, {resize_frame_stride, thumb_frame_stride, wm_frame_stride}};
+}
+inline BatchDst job_dst(const ipx_job &q) { return abi_dst(q.resize_out, q.resize_frame_stride, q.thumb_out, q.thumb_frame_stride, q.wm_out, q.wm_frame_stride); }
+
+// what the plan makes of output k: the size, the tightly packed bytes per frame (0: no such operator) and the name error texts use
+struct OutShape { int w, h; size_t bytes; const char *name; };
+inline OutShape out_shape(const ipx_plan_info &in, int k)
+{
+    if (k == kOutResize) return {in.resize_w, in.resize_h, in.resize_bytes, "resize"};
+    if (k == kOutThumb) return {in.thumb_w, in.thumb_h, in.thumb_bytes, "thumbnail"};
+    return {in.wm_w, in.wm_h, in.wm_bytes, "watermark"};
+}
+
+// How `slots` frames of every output lie in device scratch: [slots x resize][slots x thumbnail][slots x watermark], frames fs[] apart;
+// bytes and fs are 0 for an output the caller does not want or the plan does not make.  frame_rule as for src_layout.
+struct DstLayout {
+    size_t bytes[kOuts] = {0, 0, 0}, fs[kOuts] = {0, 0, 0};
+    DstLayout(const ipx_plan *pl, const BatchDst &host, size_t (*frame_rule)(size_t) = align256)
+    {
+        for (int k = 0; k < kOuts; k++)
+            if (host.out[k] && (bytes[k] = out_shape(pl->info, k).bytes) != 0) fs[k] = frame_rule(bytes[k]);
+    }
+    size_t frame_bytes() const { return fs[0] + fs[1] + fs[2]; }
+    BatchDst place(uint8_t *scratch, int slots) const
+    {
+        BatchDst d;
+        for (int k = 0; k < kOuts; scratch += fs[k++] * slots)
+            if (fs[k]) { d.out[k] = scratch; d.frame_stride[k] = fs[k]; }
+        return d;
+    }
+};
+
+// Outputs in pinned memory (hipHostMalloc / hipHostRegister: mapped into the device's address space) are written by the kernels
+// themselves, over the link, instead of into scratch and from there by a copy engine.  true: *view is the device's view of m frames of
+// every wanted output of `host`.  false -- they go through scratch, which pads: a wanted pointer or frame stride is no multiple of 16
+// (the kernels store 16 bytes per lane), a range is not pinned, or IPX_HOST_DIRECT=0.
+bool dst_direct(const DstLayout &L, const BatchDst &host, int m, BatchDst *view);
+
+// Queues the copies of m frames of every wanted output from `dev` into `host` from frame i0 on.  join_frames: output by output, one that
+// is tight on both sides (or a single frame) as one run of bytes, in pieces of `piece`; else one copy per frame and output, frame by frame.
+hipError_t dst_download(const BatchDst &host, const BatchDst &dev, const DstLayout &L, int i0, int m, hipStream_t s, const CopyPolicy &cp);
+
+// The plan's operators on m frames in HBM, outputs to device-addressable frames.  The one place that knows what a source type needs
+// first: a palette or deep pixels are expanded (stream-ordered scratch), Gray gets the flat chroma row.
+int run_dev_src(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, int m, const BatchSrc &in_hbm, const BatchDst &dst);
 
 // jpeg.Encode of up to three sets of n frames in HBM into one pinned block *blob (ipx_jpeg_runtime.hip); dcoefs: n * ipx_jpeg_coef_count
 // int16 of scratch per set.
@@ -428,6 +486,7 @@ struct PlanOutputs {
     struct Frames { uint8_t *dev[3]; int16_t *coef[3]; };     // one chunk's outputs in a device block (place)
     Output o[3];
     PlanOutputs(const ipx_plan *pl, ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, Codec res, Codec thumb, Codec wm);
+    BatchDst dst(const Frames &f) const { return BatchDst{{f.dev[0], f.dev[1], f.dev[2]}, {o[0].fs, o[1].fs, o[2].fs}}; }   // for run_dev_src
     size_t frame_bytes() const { return o[0].fs + o[1].fs + o[2].fs + o[0].coef + o[1].coef + o[2].coef; }   // per frame of a block
     // a block of `chunk` frames: [chunk x resize][chunk x thumbnail][chunk x watermark][chunk x coefficients of each JPEG output]
     Frames place(uint8_t *block, int chunk) const;

@@ -522,3 +522,136 @@ def test_host_batch_outputs_with_gaps(ctx, direct, monkeypatch, capfd):
                     np.testing.assert_array_equal(got[k][j], c.want_text[j % N], err_msg=w)
                 else:
                     _both(got[k][j], c.want[j % N][k], c.ref[j % N][k], "rgba", w)
+
+
+# ---- the output stage the pixel-out host legs share (csrc/ipx_runtime.hip: DstLayout, dst_direct, dst_download) ------------------------
+# run_host_packed above, the pool's pixel chunks and ipx_plan_run_host_ycbcr place, store and download a batch's outputs by one piece of
+# code; these hold the other two legs, and run_host_packed's single-frame path, to what test_host_batch_outputs_with_gaps asks.
+
+def _sizes(plan):
+    i = plan.info
+    return {"resize": (i.resize_bytes, (i.resize_h, i.resize_w, 4)), "thumbnail": (i.thumb_bytes, (i.thumb_h, i.thumb_w, 4)),
+            "watermark": (i.wm_bytes, (i.wm_h, i.wm_w, 4))}
+
+
+def _check_host_outputs(c, got, n, what):
+    for j in range(n):
+        for k in got:
+            w = "%s frame %d %s" % (k, j, what)
+            if k == "watermark":
+                np.testing.assert_array_equal(got[k][j], c.want_text[j % N], err_msg=w)
+            else:
+                _both(got[k][j], c.want[j % N][k], c.ref[j % N][k], c.kind, w)
+
+
+@pytest.fixture(scope="module")
+def pool():
+    import imageprocessor_amd as ipa
+    p = ipa.Pool(devices=(0,))
+    yield p
+    p.close()
+
+
+def _submit_pixels(pool, frames, shape, glyphs, outs):
+    """The ipx_job of Pool.submit for RGBA frames, with the caller's output addresses and frame strides: {output: (address, stride)}"""
+    import imageprocessor_amd as ipa
+    from imageprocessor_amd import _lib
+    w, h, resize, thumb, wm = shape
+    ops, keep = pool._ops(w, h, resize, thumb, glyphs, COL, wm)
+    j = _lib.Job()
+    j.kind, j.ops, j.n = pool.JOB_KINDS["rgba"][0], ops, frames.shape[0]
+    j.src, j.sstride, j.src_frame_stride = frames.ctypes.data, w * 4, w * h * 4
+    j.resize_out, j.resize_frame_stride = outs["resize"]
+    j.thumb_out, j.thumb_frame_stride = outs["thumbnail"]
+    j.wm_out, j.wm_frame_stride = outs["watermark"]
+    return ipa.PoolJob(pool, j, {"frames": frames, "glyphs": keep}, None, frames.shape[0])
+
+
+# (shape, frames, pinned?, extra frame stride): + 16 keeps every pointer and stride of SHAPES[0] on 16 bytes and + 4 breaks that, as in
+# HOST_GAP_CASES; 40 frames go in several chunks of several frames; pageable outputs are always downloaded
+POOL_GAP_CASES = [(L.SHAPES[0], N, True, 16), (L.SHAPES[0], N, True, 4), (L.SHAPES[0], N, False, 20),
+                  (L.HOST_GAP_SHAPE, 40, True, "to 256"), (L.HOST_GAP_SHAPE, 40, False, 20)]
+
+
+@pytest.mark.parametrize("direct", ["1", "0"])
+def test_pool_pixel_outputs_with_gaps(ctx, pool, direct, monkeypatch):
+    """Pixel jobs of the pool into outputs with gaps between the frames -- pinned on and off the 16-byte gate, pageable -- with the
+    kernels allowed to store into pinned outputs and not: the frames are correct (the text reaches the watermark's last row and
+    column) and the gaps and guards stay 0xA5.  (The pool does not say which path ran: bytes only.)"""
+    _env(monkeypatch, {"IPX_HOST_DIRECT": direct})
+    for shape, n, pinned, extra in POOL_GAP_CASES:
+        c = E.case("rgba", shape)
+        plan, gs = _plan(ctx, shape, c.glyphs)        # (for the sizes of the outputs)
+        sizes = _sizes(plan)
+        plan.close()
+        gs.close()
+        frames = np.stack([c.srcs[j % N].data for j in range(n)])
+        what = "pool IPX_HOST_DIRECT=%s %r, %d frames, %s outputs, frame stride + %s" % (direct, shape[:3], n, "pinned" if pinned else "pageable", extra)
+        held, outs = [], {}
+        try:
+            for k, (fb, shp) in sizes.items():
+                buf, first, fs = L.out_alloc(n, fb, 0, (-fb) % 256 if extra == "to 256" else extra)
+                arr = pool.host_alloc(0, buf.shape) if pinned else np.empty_like(buf)
+                arr[...] = buf
+                held.append(arr)
+                outs[k] = (arr, first, fs, fb, shp)
+            _submit_pixels(pool, frames, shape, c.glyphs, {k: (o[0].ctypes.data + o[1], o[2]) for k, o in outs.items()}).wait()
+            got = {k: L.out_frames(arr, n, fb, first, fs, shp, "%s %s" % (what, k)) for k, (arr, first, fs, fb, shp) in outs.items()}
+        finally:
+            for arr in held:
+                pool.host_free(arr)       # (a pageable array: nothing to free)
+        _check_host_outputs(c, got, n, what)
+
+
+@pytest.mark.parametrize("out_layout", [L.OUT_TIGHT, (16, 32), L.OUT_PADDED])
+def test_ycbcr_host_batch_outputs_with_gaps(ctx, out_layout, monkeypatch):
+    """ipx_plan_run_host_ycbcr into pageable outputs at an offset and with gaps between the frames: the frames are correct and the gaps
+    and guards stay 0xA5."""
+    import ctypes as C
+    import imageprocessor_amd as ipa
+    from imageprocessor_amd import _lib
+    _env(monkeypatch, {})
+    kind, shape = "ycbcr420", L.SHAPES[0]
+    c = E.case(kind, shape)
+    (y, cb, cr), _ = c.planes()
+    b = _lib.YCbCrBatch(y.ctypes.data, cb.ctypes.data, cr.ctypes.data, y.shape[2], cb.shape[2], y.shape[1] * y.shape[2],
+                        cb.shape[1] * cb.shape[2], RATIO[kind])
+    plan, gs = _plan(ctx, shape, c.glyphs)
+    try:
+        what = "%s outputs at %r" % (kind, out_layout)
+        outs = {k: L.out_alloc(N, fb, *out_layout) + (fb, shp) for k, (fb, shp) in _sizes(plan).items()}
+        args = [a for k in OUT_KEYS for a in (outs[k][0].ctypes.data + outs[k][1], outs[k][2])]
+        ipa._check(ipa.lib().ipx_plan_run_host_ycbcr(ctx.handle, plan.handle, N, C.byref(b), *args))
+        got = {k: L.out_frames(buf, N, fb, first, fs, shp, "%s %s" % (what, k)) for k, (buf, first, fs, fb, shp) in outs.items()}
+    finally:
+        plan.close()
+        gs.close()
+    _check_host_outputs(c, got, N, what)
+
+
+@pytest.mark.parametrize("shape", [L.SHAPES[0], L.HOST_GAP_SHAPE], ids=["shape0", "gap-shape"])
+def test_single_pageable_frame_by_operator_subset(ctx, shape, monkeypatch, capfd):
+    """One pageable frame through ipx_plan_run_host into pageable outputs -- run_host_packed's bounce through a pinned buffer of the
+    lane, where the three outputs come down with one copy -- wanting each non-empty subset of the plan's outputs: the wanted ones are
+    correct between guards of 0xA5.  (HOST_GAP_SHAPE's resize frame of 1500 bytes is padded to 1536 in scratch: the offsets of the
+    outputs behind it are not sums of frame bytes.)"""
+    import imageprocessor_amd as ipa
+    _env(monkeypatch, {})
+    c = E.case("rgba", shape)
+    frame = c.srcs[0].data[None].copy()
+    plan, gs = _plan(ctx, shape, c.glyphs)
+    try:
+        sizes = _sizes(plan)
+        for bits in range(1, 8):
+            keys = [k for b, k in enumerate(OUT_KEYS) if bits >> b & 1]
+            what = "one frame %r wanting %s" % (shape[:3], "+".join(keys))
+            outs = {k: L.out_alloc(1, sizes[k][0], 0, 0) for k in keys}
+            capfd.readouterr()
+            plan._run(ipa.lib().ipx_plan_run_host, (), 1, (frame.ctypes.data, shape[0] * 4, shape[0] * shape[1] * 4),
+                      [outs[k][0].ctypes.data + outs[k][1] if k in outs else None for k in OUT_KEYS])
+            assert not _direct_ran(capfd), what
+            got = {k: L.out_frames(buf, 1, sizes[k][0], first, fs, sizes[k][1], "%s %s" % (what, k)) for k, (buf, first, fs) in outs.items()}
+            _check_host_outputs(c, got, 1, what)
+    finally:
+        plan.close()
+        gs.close()
