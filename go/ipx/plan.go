@@ -150,7 +150,7 @@ type Streams struct {
 	x                        *Context
 	res                      *C.ipx_jpeg_result
 	resize, thumb, watermark []C.ipx_bytes
-	Status                   []Status // per file, RunJPEGJPEG only: Unsupported = decode this one with Go (progressive, CMYK, another size)
+	Status                   []Status // per file, RunJPEGJPEG only: Unsupported = decode this one with Go (CMYK unless IPX_JPEG_CMYK=1, 4:1:1, another size)
 }
 
 func view(b C.ipx_bytes) []byte {
@@ -242,4 +242,64 @@ func (x *Context) JPEGDecodeCounts() (counts [4]int64, err error) {
 		counts[i] = int64(c[i])
 	}
 	return counts, err
+}
+
+// CMYKFrames are the *image.CMYK frames of a JPEGDecodeCMYK call in HBM: frame i at Pix + i*FrameStride, rows Stride = 4*W bytes
+// apart, the layout ipx_plan_run_dev_deep takes with IPX_DEEP_CMYK.  Release frees them.
+type CMYKFrames struct {
+	x           *Context
+	owner       *C.ipx_jpeg_planes
+	Pix         unsafe.Pointer
+	W, H        int
+	Stride      int
+	FrameStride uintptr
+	Status      []Status // per file: Unsupported = not a four-component file Go takes, another size or vector, or the switch is off
+}
+
+func (f *CMYKFrames) Release() {
+	if f.owner != nil {
+		C.ipx_jpeg_planes_free(f.x.c, f.owner)
+		f.owner = nil
+	}
+}
+
+// JPEGDecodeCMYK: image.Decode of four-component JPEGs (Adobe CMYK / YCCK) under IPX_JPEG_CMYK=1 -- scans on the library's host threads,
+// IDCT and applyBlack on the GPU.  w, h: 0, or the size the batch must have.  files as for RunJPEGJPEG.  Pix is nil when no file was
+// decodable.
+func (x *Context) JPEGDecodeCMYK(files [][]byte, w, h int) (*CMYKFrames, error) {
+	n := len(files)
+	out := &CMYKFrames{x: x}
+	if n == 0 {
+		return out, nil
+	}
+	cf := (*[1 << 24]C.ipx_bytes)(C.malloc(C.size_t(n) * C.size_t(unsafe.Sizeof(C.ipx_bytes{}))))
+	defer C.free(unsafe.Pointer(cf))
+	var pin runtimePinner
+	defer pin.Unpin()
+	for i, f := range files {
+		pin.Pin(&f[0])
+		cf[i] = C.ipx_bytes{data: (*C.uint8_t)(unsafe.Pointer(&f[0])), len: C.size_t(len(f))}
+	}
+	var b C.ipx_cmyk_batch
+	cw, ch := C.int(w), C.int(h)
+	st := make([]C.int, n)
+	err := call(func() C.int {
+		return C.ipx_jpeg_decode_batch_cmyk(x.c, nil, &cf[0], C.int(n), &cw, &ch, &b, &st[0], &out.owner)
+	})
+	if err != nil {
+		return nil, err
+	}
+	out.Pix, out.W, out.H, out.Stride, out.FrameStride = unsafe.Pointer(b.pix), int(cw), int(ch), int(b.stride), uintptr(b.frame_stride)
+	out.Status = make([]Status, n)
+	for i := range st {
+		out.Status[i] = Status(st[i])
+	}
+	return out, nil
+}
+
+// JPEGCMYKFiles: since the Context was made, the files that reached the four-component JPEG decoder (IPX_JPEG_CMYK=1).
+func (x *Context) JPEGCMYKFiles() (int64, error) {
+	var c C.longlong
+	err := call(func() C.int { return C.ipx_jpeg_cmyk_files(x.c, &c) })
+	return int64(c), err
 }

@@ -786,6 +786,36 @@ class Context:
         _check(lib().ipx_jpeg_decode_counts(self.handle, counts))
         return list(counts)
 
+    def jpeg_decode_batch_cmyk(self, files, w=0, h=0, download=True):
+        """image.Decode of a batch of four-component JPEG byte strings (Adobe CMYK / YCCK) on the GPU, under IPX_JPEG_CMYK=1.
+        -> (info, status list); info = dict(w, h, stride, pix) with pix as an n x h x w x 4 uint8 array of *image.CMYK pixels
+        (download=True), or the device batch (CmykBatch) + `free()`; None when no file was decodable."""
+        n = len(files)
+        arr = _bytes_array(files)
+        cw, chh = C.c_int(w), C.c_int(h)
+        b = _lib.CmykBatch()
+        status = (C.c_int * max(n, 1))()
+        owner = C.c_void_p()
+        _check(lib().ipx_jpeg_decode_batch_cmyk(self.handle, None, arr, n, C.byref(cw), C.byref(chh), C.byref(b), status, C.byref(owner)))
+        st = list(status)[:n]
+        if not b.pix:
+            return None, st
+        info = {"w": cw.value, "h": chh.value, "stride": b.stride}
+        if download:
+            out = np.empty((n, b.frame_stride), np.uint8)
+            _check(lib().ipx_memcpy_d2h(self.handle, out.ctypes.data, b.pix, out.nbytes))
+            info["pix"] = out[:, :chh.value * b.stride].reshape(n, chh.value, cw.value, 4)
+            lib().ipx_jpeg_planes_free(self.handle, owner)
+        else:
+            info.update(batch=b, free=lambda: lib().ipx_jpeg_planes_free(self.handle, owner))
+        return info, st
+
+    def jpeg_cmyk_files(self):
+        """Since the context was made: files that reached the four-component JPEG decoder."""
+        files = C.c_longlong(0)
+        _check(lib().ipx_jpeg_cmyk_files(self.handle, C.byref(files)))
+        return files.value
+
     def gif_decode_batch(self, files, w=0, h=0, download=True):
         """image.Decode of a batch of GIF byte strings on the GPU (the first image of each).  -> (info, status list); info = dict(w, h,
         stride, index, palettes) with index as n x h x w and palettes as n x 256 x 4 uint8 arrays (download=True), or the device

@@ -52,6 +52,10 @@ class YCbCrBatch(C.Structure):
                 ("ratio", C.c_int32)]
 
 
+class CmykBatch(C.Structure):
+    _fields_ = [("pix", C.c_void_p), ("stride", C.c_int32), ("frame_stride", C.c_size_t)]
+
+
 class PalettedBatch(C.Structure):
     _fields_ = [("index", C.c_void_p), ("stride", C.c_int32), ("frame_stride", C.c_size_t), ("palettes", C.c_void_p)]
 
@@ -215,6 +219,9 @@ SIGNATURES = {
     "ipx_jpeg_planes_free": (None, [_P, _P]),
     "ipx_jpeg_scan_route": (_I, [_P, _Z, C.POINTER(_I)]),
     "ipx_jpeg_decode_counts": (_I, [_P, C.POINTER(C.c_longlong)]),
+    "ipx_jpeg_decode_batch_cmyk": (_I, [_P, _P, C.POINTER(Bytes), _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(CmykBatch), C.POINTER(_I),
+                                        C.POINTER(_P)]),
+    "ipx_jpeg_cmyk_files": (_I, [_P, C.POINTER(C.c_longlong)]),
     "ipx_plan_run_jpeg_jpeg": (_I, [_P, _P, _I, C.POINTER(Bytes), _I, C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(_I),
                                     C.POINTER(_P)]),
     "ipx_plan_run_host_jpeg": (_I, [_P, _P, _I, _P, _I, _Z, _I, C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(_P)]),

@@ -9,6 +9,18 @@ namespace {
 
 constexpr uint32_t kM = 0xffffu;
 
+// color.YCbCrToRGB on 8-bit samples (the uint32 overflow test of the Go code): R | G << 8 | B << 16 | 0xff << 24, as imageutil.DrawYCbCr
+// stores a pixel
+__device__ __forceinline__ uint32_t ycbcr_to_rgb8(uint32_t y, uint32_t cb, uint32_t cr)
+{
+    const int32_t yy1 = (int32_t)y * 0x10101, cb1 = (int32_t)cb - 128, cr1 = (int32_t)cr - 128;
+    int32_t r = yy1 + 91881 * cr1, g = yy1 - 22554 * cb1 - 46802 * cr1, b = yy1 + 116130 * cb1;
+    r = ((uint32_t)r & 0xff000000u) == 0 ? r >> 16 : ~(r >> 31);
+    g = ((uint32_t)g & 0xff000000u) == 0 ? g >> 16 : ~(g >> 31);
+    b = ((uint32_t)b & 0xff000000u) == 0 ? b >> 16 : ~(b >> 31);
+    return ((uint32_t)r & 0xffu) | (((uint32_t)g & 0xffu) << 8) | (((uint32_t)b & 0xffu) << 16) | 0xff000000u;
+}
+
 // v * 0x101 for byte `C` of a packed RGBA dword, as float64
 template <int C>
 __device__ __forceinline__ double widen(uint32_t px)

@@ -256,9 +256,16 @@ hipError_t launch_par_unstuff(const JpegParArgs &a, hipStream_t s);
 hipError_t launch_par_sync(const JpegParArgs &a, int round, hipStream_t s);
 hipError_t launch_par_write(const JpegParArgs &a, hipStream_t s);
 hipError_t launch_par_dc(const JpegParArgs &a, hipStream_t s);
-int jpeg_parse(const uint8_t *d, size_t len, JpegDecInfo *info, JpegDecTables *tab);
+int jpeg_parse(const uint8_t *d, size_t len, JpegDecInfo *info, JpegDecTables *tab, bool cmyk = false);
 int jpeg_host_decode(const uint8_t *d, size_t len, JpegDecInfo *info, int16_t *coefs, int16_t *dcs, size_t nblk, uint16_t qnat[3][64],
                      bool *progressive);
+// Four-component files (IPX_JPEG_CMYK=1; ipx_jpeg_dec_cmyk.hip): every scan on the host, into TWO coefficient sets the IDCT kernel reads as
+// they are -- components 0..2 as a three-component image of the file's sampling (mxx * myy * (ybl + 2) blocks in MCU order), then
+// component 3 as a Gray image of component 0's block grid, raster by block ((h0 * mxx) * (v0 * myy) blocks).  nblk is the sum; coefs, dcs
+// and the progressive flag as for jpeg_host_decode; qnat[3] is component 3's quantiser; *transform the Adobe APP14 transform byte (a
+// file without a valid APP14 segment is IPX_ERR_UNSUPPORTED: Go's "unknown color model").
+int jpeg_host_decode4(const uint8_t *d, size_t len, JpegDecInfo *info, int16_t *coefs, int16_t *dcs, size_t nblk, uint16_t qnat[4][64],
+                      bool *progressive, int *transform);
 // ---- progressive scans walked on the GPU (IPX_JPEG_PROG_GPU=1): the scan program of a file (jpeg_prog_prepass in ipx_jpeg_dec_prog.cpp)
 // and the kernel that runs it (ipx_jpeg_dec_scans.hip) ----
 constexpr int IPX_JPEG_PROG_MAX_SCANS = 64;

@@ -6,8 +6,8 @@
 // tiny: walk the markers, collect the tables the single scan refers to, and lay them out the way the kernels read them
 // (an 8-bit first-level Huffman table plus the canonical mincode / maxcode arrays for longer codes; quantisers
 // de-zig-zagged).  Anything outside the baseline subset the kernels implement is reported as IPX_ERR_UNSUPPORTED for
-// that image, so that the worker keeps Go's CPU path for it: CMYK / RGB (Adobe) files, 4:1:1 / 4:1:0 and other sampling factors,
-// 12-bit samples.  Progressive files, files coded in several scans and Huffman table ids above 1 are marked host_scans: their
+// that image, so that the worker keeps Go's CPU path for it: CMYK / RGB (Adobe) files (four-component files are taken under
+// IPX_JPEG_CMYK=1: ipx_jpeg_dec_cmyk.hip), 4:1:1 / 4:1:0 and other sampling factors, 12-bit samples.  Progressive files, files coded in several scans and Huffman table ids above 1 are marked host_scans: their
 // scans are decoded on the host (ipx_jpeg_dec_prog.cpp) and only the transform onwards runs on the GPU.  A file has to end the way
 // Go's marker loop wants it to (EOI after the last scan), or it is malformed here as it is there.
 #include <algorithm>
@@ -56,14 +56,16 @@ bool build_huff(const RawHuff &r, uint16_t lut[256], int32_t maxcode[18], int32_
 }  // namespace
 
 // 0 ok; IPX_ERR_INVALID malformed; IPX_ERR_UNSUPPORTED a valid file outside the GPU subset
-int jpeg_parse(const uint8_t *d, size_t len, JpegDecInfo *info, JpegDecTables *tab)
+// cmyk (IPX_JPEG_CMYK=1, ipx_jpeg_dec_cmyk.hip): a four-component frame with one of the two sampling vectors Go's processSOF takes is
+// IPX_OK with ncomp 4 and host_scans set -- its tables and scans are the host decoder's alone -- instead of IPX_ERR_UNSUPPORTED
+int jpeg_parse(const uint8_t *d, size_t len, JpegDecInfo *info, JpegDecTables *tab, bool cmyk)
 {
     memset(info, 0, sizeof *info);
     if (len < 4 || d[0] != 0xff || d[1] != 0xd8) return IPX_ERR_INVALID;
     uint16_t quant[4][64];
     memset(quant, 0, sizeof quant);                            // a table no DQT defined is all zero in Go's decoder, and the file decodes (to flat grey)
     RawHuff hf[2][4];
-    int ncomp = 0, ch[3] = {0, 0, 0}, cv[3] = {0, 0, 0}, ctq[3] = {0, 0, 0}, cid[3] = {0, 0, 0};
+    int ncomp = 0, ch[4] = {0, 0, 0, 0}, cv[4] = {0, 0, 0, 0}, ctq[4] = {0, 0, 0, 0}, cid[4] = {0, 0, 0, 0};
     bool jfif = false, adobe = false;
     int adobe_transform = 0;
     size_t i = 2;
@@ -88,8 +90,8 @@ int jpeg_parse(const uint8_t *d, size_t len, JpegDecInfo *info, JpegDecTables *t
             if (s[0] != 8) return IPX_ERR_UNSUPPORTED;
             info->h = (int)be16(s + 1); info->w = (int)be16(s + 3);
             ncomp = s[5];
-            if (ncomp == 4) return IPX_ERR_UNSUPPORTED;
-            if ((ncomp != 3 && ncomp != 1) || sn != (size_t)(6 + 3 * ncomp) || info->w <= 0 || info->h <= 0) return IPX_ERR_INVALID;
+            if (ncomp == 4 && !cmyk) return IPX_ERR_UNSUPPORTED;
+            if ((ncomp != 3 && ncomp != 1 && ncomp != 4) || sn != (size_t)(6 + 3 * ncomp) || info->w <= 0 || info->h <= 0) return IPX_ERR_INVALID;
             if ((long long)info->w * info->h > (1LL << 28)) return IPX_ERR_UNSUPPORTED;   // 268 Mpixel: beyond any batch this path is meant for
             for (int c = 0; c < ncomp; c++) {
                 cid[c] = s[6 + 3 * c]; ch[c] = s[7 + 3 * c] >> 4; cv[c] = s[7 + 3 * c] & 15; ctq[c] = s[8 + 3 * c];
@@ -100,6 +102,12 @@ int jpeg_parse(const uint8_t *d, size_t len, JpegDecInfo *info, JpegDecTables *t
                 if (ch[c] == 3 || cv[c] == 3) return IPX_ERR_UNSUPPORTED;
             }
             if (ncomp == 1) { ch[0] = cv[0] = 1; break; }   // processSOF: a single component is non-interleaved, its (h, v) is effectively (1, 1)
+            if (ncomp == 4) {
+                // processSOF: (h, v) = 11 11 11 11 or 22 11 11 22, everything else is "unsupported subsampling ratio"
+                if (ch[0] != cv[0] || ch[0] > 2 || ch[1] != 1 || cv[1] != 1 || ch[2] != 1 || cv[2] != 1 || ch[3] != ch[0] || cv[3] != cv[0]) return IPX_ERR_UNSUPPORTED;
+                info->host_scans = 1;
+                break;
+            }
             if (ch[1] != 1 || cv[1] != 1 || ch[2] != 1 || cv[2] != 1 || ch[0] > 2 || cv[0] > 2) return IPX_ERR_UNSUPPORTED;
             break;
         }

@@ -10,6 +10,10 @@
 // IDCT kernel reads; the coefficients go up (6.3 MB per 1080p 4:2:0 file, still less than its pixels), and dequantisation, the
 // integer IDCT, every operator and jpeg.Encode run on the GPU as for baseline files.
 //
+// Under IPX_JPEG_CMYK=1 the same decoder takes four-component files (Adobe CMYK / YCCK: jpeg_host_decode4), whose fourth component
+// goes into a block set of its own behind the three-component one (ipx_jpeg_dec_cmyk.hip; the four-component rules are recalled, not
+// read: DESIGN.md section 4.6).
+//
 // Restated from Go 1.24 image/jpeg (reader.go: decode's marker loop, processSOF / DQT / DHT / DRI; scan.go: processSOS, refine,
 // refineNonZeroes; huffman.go: decodeHuffman, receiveExtend, decodeBit(s)): garbage between segments is skipped, "\xff\x00" outside
 // a scan is ignored, a stray RSTn is ignored, EOI is required.  What Go does and this path does not is reported, never guessed at:
@@ -131,7 +135,8 @@ struct Decoder {
     size_t len;
     int w = 0, h = 0, ncomp = 0;
     bool progressive = false, baseline = false;
-    int cid[3], ch[3], cv[3], ctq[3];
+    bool cmyk = false;                // IPX_JPEG_CMYK=1 (jpeg_host_decode4): a four-component frame is taken, with component 3 in a block set of its own
+    int cid[4], ch[4], cv[4], ctq[4];
     uint16_t quant[4][64];
     Huff hf[2][4];
     int ri = 0;
@@ -158,6 +163,7 @@ struct Decoder {
         // sampling factors are 1 or 2 here (everything else was refused at the frame header): shifts and masks, no division -- this
         // runs once per block and scan
         const int sx = ch[k] - 1, sy = cv[k] - 1;
+        if (k == 3) return (size_t)mxx * myy * bpm + (size_t)by * (mxx * ch[3]) + bx;   // blackPix: raster by block, behind the three-component set
         return ((size_t)(by >> sy) * mxx + (bx >> sx)) * bpm + (k == 0 ? (size_t)((by & sy) << sx) + (bx & sx) : (size_t)ybl + k - 1);
     }
 
@@ -227,7 +233,7 @@ struct Decoder {
     }
 
     // the checks at the top of processSOS on the header at s (sn bytes); false: status is set
-    struct ScanHeader { int ns, ci[3], td[3], ta[3]; int32_t zs, ze; uint32_t ah, al; };
+    struct ScanHeader { int ns, ci[4], td[4], ta[4]; int32_t zs, ze; uint32_t ah, al; };
     bool scan_header(const uint8_t *s, size_t sn, ScanHeader *H)
     {
         if (!ncomp) return fail(IPX_ERR_INVALID), false;
@@ -235,7 +241,7 @@ struct Decoder {
         const int ns = H->ns = s[0];
         if (sn != (size_t)(4 + 2 * ns)) return fail(IPX_ERR_INVALID), false;
         int *ci = H->ci, *td = H->td, *ta = H->ta, total_hv = 0;
-        for (int i = 0; i < 3; i++) ci[i] = td[i] = ta[i] = 0;
+        for (int i = 0; i < 4; i++) ci[i] = td[i] = ta[i] = 0;
         for (int i = 0; i < ns; i++) {
             int k = -1;
             for (int j = 0; j < ncomp; j++) if (s[1 + 2 * i] == cid[j]) k = j;
@@ -325,14 +331,14 @@ struct Decoder {
         if (!out_ready) {
             ybl = ch[0] * cv[0];
             bpm = ncomp == 1 ? 1 : ybl + 2;
-            if ((size_t)mxx * myy * bpm != out_blocks) return fail(IPX_ERR_UNSUPPORTED);       // not the frame the header parser saw
+            if ((size_t)mxx * myy * (ncomp == 4 ? bpm + ybl : bpm) != out_blocks) return fail(IPX_ERR_UNSUPPORTED);       // not the frame the header parser saw
             memset(out, 0, out_blocks * 64 * sizeof(int16_t));
             if (progressive) nzmask.assign(out_blocks, 0);
             out_ready = true;
         }
         scans++;
         Bits br{d, len, *pos};
-        int32_t dc[3] = {0, 0, 0};
+        int32_t dc[4] = {0, 0, 0, 0};
         int mcu = 0, expected = 0xd0;
         int nbx = 0, nby = 0;                 // the next block of a non-interleaved scan, which walks the component's own block grid
         const int q1 = ns == 1 ? mxx * ch[ci[0]] : 0;
@@ -412,7 +418,7 @@ struct Decoder {
                     br.pos += 2;
                     expected = expected == 0xd7 ? 0xd0 : expected + 1;
                     br.acc = 0; br.n = 0;
-                    dc[0] = dc[1] = dc[2] = 0;
+                    dc[0] = dc[1] = dc[2] = dc[3] = 0;
                     eobrun = 0;
                 }
             }
@@ -452,7 +458,7 @@ struct Decoder {
             case 0xc0: case 0xc1: case 0xc2: {
                 baseline = m == 0xc0; progressive = m == 0xc2;
                 if (ncomp) return fail(IPX_ERR_INVALID);
-                if (sn == 9) ncomp = 1; else if (sn == 15) ncomp = 3; else return fail(IPX_ERR_UNSUPPORTED);
+                if (sn == 9) ncomp = 1; else if (sn == 15) ncomp = 3; else if (sn == 18 && cmyk) ncomp = 4; else return fail(IPX_ERR_UNSUPPORTED);
                 if (s[0] != 8) return fail(IPX_ERR_UNSUPPORTED);
                 h = (int)be16(s + 1); w = (int)be16(s + 3);
                 if (s[5] != ncomp) return fail(IPX_ERR_INVALID);
@@ -468,6 +474,9 @@ struct Decoder {
                     ch[c] = hh; cv[c] = vv;
                 }
                 if (ncomp == 3 && (ch[1] != 1 || cv[1] != 1 || ch[2] != 1 || cv[2] != 1 || ch[0] > 2 || cv[0] > 2)) return fail(IPX_ERR_UNSUPPORTED);
+                // processSOF, four components: 11 11 11 11 or 22 11 11 22 ("unsupported subsampling ratio" otherwise)
+                if (ncomp == 4 && (ch[0] != cv[0] || ch[0] > 2 || ch[1] != 1 || cv[1] != 1 || ch[2] != 1 || cv[2] != 1 || ch[3] != ch[0] || cv[3] != cv[0]))
+                    return fail(IPX_ERR_UNSUPPORTED);
                 if (w <= 0 || h <= 0) return fail(IPX_ERR_INVALID);
                 if ((long long)w * h > (1LL << 28)) return fail(IPX_ERR_UNSUPPORTED);
                 mxx = (w + 8 * ch[0] - 1) / (8 * ch[0]); myy = (h + 8 * cv[0] - 1) / (8 * cv[0]);
@@ -517,6 +526,7 @@ struct Decoder {
         if (status == IPX_OK && !scans) fail(IPX_ERR_INVALID);              // "missing SOS marker"
         if (status == IPX_OK && ncomp == 3 && !jfif && ((adobe && adobe_transform == 0) || (cid[0] == 'R' && cid[1] == 'G' && cid[2] == 'B')))
             fail(IPX_ERR_UNSUPPORTED);                                      // isRGB
+        if (status == IPX_OK && ncomp == 4 && !adobe) fail(IPX_ERR_UNSUPPORTED);   // applyBlack: "unknown color model" without a valid APP14
         if (status == IPX_OK && dqt_after_scan) fail(IPX_ERR_UNSUPPORTED);  // Go dequantises a sequential file scan by scan
     }
 };
@@ -547,6 +557,32 @@ int jpeg_host_decode(const uint8_t *d, size_t len, JpegDecInfo *info, int16_t *c
     for (size_t gb = 0; gb < nblk; gb++) { dcs[gb] = coefs[gb * 64]; coefs[gb * 64] = 0; }
     for (int c = 0; c < 3; c++)
         for (int zig = 0; zig < 64; zig++) qnat[c][kUnzig[zig]] = c < D.ncomp ? D.quant[D.ctq[c]][zig] : 0;
+    return IPX_OK;
+}
+
+// The same for a four-component file (ipx_internal.h): the three-component set first, component 3's raster set behind it.
+int jpeg_host_decode4(const uint8_t *d, size_t len, JpegDecInfo *info, int16_t *coefs, int16_t *dcs, size_t nblk, uint16_t qnat[4][64],
+                      bool *progressive, int *transform)
+{
+    Decoder D;
+    memset(D.quant, 0, sizeof D.quant);
+    memset(D.cid, 0, sizeof D.cid); memset(D.ch, 0, sizeof D.ch); memset(D.cv, 0, sizeof D.cv); memset(D.ctq, 0, sizeof D.ctq);
+    D.d = d; D.len = len;
+    D.out = coefs; D.out_blocks = nblk;
+    D.cmyk = true;
+    D.run();
+    if (D.status != IPX_OK) return D.status;
+    if (!D.out_ready) return IPX_ERR_INVALID;
+    if (D.ncomp != 4) return IPX_ERR_UNSUPPORTED;                            // (the caller hands over four-component files only)
+    memset(info, 0, sizeof *info);
+    info->w = D.w; info->h = D.h; info->h0 = D.ch[0]; info->v0 = D.cv[0]; info->ncomp = 4; info->ri = 0;
+    info->ratio = D.ch[0] == 1 ? IPX_YCBCR_444 : IPX_YCBCR_420;
+    *progressive = D.progressive;
+    *transform = D.adobe_transform;
+    if (D.wide) return IPX_ERR_UNSUPPORTED;
+    for (size_t gb = 0; gb < nblk; gb++) { dcs[gb] = coefs[gb * 64]; coefs[gb * 64] = 0; }
+    for (int c = 0; c < 4; c++)
+        for (int zig = 0; zig < 64; zig++) qnat[c][kUnzig[zig]] = D.quant[D.ctq[c]][zig];
     return IPX_OK;
 }
 

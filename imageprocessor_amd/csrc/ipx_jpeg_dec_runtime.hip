@@ -404,7 +404,7 @@ int ipx_jpeg_scan_route(const uint8_t *file, size_t len, int *route) try
     if (len >= ((size_t)1 << 30)) return IPX_ERR_UNSUPPORTED;
     JpegDecInfo info;
     JpegDecTables tab;
-    const int st = jpeg_parse(file, len, &info, &tab);
+    const int st = jpeg_parse(file, len, &info, &tab, jpeg_cmyk_enabled());   // (a four-component file: the host route, under IPX_JPEG_CMYK=1)
     if (st != IPX_OK) return st;
     if (info.host_scans) {
         JpegProgPlan plan;

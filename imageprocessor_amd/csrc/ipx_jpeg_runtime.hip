@@ -551,8 +551,8 @@ static int run_jpeg_jpeg_one(const char *who, ipx_ctx *ctx, const ipx_plan *pl, 
 }
 
 
-// the body of ipx_plan_run_jpeg_jpeg (texts == NULL: no text launch) and ipx_plan_run_jpeg_jpeg_texts
-static int run_jpeg_jpeg(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, const ipx_text *texts, int quality,
+// the three-component and Gray files of a call (every file, without IPX_JPEG_CMYK=1)
+static int run_jpeg_jpeg_ycbcr(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, const ipx_text *texts, int quality,
                          ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result)
 {
     *result = nullptr;
@@ -581,6 +581,97 @@ static int run_jpeg_jpeg(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int 
         if (rcs[k] && !rc) { rc = rcs[k]; set_error("%s", errs[k].c_str()); }
     }
     if (rc) return rc;
+    *result = all.release();
+    return IPX_OK;
+}
+
+// One sub-batch of four-component files (IPX_JPEG_CMYK=1; ipx_jpeg_dec_cmyk.hip): files[idx[g]], all of one sampling vector (h0), are
+// decoded to *image.CMYK frames, go through the plan as the deep CMYK source and are encoded; streams and statuses land at idx[g].
+// texts: null, or the call's texts (texts[idx[g]] is drawn on file idx[g]'s watermark frame).
+static int run_jpeg_jpeg_cmyk(const char *who, ipx_ctx *ctx, const ipx_plan *pl, const ipx_bytes *files, const ipx_text *texts, const std::vector<int> &idx,
+                              int h0, int quality, const PlanOutputs &outs, int *status, ResultOwner &res)
+{
+    const int m = (int)idx.size();
+    if (m == 0) return IPX_OK;
+    if (m > 65535) { for (int i : idx) status[i] = IPX_ERR_UNSUPPORTED; return IPX_OK; }
+    std::vector<ipx_bytes> gfiles(m);
+    std::vector<ipx_text> gtexts;
+    std::vector<int> gstatus(m, IPX_ERR_UNSUPPORTED);
+    for (int g = 0; g < m; g++) gfiles[g] = files[idx[g]];
+    LaneLease lane(ctx);
+    hipStream_t s = lane->stream;
+    int w = pl->p.sw, h = pl->p.sh;
+    ipx_cmyk_batch frames;
+    ipx_jpeg_planes *owner = nullptr;
+    memset(&frames, 0, sizeof frames);
+    int rc = jpeg_decode_cmyk_files(ctx, s, gfiles.data(), m, &w, &h, h0, &frames, gstatus.data(), &owner);
+    for (int g = 0; g < m; g++) status[idx[g]] = gstatus[g];
+    if (rc || !frames.pix) return rc;
+    struct Guard { ipx_ctx *c; ipx_jpeg_planes *o; ~Guard() { ipx_jpeg_planes_free(c, o); } } guard{ctx, owner};
+    const size_t per_frame = outs.frame_bytes();
+    if (per_frame == 0) return IPX_OK;
+    const int chunk = std::max(1, std::min(m, env_int("IPX_JPEG_JPEG_CHUNK", 256)));
+    rc = lane_reserve(lane.get(), per_frame * chunk + 256);
+    if (rc) return rc;
+    // the sub-batch's own texts as one set: chunk c0 draws texts c0 .. c0 + cm of it
+    ipx_textset ts;
+    const bool draw = texts && pl->p.do_watermark && outs.o[2].fs;
+    if (draw) {
+        gtexts.resize(m);
+        for (int g = 0; g < m; g++) gtexts[g] = texts[idx[g]];
+        if ((rc = textset_build(s, who, gtexts.data(), m, outs.o[2].w, outs.o[2].h, &ts))) return rc;
+    }
+    for (int c0 = 0; c0 < m && !rc; c0 += chunk) {
+        const int cm = std::min(chunk, m - c0);
+        const PlanOutputs::Frames f = outs.place((uint8_t *)(((uintptr_t)lane->dev + 255) & ~(uintptr_t)255), chunk);
+        const BatchSrc d = packed_src(kSrcCMYK, frames.pix + frames.frame_stride * c0, frames.stride, frames.frame_stride);
+        rc = run_dev_src(ctx, s, pl, cm, d, outs.dst(f));
+        if (!rc && draw) rc = dev_composite_texts(s, nullptr, f.dev[2], outs.o[2].w * 4, outs.o[2].fs, cm, ts, c0, nullptr);
+        if (!rc) rc = encode_outputs(ctx, s, outs, f, cm, 0, quality, status, res, idx.data() + c0);
+    }
+    (void)hipStreamSynchronize(s);
+    return rc;
+}
+
+// the body of ipx_plan_run_jpeg_jpeg (texts == NULL: no text launch) and ipx_plan_run_jpeg_jpeg_texts.  Under IPX_JPEG_CMYK=1 the
+// four-component files are taken out of the call and run as sub-batches of one sampling vector each; the rest runs as it always did.
+static int run_jpeg_jpeg(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, const ipx_text *texts, int quality,
+                         ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result)
+{
+    *result = nullptr;
+    std::vector<int> four[2], rest;
+    if (jpeg_cmyk_enabled())
+        for (int i = 0; i < n; i++) {
+            const int h0 = jpeg_cmyk_peek(files[i].data, files[i].len);
+            if (h0) four[h0 - 1].push_back(i); else rest.push_back(i);
+        }
+    if (four[0].empty() && four[1].empty()) return run_jpeg_jpeg_ycbcr(who, ctx, pl, n, files, texts, quality, resize_out, thumb_out, wm_out, status, result);
+    const PlanOutputs outs(pl, resize_out, thumb_out, wm_out, Codec::Jpeg, Codec::Jpeg, Codec::Jpeg);
+    outs.clear(n);
+    ResultOwner all(ctx);
+    const int nr = (int)rest.size();
+    if (nr) {
+        // the rest of the call, compacted: its streams and statuses go back to the files' own indices
+        std::vector<ipx_bytes> rfiles(nr), out[3];
+        std::vector<ipx_text> rtexts(texts ? nr : 0);
+        std::vector<int> rstatus(nr, IPX_OK);
+        ipx_bytes *const dst[3] = {resize_out, thumb_out, wm_out};
+        for (int k = 0; k < 3; k++) if (dst[k]) out[k].assign(nr, ipx_bytes{nullptr, 0});
+        for (int g = 0; g < nr; g++) { rfiles[g] = files[rest[g]]; if (texts) rtexts[g] = texts[rest[g]]; }
+        ipx_jpeg_result *r = nullptr;
+        const int rc = run_jpeg_jpeg_ycbcr(who, ctx, pl, nr, rfiles.data(), texts ? rtexts.data() : nullptr, quality, dst[0] ? out[0].data() : nullptr,
+                                           dst[1] ? out[1].data() : nullptr, dst[2] ? out[2].data() : nullptr, rstatus.data(), &r);
+        all.adopt(r);
+        if (rc) return rc;
+        for (int g = 0; g < nr; g++) {
+            status[rest[g]] = rstatus[g];
+            for (int k = 0; k < 3; k++) if (dst[k]) dst[k][rest[g]] = out[k][g];
+        }
+    }
+    for (int v = 0; v < 2; v++) {
+        const int rc = run_jpeg_jpeg_cmyk(who, ctx, pl, files, texts, four[v], v + 1, quality, outs, status, all);
+        if (rc) return rc;
+    }
     *result = all.release();
     return IPX_OK;
 }

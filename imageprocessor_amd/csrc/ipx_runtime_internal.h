@@ -69,6 +69,7 @@ struct ipx_ctx {
     std::map<std::pair<int, int>, std::pair<uint8_t *, KsAxisDev>> ks_axes;
     // ipx_jpeg_decode_counts: files decoded by route (IPX_JPEG_ROUTE_*) since ipx_create; [3]: files the GPU scan walk ended with a status
     std::atomic<long long> jpeg_counts[4] = {{0}, {0}, {0}, {0}};
+    std::atomic<long long> jpeg_cmyk_files{0};     // ipx_jpeg_cmyk_files: files that reached the four-component decoder (ipx_jpeg_dec_cmyk.hip)
     static constexpr size_t kFlatChromaBytes = (size_t)64 << 10;
 };
 
@@ -456,6 +457,13 @@ int gif_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w, int 
 // image.Decode of n JPEG files into planes in HBM (ipx_jpeg_dec_runtime.hip); *w x *h: the size asked for, or 0 for the first parsed file's
 int jpeg_decode_files(ipx_ctx *ctx, hipStream_t s, Lane *lane, bool planes_in_lane, const ipx_bytes *jpegs, int n, int *w, int *h,
                       ipx_ycbcr_batch *planes, int *status, ipx_jpeg_planes **owner);
+// four-component files (ipx_jpeg_dec_cmyk.hip): the switch, the legs' test of a file's frame header (its vector, 1 or 2; 0: not one
+// of these files), and the driver -- *w, *h as for jpeg_decode_files, want_h0 > 0: only files whose component 0 has that sampling
+// factor (the legs' sub-batches are of one vector)
+bool jpeg_cmyk_enabled();
+int jpeg_cmyk_peek(const uint8_t *d, size_t len);
+int jpeg_decode_cmyk_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *jpegs, int n, int *w, int *h, int want_h0, ipx_cmyk_batch *frames,
+                           int *status, ipx_jpeg_planes **owner);
 
 // the pinned blocks the streams of the compressed-out batch entries live in (ipx_jpeg_result_free)
 struct ipx_jpeg_result { std::vector<uint8_t *> blobs; };

@@ -585,7 +585,9 @@ typedef struct ipx_jpeg_planes ipx_jpeg_planes;
 /* Compressed in, compressed out: the uploads as they arrive from the object store (image_processor.go:41-47), the
  * objects as they go back (:76).  image.Decode, every operator of the plan and jpeg.Encode run on the GPU; the
  * link carries ~0.3 MB up and ~0.5 MB down per 1080p image.  status[i] as for ipx_jpeg_decode_batch (the
- * plan's frame size is the batch's size); outputs of undecodable files are {NULL, 0}. */
+ * plan's frame size is the batch's size); outputs of undecodable files are {NULL, 0}.  Under IPX_JPEG_CMYK=1 the four-component
+ * files of the call (see ipx_jpeg_decode_batch_cmyk) are taken out of it, decoded to *image.CMYK frames and run as sub-batches of one
+ * sampling vector each; streams and statuses land at the files' own indices, the rest of the call runs as without the switch. */
 int ipx_plan_run_jpeg_jpeg(ipx_ctx *ctx, const ipx_plan *plan, int n, const ipx_bytes *files, int quality,
                            ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status,
                            ipx_jpeg_result **result);
@@ -594,13 +596,27 @@ int ipx_jpeg_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *jpegs, in
 void ipx_jpeg_planes_free(ipx_ctx *ctx, ipx_jpeg_planes *owner);
 /* Which decoder a JPEG file's scans reach: the parallel Huffman kernels (one baseline scan), the host threads, or the GPU scan walk. */
 enum { IPX_JPEG_ROUTE_PAR = 0, IPX_JPEG_ROUTE_HOST_SCANS = 1, IPX_JPEG_ROUTE_GPU_SCANS = 2 };
-/* host only, no context: the route this file would take now (IPX_JPEG_PROG_GPU is read); returns the parse status, *route is
- * meaningful when that is IPX_OK */
+/* host only, no context: the route this file would take now (IPX_JPEG_PROG_GPU is read; under IPX_JPEG_CMYK=1 a four-component file of a
+ * sampling vector Go takes answers IPX_OK and the host route); returns the parse status, *route is meaningful when that is IPX_OK */
 int ipx_jpeg_scan_route(const uint8_t *file, size_t len, int *route);
 /* since ipx_create: the files that reached the decoder of route [0..2] in any decode entry of this context (whatever status they ended
  * with; files refused by the marker parser or for their geometry reach none), and [3] the files the GPU scan walk ended with a status
  * other than IPX_OK */
 int ipx_jpeg_decode_counts(ipx_ctx *ctx, long long counts[4]);
+/* Four-component JPEGs (Adobe CMYK and YCCK: print-workflow and Photoshop files), with IPX_JPEG_CMYK=1 in the environment (read on every
+ * call; unset or anything else: every such file is IPX_ERR_UNSUPPORTED in every entry, as before).  Go takes two sampling vectors,
+ * (h, v) = 11 11 11 11 and 22 11 11 22, and needs a valid Adobe APP14 segment; a file of the call's size (*w, *h: 0, or the size the
+ * batch must have) and of the first such file's vector is decoded -- every scan on the host threads, baseline and progressive alike, the
+ * IDCT and applyBlack on the GPU -- into an *image.CMYK frame: frame i at pix + i * frame_stride, rows `stride` = 4 * w bytes apart, ready
+ * for ipx_plan_run_dev_deep(..., IPX_DEEP_CMYK, ...).  status[i]: IPX_OK, IPX_ERR_INVALID (malformed) or IPX_ERR_UNSUPPORTED (any other
+ * vector, no APP14 segment, another size or vector than the batch's, and every three- or one-component file: those are
+ * ipx_jpeg_decode_batch's).  pix == NULL when no file was decodable; the frames of non-OK files are undefined.  Free the frames with
+ * ipx_jpeg_planes_free.  DESIGN.md section 4.6. */
+typedef struct { uint8_t *pix; int32_t stride; size_t frame_stride; } ipx_cmyk_batch;
+int ipx_jpeg_decode_batch_cmyk(ipx_ctx *ctx, void *stream, const ipx_bytes *jpegs, int n, int *w, int *h,
+                               ipx_cmyk_batch *frames, int *status, ipx_jpeg_planes **owner);
+/* files that reached the four-component decoder (of this entry or of a compressed-in leg) since ipx_create, whatever came of them */
+int ipx_jpeg_cmyk_files(ipx_ctx *ctx, long long *files);
 
 /* ---- image.Decode for GIFs (decoder side) ---------------------------------------------
  * For a GIF upload image.Decode is gif.Decode: the FIRST image of the file as an *image.Paletted.  The host reads the container

@@ -7,7 +7,13 @@ usage: tools/bench_jpeg_dec.py [frames ...]
            process, alternated, a warm-up first, three repetitions each; one JSON line per batch size with files/s (median, min, max),
            host CPU seconds per file (time.process_time over the timed window), bytes uploaded per file (from the shapes) and one
            file alone.  --j2j: JPEG files -> three JPEG streams (ipx_plan_run_jpeg_jpeg) instead of the decode alone.  --profile: one
-           batch of 256 each way and nothing else, for a rocprofv3 --kernel-trace --stats run."""
+           batch of 256 each way and nothing else, for a rocprofv3 --kernel-trace --stats run.
+       tools/bench_jpeg_dec.py --cmyk [--j2j] [--profile] [--corpus DIR] [frames ...]
+           four-component files under IPX_JPEG_CMYK=1 (ipx_jpeg_decode_batch_cmyk, or with --j2j the files -> three JPEG streams):
+           1080p YCCK files of the vector 22 11 11 22, baseline, written by tests/jpeg_cmyk_writer.py from the quantised DCT of the
+           pictures above (Pillow writes transform-0 files of the vector 11 11 11 11 only); a warm-up, three repetitions, one JSON
+           line per batch size.  --corpus DIR keeps the files there (writing one takes the Python writer a while) and reads them back
+           when they exist.  --profile: two batches of 256 and nothing else."""
 import io
 import json
 import os
@@ -88,6 +94,96 @@ def progressive_bench(args):
         print(json.dumps(row), flush=True)
 
 
+def cmyk_corpus(folder, count=2):
+    """count 1080p YCCK files (22 11 11 22, transform 2) from the quantised DCT of synthetic pictures"""
+    import jpeg_cmyk_writer as cw
+    import jpeg_writer as jw
+    files = []
+    k8 = np.arange(8)
+    dct = np.sqrt(2.0 / 8) * np.cos((2 * k8[None, :] + 1) * k8[:, None] * np.pi / 16)
+    dct[0] /= np.sqrt(2.0)
+    q85 = oracle.jpeg_quant(85)
+    q = {0: [int(v) for v in q85[0]], 1: [int(v) for v in q85[1]], 2: [int(v) for v in q85[0]]}
+    for k in range(count):
+        path = os.path.join(folder, "ycck_1080p_%d.jpg" % k) if folder else None
+        if path and os.path.exists(path):
+            files.append(open(path, "rb").read())
+            continue
+        frame = cw.frame4(w, h, 2)
+        planes = [np.sin(xx / (40.0 + 7 * k)) * 90 + 128, np.cos(yy / (31.0 + 5 * k)) * 40 + 128, ((xx + 2 * yy) / 6.0 + 40 * k) % 64 + 96,
+                  np.cos((xx - yy) / (53.0 + 3 * k)) * 100 + 128]
+        noise = np.random.default_rng(k)
+        blocks = []
+        for c in range(4):
+            rows, cols = frame.grid(c)
+            p = (planes[c] + noise.normal(0, 6, (h, w))).clip(0, 255)
+            if c in (1, 2):
+                p = p[::2, ::2]
+            full = np.zeros((rows * 8, cols * 8))
+            full[:p.shape[0], :p.shape[1]] = p
+            full[p.shape[0]:, :] = full[p.shape[0] - 1:p.shape[0], :]           # edge replication, as an encoder pads
+            full[:, p.shape[1]:] = full[:, p.shape[1] - 1:p.shape[1]]
+            b = (full - 128).reshape(rows, 8, cols, 8).transpose(0, 2, 1, 3)
+            coef = np.einsum("ij,rcjk,lk->rcil", dct, b, dct).reshape(rows, cols, 64)[..., jw.ZIG]
+            blocks.append(np.rint(coef / np.asarray(q[frame.comps[c][3]], float)).astype(np.int64))
+        data = cw.cmyk_file(frame, blocks, transform=2, q=q)
+        if path:
+            os.makedirs(folder, exist_ok=True)
+            with open(path, "wb") as fh:
+                fh.write(data)
+        files.append(data)
+    return files
+
+
+def cmyk_bench(args):
+    os.environ["IPX_JPEG_CMYK"] = "1"
+    flags = {x for x in args if x.startswith("--")}
+    folder = args[args.index("--corpus") + 1] if "--corpus" in args else None
+    sizes = [int(x) for x in args if x.isdigit()] or [256, 1024]
+    src = cmyk_corpus(folder)
+    if "--write-only" in flags:
+        return
+    j2j = "--j2j" in flags
+    if j2j:
+        from helpers import DEFAULT_COL, text_glyphs
+        ctx = ipx.Context(lanes=int(os.environ.get("IPX_BENCH_LANES", "5")), lane_bytes=1 << 30)
+        gs = ctx.glyphset(text_glyphs(w, h), DEFAULT_COL)
+        plan = ctx.plan(w, h, resize=(1024, 768, True), thumbnail=(200, True), watermark=gs)
+    else:
+        ctx = ipx.Context()
+
+    def run(files):
+        before = ctx.jpeg_cmyk_files()
+        c0, t0 = time.process_time(), time.perf_counter()
+        if j2j:
+            _, st = plan.run_jpeg_jpeg(files, copy=False)
+            dt, dc = time.perf_counter() - t0, time.process_time() - c0
+        else:
+            info, st = ctx.jpeg_decode_batch_cmyk(files, download=False)
+            dt, dc = time.perf_counter() - t0, time.process_time() - c0
+            info["free"]()
+        assert not any(st) and ctx.jpeg_cmyk_files() - before == len(files), st[:8]
+        return dt, dc
+
+    if "--profile" in flags:
+        for _ in range(2):
+            run([src[i % len(src)] for i in range(256)])
+        return
+    print("YCCK files: %dx%d 22 11 11 22 q85 baseline, %.0f KB each; %s" % (w, h, sum(len(p) for p in src) / len(src) / 1e3,
+                                                                           "files -> three JPEG streams" if j2j else "ipx_jpeg_decode_batch_cmyk, frames left in HBM"))
+    run(src * 32)                                                           # warm-up
+    for n in sizes:
+        files = [src[i % len(src)] for i in range(n)]
+        t = [run(files) for _ in range(3)]
+        dts = sorted(x[0] for x in t)
+        print(json.dumps({"bench": "jpeg_cmyk_j2j" if j2j else "jpeg_cmyk_decode", "batch": n,
+                          "files_per_s": [round(n / dts[1], 1), round(n / dts[-1], 1), round(n / dts[0], 1)], "ms": round(dts[1] * 1e3, 2),
+                          "host_cpu_s_per_file": round(sorted(x[1] for x in t)[1] / n, 6)}), flush=True)
+
+
+if "--cmyk" in sys.argv[1:]:
+    cmyk_bench([x for x in sys.argv[1:] if x != "--cmyk"])
+    sys.exit(0)
 if "--progressive" in sys.argv[1:]:
     progressive_bench([x for x in sys.argv[1:] if x != "--progressive"])
     sys.exit(0)
