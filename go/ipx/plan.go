@@ -7,6 +7,7 @@ package ipx
 import "C"
 
 import (
+	"fmt"
 	"image"
 	"unsafe"
 )
@@ -121,6 +122,37 @@ func (p *Plan) RunHost(n int, src, resizeOut, thumbOut, wmOut []byte) error {
 	})
 }
 
+// The library's numbering of image.YCbCrSubsampleRatio (ipx.h: IPX_YCBCR_*).  444 .. 440 are Go's own values; 411 and 410 are NOT
+// (Go: 4 and 5; the library's 4 is IPX_GRAY), so a ratio is translated with Ratio, never cast.
+const (
+	YCbCr444  = 0
+	YCbCr422  = 1
+	YCbCr420  = 2
+	YCbCr440  = 3
+	RatioGray = 4 // IPX_GRAY: *image.Gray planes out of the JPEG decoder (only Y is set)
+	YCbCr411  = 5
+	YCbCr410  = 6
+)
+
+// Ratio translates a decoded image's SubsampleRatio; false for a value image/jpeg never produces.
+func Ratio(r image.YCbCrSubsampleRatio) (int, bool) {
+	switch r {
+	case image.YCbCrSubsampleRatio444:
+		return YCbCr444, true
+	case image.YCbCrSubsampleRatio422:
+		return YCbCr422, true
+	case image.YCbCrSubsampleRatio420:
+		return YCbCr420, true
+	case image.YCbCrSubsampleRatio440:
+		return YCbCr440, true
+	case image.YCbCrSubsampleRatio411:
+		return YCbCr411, true
+	case image.YCbCrSubsampleRatio410:
+		return YCbCr410, true
+	}
+	return 0, false
+}
+
 // RunHostYCbCr does the same for decoded JPEGs as image.Decode leaves them (*image.YCbCr planes of n frames, tightly packed per
 // plane): per operator the reference converts differently (16-bit per tap inside resize; RGBA8 first for the crop thumbnail and the
 // watermark), and the results are those of the reference's helpers on the *image.YCbCr itself.
@@ -128,6 +160,10 @@ func (p *Plan) RunHost(n int, src, resizeOut, thumbOut, wmOut []byte) error {
 // unpinned Go pointers, so the planes' bases are pinned for the call (a no-op for Pinned / C memory).  Synchronous: nothing is read
 // after the return.
 func (p *Plan) RunHostYCbCr(n int, first *image.YCbCr, y, cb, cr, resizeOut, thumbOut, wmOut []byte) error {
+	ratio, ok := Ratio(first.SubsampleRatio)
+	if !ok {
+		return fmt.Errorf("ipx: unknown YCbCrSubsampleRatio %d", int(first.SubsampleRatio))
+	}
 	cw, ch := first.CStride, len(first.Cb)/first.CStride
 	var pin runtimePinner
 	defer pin.Unpin()
@@ -137,7 +173,7 @@ func (p *Plan) RunHostYCbCr(n int, first *image.YCbCr, y, cb, cr, resizeOut, thu
 		}
 	}
 	b := C.ipx_ycbcr_batch{y: ptr(y), cb: ptr(cb), cr: ptr(cr), ystride: C.int32_t(first.YStride), cstride: C.int32_t(cw),
-		y_frame_stride: C.size_t(first.YStride * p.h), c_frame_stride: C.size_t(cw * ch), ratio: C.int32_t(first.SubsampleRatio)}
+		y_frame_stride: C.size_t(first.YStride * p.h), c_frame_stride: C.size_t(cw * ch), ratio: C.int32_t(ratio)}
 	i := p.Info
 	return call(func() C.int {
 		return C.ipx_plan_run_host_ycbcr(p.x.c, p.c, C.int(n), &b, ptr(resizeOut), C.size_t(i.ResizeBytes), ptr(thumbOut),
@@ -150,7 +186,7 @@ type Streams struct {
 	x                        *Context
 	res                      *C.ipx_jpeg_result
 	resize, thumb, watermark []C.ipx_bytes
-	Status                   []Status // per file, RunJPEGJPEG only: Unsupported = decode this one with Go (CMYK unless IPX_JPEG_CMYK=1, 4:1:1, another size)
+	Status                   []Status // per file, RunJPEGJPEG only: Unsupported = decode this one with Go (CMYK unless IPX_JPEG_CMYK=1, 4:1:1 / 4:1:0 unless IPX_JPEG_411=1, another size)
 }
 
 func view(b C.ipx_bytes) []byte {

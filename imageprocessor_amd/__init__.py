@@ -12,6 +12,8 @@ OP_OVER = 0
 DEEP_NRGBA64, DEEP_RGBA64, DEEP_GRAY16, DEEP_CMYK = 0, 1, 2, 3   # ipx.h IPX_DEEP_*
 PNG_GRAY, PNG_NRGBA, PNG_RGBA, PNG_PALETTED, PNG_GRAY16, PNG_RGBA64, PNG_NRGBA64 = range(7)   # ipx.h IPX_PNG_*
 OP_SRC = 1
+# ipx.h IPX_YCBCR_* / IPX_GRAY: 0..3 are image.YCbCrSubsampleRatio's own values, 411 and 410 are not (Go: 4 and 5)
+YCBCR_444, YCBCR_422, YCBCR_420, YCBCR_440, GRAY, YCBCR_411, YCBCR_410 = range(7)
 
 
 class IpxError(RuntimeError):
@@ -751,7 +753,7 @@ class Context:
         if not b.y:
             return None, st
         info = {"w": cw.value, "h": chh.value, "ratio": b.ratio, "ystride": b.ystride, "cstride": b.cstride}
-        v0 = 2 if b.ratio in (2, 3) else 1          # 4:2:0 and 4:4:0 halve the chroma rows (Gray: 8 x 8 MCUs)
+        v0 = 2 if b.ratio in (2, 3, YCBCR_410) else 1   # 4:2:0, 4:4:0 and 4:1:0 halve the chroma rows (Gray: 8 x 8 MCUs)
         myy = (chh.value + 8 * v0 - 1) // (8 * v0)
         yrows, crows = 8 * v0 * myy, 8 * myy            # image.NewYCbCr(Rect(0, 0, 8*h0*mxx, 8*v0*myy), ratio)
         if download:

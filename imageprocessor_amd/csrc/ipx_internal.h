@@ -82,8 +82,24 @@ inline int src_of_job(int k)
 // size of the chroma planes of a w x h *image.YCbCr (image.NewYCbCr)
 inline void chroma_size(int ratio, int w, int h, int *cw, int *ch)
 {
-    *cw = ratio == IPX_YCBCR_422 || ratio == IPX_YCBCR_420 ? (w + 1) / 2 : w;
-    *ch = ratio == IPX_YCBCR_420 || ratio == IPX_YCBCR_440 ? (h + 1) / 2 : h;
+    *cw = ratio == IPX_YCBCR_422 || ratio == IPX_YCBCR_420 ? (w + 1) / 2 : ratio == IPX_YCBCR_411 || ratio == IPX_YCBCR_410 ? (w + 3) / 4 : w;
+    *ch = ratio == IPX_YCBCR_420 || ratio == IPX_YCBCR_440 || ratio == IPX_YCBCR_410 ? (h + 1) / 2 : h;
+}
+// a ratio the *image.YCbCr entries take (IPX_GRAY has entries of its own)
+inline bool ycbcr_ratio_ok(int ratio) { return (ratio >= IPX_YCBCR_444 && ratio <= IPX_YCBCR_440) || ratio == IPX_YCBCR_411 || ratio == IPX_YCBCR_410; }
+// the shifts of COffset: Cb, Cr of pixel (x, y) sit at (x >> hs, y >> vs)
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int ycbcr_hshift(int ratio) { return ratio == IPX_YCBCR_422 || ratio == IPX_YCBCR_420 ? 1 : ratio == IPX_YCBCR_411 || ratio == IPX_YCBCR_410 ? 2 : 0; }
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int ycbcr_vshift(int ratio) { return ratio == IPX_YCBCR_420 || ratio == IPX_YCBCR_440 || ratio == IPX_YCBCR_410 ? 1 : 0; }
+// the ratio of a three-component frame whose luma factors are (h0, v0) with 1x1 chroma (makeImg)
+inline int ycbcr_ratio_of(int h0, int v0)
+{
+    return h0 == 4 ? (v0 == 1 ? IPX_YCBCR_411 : IPX_YCBCR_410) : h0 == 1 ? (v0 == 1 ? IPX_YCBCR_444 : IPX_YCBCR_440) : (v0 == 1 ? IPX_YCBCR_422 : IPX_YCBCR_420);
 }
 
 // ---- kernel launchers (ipx_kernels.hip) --------------------------------------------------------
@@ -217,7 +233,7 @@ struct JpegDecArgs {
     int16_t *dcs;                    // [n][nblk] the DC coefficient of every block (coefs[...][0] stays zero)
     int n, mxx, myy, h0, v0, nblk;   // n = images
     int w, h;                        // the batch's frame size (progressive images reconstruct only blocks that hold image pixels)
-    int bpm, ybl;                    // blocks per MCU and how many of them are luma (Gray: 1, 1)
+    int bpm, ybl;                    // blocks per MCU and how many of them are luma (Gray: 1, 1; 4:1:1: 6, 4 in one row; 4:1:0: 10, 8 as 2 rows of 4)
     int nitems;                      // pieces to decode (>= images)
     int shared_tables, first_valid;   // every valid image carries the Huffman tables of image first_valid
 };
@@ -231,7 +247,7 @@ inline int jpeg_status_key(uint32_t first_mcu, int status) { return -(int)(((0x3
 // lowest priority: any real decoding error elsewhere in the file, which Go fails on as well, wins
 constexpr uint32_t kJpegStatusLast = 0x3ffffffu;
 inline int jpeg_status_of(int key) { return key >= 0 ? 0 : -(int)((uint32_t)(-key) & 7u); }
-struct JpegPlanes { uint8_t *y, *cb, *cr; int ystride, cstride; size_t y_fs, c_fs; const uint8_t *valid; /* per image: bit 0 decodable, bit 1 progressive */ };
+struct JpegPlanes { uint8_t *y, *cb, *cr; int ystride, cstride; size_t y_fs, c_fs; const uint8_t *valid; /* per image: bit 0 decodable, bit 1 progressive, bits 2..4 component 0..2 coded by non-interleaved sequential scans only (jpeg_host_decode) */ };
 // Huffman decoding parallel inside a scan (ipx_jpeg_dec_par.hip): per image and per 1 KiB sub-sequence of its scan
 struct JpegParImage { unsigned long long scan_off; uint32_t scan_len, img, nsub; size_t sub_off; uint8_t td[3], ta[3], pad[2]; };
 struct JpegParArgs {
@@ -256,9 +272,13 @@ hipError_t launch_par_unstuff(const JpegParArgs &a, hipStream_t s);
 hipError_t launch_par_sync(const JpegParArgs &a, int round, hipStream_t s);
 hipError_t launch_par_write(const JpegParArgs &a, hipStream_t s);
 hipError_t launch_par_dc(const JpegParArgs &a, hipStream_t s);
-int jpeg_parse(const uint8_t *d, size_t len, JpegDecInfo *info, JpegDecTables *tab, bool cmyk = false);
+// s411 (IPX_JPEG_411=1): three-component frames with luma factors (4,1) and (4,2) and 1x1 chroma are taken too (4:1:1, 4:1:0)
+int jpeg_parse(const uint8_t *d, size_t len, JpegDecInfo *info, JpegDecTables *tab, bool cmyk = false, bool s411 = false);
 int jpeg_host_decode(const uint8_t *d, size_t len, JpegDecInfo *info, int16_t *coefs, int16_t *dcs, size_t nblk, uint16_t qnat[3][64],
-                     bool *progressive);
+                     bool *progressive, bool s411 = false, int *alone = nullptr);
+// *alone (sequential files of several components): bit c set when component c was coded by non-interleaved scans only.  Such a scan
+// carries no data for the blocks (bx, by) of the component's own grid with bx * 8 >= w or by * 8 >= h, and Go, which reconstructs a
+// sequential block when it decodes it, never writes them: they stay zero in the planes (JpegPlanes::valid bits 2..4).
 // Four-component files (IPX_JPEG_CMYK=1; ipx_jpeg_dec_cmyk.hip): every scan on the host, into TWO coefficient sets the IDCT kernel reads as
 // they are -- components 0..2 as a three-component image of the file's sampling (mxx * myy * (ybl + 2) blocks in MCU order), then
 // component 3 as a Gray image of component 0's block grid, raster by block ((h0 * mxx) * (v0 * myy) blocks).  nblk is the sum; coefs, dcs
@@ -311,6 +331,7 @@ struct JpegPlanOptions {
     bool use_par;              // IPX_JPEG_PAR: long scans without restart markers go to the parallel decoder
     int forced_sub, max_sub;   // IPX_JPEG_PAR_SUB: 128 .. 1024 fixes the sub-sequence size, else the batch chooses; jpeg_par_sub_bytes()
     bool prog_gpu = false;     // IPX_JPEG_PROG_GPU=1: progressive files with a clean pre-pass are walked on the GPU
+    bool s411 = false;         // IPX_JPEG_411=1: 4:1:1 and 4:1:0 files are taken (never by the GPU scan walk)
 };
 struct JpegBatchPlan {
     std::vector<JpegDecInfo> info;

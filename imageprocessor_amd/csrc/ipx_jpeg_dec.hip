@@ -297,12 +297,13 @@ __device__ __forceinline__ void idct_col(uint32_t (&s)[8])   // vertical pass (i
     s[4] = asr(y8 - y6, 14); s[5] = asr(y0 - y4, 14); s[6] = asr(y3 - y2, 14); s[7] = asr(y7 - y1, 14);
 }
 
-// A workgroup takes kIdctMcus consecutive MCUs of ONE MCU row (32 for one-component files): up to 48 blocks, eight threads each.
+// A workgroup takes kIdctMcus consecutive MCUs of ONE MCU row (32 for one-component files, 4 for the ten-block MCUs of 4:1:0): up to 48
+// blocks, eight threads each.
 // The pixels go to LDS at their place in the MCU row's strip of each plane, and the strip is written out in 8-byte pieces that are
 // consecutive across lanes -- a wave's store covers a few contiguous row segments.  (The first version stored each thread's eight
 // pixels straight from the block: 64 lanes, 64 different cache lines per store instruction, 398 M eight-byte write transactions per
 // 1024 1080p files; the kernel ran at 2.8 TB/s of its 9.5 GB.)  Index arithmetic: one division by the blocks-per-MCU count, a
-// constant per branch (1, 3, 4 or 6); per-image bases in scalar registers plus 32-bit offsets.
+// constant per branch (1, 3, 4, 6 or 10); per-image bases in scalar registers plus 32-bit offsets.
 constexpr int kIdctMcus = 8, kIdctMaxBlocks = 48, kIdctThreads = kIdctMaxBlocks * 8;
 __global__ __launch_bounds__(kIdctThreads) void jpeg_idct_kernel(JpegDecArgs a, JpegPlanes pl, int wgs_per_row, int mcus_per_wg)
 {
@@ -320,7 +321,8 @@ __global__ __launch_bounds__(kIdctThreads) void jpeg_idct_kernel(JpegDecArgs a, 
     case 1: mxl = blk; bi = 0; break;
     case 3: mxl = blk / 3; bi = blk - mxl * 3; break;
     case 4: mxl = blk >> 2; bi = blk & 3; break;
-    default: mxl = blk / 6; bi = blk - mxl * 6; break;    // 6 (4:2:0)
+    case 10: mxl = blk / 10; bi = blk - mxl * 10; break;  // 4:1:0: eight Y blocks as two rows of four
+    default: mxl = blk / 6; bi = blk - mxl * 6; break;    // 6 (4:2:0: Y 2 x 2; 4:1:1: Y 4 x 1)
     }
     const int mx = mx0 + mxl;
     const bool live = mxl < mcus_per_wg && mx < a.mxx;
@@ -348,10 +350,10 @@ __global__ __launch_bounds__(kIdctThreads) void jpeg_idct_kernel(JpegDecArgs a, 
 #pragma unroll
         for (int i = 0; i < 8; i++) s[i] = ws[blk * 72 + i * 8 + r];   // column r
         idct_col(s);
-        // pixel (row i, column r) of the block -> its place in the strip (h0, v0 are 1 or 2)
+        // pixel (row i, column r) of the block -> its place in the strip (h0 is 1, 2 or 4, v0 1 or 2)
         int base, pitch;
         if (c == 0) {
-            const int bxl = a.h0 == 2 ? bi & 1 : 0, byl = a.h0 == 2 ? bi >> 1 : bi;
+            const int bxl = bi & (a.h0 - 1), byl = bi >> (a.h0 >> 1);      // Y block bi of the MCU sits at (bi % h0, bi / h0)
             pitch = ypitch; base = byl * 8 * ypitch + (a.h0 * mxl + bxl) * 8 + r;
         } else {
             pitch = cpitch; base = ybytes + (c - 1) * cbytes + mxl * 8 + r;
@@ -367,13 +369,15 @@ __global__ __launch_bounds__(kIdctThreads) void jpeg_idct_kernel(JpegDecArgs a, 
     for (int p = t; p < npieces; p += kIdctThreads) {
         int q = p, plane_i = 0;
         if (q >= ypieces) { q -= ypieces; plane_i = 1; if (q >= cpieces) { q -= cpieces; plane_i = 2; } }
-        const int ppr = (plane_i == 0 ? ypitch : cpitch) >> 3;          // pieces per strip row (a power of two: 8, 16 or 32)
+        const int ppr = (plane_i == 0 ? ypitch : cpitch) >> 3;          // pieces per strip row (a power of two: 4, 8, 16 or 32)
         const int row = q >> (31 - __builtin_clz((unsigned)ppr)), col = q & (ppr - 1);
         if (col >= mcus * (plane_i == 0 ? a.h0 : 1)) continue;          // beyond the last MCU of the row
         const int bx = (plane_i == 0 ? mx0 * a.h0 : mx0) + col, y = (plane_i == 0 ? my * 8 * a.v0 : my * 8) + row;
         const bool inside = plane_i == 0 ? bx * 8 < a.w && (y & ~7) < a.h : bx * 8 * a.h0 < a.w && my * 8 * a.v0 < a.h;   // the block's test (scan.go)
         uint2 v = *(const uint2 *)(ob + (p << 3));
         if (prog && !inside) v = make_uint2(0u, 0u);      // image.NewYCbCr's zeros: Go never writes these blocks of a progressive image
+        // nor the blocks a non-interleaved sequential scan carries no data for: outside the image by the component's OWN block grid
+        if (((vflags >> (2 + plane_i)) & 1) && (bx * 8 >= a.w || (y & ~7) >= a.h)) v = make_uint2(0u, 0u);
         uint8_t *plane = plane_i == 0 ? py : (plane_i == 1 ? pcb : pcr);
         const uint32_t stride = (uint32_t)(plane_i == 0 ? pl.ystride : pl.cstride);
         *(uint2 *)(plane + ((uint32_t)y * stride + (uint32_t)bx * 8u)) = v;
@@ -398,8 +402,10 @@ hipError_t launch_jpeg_huff(const JpegDecArgs &a, hipStream_t s)
 
 hipError_t launch_jpeg_idct(const JpegDecArgs &a, const JpegPlanes &pl, hipStream_t s)
 {
-    if (a.bpm != 1 && a.bpm != 3 && a.bpm != 4 && a.bpm != 6) return hipErrorInvalidValue;      // (the parser admits no other sampling)
-    const int mcus_per_wg = a.bpm == 1 ? 32 : kIdctMcus;                     // 32, 24, 32 or 48 blocks
+    // (the parser admits no other sampling: Gray, 4:4:4, 4:2:2 / 4:4:0, 4:2:0 / 4:1:1, 4:1:0)
+    const bool known = a.bpm == 1 ? a.ybl == 1 : (a.bpm == a.ybl + 2 && a.ybl == a.h0 * a.v0 && (a.h0 == 1 || a.h0 == 2 || a.h0 == 4) && (a.v0 == 1 || a.v0 == 2));
+    if (!known) return hipErrorInvalidValue;
+    const int mcus_per_wg = a.bpm == 1 ? 32 : a.bpm == 10 ? 4 : kIdctMcus;   // 32, 24, 32, 48 or 40 blocks: the strips fill ob exactly at 48
     const int wgs_per_row = (a.mxx + mcus_per_wg - 1) / mcus_per_wg;
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)(wgs_per_row * a.myy), a.n), dim3(kIdctThreads), 0, s, a, pl, wgs_per_row, mcus_per_wg);
     return hipGetLastError();

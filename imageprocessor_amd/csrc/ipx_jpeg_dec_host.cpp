@@ -7,7 +7,7 @@
 // (an 8-bit first-level Huffman table plus the canonical mincode / maxcode arrays for longer codes; quantisers
 // de-zig-zagged).  Anything outside the baseline subset the kernels implement is reported as IPX_ERR_UNSUPPORTED for
 // that image, so that the worker keeps Go's CPU path for it: CMYK / RGB (Adobe) files (four-component files are taken under
-// IPX_JPEG_CMYK=1: ipx_jpeg_dec_cmyk.hip), 4:1:1 / 4:1:0 and other sampling factors, 12-bit samples.  Progressive files, files coded in several scans and Huffman table ids above 1 are marked host_scans: their
+// IPX_JPEG_CMYK=1: ipx_jpeg_dec_cmyk.hip), sampling factors Go's processSOF refuses (4:1:1 / 4:1:0, which it takes, are taken under IPX_JPEG_411=1), 12-bit samples.  Progressive files, files coded in several scans and Huffman table ids above 1 are marked host_scans: their
 // scans are decoded on the host (ipx_jpeg_dec_prog.cpp) and only the transform onwards runs on the GPU.  A file has to end the way
 // Go's marker loop wants it to (EOI after the last scan), or it is malformed here as it is there.
 #include <algorithm>
@@ -58,7 +58,8 @@ bool build_huff(const RawHuff &r, uint16_t lut[256], int32_t maxcode[18], int32_
 // 0 ok; IPX_ERR_INVALID malformed; IPX_ERR_UNSUPPORTED a valid file outside the GPU subset
 // cmyk (IPX_JPEG_CMYK=1, ipx_jpeg_dec_cmyk.hip): a four-component frame with one of the two sampling vectors Go's processSOF takes is
 // IPX_OK with ncomp 4 and host_scans set -- its tables and scans are the host decoder's alone -- instead of IPX_ERR_UNSUPPORTED
-int jpeg_parse(const uint8_t *d, size_t len, JpegDecInfo *info, JpegDecTables *tab, bool cmyk)
+// s411 (IPX_JPEG_411=1): a three-component frame with Y (4,1) or (4,2) and 1x1 chroma is IPX_OK with h0 = 4 and ratio IPX_YCBCR_411 / _410
+int jpeg_parse(const uint8_t *d, size_t len, JpegDecInfo *info, JpegDecTables *tab, bool cmyk, bool s411)
 {
     memset(info, 0, sizeof *info);
     if (len < 4 || d[0] != 0xff || d[1] != 0xd8) return IPX_ERR_INVALID;
@@ -108,7 +109,8 @@ int jpeg_parse(const uint8_t *d, size_t len, JpegDecInfo *info, JpegDecTables *t
                 info->host_scans = 1;
                 break;
             }
-            if (ch[1] != 1 || cv[1] != 1 || ch[2] != 1 || cv[2] != 1 || ch[0] > 2 || cv[0] > 2) return IPX_ERR_UNSUPPORTED;
+            // processSOF: Y (1|2)x(1|2), or (4,1) / (4,2), over 1x1 chroma; v = 4 and every other vector are "unsupported subsampling ratio"
+            if (ch[1] != 1 || cv[1] != 1 || ch[2] != 1 || cv[2] != 1 || cv[0] > 2 || (ch[0] > 2 && !(s411 && ch[0] == 4))) return IPX_ERR_UNSUPPORTED;
             break;
         }
         case 0xc4: {
@@ -151,7 +153,7 @@ int jpeg_parse(const uint8_t *d, size_t len, JpegDecInfo *info, JpegDecTables *t
             if (sn < 1) return IPX_ERR_INVALID;
             info->h0 = ch[0]; info->v0 = cv[0];
             info->ncomp = ncomp;
-            info->ratio = ncomp == 1 ? IPX_GRAY : ch[0] == 1 ? (cv[0] == 1 ? IPX_YCBCR_444 : IPX_YCBCR_440) : (cv[0] == 1 ? IPX_YCBCR_422 : IPX_YCBCR_420);
+            info->ratio = ncomp == 1 ? IPX_GRAY : ycbcr_ratio_of(ch[0], cv[0]);
             if (info->host_scans) return IPX_OK;               // the frame is known; the scans are the host decoder's
             if (s[0] != ncomp) {                               // a sequential frame coded in several scans
                 if (s[0] < 1 || s[0] > 3) return IPX_ERR_INVALID;
@@ -319,11 +321,12 @@ int jpeg_plan_batch(const ipx_bytes *files, int n, const JpegPlanOptions &opt, i
     // a thousand 1080p files).  Files whose scans are walked on the host (progressive, several scans) only have their frame header
     // read here; their scans wait for the batch's geometry.
     const int rc = parallel_light(n, [&](int i) {
-        status[i] = !files[i].data ? IPX_ERR_INVALID : (files[i].len >= ((size_t)1 << 30) ? IPX_ERR_UNSUPPORTED : jpeg_parse(files[i].data, files[i].len, &P.info[i], &P.tabs[i]));
+        status[i] = !files[i].data ? IPX_ERR_INVALID : (files[i].len >= ((size_t)1 << 30) ? IPX_ERR_UNSUPPORTED : jpeg_parse(files[i].data, files[i].len, &P.info[i], &P.tabs[i], false, opt.s411));
         if (status[i] == IPX_OK && !P.info[i].host_scans) status[i] = find_restarts(files[i].data + P.info[i].scan_off, P.info[i], &marks[i]);
         // a progressive file whose marker pre-pass is wholly clean has its scans walked by jpeg_prog_kernel (opt-in); every other one
         // keeps the host route, which gives the verdict as before
-        if (status[i] == IPX_OK && opt.prog_gpu && P.info[i].progressive)
+        // (4:1:1 / 4:1:0: the scan walk's block maps know factors 1 and 2 only)
+        if (status[i] == IPX_OK && opt.prog_gpu && P.info[i].progressive && P.info[i].h0 <= 2)
             P.info[i].gpu_scans = jpeg_prog_prepass(files[i].data, files[i].len, P.info[i], &P.prog[i], P.tabs[i].qnat) ? 1 : 0;
     }, "jpeg decode: host preparation failed");
     P.parse_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

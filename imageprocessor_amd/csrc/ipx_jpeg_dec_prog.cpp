@@ -135,6 +135,7 @@ struct Decoder {
     size_t len;
     int w = 0, h = 0, ncomp = 0;
     bool progressive = false, baseline = false;
+    bool s411 = false;                // IPX_JPEG_411=1: a three-component frame with Y (4,1) or (4,2) is taken (4:1:1, 4:1:0)
     bool cmyk = false;                // IPX_JPEG_CMYK=1 (jpeg_host_decode4): a four-component frame is taken, with component 3 in a block set of its own
     int cid[4], ch[4], cv[4], ctq[4];
     uint16_t quant[4][64];
@@ -154,17 +155,18 @@ struct Decoder {
     bool wide = false;
     std::vector<uint64_t> nzmask;     // per block: which zig-zag positions hold a non-zero coefficient (progressive files)
     int bpm = 0, ybl = 0;             // blocks per MCU in the output layout, luma blocks per MCU
+    bool coded_inter[4] = {false, false, false, false}, coded_alone[4] = {false, false, false, false};   // by interleaved / non-interleaved scans
     int status = IPX_OK;
 
     void fail(int s) { if (status == IPX_OK) status = s; }
     void put(int16_t &dst, int32_t v) { if (v != (int32_t)(int16_t)v) wide = true; dst = (int16_t)v; }
     size_t block_index(int k, int bx, int by)   // block (bx, by) of component k's grid in the output layout
     {
-        // sampling factors are 1 or 2 here (everything else was refused at the frame header): shifts and masks, no division -- this
-        // runs once per block and scan
-        const int sx = ch[k] - 1, sy = cv[k] - 1;
+        // sampling factors are 1, 2 or (h of component 0 under IPX_JPEG_411=1) 4 here (everything else was refused at the frame header):
+        // shifts and masks, no division -- this runs once per block and scan
+        const int mx_ = ch[k] - 1, sx = ch[k] >> 1, sy = cv[k] - 1;     // mask and shift differ once the factor is 4; v is 1 or 2
         if (k == 3) return (size_t)mxx * myy * bpm + (size_t)by * (mxx * ch[3]) + bx;   // blackPix: raster by block, behind the three-component set
-        return ((size_t)(by >> sy) * mxx + (bx >> sx)) * bpm + (k == 0 ? (size_t)((by & sy) << sx) + (bx & sx) : (size_t)ybl + k - 1);
+        return ((size_t)(by >> sy) * mxx + (bx >> sx)) * bpm + (k == 0 ? (size_t)((by & sy) << sx) + (bx & mx_) : (size_t)ybl + k - 1);
     }
 
     // refineNonZeroes: one bit per coefficient of [zig, zig_end] that is already non-zero, up to where the nz-th zero has been passed
@@ -337,6 +339,7 @@ struct Decoder {
             out_ready = true;
         }
         scans++;
+        for (int i = 0; i < ns; i++) (ns != 1 ? coded_inter : coded_alone)[ci[i]] = true;
         Bits br{d, len, *pos};
         int32_t dc[4] = {0, 0, 0, 0};
         int mcu = 0, expected = 0xd0;
@@ -349,7 +352,7 @@ struct Decoder {
                     const int k = ci[i], hi = ch[k], vi = cv[k];
                     for (int j = 0; j < hi * vi; j++) {
                         int bx, by;
-                        if (ns != 1) { bx = hi * mx + (j & (hi - 1)); by = vi * my + (hi == 2 ? j >> 1 : j); }
+                        if (ns != 1) { bx = hi * mx + (j & (hi - 1)); by = vi * my + (j >> (hi >> 1)); }      // block j of the MCU sits at (j % hi, j / hi)
                         else {
                             bx = nbx; by = nby;
                             if (++nbx == q1) { nbx = 0; nby++; }
@@ -473,7 +476,7 @@ struct Decoder {
                     if (hh == 3 || vv == 3) return fail(IPX_ERR_UNSUPPORTED);
                     ch[c] = hh; cv[c] = vv;
                 }
-                if (ncomp == 3 && (ch[1] != 1 || cv[1] != 1 || ch[2] != 1 || cv[2] != 1 || ch[0] > 2 || cv[0] > 2)) return fail(IPX_ERR_UNSUPPORTED);
+                if (ncomp == 3 && (ch[1] != 1 || cv[1] != 1 || ch[2] != 1 || cv[2] != 1 || cv[0] > 2 || (ch[0] > 2 && !(s411 && ch[0] == 4)))) return fail(IPX_ERR_UNSUPPORTED);
                 // processSOF, four components: 11 11 11 11 or 22 11 11 22 ("unsupported subsampling ratio" otherwise)
                 if (ncomp == 4 && (ch[0] != cv[0] || ch[0] > 2 || ch[1] != 1 || cv[1] != 1 || ch[2] != 1 || cv[2] != 1 || ch[3] != ch[0] || cv[3] != cv[0]))
                     return fail(IPX_ERR_UNSUPPORTED);
@@ -539,9 +542,11 @@ struct Decoder {
 // (Go dequantises a progressive image after EOI), and *progressive says whether reconstructProgressiveImage's rule applies (blocks
 // that hold no image pixel are not reconstructed: they stay zero in the MCU-padded planes).
 int jpeg_host_decode(const uint8_t *d, size_t len, JpegDecInfo *info, int16_t *coefs, int16_t *dcs, size_t nblk, uint16_t qnat[3][64],
-                     bool *progressive)
+                     bool *progressive, bool s411, int *alone)
 {
     Decoder D;
+    D.s411 = s411;
+    if (alone) *alone = 0;
     memset(D.quant, 0, sizeof D.quant);
     memset(D.cid, 0, sizeof D.cid); memset(D.ch, 0, sizeof D.ch); memset(D.cv, 0, sizeof D.cv); memset(D.ctq, 0, sizeof D.ctq);
     D.d = d; D.len = len;
@@ -551,8 +556,10 @@ int jpeg_host_decode(const uint8_t *d, size_t len, JpegDecInfo *info, int16_t *c
     if (!D.out_ready) return IPX_ERR_INVALID;                                // (no scan at all: the marker parser refuses such a file before)
     memset(info, 0, sizeof *info);
     info->w = D.w; info->h = D.h; info->h0 = D.ch[0]; info->v0 = D.cv[0]; info->ncomp = D.ncomp; info->ri = 0;
-    info->ratio = D.ncomp == 1 ? IPX_GRAY : D.ch[0] == 1 ? (D.cv[0] == 1 ? IPX_YCBCR_444 : IPX_YCBCR_440) : (D.cv[0] == 1 ? IPX_YCBCR_422 : IPX_YCBCR_420);
+    info->ratio = D.ncomp == 1 ? IPX_GRAY : ycbcr_ratio_of(D.ch[0], D.cv[0]);
     *progressive = D.progressive;
+    if (alone && !D.progressive && D.ncomp == 3)
+        for (int c = 0; c < 3; c++) if (D.coded_alone[c] && !D.coded_inter[c]) *alone |= 1 << c;
     if (D.wide) return IPX_ERR_UNSUPPORTED;                                  // Go keeps int32; the GPU pipeline holds int16
     for (size_t gb = 0; gb < nblk; gb++) { dcs[gb] = coefs[gb * 64]; coefs[gb * 64] = 0; }
     for (int c = 0; c < 3; c++)

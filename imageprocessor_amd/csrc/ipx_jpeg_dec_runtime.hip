@@ -25,6 +25,7 @@ struct DecRun {
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     double t_alloc = 0, t_pin = 0, t_pack = 0, t_launch = 0;
     JpegBatchPlan plan;
+    bool s411 = false;                 // IPX_JPEG_411=1 as this call read it
     std::vector<int> dev_status;
     std::vector<uint8_t> prog_block;   // the scan programs of the GPU-walked files as uploaded (dec_scans)
     JpegDecArgs a{};
@@ -135,10 +136,12 @@ int dec_upload(DecRun &r)
         rc = parallel_heavy(cnt, [&](int j) {
             const int i = hfiles[g0 + j];
             bool prog = false;
+            int alone = 0;
             JpegDecInfo full;
             const int st = jpeg_host_decode(r.jpegs[i].data, r.jpegs[i].len, &full, base + (size_t)j * hslot_words, base + (size_t)j * hslot_words + hcoef_words,
-                                            (size_t)a.nblk, P.tabs[i].qnat, &prog);
+                                            (size_t)a.nblk, P.tabs[i].qnat, &prog, r.s411, &alone);
             if (st != IPX_OK) { r.status[i] = st; P.valid[i] = 0; }
+            else P.valid[i] |= (uint8_t)(alone << 2);     // the blocks a non-interleaved sequential scan skips stay zero (jpeg_idct_kernel)
         }, kPrep);
         if (rc) return rc;
         for (int j = 0; j < cnt; j++) {
@@ -361,7 +364,8 @@ int jpeg_decode_files(ipx_ctx *ctx, hipStream_t s, Lane *lane, bool planes_in_la
 {
     OwnedBlocks<ipx_jpeg_planes> own(ctx, s);
     DecRun r(ctx, s, jpegs, n, status);
-    const JpegPlanOptions opt{*w, *h, env_int("IPX_JPEG_PAR", 1) != 0, env_int("IPX_JPEG_PAR_SUB", 0), jpeg_par_sub_bytes(), env_int("IPX_JPEG_PROG_GPU", 0) == 1};
+    r.s411 = jpeg_411_enabled();
+    const JpegPlanOptions opt{*w, *h, env_int("IPX_JPEG_PAR", 1) != 0, env_int("IPX_JPEG_PAR_SUB", 0), jpeg_par_sub_bytes(), env_int("IPX_JPEG_PROG_GPU", 0) == 1, r.s411};
     int rc = jpeg_plan_batch(jpegs, n, opt, status, &r.plan);
     if (rc) return rc;
     if (r.plan.ref < 0) return IPX_OK;
@@ -375,6 +379,8 @@ int jpeg_decode_files(ipx_ctx *ctx, hipStream_t s, Lane *lane, bool planes_in_la
     *owner = own.release();
     return IPX_OK;
 }
+
+bool jpeg_411_enabled() { return env_int("IPX_JPEG_411", 0) == 1; }
 
 extern "C" {
 
@@ -404,11 +410,11 @@ int ipx_jpeg_scan_route(const uint8_t *file, size_t len, int *route) try
     if (len >= ((size_t)1 << 30)) return IPX_ERR_UNSUPPORTED;
     JpegDecInfo info;
     JpegDecTables tab;
-    const int st = jpeg_parse(file, len, &info, &tab, jpeg_cmyk_enabled());   // (a four-component file: the host route, under IPX_JPEG_CMYK=1)
+    const int st = jpeg_parse(file, len, &info, &tab, jpeg_cmyk_enabled(), jpeg_411_enabled());   // (a four-component file: the host route, under IPX_JPEG_CMYK=1)
     if (st != IPX_OK) return st;
     if (info.host_scans) {
         JpegProgPlan plan;
-        const bool gpu = env_int("IPX_JPEG_PROG_GPU", 0) == 1 && info.progressive && jpeg_prog_prepass(file, len, info, &plan, tab.qnat);
+        const bool gpu = env_int("IPX_JPEG_PROG_GPU", 0) == 1 && info.progressive && info.h0 <= 2 && jpeg_prog_prepass(file, len, info, &plan, tab.qnat);
         *route = gpu ? IPX_JPEG_ROUTE_GPU_SCANS : IPX_JPEG_ROUTE_HOST_SCANS;
     }
     return IPX_OK;

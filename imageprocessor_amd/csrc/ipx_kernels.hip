@@ -166,10 +166,10 @@ __global__ __launch_bounds__(256) void draw_ycbcr_kernel(uint8_t *dst, int dstri
     const int y = blockIdx.y;
     if (y >= h) return;
     dst += blockIdx.z * dst_fs; yp += blockIdx.z * y_fs; cb += blockIdx.z * c_fs; cr += blockIdx.z * c_fs;
+    const int hs = ycbcr_hshift(ratio), vs = ycbcr_vshift(ratio);
     for (int x = blockIdx.x * 256 + threadIdx.x; x < w; x += gridDim.x * 256) {
         const int sx = spx + x, sy = spy + y;
-        const int cx = (ratio == IPX_YCBCR_422 || ratio == IPX_YCBCR_420) ? sx / 2 : sx;
-        const int cy = (ratio == IPX_YCBCR_420 || ratio == IPX_YCBCR_440) ? sy / 2 : sy;
+        const int cx = sx >> hs, cy = sy >> vs;           // COffset: sx, sx / 2 or (4:1:1, 4:1:0) sx / 4; sy or sy / 2
         const size_t ci = (size_t)cy * cstride + cx;
         const int32_t yy1 = (int32_t)yp[(size_t)sy * ystride + sx] * 0x10101;
         const int32_t cb1 = (int32_t)cb[ci] - 128, cr1 = (int32_t)cr[ci] - 128;

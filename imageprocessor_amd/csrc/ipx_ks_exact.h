@@ -44,8 +44,7 @@ __device__ __forceinline__ Tap4 ks_tap(const KsGenArgs &a, int x, int y)
 {
     Tap4 t;
     if (KIND == IPX_SRC_YCBCR || KIND == IPX_SRC_YCBCR_CROP) {
-        const int cx = (a.ratio == IPX_YCBCR_422 || a.ratio == IPX_YCBCR_420) ? x / 2 : x;
-        const int cy = (a.ratio == IPX_YCBCR_420 || a.ratio == IPX_YCBCR_440) ? y / 2 : y;
+        const int cx = x >> ycbcr_hshift(a.ratio), cy = y >> ycbcr_vshift(a.ratio);   // COffset: x, x / 2 or (4:1:1, 4:1:0) x / 4; y or y / 2
         const size_t ci = (size_t)cy * a.cstride + cx;
         const int yy1 = (int)a.src[(size_t)y * a.sstride + x] * 0x10101;
         const int cb1 = (int)a.cb[ci] - 128, cr1 = (int)a.cr[ci] - 128;

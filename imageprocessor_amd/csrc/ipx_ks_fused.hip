@@ -72,7 +72,11 @@ __device__ __forceinline__ uint32_t ks_ftou8(double f)   // uint8(ftou(f) >> 8)
 }
 
 // ---- source types: how four pixels of a tile row come from HBM, go to LDS (as the 16-bit values scaleX weights) and to the watermark frame ----
-enum { KS_RGBA = 0, KS_NRGBA = 1, KS_YCC = 2, KS_GRAY = 3, KS_TAP64 = 4 };
+// KS_YCC4: YCbCr planes with one chroma sample per FOUR pixels across (4:1:1, 4:1:0).  A source type of its own, so that the kernels of
+// the common ratios (KS_YCC: a sample per pixel or per two) keep the code they had: with the horizontal shift as a run-time value
+// (0, 1, 2) inside one instantiation the 4:2:0 batch of tools/bench_ycbcr.py measured 0.9 % slower (1.542 against 1.528 ms per 256 frames).
+enum { KS_RGBA = 0, KS_NRGBA = 1, KS_YCC = 2, KS_GRAY = 3, KS_TAP64 = 4, KS_YCC4 = 5 };
+constexpr bool ks_is_ycc(int src) { return src == KS_YCC || src == KS_YCC4; }
 // bytes per pixel of the LDS tile: RGBA keeps the packed bytes (a tap is byte * 0x101), the converting types keep four 16-bit taps,
 // Gray one (y * 0x101)
 template <int SRC> struct KsPx { static constexpr int bytes = SRC == KS_RGBA ? 4 : SRC == KS_GRAY ? 2 : 8; };
@@ -122,12 +126,17 @@ __device__ __forceinline__ u32x4 ks_convert(const KsStageRegs &s, uint8_t *dst, 
         *(u32x4 *)(dst + 16) = u32x4{t[4], t[5], t[6], t[7]};
         px.x = __builtin_amdgcn_perm(t[1], t[0], 0x07050301u); px.y = __builtin_amdgcn_perm(t[3], t[2], 0x07050301u);   // drawNRGBASrc: the top bytes
         px.z = __builtin_amdgcn_perm(t[5], t[4], 0x07050301u); px.w = __builtin_amdgcn_perm(t[7], t[6], 0x07050301u);
-    } else {   // KS_YCC: v[0] = four luma bytes, v[1] / v[2] = the Cb / Cr bytes of their samples (two when hs, else four)
+    } else {   // KS_YCC: v[0] = four luma bytes, v[1] / v[2] = the Cb / Cr bytes of their samples (two when hs, else four; KS_YCC4: one)
         uint32_t t[8];
         // the chroma terms once per SAMPLE: two pixels share one where the planes are subsampled horizontally (hs is uniform; with the
         // sample index computed per pixel the compiler multiplied every pixel's terms anew: 6.8 multiplies per pixel instead of 3)
         int rt[4], gt[4], bt[4];
-        if (hs) {
+        if (SRC == KS_YCC4) {   // 4:1:1 / 4:1:0: a chunk starts at a multiple of four columns, so its four pixels share the sample at x / 4
+            const int cb1 = (int)(s.v[1] & 0xffu) - 128, cr1 = (int)(s.v[2] & 0xffu) - 128;
+            rt[0] = rt[1] = rt[2] = rt[3] = 91881 * cr1;
+            gt[0] = gt[1] = gt[2] = gt[3] = -22554 * cb1 - 46802 * cr1;
+            bt[0] = bt[1] = bt[2] = bt[3] = 116130 * cb1;
+        } else if (hs) {
 #pragma unroll
             for (int c = 0; c < 2; c++) {
                 const int cb1 = (int)((s.v[1] >> (8 * c)) & 0xffu) - 128, cr1 = (int)((s.v[2] >> (8 * c)) & 0xffu) - 128;
@@ -537,15 +546,18 @@ __global__ __launch_bounds__(kKsMaxThreads) void ks_fused_kernel(KsFusedArgs a)
     typedef KsRowT<NACC> Row;
     constexpr int RW = (int)(sizeof(Row) / 4);       // dwords per row entry
     constexpr int SPX = SRC == KS_RGBA || SRC == KS_NRGBA ? 4 : SRC == KS_TAP64 ? 8 : 1;   // source bytes per pixel (luma plane for YCbCr / Gray)
-    const int hs = SRC == KS_YCC && (a.ratio == IPX_YCBCR_422 || a.ratio == IPX_YCBCR_420), vs = SRC == KS_YCC && (a.ratio == IPX_YCBCR_420 || a.ratio == IPX_YCBCR_440);
+    // COffset's shifts: x >> hs (KS_YCC4: x >> 2), y >> vs
+    constexpr bool YCC = ks_is_ycc(SRC);
+    const int hs = SRC == KS_YCC && (a.ratio == IPX_YCBCR_422 || a.ratio == IPX_YCBCR_420),
+              vs = SRC == KS_YCC4 ? a.ratio == IPX_YCBCR_410 : SRC == KS_YCC && (a.ratio == IPX_YCBCR_420 || a.ratio == IPX_YCBCR_440);
 
     const uint8_t *sframe = a.src + (size_t)frame * a.src_fs;
     const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc((void *)sframe, 0, (a.sh - 1) * a.sstride + a.sw * SPX, 0x00020000);
-    const int chh = vs ? (a.sh + 1) / 2 : a.sh, cww = hs ? (a.sw + 1) / 2 : a.sw;
-    const __amdgpu_buffer_rsrc_t cbrs = __builtin_amdgcn_make_buffer_rsrc((void *)(SRC == KS_YCC ? a.cb + (size_t)frame * a.c_fs : nullptr), 0,
-                                                                         SRC == KS_YCC ? (chh - 1) * a.cstride + cww : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t crrs = __builtin_amdgcn_make_buffer_rsrc((void *)(SRC == KS_YCC ? a.cr + (size_t)frame * a.c_fs : nullptr), 0,
-                                                                         SRC == KS_YCC ? (chh - 1) * a.cstride + cww : 0, 0x00020000);
+    const int chh = vs ? (a.sh + 1) / 2 : a.sh, cww = SRC == KS_YCC4 ? (a.sw + 3) / 4 : hs ? (a.sw + 1) / 2 : a.sw;
+    const __amdgpu_buffer_rsrc_t cbrs = __builtin_amdgcn_make_buffer_rsrc((void *)(YCC ? a.cb + (size_t)frame * a.c_fs : nullptr), 0,
+                                                                         YCC ? (chh - 1) * a.cstride + cww : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t crrs = __builtin_amdgcn_make_buffer_rsrc((void *)(YCC ? a.cr + (size_t)frame * a.c_fs : nullptr), 0,
+                                                                         YCC ? (chh - 1) * a.cstride + cww : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void *)(a.wm ? a.wm + (size_t)frame * a.wm_fs : nullptr), 0,
                                                                         a.wm ? (a.sh - 1) * a.wm_stride + a.sw * 4 : 0, 0x00020000);
 
@@ -560,7 +572,9 @@ __global__ __launch_bounds__(kKsMaxThreads) void ks_fused_kernel(KsFusedArgs a)
         s_row[i] = in ? row : -1;
         s_lds[i] = row * pitch + ch * CHB;
         s_src[i] = in ? row * a.sstride + x * SPX : kOOB;
-        s_cx[i] = in ? (hs ? x >> 1 : x) : kOOB;         // chroma byte offset within its row
+        // chroma byte offset within its row.  x is a multiple of 4 (strips start at multiples of 4: ks_fused_plan keeps c0 and t0 there), so
+        // the chunk's four pixels are samples x .. x + 3, x / 2 and x / 2 + 1, or the one sample x / 4
+        s_cx[i] = in ? (SRC == KS_YCC4 ? x >> 2 : hs ? x >> 1 : x) : kOOB;
         s_np[i] = !ragged ? 4 : in ? min(4, a.sw - x) : 0;   // pixels of the chunk inside the frame
         s_wm[i] = in && x >= st.c0 && x < st.c1 ? row * a.wm_stride + x * 4 : kOOB; // owned columns only (c0 and c1 are multiples of 4)
     }
@@ -646,10 +660,13 @@ __global__ __launch_bounds__(kKsMaxThreads) void ks_fused_kernel(KsFusedArgs a)
                 }
             } else {
                 stage[i].v[0] = __builtin_amdgcn_raw_buffer_load_b32(srs, off, y0 * a.sstride, 0);     // four luma bytes
-                if (SRC == KS_YCC) {
+                if (YCC) {
                     const int cy = vs ? (y0 + s_row[i]) >> 1 : y0 + s_row[i];
                     const int coff = ok ? cy * a.cstride + s_cx[i] : kOOB;
-                    if (hs) {
+                    if (SRC == KS_YCC4) {
+                        stage[i].v[1] = (uint32_t)(unsigned char)__builtin_amdgcn_raw_buffer_load_b8(cbrs, coff, 0, 0);
+                        stage[i].v[2] = (uint32_t)(unsigned char)__builtin_amdgcn_raw_buffer_load_b8(crrs, coff, 0, 0);
+                    } else if (hs) {
                         stage[i].v[1] = (uint32_t)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(cbrs, coff, 0, 0);
                         stage[i].v[2] = (uint32_t)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(crrs, coff, 0, 0);
                     } else {
@@ -734,7 +751,7 @@ __global__ __launch_bounds__(kKsMaxThreads) void ks_fused_kernel(KsFusedArgs a)
     } while (0)
             if constexpr (FAST) {
                 // (the alpha of these sources never reaches the sums: opaque RGBA, YCbCr and Gray store 0xff)
-                if constexpr (SRC == KS_YCC) {
+                if constexpr (YCC) {
                     if (!aone) { KS_COLSF(KS_TAP_TOP); }
                     else { KS_COLSF(KS_TAP_PLAIN); }
                 } else if constexpr (SRC == KS_TAP64) {
@@ -753,7 +770,7 @@ __global__ __launch_bounds__(kKsMaxThreads) void ks_fused_kernel(KsFusedArgs a)
             } else if (SRC == KS_GRAY) {
                 if (aone) { KS_COLS(KS_TAP_PLAIN, true); }
                 else { KS_COLS(KS_TAP_PLAIN, false); }
-            } else if (SRC == KS_YCC) {
+            } else if (YCC) {
                 if (aone) { KS_COLS(KS_TAP_PLAIN, true); }
                 else { KS_COLS(KS_TAP_TOP, false); }
             } else if (SRC == KS_NRGBA) {
@@ -820,7 +837,7 @@ hipError_t launch_ks_fused(const KsFusedPlan &p, KsFusedArgs &a, const KsFix *fi
 {
     *matched = false; *text_done = false;
     if (!p.ok || a.nframes <= 0) return hipSuccess;
-    // frames are addressed through buffer descriptors with aligned dword (chroma: word) loads
+    // frames are addressed through buffer descriptors with aligned dword (chroma: dword, word or -- 4:1:1 / 4:1:0 -- byte) loads
     if ((((uintptr_t)a.src) | (uintptr_t)a.sstride | a.src_fs) & 3) return hipSuccess;
     if (a.wm && ((((uintptr_t)a.wm) | (uintptr_t)a.wm_stride | a.wm_fs) & 3)) return hipSuccess;
     int src = KS_RGBA;
@@ -831,8 +848,9 @@ hipError_t launch_ks_fused(const KsFusedPlan &p, KsFusedArgs &a, const KsFix *fi
     case IPX_SRC_YCBCR: {
         src = a.cstride == 0 ? KS_GRAY : KS_YCC;                  // a stride-0 chroma row of 128s: a Gray frame (ipx_plan_run_dev_gray)
         if (src == KS_YCC) {
-            const bool hs = a.ratio == IPX_YCBCR_422 || a.ratio == IPX_YCBCR_420;
-            const uintptr_t al = hs ? 1 : 3;
+            const int hs = ycbcr_hshift(a.ratio);                   // four, two or one chroma byte per chunk: dword, word or byte loads
+            if (hs == 2) src = KS_YCC4;
+            const uintptr_t al = hs == 2 ? 0 : hs ? 1 : 3;
             if ((((uintptr_t)a.cb) | (uintptr_t)a.cr | (uintptr_t)a.cstride | a.c_fs) & al) return hipSuccess;
         }
         break;
@@ -896,7 +914,7 @@ hipError_t launch_ks_fused(const KsFusedPlan &p, KsFusedArgs &a, const KsFix *fi
                 a.nout > 1 ? a.o[1].waves : 0, a.nout > 1 ? a.o[1].cpl : 0, a.nout > 1 ? a.o[1].wcols : 0, p.fast.open_per_wave, a.o[0].split, a.nout > 1 ? a.o[1].split : 0);
     // the float pass where the source type has one and the caller brought lists: float kernel, the listed pixels in float64, then the
     // float64 kernel on the items the float kernel gave up
-    bool fast = fix && fix->list && a.redo && (src == KS_RGBA || src == KS_YCC || src == KS_GRAY || src == KS_NRGBA || (src == KS_TAP64 && a.taps_le_alpha));
+    bool fast = fix && fix->list && a.redo && (src == KS_RGBA || ks_is_ycc(src) || src == KS_GRAY || src == KS_NRGBA || (src == KS_TAP64 && a.taps_le_alpha));
     for (int i = 0; i < a.nout; i++) fast = fast && a.o[i].feps > 0.f;       // (an output with more taps than the margin's derivation covers)
     fast = fast && p.fast.lds_bytes > 0;
     layout(false);
@@ -972,6 +990,13 @@ hipError_t launch_ks_fused(const KsFusedPlan &p, KsFusedArgs &a, const KsFix *fi
         e = p.nacc == 2 ? launch_one<KS_YCC, 3, 2, false, true>(p, a, n, s) : launch_one<KS_YCC, 3, 4, false, true>(p, a, n, s);
         layout(false);
         if (e == hipSuccess) e = after_float([&]() { return launch_src<KS_YCC, 3>(p, a, n, s); });
+        return e;
+    case KS_YCC4:
+        if (!fast) { a.redo = nullptr; return launch_src<KS_YCC4, 3>(p, a, n, s); }
+        layout(true);
+        e = p.nacc == 2 ? launch_one<KS_YCC4, 3, 2, false, true>(p, a, n, s) : launch_one<KS_YCC4, 3, 4, false, true>(p, a, n, s);
+        layout(false);
+        if (e == hipSuccess) e = after_float([&]() { return launch_src<KS_YCC4, 3>(p, a, n, s); });
         return e;
     case KS_GRAY:
         if (!fast) { a.redo = nullptr; return launch_src<KS_GRAY, 1>(p, a, n, s); }

@@ -958,7 +958,7 @@ int stage_and_run(ipx_ctx *ctx, uint8_t *dst, int dw, int dh, int dstride, size_
 
 bool ycbcr_ok(const ipx_ycbcr *y, int *cw, int *ch)
 {
-    if (!y || !y->y || !y->cb || !y->cr || y->w <= 0 || y->h <= 0 || y->ratio < 0 || y->ratio > IPX_YCBCR_440) return false;
+    if (!y || !y->y || !y->cb || !y->cr || y->w <= 0 || y->h <= 0 || !ycbcr_ratio_ok(y->ratio)) return false;
     chroma_size(y->ratio, y->w, y->h, cw, ch);
     return y->ystride >= y->w && y->cstride >= *cw;
 }
@@ -1467,7 +1467,7 @@ int src_check(const char *who, const ipx_plan *pl, const BatchSrc &b, int n, boo
     if (ok && b.type == kSrcYCbCr) {
         int cw = 0, ch = 0;
         chroma_size(b.ratio, pl->p.sw, pl->p.sh, &cw, &ch);
-        ok = b.plane[1] && b.plane[2] && b.ratio >= 0 && b.ratio <= IPX_YCBCR_440 && b.stride[1] >= cw;
+        ok = b.plane[1] && b.plane[2] && ycbcr_ratio_ok(b.ratio) && b.stride[1] >= cw;
     }
     if (ok && b.type == kSrcPaletted) ok = b.palettes && !(in_hbm && ((uintptr_t)b.palettes & 3));
     if (ok && in_hbm && b.type >= kSrcNRGBA64)       // the expansion reads whole 16-bit samples (CMYK: whole pixels)

@@ -457,6 +457,8 @@ int gif_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w, int 
 // image.Decode of n JPEG files into planes in HBM (ipx_jpeg_dec_runtime.hip); *w x *h: the size asked for, or 0 for the first parsed file's
 int jpeg_decode_files(ipx_ctx *ctx, hipStream_t s, Lane *lane, bool planes_in_lane, const ipx_bytes *jpegs, int n, int *w, int *h,
                       ipx_ycbcr_batch *planes, int *status, ipx_jpeg_planes **owner);
+// IPX_JPEG_411=1, read on every call that parses files: 4:1:1 and 4:1:0 files are decoded instead of refused (handed to jpeg_parse)
+bool jpeg_411_enabled();
 // four-component files (ipx_jpeg_dec_cmyk.hip): the switch, the legs' test of a file's frame header (its vector, 1 or 2; 0: not one
 // of these files), and the driver -- *w, *h as for jpeg_decode_files, want_h0 > 0: only files whose component 0 has that sampling
 // factor (the legs' sub-batches are of one vector)

@@ -160,9 +160,13 @@ int ipx_scale_bilinear_nrgba8(ipx_ctx *ctx, uint8_t *dst, int dw, int dh, int ds
 int ipx_draw_nrgba8(ipx_ctx *ctx, uint8_t *dst, int dw, int dh, int dstride, ipx_rect r,
                     const uint8_t *src, int sw, int sh, int sstride, int spx, int spy, int op);
 
-/* *image.YCbCr with Rect.Min = (0,0); ratio numbered as image.YCbCrSubsampleRatio */
+/* *image.YCbCr with Rect.Min = (0,0); ratio 0..3 numbered as image.YCbCrSubsampleRatio */
 enum { IPX_YCBCR_444 = 0, IPX_YCBCR_422 = 1, IPX_YCBCR_420 = 2, IPX_YCBCR_440 = 3,
-       IPX_GRAY = 4 /* *image.Gray: only the y plane is set (one-component JPEGs) */ };
+       IPX_GRAY = 4 /* *image.Gray: only the y plane is set (one-component JPEGs) */,
+       /* YCbCrSubsampleRatio411 and ...410: one chroma sample per 4 x 1 and 4 x 2 luma samples (Cb, Cr at (x / 4, y) and (x / 4, y / 2);
+        * planes (w + 3) / 4 wide).  NOT Go's own enum values (there 411 = 4 and 410 = 5; 4 is IPX_GRAY here): translate, do not cast.
+        * The pixel entries below take them on caller-supplied planes as they are; the JPEG decoder hands them out under IPX_JPEG_411=1. */
+       IPX_YCBCR_411 = 5, IPX_YCBCR_410 = 6 };
 typedef struct {
     const uint8_t *y, *cb, *cr;
     int32_t ystride, cstride, w, h, ratio;
@@ -265,7 +269,8 @@ int ipx_plan_query(const ipx_plan *plan, ipx_plan_info *info);
  *                  same bytes, slower.
  *   Gray, Y        pointer, row stride and frame stride multiples of 4 AND a width that is a multiple of 4: the one-pass kernel;
  *                  otherwise one kernel per output (byte loads), slower.
- *   Cb, Cr         as Y, but multiples of 2 are enough for 4:2:2 and 4:2:0 (4:4:4 and 4:4:0: 4).
+ *   Cb, Cr         as Y, but multiples of 2 are enough for 4:2:2 and 4:2:0 (4:4:4 and 4:4:0: 4; 4:1:1 and 4:1:0: any, their chroma
+ *                  is read a byte per four pixels).
  *   index planes   any layout; multiples of 4 (and a width that is one) take the expansion's vector path.  The expanded frames are
  *                  the library's own, so the one-pass kernel runs whatever the index planes' layout.
  *   palettes       REQUIRED 4-byte aligned (IPX_ERR_INVALID otherwise).
@@ -565,7 +570,9 @@ int ipx_plan_run_host_png(ipx_ctx *ctx, const ipx_plan *plan, int n, const uint8
 
 /* ---- image.Decode for JPEGs (decoder side) -------------------------------------------
  * image_processor.go:47 decodes every upload; for JPEG files that is Go's image/jpeg.  A batch of
- * files of one size and one kind (three components at 4:4:4 / 4:2:2 / 4:2:0 / 4:4:0, or one component) is decoded here.  Baseline files:
+ * files of one size and one kind (three components at 4:4:4 / 4:2:2 / 4:2:0 / 4:4:0, or one component; with IPX_JPEG_411=1 in the
+ * environment -- read on every call; unset or anything else: as before -- also 4:1:1 and 4:1:0, luma factors (4,1) and (4,2) with 1x1
+ * chroma, planes->ratio IPX_YCBCR_411 / IPX_YCBCR_410; their progressive and multi-scan files keep the host route) is decoded here.  Baseline files:
  * the compressed bytes go up, Huffman decoding runs in parallel inside each scan (or per restart interval), the integer IDCT of idct.go runs
  * block-parallel.  Progressive (SOF2), multi-scan and extended-sequential files: their scans are decoded by the host threads that parse
  * the batch (the scans refine each other), the coefficients go up, IDCT onwards is the same GPU path.  With IPX_JPEG_PROG_GPU=1 in the
@@ -597,7 +604,8 @@ void ipx_jpeg_planes_free(ipx_ctx *ctx, ipx_jpeg_planes *owner);
 /* Which decoder a JPEG file's scans reach: the parallel Huffman kernels (one baseline scan), the host threads, or the GPU scan walk. */
 enum { IPX_JPEG_ROUTE_PAR = 0, IPX_JPEG_ROUTE_HOST_SCANS = 1, IPX_JPEG_ROUTE_GPU_SCANS = 2 };
 /* host only, no context: the route this file would take now (IPX_JPEG_PROG_GPU is read; under IPX_JPEG_CMYK=1 a four-component file of a
- * sampling vector Go takes answers IPX_OK and the host route); returns the parse status, *route is meaningful when that is IPX_OK */
+ * sampling vector Go takes answers IPX_OK and the host route; under IPX_JPEG_411=1 a 4:1:1 or 4:1:0 file answers IPX_OK with the parallel
+ * route for one baseline scan and the host route otherwise, never the GPU scan walk); returns the parse status, *route is meaningful when that is IPX_OK */
 int ipx_jpeg_scan_route(const uint8_t *file, size_t len, int *route);
 /* since ipx_create: the files that reached the decoder of route [0..2] in any decode entry of this context (whatever status they ended
  * with; files refused by the marker parser or for their geometry reach none), and [3] the files the GPU scan walk ended with a status

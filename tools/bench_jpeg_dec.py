@@ -13,7 +13,12 @@ usage: tools/bench_jpeg_dec.py [frames ...]
            1080p YCCK files of the vector 22 11 11 22, baseline, written by tests/jpeg_cmyk_writer.py from the quantised DCT of the
            pictures above (Pillow writes transform-0 files of the vector 11 11 11 11 only); a warm-up, three repetitions, one JSON
            line per batch size.  --corpus DIR keeps the files there (writing one takes the Python writer a while) and reads them back
-           when they exist.  --profile: two batches of 256 and nothing else."""
+           when they exist.  --profile: two batches of 256 and nothing else.
+       tools/bench_jpeg_dec.py --411 [--corpus DIR] [frames ...]
+           4:1:1 files (Y 4x1 over 1x1 chroma) under IPX_JPEG_411=1 beside 4:2:0 files of the same pictures, same quantisers and same
+           Huffman tables in the same process: 1080p baseline files written by tests/jpeg_writer.py from the quantised DCT of the
+           pictures above (libjpeg-turbo's Python front end writes no 4:1:1); a warm-up, three repetitions alternated, one JSON line per
+           batch size (default 1, 256, 1024) with files/s (median, min, max) of both.  --corpus DIR as for --cmyk."""
 import io
 import json
 import os
@@ -181,6 +186,85 @@ def cmyk_bench(args):
                           "host_cpu_s_per_file": round(sorted(x[1] for x in t)[1] / n, 6)}), flush=True)
 
 
+def sampled_corpus(folder, h0, v0, count=2):
+    """count 1080p baseline files with luma factors (h0, v0) over 1x1 chroma, from the quantised DCT of synthetic pictures"""
+    import jpeg_edge_corpus as ec
+    import jpeg_writer as jw
+    files = []
+    k8 = np.arange(8)
+    dct = np.sqrt(2.0 / 8) * np.cos((2 * k8[None, :] + 1) * k8[:, None] * np.pi / 16)
+    dct[0] /= np.sqrt(2.0)
+    q85 = oracle.jpeg_quant(85)
+    q = {0: [int(v) for v in q85[0]], 1: [int(v) for v in q85[1]]}
+    dc, ac, _ = ec.tables_short()
+    for k in range(count):
+        path = os.path.join(folder, "y%dx%d_1080p_%d.jpg" % (h0, v0, k)) if folder else None
+        if path and os.path.exists(path):
+            files.append(open(path, "rb").read())
+            continue
+        frame = jw.Frame(w, h, [(1, h0, v0, 0), (2, 1, 1, 1), (3, 1, 1, 1)])
+        planes = [np.sin(xx / (40.0 + 7 * k)) * 90 + 128, np.cos(yy / (31.0 + 5 * k)) * 40 + 128, ((xx + 2 * yy) / 6.0 + 40 * k) % 64 + 96]
+        noise = np.random.default_rng(k)
+        blocks = []
+        for c in range(3):
+            rows, cols = frame.grid(c)
+            p = (planes[c] + noise.normal(0, 6, (h, w))).clip(0, 255)
+            if c:
+                p = p[::v0, ::h0]
+            full = np.zeros((rows * 8, cols * 8))
+            full[:p.shape[0], :p.shape[1]] = p
+            full[p.shape[0]:, :] = full[p.shape[0] - 1:p.shape[0], :]           # edge replication, as an encoder pads
+            full[:, p.shape[1]:] = full[:, p.shape[1] - 1:p.shape[1]]
+            b = (full - 128).reshape(rows, 8, cols, 8).transpose(0, 2, 1, 3)
+            coef = np.einsum("ij,rcjk,lk->rcil", dct, b, dct).reshape(rows, cols, 64)[..., jw.ZIG]
+            blocks.append(np.rint(coef / np.asarray(q[frame.comps[c][3]], float)).astype(np.int64))
+        data = ec.file(w, h, frame.comps, blocks, {(0, 0): dc, (1, 0): ac, (0, 1): dc, (1, 1): ac}, {0: (q[0], 0), 1: (q[1], 0)})
+        if path:
+            os.makedirs(folder, exist_ok=True)
+            with open(path, "wb") as fh:
+                fh.write(data)
+        files.append(data)
+    return files
+
+
+def s411_bench(args):
+    os.environ["IPX_JPEG_411"] = "1"
+    flags = {x for x in args if x.startswith("--")}
+    folder = args[args.index("--corpus") + 1] if "--corpus" in args else None
+    sizes = [int(x) for x in args if x.isdigit()] or [1, 256, 1024]
+    src = {"411": sampled_corpus(folder, 4, 1), "420": sampled_corpus(folder, 2, 2)}
+    if "--write-only" in flags:
+        return
+    ctx = ipx.Context()
+
+    def run(files):
+        t0 = time.perf_counter()
+        info, st = ctx.jpeg_decode_batch(files, download=False)
+        dt = time.perf_counter() - t0
+        info["free"]()
+        assert not any(st), st[:8]
+        return dt
+
+    print("files: %dx%d q85 baseline, one scan, the writer's Huffman tables; 4:1:1 %.0f KB each, 4:2:0 %.0f KB each; ipx_jpeg_decode_batch, planes left in HBM"
+          % (w, h, sum(len(p) for p in src["411"]) / len(src["411"]) / 1e3, sum(len(p) for p in src["420"]) / len(src["420"]) / 1e3))
+    for kind in src:
+        run(src[kind] * 32)                                                 # warm-up
+    for n in sizes:
+        t = {kind: [] for kind in src}
+        for rep in range(3 if n > 1 else 5):
+            for kind in src:
+                t[kind].append(run([src[kind][i % len(src[kind])] for i in range(n)]))
+        row = {"bench": "jpeg_411_decode", "batch": n}
+        for kind in src:
+            dts = sorted(t[kind])
+            med = dts[len(dts) // 2]
+            row[kind] = {"files_per_s": [round(n / med, 1), round(n / dts[-1], 1), round(n / dts[0], 1)], "ms": round(med * 1e3, 2)}
+        print(json.dumps(row), flush=True)
+
+
+if "--411" in sys.argv[1:]:
+    s411_bench([x for x in sys.argv[1:] if x != "--411"])
+    sys.exit(0)
 if "--cmyk" in sys.argv[1:]:
     cmyk_bench([x for x in sys.argv[1:] if x != "--cmyk"])
     sys.exit(0)
