@@ -398,9 +398,7 @@ int ipx_plan_run_host_paletted_gif(ipx_ctx *ctx, const ipx_plan *pl, int n, cons
         if (outs.frame_bytes()) IPX_HIP(mem.get(&dout, outs.frame_bytes() * m));
         BatchSrc d;
         IPX_HIP(src_upload(host, L, i0, m, dsrc, m, s, kCopyFrameRows, &d));
-        const PlanOutputs::Frames f = outs.place(dout, m);
-        int rc = run_dev_src(ctx, s, pl, m, d, outs.dst(f));
-        if (!rc) rc = encode_outputs(ctx, s, outs, f, m, i0, quality, nullptr, res);
+        const int rc = run_chunk(ctx, s, pl, outs, dout, m, d, all_files(n), i0, m, nullptr, nullptr, quality, nullptr, res);
         if (rc) return rc;
     }
     *result = res.release();

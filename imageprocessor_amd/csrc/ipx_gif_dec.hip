@@ -319,11 +319,12 @@ int ipx_gif_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *gifs, int 
 IPX_CATCH_STATUS
 
 // The GIF task's GPU leg from the uploads on: per chunk of files, the host parse and the upload of the LZW data, the walk and the
-// expansion into HBM, the operators (run_dev_src), then gif.Encode of the resize and thumbnail outputs and jpeg.Encode of the watermark
-// output (a GIF watermark becomes a JPEG, watermark.go:73).  Chunks are bounded as in ipx_plan_run_host_paletted_gif.  The operators run
+// expansion into HBM, then the chunk step (run_chunk): the operators, gif.Encode of the resize and thumbnail outputs and jpeg.Encode of the
+// watermark output (a GIF watermark becomes a JPEG, watermark.go:73).  Chunks are bounded as in ipx_plan_run_host_paletted_gif.  The operators run
 // on every slot of a chunk (a failed file's slot holds whatever its frame holds); only OK files' streams are handed out.
 // (the body of ipx_plan_run_gif_gif -- texts == NULL: no text launch -- and of ipx_plan_run_gif_gif_texts, where texts[i] is drawn on
-// file i's watermark frame between the operators and the encoders: one text set per call, chunk i0 draws texts i0 .. i0 + m)
+// file i's watermark frame between the operators and the encoders: one text set per call, the selection is the whole call and chunk i0
+// is its slots i0 .. i0 + m)
 static int run_gif_gif(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, const ipx_text *texts, int quality,
                        ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result)
 {
@@ -346,9 +347,8 @@ static int run_gif_gif(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n,
     LaneLease lane(ctx);
     hipStream_t s = lane->stream;
     std::vector<GifFileInfo> info(chunk);
-    ipx_textset ts;
-    const bool draw = texts && pl->p.do_watermark && outs.o[2].fs;
-    if (draw && (rc = textset_build(s, who, texts, n, outs.o[2].w, outs.o[2].h, &ts))) return rc;
+    LegTexts lt;
+    if ((rc = lt.build(s, who, pl, outs, texts, all_files(n), true))) return rc;
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const int m = std::min(chunk, n - i0);
         int bw = sw, bh = sh;
@@ -364,10 +364,7 @@ static int run_gif_gif(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n,
         rc = gif_decode_files(ctx, s, files + i0, m, info, didx, fsrc, dpal, status + i0);
         if (rc) return rc;
         if (!any_ok(status + i0, m)) continue;
-        const PlanOutputs::Frames f = outs.place(dout, m);
-        rc = run_dev_src(ctx, s, pl, m, packed_src(kSrcPaletted, didx, sw, fsrc, dpal), outs.dst(f));
-        if (!rc && draw) rc = dev_composite_texts(s, nullptr, f.dev[2], outs.o[2].w * 4, outs.o[2].fs, m, ts, i0, nullptr);
-        if (!rc) rc = encode_outputs(ctx, s, outs, f, m, i0, quality, status, res);
+        rc = run_chunk(ctx, s, pl, outs, dout, m, packed_src(kSrcPaletted, didx, sw, fsrc, dpal), all_files(n), i0, m, &lt, nullptr, quality, status, res);
         if (rc) return rc;
     }
     *result = res.release();
@@ -378,7 +375,7 @@ int ipx_plan_run_gif_gif(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_byte
                          ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result) try
 {
     IPX_ENTER(ctx);
-    if (!pl || n < 0 || !files || !status || !result) { set_error("ipx_plan_run_gif_gif: bad argument"); return IPX_ERR_INVALID; }
+    if (const int rc = leg_entry_check("ipx_plan_run_gif_gif", pl, n, files, status, result, false, nullptr)) return rc;
     return run_gif_gif("ipx_plan_run_gif_gif", ctx, pl, n, files, nullptr, quality, resize_out, thumb_out, wm_out, status, result);
 }
 IPX_CATCH_STATUS
@@ -387,10 +384,7 @@ int ipx_plan_run_gif_gif_texts(ipx_ctx *ctx, const ipx_plan *pl, int n, const ip
                                ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result) try
 {
     IPX_ENTER(ctx);
-    if (!pl || n < 0 || !files || !status || !result) { set_error("ipx_plan_run_gif_gif_texts: bad argument"); return IPX_ERR_INVALID; }
-    *result = nullptr;
-    const int rc = leg_texts_check("ipx_plan_run_gif_gif_texts", pl, texts, n);
-    if (rc) return rc;
+    if (const int rc = leg_entry_check("ipx_plan_run_gif_gif_texts", pl, n, files, status, result, true, texts)) return rc;
     return run_gif_gif("ipx_plan_run_gif_gif_texts", ctx, pl, n, files, texts, quality, resize_out, thumb_out, wm_out, status, result);
 }
 IPX_CATCH_STATUS

@@ -3,6 +3,7 @@
 // ipx_jpeg_entropy.hip; host half: ipx_jpeg_host.cpp.
 #include <atomic>
 #include <chrono>
+#include <optional>
 #include <string>
 
 #include "ipx_png.h"
@@ -321,13 +322,16 @@ int PlanOutputs::check_gif() const
     return IPX_OK;
 }
 
-int encode_outputs(ipx_ctx *ctx, hipStream_t s, const PlanOutputs &outs, const PlanOutputs::Frames &f, int m, int i0, int quality,
-                   const int *status, ResultOwner &res, const int *idx)
+// Encodes the sel.n frames of every present output and publishes {blob + off, len} of frame i into dst[sel.at(i)].  All JPEG outputs go
+// into one jpeg_encode_sets call (three waits for the device in all); PNG and GIF outputs are encoded one after the other.
+static int encode_outputs(ipx_ctx *ctx, hipStream_t s, const PlanOutputs &outs, const PlanOutputs::Frames &f, const FileSel &sel, int quality,
+                   const int *status, ResultOwner &res)
 {
+    const int m = sel.n;
     std::vector<size_t> offs(3 * (size_t)m), lens(3 * (size_t)m);
     auto publish = [&](const PlanOutputs::Output &o, const uint8_t *blob, const size_t *off, const size_t *len) {
         for (int i = 0; i < m; i++) {
-            const int j = idx ? idx[i] : i0 + i;
+            const int j = sel.at(i);
             if (!status || status[j] == IPX_OK) o.dst[j] = ipx_bytes{blob + off[i], len[i]};
         }
     };
@@ -355,6 +359,31 @@ int encode_outputs(ipx_ctx *ctx, hipStream_t s, const PlanOutputs &outs, const P
     res.add(blob);
     for (int k = 0; k < K; k++) publish(outs.o[who[k]], blob, sets[k].offs, sets[k].lens);
     return IPX_OK;
+}
+
+int LegTexts::build(hipStream_t s, const char *who, const ipx_plan *pl, const PlanOutputs &outs, const ipx_text *texts, const FileSel &sel, bool slots)
+{
+    draw = texts && pl->p.do_watermark && outs.o[2].fs;
+    by_slot = slots;
+    if (!draw) return IPX_OK;
+    std::vector<ipx_text> own(sel.idx ? sel.n : 0);           // (textset_build returns with its uploads finished)
+    for (size_t g = 0; g < own.size(); g++) own[g] = texts[sel.idx[g]];
+    return textset_build(s, who, sel.idx ? own.data() : texts + sel.first, sel.n, outs.o[2].w, outs.o[2].h, &ts);
+}
+
+int run_chunk(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, const PlanOutputs &outs, uint8_t *block, int slots, const BatchSrc &d,
+              const FileSel &sel, int c0, int m, const LegTexts *texts, AsyncFree *mem, int quality, const int *status, ResultOwner &res)
+{
+    const PlanOutputs::Frames f = outs.place(block, slots);
+    const FileSel here = sel.slice(c0, m);
+    int rc = run_dev_src(ctx, s, pl, m, d, outs.dst(f));
+    if (!rc && texts && texts->draw) {
+        const bool map = !texts->by_slot && here.idx;
+        rc = dev_composite_texts(s, mem, f.dev[2], outs.o[2].w * 4, outs.o[2].fs, m, texts->ts, map ? 0 : texts->by_slot ? c0 : here.first,
+                                 map ? here.idx : nullptr);
+    }
+    if (!rc) rc = encode_outputs(ctx, s, outs, f, here, quality, status, res);
+    return rc;
 }
 
 // frames of any source type in host memory through the plan, every output JPEG-encoded
@@ -394,12 +423,10 @@ static int run_host_jpeg_impl(const char *who, ipx_ctx *ctx, const ipx_plan *pl,
         for (int c = next.fetch_add(1); !rc && c < nchunks && status == IPX_OK; c = next.fetch_add(1)) {
             const int i0 = c * chunk, m = std::min(chunk, n - i0);
             uint8_t *dsrc = (uint8_t *)(((uintptr_t)l->dev + 255) & ~(uintptr_t)255);
-            const PlanOutputs::Frames f = outs.place(dsrc + fsrc * chunk, chunk);
             BatchSrc d;
             const hipError_t e = src_upload(host, L, i0, m, dsrc, chunk, l->stream, kCopyWholePlanes, &d);
             if (e != hipSuccess) { set_error("upload failed: %s", hipGetErrorString(e)); rc = IPX_ERR_HIP; break; }
-            rc = run_dev_src(ctx, l->stream, pl, m, d, outs.dst(f));
-            if (!rc) rc = encode_outputs(ctx, l->stream, outs, f, m, i0, quality, nullptr, mine);
+            rc = run_chunk(ctx, l->stream, pl, outs, dsrc + fsrc * chunk, chunk, d, all_files(n), i0, m, nullptr, nullptr, quality, nullptr, mine);
         }
         {
             std::lock_guard<std::mutex> lk(res_mu);
@@ -481,16 +508,22 @@ IPX_CATCH_STATUS
 // ---- compressed in, compressed out: image.Decode, the operators and jpeg.Encode without leaving the GPU ------
 extern "C" {
 
-// texts: null, or this part's own n texts (texts[i] for files[i])
-static int run_jpeg_jpeg_one(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, const ipx_text *texts, int quality,
-                             ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result)
+// One part of a JPEG call on a lane of its own: the files of `sel`, all of one kind, are decoded and go chunk by chunk through
+// run_chunk.  h0 == 0: three-component and Gray files, decoded to planes (jpeg_decode_files); h0 > 0: four-component files of that
+// sampling vector (IPX_JPEG_CMYK=1; ipx_jpeg_dec_cmyk.hip), decoded to *image.CMYK frames that go through the plan as the deep CMYK
+// source.  The decoders take files and statuses side by side: a selection through an index list is gathered for them and its statuses
+// go back to at(g), one without is handed on where it lies.  texts: null, or the call's; the part draws texts[sel.at(g)] as a set of
+// its own.  The jj_active slot, the lane arena and the timing line are the three-component parts'.
+static int run_jpeg_part(const char *who, ipx_ctx *ctx, const ipx_plan *pl, const ipx_bytes *files, const ipx_text *texts, const FileSel &sel,
+                         int h0, int quality, const PlanOutputs &outs, int *status, ipx_jpeg_result **result)
 {
     IPX_ENTER(ctx);
     *result = nullptr;
+    const int n = sel.n;
     if (n == 0) return IPX_OK;
-    const PlanOutputs outs(pl, resize_out, thumb_out, wm_out, Codec::Jpeg, Codec::Jpeg, Codec::Jpeg);
-    outs.clear(n);
-    const bool dbg = getenv("IPX_DEBUG") != nullptr;
+    const bool four = h0 > 0;
+    if (four && n > 65535) { for (int g = 0; g < n; g++) status[sel.at(g)] = IPX_ERR_UNSUPPORTED; return IPX_OK; }
+    const bool dbg = !four && getenv("IPX_DEBUG") != nullptr;
     struct Slot {
         ipx_ctx *c;
         explicit Slot(ipx_ctx *ctx) : c(ctx)
@@ -505,20 +538,36 @@ static int run_jpeg_jpeg_one(const char *who, ipx_ctx *ctx, const ipx_plan *pl, 
             { std::lock_guard<std::mutex> lk(c->mu); c->jj_active--; }
             c->cv.notify_all();
         }
-    } slot(ctx);
+    };
+    std::optional<Slot> slot;
+    if (!four) slot.emplace(ctx);
     const auto t0 = std::chrono::steady_clock::now();
     auto ms_since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
     LaneLease lane(ctx);
     const double t_lane = ms_since(t0);
     hipStream_t s = lane->stream;
-    int w = pl->p.sw, h = pl->p.sh;
-    ipx_ycbcr_batch planes;
+    std::vector<ipx_bytes> gfiles(sel.idx ? n : 0);
+    std::vector<int> gstatus(gfiles.size(), IPX_OK);
+    for (size_t g = 0; g < gfiles.size(); g++) gfiles[g] = files[sel.idx[g]];
+    const ipx_bytes *fl = sel.idx ? gfiles.data() : files + sel.first;
+    int *st = sel.idx ? gstatus.data() : status + sel.first;
+    int w = pl->p.sw, h = pl->p.sh, rc;
+    BatchSrc src;                                             // the part's frames in HBM: no plane 0 when nothing was decodable
     ipx_jpeg_planes *owner = nullptr;
-    memset(&planes, 0, sizeof planes);
-    int rc = n > 65535 ? IPX_ERR_UNSUPPORTED : jpeg_decode_files(ctx, s, env_int("IPX_JPEG_LANE_ARENA", 1) ? &lane.get() : nullptr, true, files, n, &w, &h, &planes, status, &owner);
+    if (four) {
+        ipx_cmyk_batch frames{};
+        std::fill(st, st + n, IPX_ERR_UNSUPPORTED);
+        rc = jpeg_decode_cmyk_files(ctx, s, fl, n, &w, &h, h0, &frames, st, &owner);
+        src = packed_src(kSrcCMYK, frames.pix, frames.stride, frames.frame_stride);
+    } else {
+        ipx_ycbcr_batch planes{};
+        rc = n > 65535 ? IPX_ERR_UNSUPPORTED : jpeg_decode_files(ctx, s, env_int("IPX_JPEG_LANE_ARENA", 1) ? &lane.get() : nullptr, true, fl, n, &w, &h, &planes, st, &owner);
+        src = ycbcr_src(&planes);                             // (ratio IPX_GRAY: only y is set)
+        if (planes.ratio == IPX_GRAY) src.type = kSrcGray;
+    }
     const double t_dec = ms_since(t0);
-    if (rc) return rc;
-    if (!planes.y) return IPX_OK;                         // nothing decodable: every status says why
+    for (size_t g = 0; g < gstatus.size(); g++) status[sel.idx[g]] = gstatus[g];
+    if (rc || !src.plane[0]) return rc;                       // nothing decodable: every status says why
     struct Guard { ipx_ctx *c; ipx_jpeg_planes *o; ~Guard() { ipx_jpeg_planes_free(c, o); } } guard{ctx, owner};
     // (a coefficient buffer per output: the three encodes run stage by stage together, jpeg_encode_sets)
     const size_t per_frame = outs.frame_bytes();
@@ -528,21 +577,11 @@ static int run_jpeg_jpeg_one(const char *who, ipx_ctx *ctx, const ipx_plan *pl, 
     if (rc) return rc;
     const double t_res = ms_since(t0);
     ResultOwner res(ctx);
-    // a text per file: the set is uploaded once per part, chunk i0 draws texts i0 .. i0 + m behind the plan's copy of the frame
-    ipx_textset ts;
-    const bool draw = texts && pl->p.do_watermark && outs.o[2].fs;
-    if (draw && (rc = textset_build(s, who, texts, n, outs.o[2].w, outs.o[2].h, &ts))) return rc;
-    for (int i0 = 0; i0 < n && !rc; i0 += chunk) {
-        const int m = std::min(chunk, n - i0);
-        const PlanOutputs::Frames f = outs.place((uint8_t *)(((uintptr_t)lane->dev + 255) & ~(uintptr_t)255), chunk);
-        BatchSrc d = ycbcr_src(&planes);                      // (ratio IPX_GRAY: only y is set)
-        if (planes.ratio == IPX_GRAY) d.type = kSrcGray;
-        d.plane[0] += d.frame_stride[0] * i0;
-        if (d.plane[1]) { d.plane[1] += d.frame_stride[1] * i0; d.plane[2] += d.frame_stride[1] * i0; }
-        rc = run_dev_src(ctx, s, pl, m, d, outs.dst(f));
-        if (!rc && draw) rc = dev_composite_texts(s, nullptr, f.dev[2], outs.o[2].w * 4, outs.o[2].fs, m, ts, i0, nullptr);
-        if (!rc) rc = encode_outputs(ctx, s, outs, f, m, i0, quality, status, res);
-    }
+    LegTexts lt;                                              // uploaded once per part; chunk c0 draws texts c0 .. c0 + m of the set
+    if ((rc = lt.build(s, who, pl, outs, texts, sel, true))) return rc;
+    uint8_t *const block = (uint8_t *)(((uintptr_t)lane->dev + 255) & ~(uintptr_t)255);
+    for (int c0 = 0; c0 < n && !rc; c0 += chunk)
+        rc = run_chunk(ctx, s, pl, outs, block, chunk, src.from(c0), sel, c0, std::min(chunk, n - c0), &lt, nullptr, quality, status, res);
     (void)hipStreamSynchronize(s);
     if (dbg) fprintf(stderr, "[ipx] jpeg->jpeg part of %d files: lane after %.1f ms, decoded at %.1f, scratch at %.1f, done at %.1f\n", n, t_lane, t_dec, t_res, ms_since(t0));
     if (rc) return rc;
@@ -550,26 +589,24 @@ static int run_jpeg_jpeg_one(const char *who, ipx_ctx *ctx, const ipx_plan *pl, 
     return IPX_OK;
 }
 
-
 // the three-component and Gray files of a call (every file, without IPX_JPEG_CMYK=1)
-static int run_jpeg_jpeg_ycbcr(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, const ipx_text *texts, int quality,
-                         ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result)
+static int run_jpeg_jpeg_ycbcr(const char *who, ipx_ctx *ctx, const ipx_plan *pl, const ipx_bytes *files, const ipx_text *texts, const FileSel &sel,
+                               int quality, const PlanOutputs &outs, int *status, ipx_jpeg_result **result)
 {
     *result = nullptr;
     // a large batch is cut into parts that run on lanes of their own, one host thread each: while one part is in its (host-paced)
     // encode read-backs another decodes.  Two callers with 1024 files each measured 15 k images/s against 11.7 k for one.
     // Four parts of 256 measured 9 % above two of 512 or three of 341 (tools/j2j_parts.sh: 55.3 ms against 60.4 per 1024 files); more
     // than four gain nothing.  One lane stays free for a per-operator call that arrives while the batch runs.
-    const int nl = (int)ctx->lanes.size();
+    const int n = sel.n, nl = (int)ctx->lanes.size();
     const int parts = std::max(1, std::min({nl >= 3 ? nl - 1 : nl, n / std::max(1, env_int("IPX_JPEG_JPEG_PART", 256)), env_int("IPX_JPEG_JPEG_MAXPARTS", 4)}));
-    if (parts == 1) return run_jpeg_jpeg_one(who, ctx, pl, n, files, texts, quality, resize_out, thumb_out, wm_out, status, result);
+    if (parts == 1) return run_jpeg_part(who, ctx, pl, files, texts, sel, 0, quality, outs, status, result);
     std::vector<ipx_jpeg_result *> res(parts, nullptr);
     std::vector<int> rcs(parts, IPX_OK);
     std::vector<std::string> errs(parts);
     auto work = [&](int k) {
-        const int i0 = (int)((long long)n * k / parts), i1 = (int)((long long)n * (k + 1) / parts);
-        rcs[k] = run_jpeg_jpeg_one(who, ctx, pl, i1 - i0, files + i0, texts ? texts + i0 : nullptr, quality, resize_out ? resize_out + i0 : nullptr,
-                                   thumb_out ? thumb_out + i0 : nullptr, wm_out ? wm_out + i0 : nullptr, status + i0, &res[k]);
+        const int g0 = (int)((long long)n * k / parts), g1 = (int)((long long)n * (k + 1) / parts);
+        rcs[k] = run_jpeg_part(who, ctx, pl, files, texts, sel.slice(g0, g1 - g0), 0, quality, outs, status, &res[k]);
         if (rcs[k]) errs[k] = ipx_last_error();
     };
     auto guarded = [&](int k) { const int rc = guarded_status([&] { work(k); }, &errs[k]); if (rc) rcs[k] = rc; };
@@ -585,91 +622,29 @@ static int run_jpeg_jpeg_ycbcr(const char *who, ipx_ctx *ctx, const ipx_plan *pl
     return IPX_OK;
 }
 
-// One sub-batch of four-component files (IPX_JPEG_CMYK=1; ipx_jpeg_dec_cmyk.hip): files[idx[g]], all of one sampling vector (h0), are
-// decoded to *image.CMYK frames, go through the plan as the deep CMYK source and are encoded; streams and statuses land at idx[g].
-// texts: null, or the call's texts (texts[idx[g]] is drawn on file idx[g]'s watermark frame).
-static int run_jpeg_jpeg_cmyk(const char *who, ipx_ctx *ctx, const ipx_plan *pl, const ipx_bytes *files, const ipx_text *texts, const std::vector<int> &idx,
-                              int h0, int quality, const PlanOutputs &outs, int *status, ResultOwner &res)
-{
-    const int m = (int)idx.size();
-    if (m == 0) return IPX_OK;
-    if (m > 65535) { for (int i : idx) status[i] = IPX_ERR_UNSUPPORTED; return IPX_OK; }
-    std::vector<ipx_bytes> gfiles(m);
-    std::vector<ipx_text> gtexts;
-    std::vector<int> gstatus(m, IPX_ERR_UNSUPPORTED);
-    for (int g = 0; g < m; g++) gfiles[g] = files[idx[g]];
-    LaneLease lane(ctx);
-    hipStream_t s = lane->stream;
-    int w = pl->p.sw, h = pl->p.sh;
-    ipx_cmyk_batch frames;
-    ipx_jpeg_planes *owner = nullptr;
-    memset(&frames, 0, sizeof frames);
-    int rc = jpeg_decode_cmyk_files(ctx, s, gfiles.data(), m, &w, &h, h0, &frames, gstatus.data(), &owner);
-    for (int g = 0; g < m; g++) status[idx[g]] = gstatus[g];
-    if (rc || !frames.pix) return rc;
-    struct Guard { ipx_ctx *c; ipx_jpeg_planes *o; ~Guard() { ipx_jpeg_planes_free(c, o); } } guard{ctx, owner};
-    const size_t per_frame = outs.frame_bytes();
-    if (per_frame == 0) return IPX_OK;
-    const int chunk = std::max(1, std::min(m, env_int("IPX_JPEG_JPEG_CHUNK", 256)));
-    rc = lane_reserve(lane.get(), per_frame * chunk + 256);
-    if (rc) return rc;
-    // the sub-batch's own texts as one set: chunk c0 draws texts c0 .. c0 + cm of it
-    ipx_textset ts;
-    const bool draw = texts && pl->p.do_watermark && outs.o[2].fs;
-    if (draw) {
-        gtexts.resize(m);
-        for (int g = 0; g < m; g++) gtexts[g] = texts[idx[g]];
-        if ((rc = textset_build(s, who, gtexts.data(), m, outs.o[2].w, outs.o[2].h, &ts))) return rc;
-    }
-    for (int c0 = 0; c0 < m && !rc; c0 += chunk) {
-        const int cm = std::min(chunk, m - c0);
-        const PlanOutputs::Frames f = outs.place((uint8_t *)(((uintptr_t)lane->dev + 255) & ~(uintptr_t)255), chunk);
-        const BatchSrc d = packed_src(kSrcCMYK, frames.pix + frames.frame_stride * c0, frames.stride, frames.frame_stride);
-        rc = run_dev_src(ctx, s, pl, cm, d, outs.dst(f));
-        if (!rc && draw) rc = dev_composite_texts(s, nullptr, f.dev[2], outs.o[2].w * 4, outs.o[2].fs, cm, ts, c0, nullptr);
-        if (!rc) rc = encode_outputs(ctx, s, outs, f, cm, 0, quality, status, res, idx.data() + c0);
-    }
-    (void)hipStreamSynchronize(s);
-    return rc;
-}
-
 // the body of ipx_plan_run_jpeg_jpeg (texts == NULL: no text launch) and ipx_plan_run_jpeg_jpeg_texts.  Under IPX_JPEG_CMYK=1 the
 // four-component files are taken out of the call and run as sub-batches of one sampling vector each; the rest runs as it always did.
+// All three are selections of the call's files handed to the same part runner, which reaches the caller's arrays through them.
 static int run_jpeg_jpeg(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, const ipx_text *texts, int quality,
                          ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result)
 {
-    *result = nullptr;
+    const PlanOutputs outs(pl, resize_out, thumb_out, wm_out, Codec::Jpeg, Codec::Jpeg, Codec::Jpeg);
+    outs.clear(n);
     std::vector<int> four[2], rest;
     if (jpeg_cmyk_enabled())
         for (int i = 0; i < n; i++) {
             const int h0 = jpeg_cmyk_peek(files[i].data, files[i].len);
             if (h0) four[h0 - 1].push_back(i); else rest.push_back(i);
         }
-    if (four[0].empty() && four[1].empty()) return run_jpeg_jpeg_ycbcr(who, ctx, pl, n, files, texts, quality, resize_out, thumb_out, wm_out, status, result);
-    const PlanOutputs outs(pl, resize_out, thumb_out, wm_out, Codec::Jpeg, Codec::Jpeg, Codec::Jpeg);
-    outs.clear(n);
+    if (four[0].empty() && four[1].empty()) return run_jpeg_jpeg_ycbcr(who, ctx, pl, files, texts, all_files(n), quality, outs, status, result);
     ResultOwner all(ctx);
-    const int nr = (int)rest.size();
-    if (nr) {
-        // the rest of the call, compacted: its streams and statuses go back to the files' own indices
-        std::vector<ipx_bytes> rfiles(nr), out[3];
-        std::vector<ipx_text> rtexts(texts ? nr : 0);
-        std::vector<int> rstatus(nr, IPX_OK);
-        ipx_bytes *const dst[3] = {resize_out, thumb_out, wm_out};
-        for (int k = 0; k < 3; k++) if (dst[k]) out[k].assign(nr, ipx_bytes{nullptr, 0});
-        for (int g = 0; g < nr; g++) { rfiles[g] = files[rest[g]]; if (texts) rtexts[g] = texts[rest[g]]; }
+    for (int v = 0; v < 3; v++) {                             // the rest, then the two vectors
+        const std::vector<int> &of = v ? four[v - 1] : rest;
+        const FileSel sel{of.data(), 0, (int)of.size()};
         ipx_jpeg_result *r = nullptr;
-        const int rc = run_jpeg_jpeg_ycbcr(who, ctx, pl, nr, rfiles.data(), texts ? rtexts.data() : nullptr, quality, dst[0] ? out[0].data() : nullptr,
-                                           dst[1] ? out[1].data() : nullptr, dst[2] ? out[2].data() : nullptr, rstatus.data(), &r);
+        const int rc = v ? run_jpeg_part(who, ctx, pl, files, texts, sel, v, quality, outs, status, &r)
+                         : run_jpeg_jpeg_ycbcr(who, ctx, pl, files, texts, sel, quality, outs, status, &r);
         all.adopt(r);
-        if (rc) return rc;
-        for (int g = 0; g < nr; g++) {
-            status[rest[g]] = rstatus[g];
-            for (int k = 0; k < 3; k++) if (dst[k]) dst[k][rest[g]] = out[k][g];
-        }
-    }
-    for (int v = 0; v < 2; v++) {
-        const int rc = run_jpeg_jpeg_cmyk(who, ctx, pl, files, texts, four[v], v + 1, quality, outs, status, all);
         if (rc) return rc;
     }
     *result = all.release();
@@ -680,7 +655,7 @@ int ipx_plan_run_jpeg_jpeg(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_by
                            ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result) try
 {
     IPX_ENTER(ctx);
-    if (!pl || n < 0 || !files || !status || !result) { set_error("ipx_plan_run_jpeg_jpeg: bad argument"); return IPX_ERR_INVALID; }
+    if (const int rc = leg_entry_check("ipx_plan_run_jpeg_jpeg", pl, n, files, status, result, false, nullptr)) return rc;
     return run_jpeg_jpeg("ipx_plan_run_jpeg_jpeg", ctx, pl, n, files, nullptr, quality, resize_out, thumb_out, wm_out, status, result);
 }
 IPX_CATCH_STATUS
@@ -689,10 +664,7 @@ int ipx_plan_run_jpeg_jpeg_texts(ipx_ctx *ctx, const ipx_plan *pl, int n, const 
                                  ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result) try
 {
     IPX_ENTER(ctx);
-    if (!pl || n < 0 || !files || !status || !result) { set_error("ipx_plan_run_jpeg_jpeg_texts: bad argument"); return IPX_ERR_INVALID; }
-    *result = nullptr;
-    const int rc = leg_texts_check("ipx_plan_run_jpeg_jpeg_texts", pl, texts, n);
-    if (rc) return rc;
+    if (const int rc = leg_entry_check("ipx_plan_run_jpeg_jpeg_texts", pl, n, files, status, result, true, texts)) return rc;
     return run_jpeg_jpeg("ipx_plan_run_jpeg_jpeg_texts", ctx, pl, n, files, texts, quality, resize_out, thumb_out, wm_out, status, result);
 }
 IPX_CATCH_STATUS

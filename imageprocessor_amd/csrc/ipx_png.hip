@@ -823,9 +823,7 @@ int ipx_plan_run_host_png(ipx_ctx *ctx, const ipx_plan *pl, int n, const uint8_t
         if (outs.frame_bytes()) IPX_HIP(mem.get(&dout, outs.frame_bytes() * m));
         BatchSrc d;
         IPX_HIP(src_upload(host, L, i0, m, dsrc, m, s, kCopyFrameRows, &d));
-        const PlanOutputs::Frames f = outs.place(dout, m);
-        int rc = run_dev_src(ctx, s, pl, m, d, outs.dst(f));
-        if (!rc) rc = encode_outputs(ctx, s, outs, f, m, i0, 0, nullptr, res);
+        const int rc = run_chunk(ctx, s, pl, outs, dout, m, d, all_files(n), i0, m, nullptr, nullptr, 0, nullptr, res);
         if (rc) return rc;
     }
     *result = res.release();

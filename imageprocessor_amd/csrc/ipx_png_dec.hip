@@ -826,11 +826,11 @@ extern "C" {
 
 // The PNG task's GPU leg from the uploads on: the host parse of every file, then per kind, per decode group (IPX_HOST_CHUNK_PNG_DEC
 // files, at most ~4 GiB of frames): upload, CRC, inflate and unfilter into HBM; then per chunk of IPX_HOST_CHUNK_PNG frames the
-// operators on frames of that kind (run_dev_src) and png.Encode of all three outputs.  The operators run on every slot of a chunk (a failed file's slot
+// operators on frames of that kind and png.Encode of all three outputs (run_chunk).  The operators run on every slot of a chunk (a failed file's slot
 // holds whatever its frame holds); only OK files' streams are handed out.
 // (the body of ipx_plan_run_png_png -- texts == NULL: no text launch -- and of ipx_plan_run_png_png_texts, where texts[i] is drawn on
-// file i's watermark frame between the operators and the encoder: one text set per call; the files are sorted by kind here, so the
-// frames of a chunk take their texts through the chunk's own slice of idx)
+// file i's watermark frame between the operators and the encoder: one text set per call, indexed by the caller's index; the files are
+// sorted by kind here, so a group is a selection through its idx and run_chunk takes texts, statuses and output slots through it)
 static int run_png_png(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, const ipx_text *texts,
                        ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result)
 {
@@ -849,9 +849,8 @@ static int run_png_png(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n,
     ResultOwner res(ctx);
     LaneLease lane(ctx);
     hipStream_t s = lane->stream;
-    ipx_textset ts;
-    const bool draw = texts && pl->p.do_watermark && outs.o[2].fs;
-    if (draw && (rc = textset_build(s, who, texts, n, outs.o[2].w, outs.o[2].h, &ts))) return rc;
+    LegTexts lt;                        // one set per call, indexed by the caller's index: a group's chunks select through its idx
+    if ((rc = lt.build(s, who, pl, outs, texts, all_files(n), false))) return rc;
     for (int kind = 0; kind < kPngKinds; kind++) {
         std::vector<int> of_kind;
         for (int i = 0; i < n; i++)
@@ -880,12 +879,9 @@ static int run_png_png(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n,
                 AsyncFree omem{s, {}};
                 uint8_t *dout = nullptr;
                 if (per_out) IPX_HIP(omem.get(&dout, per_out * cm));
-                const PlanOutputs::Frames f = outs.place(dout, cm);
-                const BatchSrc d = packed_src(src_of_png(kind), dfr + fs * c0, sw * kb, fs, dpal ? dpal + (size_t)1024 * c0 : nullptr);
-                rc = run_dev_src(ctx, s, pl, cm, d, outs.dst(f));
-                // (idx outlives the group's wait for the stream, and with it the copy of this slice)
-                if (!rc && draw) rc = dev_composite_texts(s, &omem, f.dev[2], outs.o[2].w * 4, outs.o[2].fs, cm, ts, 0, idx.data() + c0);
-                if (!rc) rc = encode_outputs(ctx, s, outs, f, cm, 0, 0, status, res, idx.data() + c0);
+                const BatchSrc d = packed_src(src_of_png(kind), dfr, sw * kb, fs, dpal).from(c0);
+                // (idx outlives the group's wait for the stream, and with it the copy of this chunk's slice in omem)
+                rc = run_chunk(ctx, s, pl, outs, dout, cm, d, FileSel{idx.data(), 0, m}, c0, cm, &lt, &omem, 0, status, res);
                 if (rc) return rc;
             }
         }
@@ -898,7 +894,7 @@ int ipx_plan_run_png_png(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_byte
                          ipx_bytes *wm_out, int *status, ipx_jpeg_result **result) try
 {
     IPX_ENTER(ctx);
-    if (!pl || n < 0 || !files || !status || !result) { set_error("ipx_plan_run_png_png: bad argument"); return IPX_ERR_INVALID; }
+    if (const int rc = leg_entry_check("ipx_plan_run_png_png", pl, n, files, status, result, false, nullptr)) return rc;
     return run_png_png("ipx_plan_run_png_png", ctx, pl, n, files, nullptr, resize_out, thumb_out, wm_out, status, result);
 }
 IPX_CATCH_STATUS
@@ -907,10 +903,7 @@ int ipx_plan_run_png_png_texts(ipx_ctx *ctx, const ipx_plan *pl, int n, const ip
                                ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result) try
 {
     IPX_ENTER(ctx);
-    if (!pl || n < 0 || !files || !status || !result) { set_error("ipx_plan_run_png_png_texts: bad argument"); return IPX_ERR_INVALID; }
-    *result = nullptr;
-    const int rc = leg_texts_check("ipx_plan_run_png_png_texts", pl, texts, n);
-    if (rc) return rc;
+    if (const int rc = leg_entry_check("ipx_plan_run_png_png_texts", pl, n, files, status, result, true, texts)) return rc;
     return run_png_png("ipx_plan_run_png_png_texts", ctx, pl, n, files, texts, resize_out, thumb_out, wm_out, status, result);
 }
 IPX_CATCH_STATUS

@@ -315,9 +315,13 @@ int dev_composite_texts(hipStream_t s, AsyncFree *mem, uint8_t *dst, int dstride
     return IPX_OK;
 }
 
-int leg_texts_check(const char *who, const ipx_plan *pl, const ipx_text *texts, int n)
+int leg_entry_check(const char *who, const ipx_plan *pl, int n, const ipx_bytes *files, const int *status, ipx_jpeg_result **result,
+                    bool texts_entry, const ipx_text *texts)
 {
-    if (!texts) { set_error("%s: bad argument", who); return IPX_ERR_INVALID; }
+    const bool ok = pl && n >= 0 && files && status && result;
+    if (ok) *result = nullptr;
+    if (!ok || (texts_entry && !texts)) { set_error("%s: bad argument", who); return IPX_ERR_INVALID; }
+    if (!texts_entry) return IPX_OK;
     if (pl->p.glyphs) {
         set_error("%s: the plan carries a glyph set of its own; per-file texts need a plan created with glyphs == NULL (copy only)", who);
         return IPX_ERR_INVALID;

@@ -315,8 +315,10 @@ int textset_build(hipStream_t s, const char *who, const ipx_text *texts, int n, 
 // *mem and read by that copy until `s` has been waited for; indices are checked here, before the launch.
 int dev_composite_texts(hipStream_t s, AsyncFree *mem, uint8_t *dst, int dstride, size_t frame_stride, int n_frames, const ipx_textset &ts,
                         int first, const int *map);
-// what a _texts leg checks before it does anything: the plan is copy-only (no glyph set of its own) and the texts are well-formed
-int leg_texts_check(const char *who, const ipx_plan *pl, const ipx_text *texts, int n);
+// what the six compressed-in / compressed-out entries check before they do anything: the arguments and, in a _texts entry, that the plan
+// is copy-only (no glyph set of its own) and the texts are well-formed; *result is null from here on
+int leg_entry_check(const char *who, const ipx_plan *pl, int n, const ipx_bytes *files, const int *status, ipx_jpeg_result **result,
+                    bool texts_entry, const ipx_text *texts);
 
 // Waits for its stream on every way out of the scope.  Declare it AFTER every host buffer that copies queued on the stream read or write:
 // locals go in reverse order, so the wait then comes before those buffers are destroyed.
@@ -336,6 +338,13 @@ struct BatchSrc {
     int stride[2] = {0, 0};                                // bytes per row of plane 0, of the chroma planes
     size_t frame_stride[2] = {0, 0};
     const uint8_t *palettes = nullptr;                     // kSrcPaletted: 256 x RGBA per frame, 1024 bytes apart
+    BatchSrc from(int i0) const                            // the same from frame i0 on
+    {
+        BatchSrc b = *this;
+        for (int p = 0; p < 3; p++) if (b.plane[p]) b.plane[p] += (size_t)i0 * frame_stride[p ? 1 : 0];
+        if (b.palettes) b.palettes += (size_t)i0 * 1024;
+        return b;
+    }
 };
 inline BatchSrc packed_src(int type, const uint8_t *pix, int stride, size_t frame_stride, const uint8_t *palettes = nullptr)
 {
@@ -504,8 +513,31 @@ struct PlanOutputs {
     int check_gif() const;        // every GIF output within gif.Encode's limits: IPX_OK, or IPX_ERR_INVALID with the error text set
 };
 
-// Encodes the m frames of every present output and publishes {blob + off, len} into dst[i0 + i] (dst[idx[i]] when idx is given) --
-// every slot when status is null, else only those whose status is IPX_OK -- with the blocks going to *res.  All JPEG outputs go into one
-// jpeg_encode_sets call (three waits for the device in all); PNG and GIF outputs are encoded one after the other.
-int encode_outputs(ipx_ctx *ctx, hipStream_t s, const PlanOutputs &outs, const PlanOutputs::Frames &f, int m, int i0, int quality,
-                   const int *status, ResultOwner &res, const int *idx = nullptr);
+// Which files of a call a leg, or a part, sub-batch or chunk of one, works on: slot g is the caller's file at(g).  What a leg makes for
+// itself (gathered files, decoded frames, a text set of its own texts) is indexed by the slot; the caller's arrays (files, texts, status,
+// the three ipx_bytes arrays) are reached through at(g) and nothing else.
+struct FileSel {
+    const int *idx;    // null: the n files from `first` on
+    int first, n;
+    int at(int g) const { return idx ? idx[g] : first + g; }
+    FileSel slice(int g0, int m) const { return FileSel{idx ? idx + g0 : nullptr, first + g0, m}; }
+};
+inline FileSel all_files(int n) { return FileSel{nullptr, 0, n}; }
+
+// A leg's per-file texts: whether they are drawn at all, the set, and what indexes it -- the slot in the selection it was built from
+// (the JPEG parts and sub-batches, the GIF leg) or the caller's index (the PNG leg: one set per call, its groups select through idx).
+struct LegTexts {
+    bool draw = false, by_slot = true;
+    ipx_textset ts;
+    // draw: texts are given and the plan makes the watermark output the caller wants; then texts[sel.at(g)] become one set, on `s`
+    int build(hipStream_t s, const char *who, const ipx_plan *pl, const PlanOutputs &outs, const ipx_text *texts, const FileSel &sel, bool slots);
+};
+
+// The step every compressed-out leg takes for a chunk of m frames that lie in HBM (`d`), slots c0 .. c0 + m of `sel`: the outputs are
+// placed in `block` (laid out for `slots` frames), the operators run, the chunk's texts are drawn in one launch (texts: null, or the
+// leg's) and the streams of every present output are published in the caller's arrays at sel.at(c0 + i) -- every slot when status is
+// null, else only those whose status there is IPX_OK -- with the blocks going to *res.  Both the text index and the output index come
+// from (sel, c0) here.  mem: where the copy of a frame-to-text map goes (texts by the caller's index through an index list); it is read
+// until `s` has been waited for.
+int run_chunk(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, const PlanOutputs &outs, uint8_t *block, int slots, const BatchSrc &d,
+              const FileSel &sel, int c0, int m, const LegTexts *texts, AsyncFree *mem, int quality, const int *status, ResultOwner &res);

@@ -72,13 +72,24 @@ def corpus():
 GLYPHS = text_glyphs(W, H, n=4, width_px=30, height_px=12)
 
 
+# the default (one part, one chunk), and the cut at its smallest: "the rest" of the corpus as two parts of two files, every part and
+# every four-component sub-batch in one-file chunks (both variables are read on every call)
+CUTS = [pytest.param({}, id="default"), pytest.param({"IPX_JPEG_JPEG_PART": "2", "IPX_JPEG_JPEG_CHUNK": "1"}, id="part2-chunk1")]
+
+
+@pytest.fixture(params=CUTS)
+def cut(request, monkeypatch):
+    for k, v in request.param.items():
+        monkeypatch.setenv(k, v)
+
+
 def cmyk_chain(pix, glyphs, col):
     """model pixels -> the three streams"""
     frames = _expect(oracle.deep_pix(pix, DEEP_CMYK), DEEP_CMYK, W, H, RESIZE, THUMB, glyphs, col)
     return {k: oracle.jpeg_encode_rgba(f, QUALITY) for k, f in zip(KEYS, frames)}
 
 
-def test_leg(ctx, on, corpus):
+def test_leg(ctx, on, cut, corpus):
     files, pixels = corpus
     gs = ctx.glyphset(GLYPHS, DEFAULT_COL)
     plan = ctx.plan(W, H, resize=RESIZE, thumbnail=THUMB, watermark=gs)
@@ -107,7 +118,7 @@ def test_leg(ctx, on, corpus):
     gs.close()
 
 
-def test_leg_texts(ctx, on, corpus):
+def test_leg_texts(ctx, on, cut, corpus):
     files, pixels = corpus
     texts = file_texts(len(files), W, H, 53)
     plan = ctx.plan(W, H, resize=RESIZE, thumbnail=THUMB, watermark=True)
