@@ -59,7 +59,7 @@ MOST_PADDED = (12, 16, 20)
 UNALIGNED_LAYOUTS = [(1, 0, 0), (2, 0, 0), (0, 1, 0), (0, 2, 0), (0, 0, 2)]                           # not dword-aligned
 SRC_LAYOUTS = [TIGHT] + DWORD_LAYOUTS + UNALIGNED_LAYOUTS
 # chroma planes, next to a tight Y plane: 2 leaves the gate of 4:4:4 / 4:4:0 (dword loads) and stays inside that of 4:2:0 / 4:2:2 (word
-# loads); 1 leaves both
+# loads); 1 leaves both, and none leaves that of 4:1:1 / 4:1:0 (byte loads)
 CHROMA_LAYOUTS = [(2, 0, 0), (0, 2, 0), (0, 0, 2), (1, 0, 0), (0, 1, 0), (0, 0, 1)]
 # outputs: (offset, extra frame stride)
 OUT_TIGHT = (0, 0)
@@ -75,8 +75,8 @@ SHAPES = [(104, 61, (52, 30, False), (24, True), True),
 # host batches into outputs with gaps (RGBA only): a resize output of 1500 bytes, no multiple of 16, which the lanes' scratch pads to 256
 HOST_GAP_SHAPE = (104, 61, (25, 15, False), (24, True), True)
 DEEP_KINDS = ("nrgba64", "rgba64", "gray16", "cmyk")
-RATIO = {"ycbcr444": 0, "ycbcr422": 1, "ycbcr420": 2, "ycbcr440": 3}      # image.YCbCrSubsampleRatio, as scaler_cases has it
-FULL_KINDS = ["rgba", "nrgba", "gray", "ycbcr420", "ycbcr444"]      # every layout; the others: three each (kind_layouts)
+RATIO = {"ycbcr444": 0, "ycbcr422": 1, "ycbcr420": 2, "ycbcr440": 3, "ycbcr411": 5, "ycbcr410": 6}      # include/ipx.h's IPX_YCBCR_*, as scaler_cases has it
+FULL_KINDS = ["rgba", "nrgba", "gray", "ycbcr420", "ycbcr444", "ycbcr411"]      # every layout; the others: three to five each (kind_layouts)
 COL = (255, 255, 255, 127)
 
 
@@ -100,6 +100,8 @@ def kind_layouts(kind):
         if kind.startswith("ycbcr"):
             out += [(TIGHT, c) for c in CHROMA_LAYOUTS]
         return out
+    if kind == "ycbcr410":                         # tight, padded, chroma at an odd pointer, at odd strides (all inside its gate), Y off its gate
+        return [(TIGHT, None), (MOST_PADDED, None), (TIGHT, (1, 0, 0)), (TIGHT, (0, 1, 1)), ((1, 0, 0), TIGHT)]
     if kind.startswith("ycbcr"):                   # 4:2:2, 4:4:0: tight, padded, chroma off its gate, Y off its gate
         return [(TIGHT, None), (MOST_PADDED, None), (TIGHT, (2, 0, 0)), (TIGHT, (0, 1, 0)), ((1, 0, 0), TIGHT)]
     # Paletted and the deep types are expanded into scratch of the library's own before the scaler sees them: no legal source layout leaves
@@ -134,6 +136,8 @@ def one_pass(kind, shape, layout, chroma, env=None):
     if kind == "gray":
         return True
     ratio = RATIO[kind]
+    if ratio in (5, 6):                            # 4:1:1 and 4:1:0 load one byte of chroma per chunk (`al = hs == 2 ? 0 : ...`): planes of
+        return True                                # (w + 3) // 4 columns and h or (h + 1) // 2 rows pass at any pointer, stride and frame stride
     cw, chh = (w + 1) // 2 if ratio in (1, 2) else w, (h + 1) // 2 if ratio in (2, 3) else h     # image.YCbCr's chroma planes
     coff, ces, cef = layout if chroma is None else chroma
     cstride = cw + ces

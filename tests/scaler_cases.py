@@ -2,15 +2,20 @@
 (tests/scaler_reference.py), for tests/test_scaler_reference.py and tests/test_scaler_reference_gpu.py."""
 import numpy as np
 
+import jpeg_411_model as M411
 import oracle
 import scaler_reference as R
 from oracle import DEEP_CMYK, DEEP_GRAY16, DEEP_NRGBA64, DEEP_RGBA64
 
-KINDS = ["rgba", "nrgba", "gray", "ycbcr444", "ycbcr422", "ycbcr420", "ycbcr440", "paletted-gif", "paletted-trns",
-         "nrgba64", "rgba64", "gray16", "cmyk"]
+KINDS = ["rgba", "nrgba", "gray", "ycbcr444", "ycbcr422", "ycbcr420", "ycbcr440", "ycbcr411", "ycbcr410", "paletted-gif",
+         "paletted-trns", "nrgba64", "rgba64", "gray16", "cmyk"]
 ALPHA_KINDS = ["rgba", "nrgba", "paletted-trns", "nrgba64", "rgba64"]
 DEEP = {"nrgba64": DEEP_NRGBA64, "rgba64": DEEP_RGBA64, "gray16": DEEP_GRAY16, "cmyk": DEEP_CMYK}
-RATIO = {"ycbcr444": 0, "ycbcr422": 1, "ycbcr420": 2, "ycbcr440": 3}
+RATIO = {"ycbcr444": 0, "ycbcr422": 1, "ycbcr420": 2, "ycbcr440": 3, "ycbcr411": M411.RATIO_411, "ycbcr410": M411.RATIO_410}
+# 4:1:1 and 4:1:0 have no routine of their own in the oracle: x/image/draw takes them through At(x, y).RGBA(), the same integer
+# conversion with the chroma sample at (x / 4, y or y / 2) (DESIGN.md section 4.2), so the oracle runs at 4:4:4 on planes whose samples
+# are replicated (jpeg_411_model.upsample).  The float64 reference reads the subsampled planes themselves.
+RATIOS_41X = (M411.RATIO_411, M411.RATIO_410)
 
 # The largest share of ambiguous bytes (exact value within the integer code's error bound of a rounding boundary) a case may
 # have, per source type: about twice the most seen over this suite's cases (outputs of 1000 bytes and more; assert_matches allows
@@ -62,10 +67,14 @@ class Source:
             self.rgba = np.dstack([self.data] * 3 + [np.full_like(self.data, 255)])    # the oracle's only route for Gray
         elif kind.startswith("ycbcr"):
             ratio = RATIO[kind]
-            chh, cw = oracle.chroma_shape(w, h, ratio)
+            chh, cw = M411.chroma_size(ratio, w, h)[::-1] if ratio in RATIOS_41X else oracle.chroma_shape(w, h, ratio)
             self.data = (rng.integers(0, 256, (h, w), dtype=np.uint8), rng.integers(0, 256, (chh, cw), dtype=np.uint8),
                          rng.integers(0, 256, (chh, cw), dtype=np.uint8), ratio)
             self.ref = R.ycbcr(*self.data)
+            self.oracle_data = self.data     # what the oracle's 4:4:4 routine reads in place of a 4:1:x image
+            if ratio in RATIOS_41X:
+                y, cb, cr, _ = self.data
+                self.oracle_data = (y, M411.upsample(cb, ratio, w, h), M411.upsample(cr, ratio, w, h), 0)
         elif kind.startswith("paletted"):
             pal = rng.integers(0, 256, (256, 4), dtype=np.uint8)
             if kind == "paletted-gif":        # opaque color.RGBA entries and a transparent index (the zero colour)
@@ -109,7 +118,7 @@ class Source:
         if k == "gray":
             return oracle.scale_bilinear(self.rgba, dw, dh, sr=sr, op=op, dst=dst)
         if k.startswith("ycbcr"):
-            return oracle.scale_bilinear_ycbcr(*self.data, dw, dh, sr=sr, dst=dst)
+            return oracle.scale_bilinear_ycbcr(*self.oracle_data, dw, dh, sr=sr, dst=dst)
         if k.startswith("paletted"):
             return oracle.scale_bilinear_paletted(self.data[0], self.pal16, dw, dh, sr=sr, op=op, dst=dst)
         return oracle.scale_bilinear_deep(self.data, DEEP[k], dw, dh, sr=sr, op=op, dst=dst)
@@ -124,7 +133,7 @@ class Source:
         if k == "gray":
             return oracle.draw(dst, r, self.rgba, sp, op)
         if k.startswith("ycbcr"):
-            return oracle.draw_ycbcr(dst, r, *self.data, sp)
+            return oracle.draw_ycbcr(dst, r, *self.oracle_data, sp)
         if k.startswith("paletted"):
             return oracle.draw_paletted(dst, r, self.data[0], self.pal16, sp, op)
         return oracle.draw_deep(dst, r, self.data, DEEP[k], sp, op)

@@ -91,6 +91,7 @@ def gray(g):
 
 
 RATIO_444, RATIO_422, RATIO_420, RATIO_440 = 0, 1, 2, 3
+RATIO_411, RATIO_410 = 5, 6                    # include/ipx.h's numbers (4 is Gray there; Go's own values differ)
 
 
 def ycbcr_real(y, cb, cr, ratio, x0=0, y0=0):
@@ -98,8 +99,8 @@ def ycbcr_real(y, cb, cr, ratio, x0=0, y0=0):
     the sample at (x >> hs, y >> vs) of the ABSOLUTE coordinate.  Unclamped, (h, w, 3)."""
     y = np.asarray(y, np.float64)
     h, w = y.shape
-    hs = 1 if ratio in (RATIO_422, RATIO_420) else 0
-    vs = 1 if ratio in (RATIO_420, RATIO_440) else 0
+    hs = 2 if ratio in (RATIO_411, RATIO_410) else 1 if ratio in (RATIO_422, RATIO_420) else 0
+    vs = 1 if ratio in (RATIO_420, RATIO_440, RATIO_410) else 0
     ys, xs = np.arange(y0, h)[:, None], np.arange(x0, w)[None, :]
     cbp = np.asarray(cb, np.float64)[ys >> vs, xs >> hs] - 128.0
     crp = np.asarray(cr, np.float64)[ys >> vs, xs >> hs] - 128.0

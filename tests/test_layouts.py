@@ -89,7 +89,7 @@ def test_the_path_table_is_consistent():
         assert L.one_pass(kind, s0, L.TIGHT, None) and L.one_pass(kind, s0, L.MOST_PADDED, None, {"IPX_KS_FAST": "0"})
         ragged_ok = kind in ("rgba", "nrgba") or kind.startswith("paletted")
         assert L.one_pass(kind, s1, L.TIGHT, None) == ragged_ok
-    for kind in ("rgba", "nrgba", "gray", "ycbcr420", "ycbcr444"):
+    for kind in ("rgba", "nrgba", "gray", "ycbcr420", "ycbcr444", "ycbcr411", "ycbcr410"):
         for l in L.DWORD_LAYOUTS:
             assert L.one_pass(kind, s0, l, None)
         for l in L.UNALIGNED_LAYOUTS:
@@ -97,6 +97,10 @@ def test_the_path_table_is_consistent():
     for c in L.CHROMA_LAYOUTS:
         assert L.one_pass("ycbcr420", s0, L.TIGHT, c) == L.one_pass("ycbcr422", s0, L.TIGHT, c) == all(v % 2 == 0 for v in c)
         assert not L.one_pass("ycbcr444", s0, L.TIGHT, c) and not L.one_pass("ycbcr440", s0, L.TIGHT, c)
+        assert L.one_pass("ycbcr411", s0, L.TIGHT, c) and L.one_pass("ycbcr410", s0, L.TIGHT, c)       # byte loads: no chroma layout leaves
+        assert not L.one_pass("ycbcr411", s0, (1, 0, 0), c) and not L.one_pass("ycbcr411", s1, L.TIGHT, c)
+    assert sum(any(v % 2 for v in c) for _, c in L.kind_layouts("ycbcr410") if c) == 2      # an odd pointer, odd strides
+    assert sum(not L.one_pass("ycbcr410", s0, l, c) for l, c in L.kind_layouts("ycbcr410")) == 1
 
 
 @pytest.mark.parametrize("kind", KINDS)

@@ -1,9 +1,12 @@
-"""GPU: the kernels against the float64 reference of tests/scaler_reference.py, at the edge geometries and for every source type.
+"""GPU: the kernels against the float64 reference of tests/scaler_reference.py, at the edge geometries: the batch plans for every
+kind of scaler_cases.KINDS (RGBA, NRGBA, Gray, YCbCr at 4:4:4, 4:2:2, 4:2:0, 4:4:0, 4:1:1 and 4:1:0, both palettes, the four deep
+types), the per-operation seam for the kinds that have entries there (SEAM_KINDS: all but Gray and the palettes).
 
 Two conditions per byte: it equals the reference wherever the reference is clear of a rounding boundary, and it equals the oracle
 everywhere -- where the exact value is ambiguous, Go's order of operations decides, and the oracle restates that order.  The
 per-operation seam (Context.scale_bilinear*, Context.draw*) and the batch plans (run_host*: resize, thumbnail, a watermark copy
-without text) run under the kernel-path switches the rest of the suite enumerates."""
+without text) run under the kernel-path switches the rest of the suite enumerates.  For 4:1:1 and 4:1:0 the oracle's bytes are those
+of its 4:4:4 routine on replicated chroma samples (scaler_cases.Source); the reference reads the subsampled planes."""
 import os
 
 import numpy as np
@@ -22,7 +25,7 @@ SOURCE_PATHS = [{"IPX_FUSED": "1"}, {"IPX_FUSED": "0"},
                 {"IPX_FUSED": "1", "IPX_KS_FAST": "0"}, {"IPX_FUSED": "1", "IPX_KS_FIX_CAP": "9"}]
 ALL_PATHS = PATH_ENVS + [e for e in SOURCE_PATHS if e not in PATH_ENVS]
 SEAM_PATHS = [{}, {"IPX_KS_FAST": "0"}, {"IPX_FUSED": "0"}]
-SEAM_KINDS = ["rgba", "nrgba", "ycbcr444", "ycbcr422", "ycbcr420", "ycbcr440", "nrgba64", "rgba64", "gray16", "cmyk"]
+SEAM_KINDS = ["rgba", "nrgba", "ycbcr444", "ycbcr422", "ycbcr420", "ycbcr440", "ycbcr411", "ycbcr410", "nrgba64", "rgba64", "gray16", "cmyk"]
 KNOBS = sorted({k for e in ALL_PATHS + SEAM_PATHS for k in e})
 
 # (w, h, resize, thumbnail) for the batch plans

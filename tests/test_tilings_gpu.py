@@ -1,4 +1,5 @@
-"""GPU: the one-pass scaler at the tilings ks_fused_plan picks BY ITSELF for wide frames, for every source type.
+"""GPU: the one-pass scaler at the tilings ks_fused_plan picks BY ITSELF for wide frames, for every kind of
+scaler_cases.KINDS: every source type the one-pass kernel is instantiated for, YCbCr at 4:1:1 and 4:1:0 (KS_YCC4, 8-byte tiles) included.
 
 No tiling knob is set.  Each case of tests/tiling_cases.py claims a class per tile size -- strips, accumulators, one or two tile
 buffers in either LDS layout, the float pass's list entries per wave, lanes per column -- and the library's IPX_KS_DEBUG line has to
