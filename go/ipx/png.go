@@ -74,3 +74,15 @@ func (p *Plan) RunPNGPNG(files [][]byte) (*Streams, error) {
 	}
 	return s, nil
 }
+
+// PNGDecodeCounts: since the Context was made, under IPX_PNG_PAR=1 in the environment -- [0] the files that entered the parallel inflate,
+// [1] the files it finished itself, [2] the files its redo bit handed to the serial decoder, [3] the tokens decoded by the parallel
+// lanes and [4] those decoded by the wave-uniform loop inside that kernel (both over the files of [1]).  All 0 while the switch is unset.
+func (x *Context) PNGDecodeCounts() (counts [5]int64, err error) {
+	var c [5]C.longlong
+	err = call(func() C.int { return C.ipx_png_decode_counts(x.c, &c[0]) })
+	for i := range c {
+		counts[i] = int64(c[i])
+	}
+	return counts, err
+}

@@ -788,6 +788,14 @@ class Context:
         _check(lib().ipx_jpeg_decode_counts(self.handle, counts))
         return list(counts)
 
+    def png_decode_counts(self):
+        """Since the context was made, under IPX_PNG_PAR=1: [0] files that entered the parallel inflate, [1] files it finished, [2] files
+        its redo bit handed to the serial decoder, [3] tokens decoded by the parallel lanes, [4] tokens decoded by the wave-uniform
+        loop inside that kernel ([3], [4]: files of [1] only).  All 0 while the switch is unset."""
+        counts = (C.c_longlong * 5)()
+        _check(lib().ipx_png_decode_counts(self.handle, counts))
+        return list(counts)
+
     def jpeg_decode_batch_cmyk(self, files, w=0, h=0, download=True):
         """image.Decode of a batch of four-component JPEG byte strings (Adobe CMYK / YCCK) on the GPU, under IPX_JPEG_CMYK=1.
         -> (info, status list); info = dict(w, h, stride, pix) with pix as an n x h x w x 4 uint8 array of *image.CMYK pixels
@@ -947,6 +955,15 @@ class Pool:
 
     def frames_done(self, slot):
         return lib().ipx_pool_frames_done(self.handle, slot)
+
+    def png_decode_counts(self):
+        """Context.png_decode_counts summed over the pool's slots (IPX_JOB_PNG and the micro-batcher decode on the slots' contexts)"""
+        total = [0] * 5
+        for slot in range(self.slots()):
+            counts = (C.c_longlong * 5)()
+            _check(lib().ipx_pool_png_decode_counts(self.handle, slot, counts))
+            total = [a + b for a, b in zip(total, counts)]
+        return total
 
     def host_alloc(self, slot, shape, dtype=np.uint8):
         n = int(np.prod(shape)) * np.dtype(dtype).itemsize

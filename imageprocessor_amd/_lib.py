@@ -219,6 +219,7 @@ SIGNATURES = {
     "ipx_jpeg_planes_free": (None, [_P, _P]),
     "ipx_jpeg_scan_route": (_I, [_P, _Z, C.POINTER(_I)]),
     "ipx_jpeg_decode_counts": (_I, [_P, C.POINTER(C.c_longlong)]),
+    "ipx_png_decode_counts": (_I, [_P, C.POINTER(C.c_longlong)]),
     "ipx_jpeg_decode_batch_cmyk": (_I, [_P, _P, C.POINTER(Bytes), _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(CmykBatch), C.POINTER(_I),
                                         C.POINTER(_P)]),
     "ipx_jpeg_cmyk_files": (_I, [_P, C.POINTER(C.c_longlong)]),
@@ -266,6 +267,7 @@ SIGNATURES = {
     "ipx_pool_destroy": (None, [_P]),
     "ipx_pool_slots": (_I, [_P]),
     "ipx_pool_frames_done": (C.c_longlong, [_P, _I]),
+    "ipx_pool_png_decode_counts": (_I, [_P, _I, C.POINTER(C.c_longlong)]),
     "ipx_pool_host_alloc": (_P, [_P, _I, _Z]),
     "ipx_pool_host_free": (_I, [_P, _I, _P]),
     "ipx_job_submit": (_I, [_P, C.POINTER(Job), C.POINTER(C.c_uint64)]),

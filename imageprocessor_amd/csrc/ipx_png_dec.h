@@ -83,6 +83,17 @@ hipError_t launch_png_crc(const uint8_t *blob, const PngCrcPiece *pieces, int np
 hipError_t launch_png_crc_check(const uint8_t *blob, const PngChunk *chunks, int nchunks, const uint32_t *acc, uint32_t *status,
                                 hipStream_t s);
 hipError_t launch_png_inflate(const uint8_t *zlib, const PngDecDesc *desc, int n, uint8_t *raw, uint32_t *status, hipStream_t s);
+// under IPX_PNG_PAR=1: the parallel inflate (ipx_png_dec_par.hip) and, behind it, the serial one for the files whose redo bit it set.
+// par: the launch's word pairs (below), zero before; sub: the sub-sequence size in bits, kPngParSubMin .. kPngParSubMax.
+// The per-file word pair of a launch under IPX_PNG_PAR=1 (par + 2 * slot): word 0 the tokens the parallel lanes decoded, word 1 those
+// of the wave-uniform loop inside the parallel kernel; bit 31 of word 1 is the redo bit (the parallel kernel left the file: the serial
+// launch behind it decodes it from scratch, and the two counts are 0).
+constexpr uint32_t kPngParRedo = 0x80000000u;
+constexpr int kPngParSub = 256, kPngParSubMin = 48, kPngParSubMax = 1000;
+hipError_t launch_png_inflate_par(const uint8_t *zlib, const PngDecDesc *desc, int n, uint8_t *raw, const uint32_t *status, uint32_t *par,
+                                  uint32_t sub, hipStream_t s);
+hipError_t launch_png_inflate_redo(const uint8_t *zlib, const PngDecDesc *desc, int n, uint8_t *raw, uint32_t *status, const uint32_t *par,
+                                   hipStream_t s);
 hipError_t launch_png_unfilter(const PngDecDesc *desc, int n, uint8_t *raw, uint8_t *frames, uint32_t *status, hipStream_t s);
 hipError_t launch_png_unfilter_adam7(const PngDecDesc *desc, int n, uint8_t *raw, uint8_t *frames, uint32_t *status, hipStream_t s);
 

@@ -647,9 +647,15 @@ static int png_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
     if (n == 0) return IPX_OK;
     PinnedBlocks pinned(ctx, s);
     AsyncFree mem{s, {}};
+    // IPX_PNG_PAR=1 in the environment, read on every call: the inflate is png_inflate_par_kernel with the serial decoder behind it for
+    // the files it leaves; anything else keeps the serial kernel alone.  IPX_PNG_PAR_SUB: its sub-sequence size in bits (tests).
+    const bool par = env_int("IPX_PNG_PAR", 0) == 1;
+    const uint32_t par_sub = (uint32_t)std::min(kPngParSubMax, std::max(kPngParSubMin, env_int("IPX_PNG_PAR_SUB", kPngParSub)));
+    const size_t words = par ? (size_t)n * 3 : (size_t)n;        // the status words, then the parallel kernel's word pairs
     uint32_t *dstate;
-    IPX_HIP(mem.get(&dstate, (size_t)n * 4));
-    IPX_HIP(hipMemsetAsync(dstate, 0, (size_t)n * 4, s));
+    IPX_HIP(mem.get(&dstate, words * 4));
+    IPX_HIP(hipMemsetAsync(dstate, 0, words * 4, s));
+    uint32_t *dpar = dstate + n;
     if (palettes) {     // one upload of every slot up to the last (zero for slots not decoded here)
         const int nslot = *std::max_element(slot.begin(), slot.end()) + 1;
         uint8_t *hpal = pinned.get((size_t)nslot * 1024);
@@ -743,7 +749,12 @@ static int png_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
         IPX_HIP(hipMemsetAsync(dacc, 0, chunks.size() * 4, s));
         IPX_HIP(launch_png_crc(dblob, dpieces, (int)pieces.size(), dacc, dz, s));
         IPX_HIP(launch_png_crc_check(dblob, dchunks, (int)chunks.size(), dacc, dstate, s));
-        IPX_HIP(launch_png_inflate(dz, ddesc, m, draw, dstate, s));
+        if (par) {
+            IPX_HIP(launch_png_inflate_par(dz, ddesc, m, draw, dstate, dpar, par_sub, s));
+            IPX_HIP(launch_png_inflate_redo(dz, ddesc, m, draw, dstate, dpar, s));
+        } else {
+            IPX_HIP(launch_png_inflate(dz, ddesc, m, draw, dstate, s));
+        }
         IPX_HIP(launch_png_unfilter(ddesc, m0, draw, frames, dstate, s));
         IPX_HIP(launch_png_unfilter_adam7(ddesc + m0, m - m0, draw, frames, dstate, s));
         // the host vectors must outlive the copies: wait before they go
@@ -754,9 +765,20 @@ static int png_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
     std::iota(all.begin(), all.end(), 0);
     const int rc = for_groups_under(all, budget, [&](int g) { return png_group_bytes(info[idx[g]]); }, run_group);
     if (rc) return rc;
-    std::vector<uint32_t> st(n);
-    IPX_HIP(hipMemcpyAsync(st.data(), dstate, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    std::vector<uint32_t> st(words);
+    IPX_HIP(hipMemcpyAsync(st.data(), dstate, words * 4, hipMemcpyDeviceToHost, s));
     IPX_HIP(hipStreamSynchronize(s));
+    if (par) {                                                   // ipx_png_decode_counts
+        long long c[5] = {n, 0, 0, 0, 0};
+        for (int g = 0; g < n; g++) {
+            const uint32_t a = st[n + 2 * g], b = st[n + 2 * g + 1];
+            if (b & kPngParRedo) { c[2]++; continue; }
+            c[1]++;
+            c[3] += a;
+            c[4] += b;
+        }
+        for (int k = 0; k < 5; k++) ctx->png_counts[k] += c[k];
+    }
     for (int g = 0; g < n; g++) {
         const uint32_t v = st[g];
         status[idx[g]] = v == 0 ? IPX_OK : (v & ~kPngTrailing) ? IPX_ERR_INVALID : IPX_ERR_UNSUPPORTED;
@@ -766,6 +788,14 @@ static int png_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
 
 // ---- the entries -----------------------------------------------------------------------------------------------------------------
 extern "C" {
+
+int ipx_png_decode_counts(ipx_ctx *ctx, long long counts[5])
+{
+    clear_error();
+    if (!ctx || !counts) { set_error("ipx_png_decode_counts: bad argument"); return IPX_ERR_INVALID; }
+    for (int k = 0; k < 5; k++) counts[k] = ctx->png_counts[k].load();
+    return IPX_OK;
+}
 
 void ipx_png_frames_free(ipx_ctx *ctx, ipx_png_frames *o) { dev_blocks_free(ctx, o); }
 

@@ -347,6 +347,12 @@ long long ipx_pool_frames_done(const ipx_pool *pool, int slot)
     return pool && slot >= 0 && slot < (int)pool->slots.size() ? pool->core.units_done(slot) : -1;
 }
 
+int ipx_pool_png_decode_counts(const ipx_pool *pool, int slot, long long counts[5])
+{
+    if (!pool || slot < 0 || slot >= (int)pool->slots.size()) return IPX_ERR_INVALID;
+    return ipx_png_decode_counts(pool->slots[slot]->ctx, counts);
+}
+
 void *ipx_pool_host_alloc(ipx_pool *pool, int slot, size_t bytes) try
 {
     clear_error();

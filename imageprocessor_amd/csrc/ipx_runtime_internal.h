@@ -69,6 +69,8 @@ struct ipx_ctx {
     std::map<std::pair<int, int>, std::pair<uint8_t *, KsAxisDev>> ks_axes;
     // ipx_jpeg_decode_counts: files decoded by route (IPX_JPEG_ROUTE_*) since ipx_create; [3]: files the GPU scan walk ended with a status
     std::atomic<long long> jpeg_counts[4] = {{0}, {0}, {0}, {0}};
+    // ipx_png_decode_counts: files and tokens of the parallel inflate (IPX_PNG_PAR=1) since ipx_create
+    std::atomic<long long> png_counts[5] = {{0}, {0}, {0}, {0}, {0}};
     std::atomic<long long> jpeg_cmyk_files{0};     // ipx_jpeg_cmyk_files: files that reached the four-component decoder (ipx_jpeg_dec_cmyk.hip)
     static constexpr size_t kFlatChromaBytes = (size_t)64 << 10;
 };

@@ -678,6 +678,17 @@ typedef struct ipx_png_frames ipx_png_frames;
 int ipx_png_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *files, int n, int *w, int *h, int *kind, ipx_png_batch *frames,
                          int *status, ipx_png_frames **owner);
 void ipx_png_frames_free(ipx_ctx *ctx, ipx_png_frames *owner);
+/* The parallel inflate, with IPX_PNG_PAR=1 in the environment (read on every call that decodes PNG files; unset or anything else: the
+ * serial inflate alone, as before).  In every entry that decodes PNG files -- this one, ipx_plan_run_png_png and its _texts twin, the
+ * pool's IPX_JOB_PNG, the micro-batcher -- a Huffman block's body is then parsed by the 64 lanes of the file's wave side by side
+ * (speculative starts at sub-sequence boundaries, rounds until the lanes fall into step).  That kernel decides
+ * no error: a stream that breaks any rule, fails its Adler-32 or has bytes behind it is handed, by a per-file redo bit and without a host
+ * round trip, to the serial decoder, so frames, palettes and statuses are byte for byte those without the switch.
+ * ipx_png_decode_counts, since ipx_create: [0] files that entered the parallel kernel, [1] files it finished itself, [2] files handed
+ * to the serial decoder by the redo bit ([0] = [1] + [2]), [3] tokens (literals, matches and end-of-block symbols, one each) decoded by
+ * the parallel lanes and [4] tokens decoded by the wave-uniform loop inside that kernel (a sub-sequence whose output alone exceeds one
+ * 16 KiB flush unit), both over the files of [1] only.  All five stay 0 while the switch is unset. */
+int ipx_png_decode_counts(ipx_ctx *ctx, long long counts[5]);
 /* The PNG task compressed in, compressed out: the uploads as the object store returns them, png.Decode, every operator of the plan
  * (the plan's frame size is the batch's size) and png.Encode of all three outputs (a PNG watermark stays PNG), all on the GPU; only
  * compressed bytes cross the link.  Files of any kind may be mixed: they are grouped by kind on the host, decoded in large groups
@@ -720,6 +731,8 @@ int ipx_pool_create(const int *devices, int n_devices, const ipx_pool_config *cf
 void ipx_pool_destroy(ipx_pool *pool);                        /* finishes what is queued, frees what was not released */
 int ipx_pool_slots(const ipx_pool *pool);
 long long ipx_pool_frames_done(const ipx_pool *pool, int slot); /* frames (files) slot `slot` has processed so far */
+/* ipx_png_decode_counts of slot `slot`'s own context (the pool's IPX_JOB_PNG and the micro-batcher decode there): since ipx_pool_create */
+int ipx_pool_png_decode_counts(const ipx_pool *pool, int slot, long long counts[5]);
 /* hipHostMalloc'd memory, allocated and first touched on a thread bound to the CPUs next to slot `slot`'s GPU (sysfs local_cpulist):
  * staging on the GPU's NUMA node.  Free with ipx_pool_host_free. */
 void *ipx_pool_host_alloc(ipx_pool *pool, int slot, size_t bytes);

@@ -11,6 +11,9 @@ corpora written by Pillow at its defaults (photo-like RGB, photo-like RGBA, flat
   python tools/bench_png_decode.py --quick       # 200x200 only, batches 1 and 64
   python tools/bench_png_decode.py --adam7       # the same corpora as Adam7 files (IPX_PNG_ADAM7=1 is set for the run): each file's
                                                  # samples re-wrapped by tests/png_adam7_corpus.py (Paeth rows, zlib level 6)
+  python tools/bench_png_decode.py --par         # the parallel inflate (IPX_PNG_PAR=1 is set for the run); each row then carries the
+                                                 # rise of ipx_png_decode_counts over its decode-only calls
+  --shapes 1024x768 --corpora rgb,rgba --decode-only     # narrow a run: these sizes, these corpora, no PNG-to-PNG or host leg
 
 Files: 16 distinct seeded files per corpus, repeated through the batch."""
 import argparse
@@ -83,9 +86,15 @@ def main():
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--adam7", action="store_true")
+    ap.add_argument("--par", action="store_true")
+    ap.add_argument("--shapes", default="")
+    ap.add_argument("--corpora", default="")
+    ap.add_argument("--decode-only", action="store_true")
     a = ap.parse_args()
     if a.adam7:
         os.environ["IPX_PNG_ADAM7"] = "1"
+    if a.par:
+        os.environ["IPX_PNG_PAR"] = "1"
     import imageprocessor_amd as ipx
     import png_decode_model as dm
     if ipx.device_count() < 1:
@@ -93,6 +102,10 @@ def main():
     shapes = [(200, 200)] if a.quick else [(200, 200), (1024, 768)]
     batches = [1, 64] if a.quick else [1, 64, 1024]
     corpora = ["rgb", "rgba", "palette", "own"]
+    if a.shapes:
+        shapes = [tuple(int(v) for v in s.split("x")) for s in a.shapes.split(",")]
+    if a.corpora:
+        corpora = a.corpora.split(",")
     if a.profile:
         shapes, batches, a.reps, corpora = [(1024, 768)], [64], 1, ["rgb"]
     pool = cf.ThreadPoolExecutor(16)
@@ -122,12 +135,14 @@ def main():
                         info["free"]()
                         assert st.count(0) == n, st[:8]
 
+                    before = ctx.png_decode_counts()
                     td = timed(decode_only, a.reps)
-                    row = {"bench": "png_decode", "adam7": a.adam7, "corpus": corpus, "kind": kind, "w": w, "h": h, "batch": n,
+                    row = {"bench": "png_decode", "adam7": a.adam7, "par": a.par,
+                           "par_counts_rose": [x - y for x, y in zip(ctx.png_decode_counts(), before)], "corpus": corpus, "kind": kind, "w": w, "h": h, "batch": n,
                            "bytes_per_file": sum(len(f) for f in distinct) // len(distinct),
                            "decode_ms": round(td * 1e3, 3), "decode_files_per_s": round(n / td, 1),
                            "pillow_one_thread_decode_ms_per_file_not_go": round(pil_one * 1e3, 3)}
-                    if n == max(batches):
+                    if n == max(batches) and not a.decode_only:
                         t16 = timed(lambda: list(pool.map(pillow_decode, files)), 1)
                         row["pillow_16_threads_files_per_s_not_go"] = round(n / t16, 1)
 
