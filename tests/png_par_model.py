@@ -11,7 +11,8 @@ inflater: its tables (canonical, go_huffman_ok), its header rules and its errors
 
   Result: redo (the kernel would leave the file: any rule of Go's reader broken, the Adler-32, bytes behind it), data (the bytes),
   tokens [Tok] in stream order (literals, matches and end-of-block symbols), lane_tokens / uniform_tokens (how many of them the lanes
-  and the uniform loop decoded), blocks [(kind, first token bit or None)] and windows [Window].
+  and the uniform loop decoded), blocks [(kind, first token bit or None)], windows [Window] and stored [(block, first output byte,
+  bytes)], the stored blocks.
 
 The token at a bit position does not depend on `sub`, so a Model keeps what it decoded across run() calls."""
 import struct
@@ -65,6 +66,7 @@ class Result:
     uniform_tokens: int = 0
     blocks: list = field(default_factory=list)
     windows: list = field(default_factory=list)
+    stored: list = field(default_factory=list)      # (block, first output byte, bytes) of every stored block
 
 
 class _Code:
@@ -241,6 +243,7 @@ class Model:
             final, kind, codes, stored = self._head(br)
             if kind == "stored":
                 res.blocks.append((kind, None))
+                res.stored.append((b, len(out), len(stored)))
                 out += stored
                 if self.limit is not None and len(out) > self.limit:
                     raise _Redo("too much pixel data")
