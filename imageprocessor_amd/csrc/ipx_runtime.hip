@@ -1414,7 +1414,8 @@ static int run_dev_any(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, int n, c
         bool matched = false, text_done = false;
         hipError_t e = launch_ks_fused(fp, a, fix, txt, ctx->cus, s, &matched, &text_done);
         if (fix && matched && e == hipSuccess && env_int("IPX_KS_STATS", 0)) {   // diagnostic: how full the float pass's lists got, how many items went to float64
-            std::vector<int> cnt((size_t)n * 2), flags((size_t)max_items);
+            // (only the items of the segmentation that ran have a flag: the block holds max_items of them and is not cleared)
+            std::vector<int> cnt((size_t)n * 2), flags((size_t)n * a.nstrips * a.nseg);
             (void)hipMemcpyAsync(cnt.data(), fixv.count, cnt.size() * sizeof(int), hipMemcpyDeviceToHost, s);
             (void)hipMemcpyAsync(flags.data(), redo, flags.size() * sizeof(int), hipMemcpyDeviceToHost, s);
             (void)hipStreamSynchronize(s);
@@ -1422,7 +1423,7 @@ static int run_dev_any(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, int n, c
             for (int i = 0; i < n; i++) for (int k = 0; k < 2; k++) { tot[k] += cnt[2 * i + k]; mx[k] = std::max(mx[k], cnt[2 * i + k]); }
             for (int f : flags) nredo += f != 0;
             fprintf(stderr, "[ipx ks stats] %d frames: undecided pixels per frame resize mean %.1f max %d (room %d), thumbnail mean %.1f max %d (room %d); %d of %d items redone in float64\n", n,
-                    (double)tot[0] / n, mx[0], fixv.cap[0], (double)tot[1] / n, mx[1], fixv.cap[1], nredo, max_items);
+                    (double)tot[0] / n, mx[0], fixv.cap[0], (double)tot[1] / n, mx[1], fixv.cap[1], nredo, (int)flags.size());
         }
 #if IPX_DIAG
         if (a.stamps && matched) {
