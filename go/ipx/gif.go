@@ -95,3 +95,15 @@ func (p *Plan) RunGIFGIF(files [][]byte, quality int) (*Streams, error) {
 	}
 	return s, nil
 }
+
+// GIFDecodeCounts: since the Context was made, under IPX_GIF_PAR=1 in the environment -- [0] the files that entered the parallel code
+// walk, [1] the files it finished itself, [2] the files its redo bit handed to the serial walk, [3] the code records written by the
+// parallel lanes (over the files of [1]).  All 0 while the switch is unset.
+func (x *Context) GIFDecodeCounts() (counts [4]int64, err error) {
+	var c [4]C.longlong
+	err = call(func() C.int { return C.ipx_gif_decode_counts(x.c, &c[0]) })
+	for i := range c {
+		counts[i] = int64(c[i])
+	}
+	return counts, err
+}

@@ -796,6 +796,14 @@ class Context:
         _check(lib().ipx_png_decode_counts(self.handle, counts))
         return list(counts)
 
+    def gif_decode_counts(self):
+        """Since the context was made, under IPX_GIF_PAR=1: [0] files that entered the parallel code walk, [1] files it finished, [2]
+        files its redo bit handed to the serial walk, [3] code records written by the parallel lanes (files of [1] only).  All 0
+        while the switch is unset."""
+        counts = (C.c_longlong * 4)()
+        _check(lib().ipx_gif_decode_counts(self.handle, counts))
+        return list(counts)
+
     def jpeg_decode_batch_cmyk(self, files, w=0, h=0, download=True):
         """image.Decode of a batch of four-component JPEG byte strings (Adobe CMYK / YCCK) on the GPU, under IPX_JPEG_CMYK=1.
         -> (info, status list); info = dict(w, h, stride, pix) with pix as an n x h x w x 4 uint8 array of *image.CMYK pixels
@@ -962,6 +970,15 @@ class Pool:
         for slot in range(self.slots()):
             counts = (C.c_longlong * 5)()
             _check(lib().ipx_pool_png_decode_counts(self.handle, slot, counts))
+            total = [a + b for a, b in zip(total, counts)]
+        return total
+
+    def gif_decode_counts(self):
+        """Context.gif_decode_counts summed over the pool's slots (IPX_JOB_GIF and the micro-batcher decode on the slots' contexts)"""
+        total = [0] * 4
+        for slot in range(self.slots()):
+            counts = (C.c_longlong * 4)()
+            _check(lib().ipx_pool_gif_decode_counts(self.handle, slot, counts))
             total = [a + b for a, b in zip(total, counts)]
         return total
 

@@ -240,6 +240,7 @@ SIGNATURES = {
     "ipx_gif_decode_batch": (_I, [_P, _P, C.POINTER(Bytes), _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(PalettedBatch), C.POINTER(_I),
                                   C.POINTER(_P)]),
     "ipx_gif_frames_free": (None, [_P, _P]),
+    "ipx_gif_decode_counts": (_I, [_P, C.POINTER(C.c_longlong)]),
     "ipx_plan_run_gif_gif": (_I, [_P, _P, _I, C.POINTER(Bytes), _I, C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(_I),
                                   C.POINTER(_P)]),
     "ipx_png_decode_batch": (_I, [_P, _P, C.POINTER(Bytes), _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(PngBatch),
@@ -268,6 +269,7 @@ SIGNATURES = {
     "ipx_pool_slots": (_I, [_P]),
     "ipx_pool_frames_done": (C.c_longlong, [_P, _I]),
     "ipx_pool_png_decode_counts": (_I, [_P, _I, C.POINTER(C.c_longlong)]),
+    "ipx_pool_gif_decode_counts": (_I, [_P, _I, C.POINTER(C.c_longlong)]),
     "ipx_pool_host_alloc": (_P, [_P, _I, _Z]),
     "ipx_pool_host_free": (_I, [_P, _I, _P]),
     "ipx_job_submit": (_I, [_P, C.POINTER(Job), C.POINTER(C.c_uint64)]),

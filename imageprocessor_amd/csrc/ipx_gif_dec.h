@@ -53,10 +53,15 @@ struct GifDecDesc {              // one file of a launch
 // packed: value (12 bits) | the previous code's value in the segment (12 bits) << 12 | the first byte of its string << 24.
 struct GifCode { uint32_t off, segb, packed; };
 // per file, after the walk: [0] status (0: decoded, 1: Go's reader fails on the image data, 2: the code scratch was too small --
-// cannot happen with gif_code_cap), [1] records written
-constexpr int kGifStateWords = 2;
+// cannot happen with gif_code_cap), [1] records written; under IPX_GIF_PAR=1 also [2] the redo word (gif_walk_par_kernel left the file
+// to the serial walk) and [3] the records the parallel lanes wrote (0 for a file it left)
+constexpr int kGifStateWords = 4;
 
-hipError_t launch_gif_walk(const uint8_t *blob, const GifDecDesc *desc, int n, GifCode *codes, uint32_t *state, hipStream_t s);
+// redo: nullptr, or the files' redo words (redo[kGifStateWords * slot]): then only the files whose word is set are walked
+hipError_t launch_gif_walk(const uint8_t *blob, const GifDecDesc *desc, int n, GifCode *codes, uint32_t *state, const uint32_t *redo,
+                           hipStream_t s);
+// under IPX_GIF_PAR=1 (ipx_gif_dec_par.hip): the 64 lanes of a file's wave read its codes side by side; writes all four state words
+hipError_t launch_gif_walk_par(const uint8_t *blob, const GifDecDesc *desc, int n, GifCode *codes, uint32_t *state, hipStream_t s);
 // blocks_per_file: workgroups of 256 lanes striding over a file's records
 hipError_t launch_gif_expand(const GifDecDesc *desc, int n, const GifCode *codes, const uint32_t *state, uint8_t *frames,
                              size_t frame_stride, int blocks_per_file, hipStream_t s);

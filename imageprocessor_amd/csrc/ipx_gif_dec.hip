@@ -2,7 +2,8 @@
 // the ABI entries built on it.  Kernels: the code walk (one lane per file reads the codes, keeps the live dictionary's lengths and
 // first bytes in LDS and checks every rule of the reader, O(1) work per code) and the expansion (every lane of a grid takes one code and
 // writes its string backwards along the entry -> code-ordinal map of its segment, straight into the de-interlaced row).  Host half:
-// ipx_gif_dec_host.cpp.  DESIGN.md section 4.8 has the restatement and the numbers.
+// ipx_gif_dec_host.cpp.  Under IPX_GIF_PAR=1 the walk is gif_walk_par_kernel (ipx_gif_dec_par.hip: all 64 lanes read codes) with the walk
+// of this file behind it for the files it leaves.  DESIGN.md section 4.8 has the restatement and the numbers.
 #include <vector>
 
 #include "ipx_gif_dec.h"
@@ -18,10 +19,13 @@ namespace ipx {
 // set of literal codes read: Go's per-pixel "invalid pixel value" check and this per-code one fail on the same files).  At the EOF code,
 // blockReader.close's rule: the code's last byte lies in the last sub-block, or the data ended exactly on a sub-block boundary and one
 // sub-block of one byte follows; either way a block terminator comes next.  Records are bounded by the host's code_cap.
+// redo (under IPX_GIF_PAR=1, behind gif_walk_par_kernel): the files' redo words, redo[kGifStateWords * slot]; only the files whose word
+// is set are walked, from scratch.  nullptr: every file.
 constexpr int kWalkChunk = 4096;
 
 __global__ __launch_bounds__(64) void gif_walk_kernel(const uint8_t *__restrict__ blob, const GifDecDesc *__restrict__ desc,
-                                                      GifCode *__restrict__ codes, uint32_t *__restrict__ state)
+                                                      GifCode *__restrict__ codes, uint32_t *__restrict__ state,
+                                                      const uint32_t *__restrict__ redo)
 {
     __shared__ uint16_t s_len[4096];
     __shared__ uint8_t s_first[4096];
@@ -30,6 +34,7 @@ __global__ __launch_bounds__(64) void gif_walk_kernel(const uint8_t *__restrict_
     __shared__ int s_done;
     const int lane = threadIdx.x;
     const GifDecDesc d = desc[blockIdx.x];
+    if (redo && redo[kGifStateWords * d.slot] == 0) return;
     const uint8_t *src = blob + d.data_off;
     GifCode *rec = codes + d.code_off;
     const uint32_t clear = 1u << d.lit, eof = clear + 1, npix = d.w * d.h;
@@ -105,10 +110,11 @@ __global__ __launch_bounds__(64) void gif_walk_kernel(const uint8_t *__restrict_
     }
 }
 
-hipError_t launch_gif_walk(const uint8_t *blob, const GifDecDesc *desc, int n, GifCode *codes, uint32_t *state, hipStream_t s)
+hipError_t launch_gif_walk(const uint8_t *blob, const GifDecDesc *desc, int n, GifCode *codes, uint32_t *state, const uint32_t *redo,
+                           hipStream_t s)
 {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(gif_walk_kernel, dim3(n), dim3(64), 0, s, blob, desc, codes, state);
+    hipLaunchKernelGGL(gif_walk_kernel, dim3(n), dim3(64), 0, s, blob, desc, codes, state, redo);
     return hipGetLastError();
 }
 
@@ -201,6 +207,9 @@ static int gif_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
 {
     PinnedBlocks pinned(ctx, s);
     AsyncFree mem{s, {}};
+    // IPX_GIF_PAR=1 in the environment, read on every call: the walk is gif_walk_par_kernel with the serial walk behind it for the files
+    // it leaves; anything else keeps the serial walk alone
+    const bool par = env_int("IPX_GIF_PAR", 0) == 1;
     uint32_t *dstate;
     IPX_HIP(mem.get(&dstate, (size_t)n * kGifStateWords * 4));
     // palettes: one upload of every slot
@@ -251,7 +260,12 @@ static int gif_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
         IPX_HIP(mem.get(&dcodes, codes * sizeof(GifCode)));
         IPX_HIP(hipMemcpyAsync(dblob, hblob, desc_bytes + data_bytes, hipMemcpyHostToDevice, s));
         const GifDecDesc *ddesc = (const GifDecDesc *)dblob;
-        IPX_HIP(launch_gif_walk(dblob + desc_bytes, ddesc, m, dcodes, dstate, s));
+        if (par) {
+            IPX_HIP(launch_gif_walk_par(dblob + desc_bytes, ddesc, m, dcodes, dstate, s));
+            IPX_HIP(launch_gif_walk(dblob + desc_bytes, ddesc, m, dcodes, dstate, dstate + 2, s));
+        } else {
+            IPX_HIP(launch_gif_walk(dblob + desc_bytes, ddesc, m, dcodes, dstate, nullptr, s));
+        }
         const int bpf = (int)std::max<uint32_t>(1, std::min<uint32_t>((max_cap + 255) / 256, (uint32_t)std::max(1, 16384 / m)));
         IPX_HIP(launch_gif_expand(ddesc, m, dcodes, dstate, frames, frame_stride, bpf, s));
         return IPX_OK;
@@ -263,6 +277,17 @@ static int gif_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
     std::vector<uint32_t> st((size_t)n * kGifStateWords);
     IPX_HIP(hipMemcpyAsync(st.data(), dstate, st.size() * 4, hipMemcpyDeviceToHost, s));
     IPX_HIP(hipStreamSynchronize(s));
+    if (par) {                                                   // ipx_gif_decode_counts
+        long long c[4] = {0, 0, 0, 0};
+        for (int i = 0; i < n; i++) {
+            if (status[i] != IPX_OK) continue;
+            c[0]++;
+            if (st[(size_t)kGifStateWords * i + 2]) { c[2]++; continue; }
+            c[1]++;
+            c[3] += st[(size_t)kGifStateWords * i + 3];
+        }
+        for (int k = 0; k < 4; k++) ctx->gif_counts[k] += c[k];
+    }
     for (int i = 0; i < n; i++) {
         if (status[i] != IPX_OK) continue;
         const uint32_t v = st[(size_t)kGifStateWords * i];
@@ -273,6 +298,14 @@ static int gif_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
 
 // ---- the entries -----------------------------------------------------------------------------------------------------------------
 extern "C" {
+
+int ipx_gif_decode_counts(ipx_ctx *ctx, long long counts[4])
+{
+    clear_error();
+    if (!ctx || !counts) { set_error("ipx_gif_decode_counts: bad argument"); return IPX_ERR_INVALID; }
+    for (int k = 0; k < 4; k++) counts[k] = ctx->gif_counts[k].load();
+    return IPX_OK;
+}
 
 void ipx_gif_frames_free(ipx_ctx *ctx, ipx_gif_frames *o) { dev_blocks_free(ctx, o); }
 

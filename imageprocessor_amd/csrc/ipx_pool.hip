@@ -353,6 +353,12 @@ int ipx_pool_png_decode_counts(const ipx_pool *pool, int slot, long long counts[
     return ipx_png_decode_counts(pool->slots[slot]->ctx, counts);
 }
 
+int ipx_pool_gif_decode_counts(const ipx_pool *pool, int slot, long long counts[4])
+{
+    if (!pool || slot < 0 || slot >= (int)pool->slots.size()) return IPX_ERR_INVALID;
+    return ipx_gif_decode_counts(pool->slots[slot]->ctx, counts);
+}
+
 void *ipx_pool_host_alloc(ipx_pool *pool, int slot, size_t bytes) try
 {
     clear_error();

@@ -71,6 +71,8 @@ struct ipx_ctx {
     std::atomic<long long> jpeg_counts[4] = {{0}, {0}, {0}, {0}};
     // ipx_png_decode_counts: files and tokens of the parallel inflate (IPX_PNG_PAR=1) since ipx_create
     std::atomic<long long> png_counts[5] = {{0}, {0}, {0}, {0}, {0}};
+    // ipx_gif_decode_counts: files and records of the parallel code walk (IPX_GIF_PAR=1) since ipx_create
+    std::atomic<long long> gif_counts[4] = {{0}, {0}, {0}, {0}};
     std::atomic<long long> jpeg_cmyk_files{0};     // ipx_jpeg_cmyk_files: files that reached the four-component decoder (ipx_jpeg_dec_cmyk.hip)
     static constexpr size_t kFlatChromaBytes = (size_t)64 << 10;
 };

@@ -642,6 +642,19 @@ typedef struct ipx_gif_frames ipx_gif_frames;
 int ipx_gif_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *gifs, int n, int *w, int *h, ipx_paletted_batch *frames,
                          int *status, ipx_gif_frames **owner);
 void ipx_gif_frames_free(ipx_ctx *ctx, ipx_gif_frames *owner);
+/* The parallel code walk, with IPX_GIF_PAR=1 in the environment (read on every call that decodes GIF files; unset or anything else: the
+ * serial walk alone, as before).  In every entry that decodes GIF files -- this one, ipx_plan_run_gif_gif and its _texts twin, the
+ * pool's IPX_JOB_GIF, the micro-batcher -- the 64 lanes of the file's wave then read 64 consecutive codes at once: between two clear
+ * codes the code at ordinal t is min(12, bitlen(eof + t)) bits wide whatever the codes' values, so its bit offset is a closed form of t
+ * and the literal width; the strings' lengths follow by pointer jumping, the output offsets by a prefix sum.
+ * That kernel accepts a file only at an EOF code that meets the reader's rules and decides no error: an invalid code or pixel value, a
+ * string past the frame, data that end without an EOF code or an EOF code that comes early or breaks the sub-block rule hand the file,
+ * by a per-file redo bit and without a host round trip, to the serial walk, so frames, palettes and statuses are byte for byte those
+ * without the switch.
+ * ipx_gif_decode_counts, since ipx_create: [0] files that entered the parallel walk, [1] files it finished itself, [2] files handed
+ * to the serial walk by the redo bit ([0] = [1] + [2]), [3] code records written by the parallel lanes, over the files of [1] only.
+ * All four stay 0 while the switch is unset. */
+int ipx_gif_decode_counts(ipx_ctx *ctx, long long counts[4]);
 /* The GIF task compressed in, compressed out: the uploads as the object store returns them, gif.Decode, every operator of the plan
  * (the plan's frame size is the batch's size), gif.Encode of the resize and thumbnail outputs and jpeg.Encode at `quality` of the
  * watermark output (watermark.go:66-79), all on the GPU; only compressed bytes cross the link.  status[i] as for
@@ -733,6 +746,8 @@ int ipx_pool_slots(const ipx_pool *pool);
 long long ipx_pool_frames_done(const ipx_pool *pool, int slot); /* frames (files) slot `slot` has processed so far */
 /* ipx_png_decode_counts of slot `slot`'s own context (the pool's IPX_JOB_PNG and the micro-batcher decode there): since ipx_pool_create */
 int ipx_pool_png_decode_counts(const ipx_pool *pool, int slot, long long counts[5]);
+/* ipx_gif_decode_counts of slot `slot`'s own context (the pool's IPX_JOB_GIF and the micro-batcher decode there): since ipx_pool_create */
+int ipx_pool_gif_decode_counts(const ipx_pool *pool, int slot, long long counts[4]);
 /* hipHostMalloc'd memory, allocated and first touched on a thread bound to the CPUs next to slot `slot`'s GPU (sysfs local_cpulist):
  * staging on the GPU's NUMA node.  Free with ipx_pool_host_free. */
 void *ipx_pool_host_alloc(ipx_pool *pool, int slot, size_t bytes);

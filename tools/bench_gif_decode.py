@@ -7,6 +7,9 @@ batches of 1, 64 and 1024, on seeded photo-like and flat-graphics GIFs written b
   python tools/bench_gif_decode.py               # the table, one JSON line per case
   python tools/bench_gif_decode.py --profile     # a short run meant for rocprofv3 --kernel-trace --stats (kernel times per launch)
   python tools/bench_gif_decode.py --quick       # 200x200 only, batches 1 and 64
+  python tools/bench_gif_decode.py --par         # the parallel code walk (IPX_GIF_PAR=1 is set for the run); each row then carries the
+                                                 # rise of ipx_gif_decode_counts over its decode-only calls
+  python tools/bench_gif_decode.py --no-host     # without the host-decoded leg beside each row
 
 Files: 16 distinct seeded files per kind, repeated through the batch."""
 import argparse
@@ -43,7 +46,7 @@ def timed(fn, reps):
         t0 = time.perf_counter()
         fn()
         ts.append(time.perf_counter() - t0)
-    return float(np.median(ts)), float(min(ts))
+    return float(np.median(ts)), float(min(ts)), float(max(ts))
 
 
 def main():
@@ -51,7 +54,13 @@ def main():
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--par", action="store_true")
+    ap.add_argument("--no-host", action="store_true")
     a = ap.parse_args()
+    if a.par:
+        os.environ["IPX_GIF_PAR"] = "1"
+    else:
+        os.environ.pop("IPX_GIF_PAR", None)
     import gif_corpus
     import imageprocessor_amd as ipx
     if ipx.device_count() < 1:
@@ -89,14 +98,18 @@ def main():
                             pillow_decode(f)
                         plan.run_host_paletted_gif(idx, pal, copy=False)
 
-                    td, tdm = timed(decode_only, a.reps)
-                    tg, tgm = timed(gif_gif, a.reps)
-                    th, _ = timed(host_leg, 1 if n >= 1024 else a.reps)
-                    print(json.dumps({"bench": "gif_decode", "kind": kind, "w": w, "h": h, "batch": n,
+                    before = ctx.gif_decode_counts()
+                    td, tdm, tdx = timed(decode_only, a.reps)
+                    rose = [x - y for x, y in zip(ctx.gif_decode_counts(), before)]
+                    tg, tgm, tgx = timed(gif_gif, a.reps)
+                    th = None if a.no_host else timed(host_leg, 1 if n >= 1024 else a.reps)[0]
+                    print(json.dumps({"bench": "gif_decode", "par": a.par, "par_counts_rose": rose, "kind": kind, "w": w, "h": h, "batch": n,
                                       "bytes_per_file": sum(len(f) for f in distinct) // len(distinct),
-                                      "decode_ms": round(td * 1e3, 3), "decode_files_per_s": round(n / td, 1),
-                                      "gif_gif_ms": round(tg * 1e3, 3), "gif_gif_files_per_s": round(n / tg, 1),
-                                      "host_decoded_leg_files_per_s": round(n / th, 1),
+                                      "decode_ms": round(td * 1e3, 3), "decode_ms_min_max": [round(tdm * 1e3, 3), round(tdx * 1e3, 3)],
+                                      "decode_files_per_s": round(n / td, 1),
+                                      "gif_gif_ms": round(tg * 1e3, 3), "gif_gif_ms_min_max": [round(tgm * 1e3, 3), round(tgx * 1e3, 3)],
+                                      "gif_gif_files_per_s": round(n / tg, 1),
+                                      "host_decoded_leg_files_per_s": None if th is None else round(n / th, 1),
                                       "pillow_one_thread_decode_ms_per_file_not_go": round(host_dec * 1e3, 3)}), flush=True)
             plan.close()
 
