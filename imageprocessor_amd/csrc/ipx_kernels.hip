@@ -216,7 +216,7 @@ __global__ __launch_bounds__(256) void composite_kernel(uint8_t *dst, int dstrid
 }
 
 // composite_kernel with everything that is per batch there made per frame: frame z of the launch draws text map[z] (first + z without a
-// map) of one text set -- a descriptor table and ONE glyph table all texts share (ipx_textset, ipx_runtime.hip).  The grid spans the
+// map) of one text set -- a descriptor table and ONE glyph table all texts share (ipx_textset, ipx_text.hip).  The grid spans the
 // largest clipped box of the chunk; a block outside its own frame's box leaves before it loads anything (blockIdx and the descriptor
 // are uniform over the block, so no barrier is skipped by part of a wave), and a text with an empty box costs nothing.
 __global__ __launch_bounds__(256) void composite_texts_kernel(uint8_t *dst, int dstride, size_t frame_stride,

@@ -1,6 +1,7 @@
 // ipx_runtime_internal.h -- the runtime's own types (context, lanes, glyph sets, plans) and the small helpers every
-// translation unit that implements ABI entries needs (ipx_runtime.hip, ipx_jpeg_runtime.hip, ipx_jpeg_dec_runtime.hip, the GIF and PNG
-// halves).  What only the decode drivers share sits on top of it in ipx_decode_common.h.  Not part of the ABI.
+// translation unit that implements ABI entries needs (ipx_context.hip, ipx_image_ops.hip, ipx_text.hip, ipx_plan.hip, ipx_runtime.hip,
+// ipx_jpeg_runtime.hip, ipx_jpeg_dec_runtime.hip, the GIF and PNG halves).  What only the decode drivers share sits on top of it in
+// ipx_decode_common.h.  Not part of the ABI.
 #pragma once
 
 #include <atomic>
@@ -330,6 +331,54 @@ struct StreamSync {
     hipStream_t s;
     ~StreamSync() { (void)hipStreamSynchronize(s); }
 };
+
+// ---- Scale and Draw on frames in HBM (ipx_image_ops.hip) -----------------------------------------------------------------------------
+
+// a source image resident in HBM: RGBA / NRGBA pixels, or the three planes of a YCbCr image
+struct DevSrc {
+    int kind = IPX_SRC_RGBA;
+    const uint8_t *pix = nullptr;   // pixels, or the Y plane
+    int stride = 0;                 // bytes per row of pix
+    const uint8_t *cb = nullptr, *cr = nullptr;
+    int cstride = 0, ratio = 0;
+    int w = 0, h = 0;
+    int nframes = 1;                // a batch: frames frame_stride / c_frame_stride bytes apart
+    size_t frame_stride = 0, c_frame_stride = 0;
+    bool le_alpha = false;          // IPX_SRC_TAP64: no colour tap exceeds its alpha tap (NRGBA64, Gray16, CMYK after the expansion; not RGBA64)
+};
+
+// dst / src are device pointers at pixel (0,0)
+int dev_draw_src(hipStream_t s, uint8_t *dst, int dw, int dh, int dstride, Rect r, const DevSrc &src, int spx, int spy, int op, size_t dst_fs = 0);
+// xdraw.BiLinear.Scale(dst, dr, src, sr, op, nil) on device frames.  kind_override >= 0: the tap kind to read the source with (the
+// crop thumbnail's second scale, ipx_ks.h); axes: the plan's own tables, or NULL to take them from the context's cache
+int dev_scale_src(ipx_ctx *ctx, hipStream_t s, int *flag, uint8_t *dst, int dw, int dh, int dstride, const Rect &dr, const DevSrc &src,
+                  const Rect &sr, int op, size_t dst_fs = 0, int kind_override = -1, const KsAxisDev *axes = nullptr);
+
+// The one staging path of the single-image host entries (the eight of ipx_image_ops.hip, ipx_composite_glyphs_rgba8 of ipx_text.hip):
+// a leased lane's scratch as [dst][src_bytes of source][1024 bytes of slack]; dst goes up, `upload_and_run` uploads what source it has
+// and launches on the lane's stream, dst comes down and the stream is waited for.  A failing run drains the stream before its status
+// is returned: copies queued on it read the caller's memory.
+template <typename F>
+int stage_and_run(ipx_ctx *ctx, uint8_t *dst, int dw, int dh, int dstride, size_t src_bytes, F &&upload_and_run)
+{
+    LaneLease lane(ctx);
+    const size_t dbytes = align256((size_t)dw * dh * 4);
+    int rc = lane_reserve(lane.get(), dbytes + src_bytes + 1024);
+    if (rc) return rc;
+    uint8_t *ddst = lane->dev, *dsrc = lane->dev + dbytes;
+    hipStream_t s = lane->stream;
+    IPX_HIP(hipMemcpy2DAsync(ddst, (size_t)dw * 4, dst, dstride, (size_t)dw * 4, dh, hipMemcpyHostToDevice, s));
+    rc = upload_and_run(s, lane->flag, ddst, dsrc);
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    IPX_HIP(hipMemcpy2DAsync(dst, dstride, ddst, (size_t)dw * 4, (size_t)dw * 4, dh, hipMemcpyDeviceToHost, s));
+    IPX_HIP(hipStreamSynchronize(s));
+    return IPX_OK;
+}
+
+// ---- glyph sets (ipx_text.hip) -------------------------------------------------------------------------------------------------------
+
+// clip every glyph against a dw x dh frame (image/draw.clip) and cache the device table
+int glyphs_for_frame(const ipx_glyphset *gs, int dw, int dh, ClippedGlyphs *out);
 
 // ---- the input side of the plan entries (ipx_runtime.hip) ---------------------------------------------------------------------------
 
