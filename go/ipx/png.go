@@ -75,6 +75,51 @@ func (p *Plan) RunPNGPNG(files [][]byte) (*Streams, error) {
 	return s, nil
 }
 
+// RunPNGPNGMixed is the PNG task compressed in, compressed out for uploads of ANY sizes and kinds in one call: one decode pass per group of
+// files, the operators once per run of one size (plans by content from the context's cache) and one mixed-size png.Encode per output.
+// o describes the operators; o.Glyphs must be empty, because a positioned glyph list is anchored for one frame size.  texts is nil (the
+// watermark is the plain copy) or one Text per file, positioned by the caller for that file's size.  Status[i] and the three streams of
+// files[i] are what RunPNGPNG (or RunPNGPNGTexts) returns for that file in a call of its own with a plan of its size.
+func (x *Context) RunPNGPNGMixed(o Ops, files [][]byte, texts []Text) (*Streams, error) {
+	n := len(files)
+	if texts != nil && len(texts) != n {
+		return nil, &Error{Status: Invalid, Text: "one text per file"}
+	}
+	if len(o.Glyphs) != 0 {
+		return nil, &Error{Status: Invalid, Text: "a mixed-size call carries no glyphs of its own"}
+	}
+	s := &Streams{x: x, resize: make([]C.ipx_bytes, n), thumb: make([]C.ipx_bytes, n), watermark: make([]C.ipx_bytes, n),
+		Status: make([]Status, n)}
+	if n == 0 {
+		return s, nil
+	}
+	var c C.ipx_pool_ops
+	if o.Resize != nil {
+		c.do_resize, c.resize_w, c.resize_h, c.keep_aspect = 1, C.int32_t(o.Resize.W), C.int32_t(o.Resize.H), b2i(o.Resize.KeepAspect)
+	}
+	if o.Thumb != nil {
+		c.do_thumbnail, c.thumb_size, c.crop_to_fit = 1, C.int32_t(o.Thumb.Size), b2i(o.Thumb.CropToFit)
+	}
+	if o.Watermark || texts != nil {
+		c.do_watermark = 1
+	}
+	cf, freeFiles := cFiles(files)
+	defer freeFiles()
+	ct, freeTexts := cTexts(texts)
+	defer freeTexts()
+	st := make([]C.int, n)
+	err := call(func() C.int {
+		return C.ipx_run_png_png_mixed(x.c, &c, C.int(n), cf, ct, &s.resize[0], &s.thumb[0], &s.watermark[0], &st[0], &s.res)
+	})
+	if err != nil {
+		return nil, err
+	}
+	for i := range st {
+		s.Status[i] = Status(st[i])
+	}
+	return s, nil
+}
+
 // PNGDecodeCounts: since the Context was made, under IPX_PNG_PAR=1 in the environment -- [0] the files that entered the parallel inflate,
 // [1] the files it finished itself, [2] the files its redo bit handed to the serial decoder, [3] the tokens decoded by the parallel
 // lanes and [4] those decoded by the wave-uniform loop inside that kernel (both over the files of [1]).  All 0 while the switch is unset.

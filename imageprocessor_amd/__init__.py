@@ -893,6 +893,93 @@ class Context:
             info.update(batch=b, free=lambda: lib().ipx_png_frames_free(self.handle, owner))
         return info, st
 
+    def png_decode_mixed(self, files, download=True):
+        """image.Decode of PNG byte strings of ANY sizes and kinds in one decode pass (ipx_png_decode_mixed).  -> (frames, status
+        list); frames[i] is None for a non-OK file, else dict(w, h, kind, stride, pix, palette) with pix as h x (w * bytes per pixel)
+        uint8 (Go's Pix rows) and palette as 256 x 4 uint8 (PNG_PALETTED) or None (download=True), or the device pointers.  With
+        download=False a third value, free(), releases the frames."""
+        n = len(files)
+        arr = _bytes_array(files)
+        fr = (_lib.PngFrame * max(n, 1))()
+        status = (C.c_int * max(n, 1))()
+        owner = C.c_void_p()
+        _check(lib().ipx_png_decode_mixed(self.handle, None, arr, n, fr, status, C.byref(owner)))
+        st = list(status)[:n]
+        out = []
+        try:
+            for i in range(n):
+                f = fr[i]
+                if not f.pix:
+                    out.append(None)
+                    continue
+                d = {"w": f.w, "h": f.h, "kind": f.kind, "stride": f.stride, "pix": f.pix, "palette": f.palette}
+                if download:
+                    pix = np.empty((f.h, f.stride), np.uint8)
+                    _check(lib().ipx_memcpy_d2h(self.handle, pix.ctypes.data, f.pix, pix.nbytes))
+                    d["pix"], d["palette"] = pix, None
+                    if f.palette:
+                        pal = np.empty((256, 4), np.uint8)
+                        _check(lib().ipx_memcpy_d2h(self.handle, pal.ctypes.data, f.palette, pal.nbytes))
+                        d["palette"] = pal
+                out.append(d)
+        finally:
+            if download:
+                lib().ipx_png_frames_free(self.handle, owner)
+        if download:
+            return out, st
+        return out, st, (lambda: lib().ipx_png_frames_free(self.handle, owner))
+
+    def png_encode_mixed_dev(self, frames, copy=True):
+        """frames: (device pointer, w, h, stride) per RGBA8 frame in HBM, of any sizes -> one PNG stream each (ipx_png_encode_mixed_dev).
+        copy=False returns (memoryviews into the pinned block, release()) instead of bytes."""
+        frames = list(frames)
+        n = len(frames)
+        arr = (_lib.RgbaFrame * max(n, 1))()
+        for i, (ptr, w, h, stride) in enumerate(frames):
+            arr[i] = _lib.RgbaFrame(ptr, int(w), int(h), int(stride))
+        blob, offs, lens = C.c_void_p(), (C.c_size_t * max(n, 1))(), (C.c_size_t * max(n, 1))()
+        _check(lib().ipx_png_encode_mixed_dev(self.handle, arr, n, C.byref(blob), offs, lens))
+        if n == 0:
+            return ([], (lambda: None)) if not copy else []
+        if not copy:
+            total = offs[n - 1] + lens[n - 1]
+            buf = (C.c_uint8 * total).from_address(blob.value)
+            mv = memoryview(buf)
+            return [mv[offs[i]:offs[i] + lens[i]] for i in range(n)], (lambda: lib().ipx_host_free(self.handle, blob))
+        res = [C.string_at(blob.value + offs[i], lens[i]) for i in range(n)]
+        lib().ipx_host_free(self.handle, blob)
+        return res
+
+    def run_png_png_mixed(self, ops, files, want=("resize", "thumbnail", "watermark"), copy=True, texts=None):
+        """PNG byte strings of ANY sizes and kinds in -> ({operator: [png bytes | None] * n}, status list): one decode pass per group,
+        the operators per run of one size, one mixed-size png.Encode per output (ipx_run_png_png_mixed).  ops: a PoolOps with sw = sh
+        = 0 and no glyphs, or dict(resize=(w, h, keep_aspect) | None, thumbnail=(size, crop_to_fit) | None, watermark=bool).
+        texts: None, or one (glyphs, col) per file, positioned for that file's size.  copy=False: lengths instead of bytes."""
+        if isinstance(ops, dict):
+            o = _lib.PoolOps()
+            if ops.get("resize"):
+                o.do_resize, o.resize_w, o.resize_h, o.keep_aspect = 1, ops["resize"][0], ops["resize"][1], int(bool(ops["resize"][2]))
+            if ops.get("thumbnail"):
+                o.do_thumbnail, o.thumb_size, o.crop_to_fit = 1, ops["thumbnail"][0], int(bool(ops["thumbnail"][1]))
+            o.do_watermark = int(bool(ops.get("watermark")))
+            ops = o
+        n = len(files)
+        tarr, keep = (None, None)
+        if texts is not None:
+            texts = list(texts)
+            if len(texts) != n:
+                raise ValueError("one text per file")
+            tarr, keep = _text_array(texts)
+        arrs = {k: (_lib.Bytes * max(n, 1))() for k in ("resize", "thumbnail", "watermark") if k in want}
+        status = (C.c_int * max(n, 1))()
+        res = C.c_void_p()
+        _check(lib().ipx_run_png_png_mixed(self.handle, C.byref(ops), n, _bytes_array(files), tarr, arrs.get("resize"),
+                                           arrs.get("thumbnail"), arrs.get("watermark"), status, C.byref(res)))
+        out = {k: [(C.string_at(a[j].data, a[j].len) if copy else a[j].len) if a[j].data else None for j in range(n)]
+               for k, a in arrs.items()}
+        lib().ipx_jpeg_result_free(self.handle, res)
+        return out, list(status)[:n]
+
     def composite_glyphs(self, dst, glyphs, col):
         dstride = _dst(dst)
         dh, dw = dst.shape[:2]

@@ -64,6 +64,15 @@ class PngBatch(C.Structure):
     _fields_ = [("pix", C.c_void_p), ("stride", C.c_int32), ("frame_stride", C.c_size_t), ("palettes", C.c_void_p)]
 
 
+class PngFrame(C.Structure):
+    _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("kind", C.c_int32), ("pix", C.c_void_p), ("stride", C.c_int32),
+                ("palette", C.c_void_p)]
+
+
+class RgbaFrame(C.Structure):
+    _fields_ = [("pix", C.c_void_p), ("w", C.c_int32), ("h", C.c_int32), ("stride", C.c_int32)]
+
+
 class Param(C.Structure):
     _fields_ = [("key", C.c_char_p), ("type", C.c_int32), ("f64", C.c_double), ("i64", C.c_int64),
                 ("str", C.c_char_p)]
@@ -246,6 +255,10 @@ SIGNATURES = {
     "ipx_png_decode_batch": (_I, [_P, _P, C.POINTER(Bytes), _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(PngBatch),
                                   C.POINTER(_I), C.POINTER(_P)]),
     "ipx_png_frames_free": (None, [_P, _P]),
+    "ipx_png_decode_mixed": (_I, [_P, _P, C.POINTER(Bytes), _I, C.POINTER(PngFrame), C.POINTER(_I), C.POINTER(_P)]),
+    "ipx_png_encode_mixed_dev": (_I, [_P, C.POINTER(RgbaFrame), _I, C.POINTER(_P), C.POINTER(_Z), C.POINTER(_Z)]),
+    "ipx_run_png_png_mixed": (_I, [_P, C.POINTER(PoolOps), _I, C.POINTER(Bytes), C.POINTER(Text), C.POINTER(Bytes), C.POINTER(Bytes),
+                                   C.POINTER(Bytes), C.POINTER(_I), C.POINTER(_P)]),
     "ipx_plan_run_png_png": (_I, [_P, _P, _I, C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(_I),
                                   C.POINTER(_P)]),
     "ipx_plan_run_jpeg_jpeg_texts": (_I, [_P, _P, _I, C.POINTER(Bytes), C.POINTER(Text), _I, C.POINTER(Bytes), C.POINTER(Bytes),

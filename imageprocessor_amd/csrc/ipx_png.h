@@ -8,6 +8,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "../../include/ipx.h"
+
 namespace ipx {
 
 constexpr int kPngSegMin = 65536;      // a segment: whole rows, at least this many filtered bytes (the frame's last takes the remainder)
@@ -36,6 +38,18 @@ struct PngSegs {
 
 // chunk data bytes of a segment of `len` filtered bytes sent as stored blocks (<= 65535 bytes each) and the empty stored block
 __host__ __device__ inline size_t png_stored_bytes(size_t len, bool first) { return (first ? 2 : 0) + 5 * ((len + 65534) / 65535) + len + 5; }
+
+// where the pieces of a frame's stream sit in its region of the output: the head at 0, the segments' chunks from kPngSegBase (each in
+// a slot of its stored bound, 4-byte aligned), the tail behind them
+constexpr size_t kPngSegBase = 36;
+inline size_t png_slot_bytes(size_t len, bool first) { return (12 + png_stored_bytes(len, first) + 3) & ~(size_t)3; }
+inline size_t png_segs_bytes(int w, int h, int bpp)
+{
+    const PngSegs g(w, h, bpp);
+    size_t b = 0;
+    for (int s = 0; s < g.nseg; s++) b += png_slot_bytes((size_t)(g.row0(s + 1, h) - g.row0(s, h)) * g.stride, s == 0);
+    return b;
+}
 
 // one segment to compress (a workgroup of png_deflate_kernel): frame, byte range [s0, s1) of the frame's filtered stream, where its
 // IDAT chunk goes in the output regions (4-byte aligned) and whether it is the frame's first / last
@@ -130,6 +144,29 @@ hipError_t launch_png_frame(const uint8_t *heads, const uint32_t *alpha, const u
                             int n, uint8_t *out, size_t region, size_t tail, hipStream_t s);
 hipError_t launch_png_pack(const uint8_t *out, const PngPiece *pieces, int npieces, uint8_t *dst, hipStream_t s);
 
+// ---- frames of any sizes in one launch per stage (ipx_png_mixed.hip) ----
+// One frame of a mixed-size encode, in HBM: where its pixels are and where its pieces go.  The host fills src, w, h, stride before the
+// opacity launch and the rest once the colour types are known.
+struct PngMixFrame {
+    const uint8_t *src;          // RGBA8 rows, `stride` bytes apart
+    int32_t w, h, stride;
+    uint32_t row0;               // the frame's first row among the rows of all frames (the filter's workgroups)
+    uint32_t seg0, seg1;         // its segments in the segment table
+    uint32_t tail;               // its region: the head at 0, the tail here
+    unsigned long long filt;     // its filtered stream in the filter scratch (bytes); its match scratch is the same number of words in
+    unsigned long long region;   // its region in the output scratch (bytes, 256-byte aligned)
+};
+// alpha[i] |= 1 when frame i has an alpha byte other than 0xff (alpha: n zeroed words); only src, w, h, stride of the table are read
+hipError_t launch_png_mixed_opacity(const PngMixFrame *frames, int n, size_t max_pixels, uint32_t *alpha, hipStream_t s);
+// a workgroup per row of every frame (rows: their sum): frame i's filtered stream at filt + frames[i].filt
+hipError_t launch_png_mixed_filter(const PngMixFrame *frames, int n, size_t rows, const uint32_t *alpha, uint8_t *filt, hipStream_t s);
+// a workgroup per segment, as launch_png_deflate; seg.frame indexes the table
+hipError_t launch_png_mixed_deflate(const PngMixFrame *frames, const uint8_t *filt, uint32_t *match, const uint32_t *alpha, const PngSeg *segs,
+                                    int nseg, uint8_t *out, uint32_t *lens, uint32_t *adler, hipStream_t s);
+// per frame: signature and the frame's own IHDR at its region, the Adler-32 chunk and IEND at its tail
+hipError_t launch_png_mixed_frame(const PngMixFrame *frames, int n, const uint32_t *alpha, const PngSeg *segs, const uint32_t *adler,
+                                  uint8_t *out, hipStream_t s);
+
 }  // namespace ipx
 
 struct ipx_ctx;
@@ -138,5 +175,8 @@ namespace ipx {
 // is filled (ipx_png.hip; the PNG legs of ipx_png.hip and ipx_png_dec.hip)
 int png_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w, int h, int stride, size_t frame_stride, int n,
                     uint8_t **blob, size_t *offs, size_t *lens);
+// the same for n frames of any sizes, one launch per stage (ipx_png_mixed.hip; the mixed PNG leg of ipx_png_dec.hip).  The frames are
+// taken as checked (ipx_png_encode_mixed_dev checks them).
+int png_encode_mixed_core(ipx_ctx *ctx, hipStream_t s, const ipx_rgba_frame *frames, int n, uint8_t **blob, size_t *offs, size_t *lens);
 
 }  // namespace ipx

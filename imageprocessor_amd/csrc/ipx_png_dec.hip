@@ -3,12 +3,16 @@
 // into one zlib stream per file, the per-chunk check, the inflate (one wave per file: input, Huffman tables and the 32 KiB window in
 // LDS, match copies spread over the lanes, coalesced flushes with the Adler-32) and the unfilter (a diagonal wavefront of 64 rows that
 // writes the frame layout of the type Go returns; for Adam7 files, taken under IPX_PNG_ADAM7=1, one such wave per pass that scatters
-// its pixels to where the pass puts them).  Host half: ipx_png_dec_host.cpp.  DESIGN.md section 4.10.
+// its pixels to where the pass puts them).  Every kernel takes a workgroup per file and reads the file's own descriptor, so one pass
+// decodes files of any sizes and kinds (ipx_png_decode_mixed; the mixed-size leg ipx_run_png_png_mixed at the end of this file).
+// Host half: ipx_png_dec_host.cpp.  DESIGN.md section 4.10.
+#include <map>
 #include <numeric>
 #include <vector>
 
 #include "ipx_png.h"
 #include "ipx_png_dec.h"
+#include "ipx_png_mixed_plan.h"
 #include "ipx_decode_common.h"
 
 namespace ipx {
@@ -636,12 +640,14 @@ void png_select(const std::vector<PngFileInfo> &info, int n, int *w, int *h, int
 size_t png_group_bytes(const PngFileInfo &f) { return align256(f.file_len) + align256(f.idat_len + 32) + align256(f.raw_len); }
 }  // namespace
 
-// Decodes files[idx[g]] (status IPX_OK, all of one size and kind) into frames + slot[g] * frame_stride and, when palettes is set,
-// their palettes to palettes + slot[g] * 1024, on stream s; the verdicts land in status[idx[g]].  The scratch (the files' pinned upload
+// Decodes files[idx[g]] (status IPX_OK, of any sizes and kinds: the kernels read everything from the file's descriptor) into
+// frames + frame_off[g] and, when palettes is set, the palette of a file with slot[g] >= 0 to palettes + slot[g] * 1024, on stream s; the
+// verdicts land in status[idx[g]].  All of them go through the same launches.  The scratch (the files' pinned upload
 // block and, in HBM, the files, zlib streams, filtered rows and tables) is cut into groups of at most IPX_PNG_DEC_SCRATCH_MB, and each
 // group's scratch is released before the next group takes its own; one read-back of the per-file words at the end.
 static int png_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files, const std::vector<int> &idx, const std::vector<int> &slot,
-                            const std::vector<PngFileInfo> &info, uint8_t *frames, size_t frame_stride, uint8_t *palettes, int *status)
+                            const std::vector<size_t> &frame_off, const std::vector<PngFileInfo> &info, uint8_t *frames, uint8_t *palettes,
+                            int *status)
 {
     const int n = (int)idx.size();
     if (n == 0) return IPX_OK;
@@ -656,12 +662,13 @@ static int png_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
     IPX_HIP(mem.get(&dstate, words * 4));
     IPX_HIP(hipMemsetAsync(dstate, 0, words * 4, s));
     uint32_t *dpar = dstate + n;
-    if (palettes) {     // one upload of every slot up to the last (zero for slots not decoded here)
-        const int nslot = *std::max_element(slot.begin(), slot.end()) + 1;
+    const int nslot = *std::max_element(slot.begin(), slot.end()) + 1;
+    if (palettes && nslot > 0) {     // one upload of every slot up to the last (zero for slots not decoded here)
         uint8_t *hpal = pinned.get((size_t)nslot * 1024);
         if (!hpal) return IPX_ERR_NOMEM;
         memset(hpal, 0, (size_t)nslot * 1024);
-        for (int g = 0; g < n; g++) memcpy(hpal + (size_t)slot[g] * 1024, info[idx[g]].pal, 1024);
+        for (int g = 0; g < n; g++)
+            if (slot[g] >= 0) memcpy(hpal + (size_t)slot[g] * 1024, info[idx[g]].pal, 1024);
         IPX_HIP(hipMemcpyAsync(palettes, hpal, (size_t)nslot * 1024, hipMemcpyHostToDevice, s));
     }
     const size_t budget = (size_t)env_int("IPX_PNG_DEC_SCRATCH_MB", 8192) << 20;
@@ -682,7 +689,7 @@ static int png_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
             foff[g] = fbytes;
             d.zoff = zbytes;
             d.roff = rbytes;
-            d.foff = (uint64_t)slot[group[g]] * frame_stride;
+            d.foff = (uint64_t)frame_off[group[g]];
             d.zlen = f.idat_len;
             d.zlast = f.idat_last;
             d.raw_len = (uint32_t)f.raw_len;
@@ -833,7 +840,9 @@ int ipx_png_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *files, int
         return IPX_ERR_NOMEM;
     }
     if (dpal) IPX_HIP(hipMemsetAsync(dpal, 0, (size_t)n * 1024, s));
-    rc = png_decode_files(ctx, s, files, idx, idx, info, dframes, fs, dpal, status);     // frame i of file i
+    std::vector<size_t> foff(idx.size());
+    for (size_t g = 0; g < idx.size(); g++) foff[g] = (size_t)idx[g] * fs;
+    rc = png_decode_files(ctx, s, files, idx, idx, foff, info, dframes, dpal, status);     // frame i of file i
     if (rc) return rc;
     *w = bw;
     *h = bh;
@@ -843,6 +852,56 @@ int ipx_png_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *files, int
     frames->stride = bw * kb;
     frames->frame_stride = fs;
     frames->palettes = dpal;
+    *owner = o.release();
+    return IPX_OK;
+}
+IPX_CATCH_STATUS
+
+// n files of any sizes and kinds: every file that parses goes through ONE png_decode_files call, its frame at an offset of its own in
+// one block (256-byte aligned, rows tight) and, for a paletted file, its palette in the next free slot of a second block
+int ipx_png_decode_mixed(ipx_ctx *ctx, void *stream, const ipx_bytes *files, int n, ipx_png_frame *frames, int *status,
+                         ipx_png_frames **owner) try
+{
+    IPX_ENTER(ctx);
+    if (n < 0 || !owner || (n && (!files || !frames || !status))) { set_error("ipx_png_decode_mixed: bad argument"); return IPX_ERR_INVALID; }
+    *owner = nullptr;
+    if (n == 0) return IPX_OK;
+    if (n > 65535) { set_error("ipx_png_decode_mixed: at most 65535 files per call"); return IPX_ERR_UNSUPPORTED; }
+    memset(frames, 0, (size_t)n * sizeof *frames);
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    std::vector<PngFileInfo> info(n);
+    int rc = png_parse_all(files, n, info, status);
+    if (rc) return rc;
+    std::vector<int> idx, slot;
+    std::vector<size_t> foff;
+    size_t fbytes = 0;
+    int npal = 0;
+    for (int i = 0; i < n; i++) {
+        if (status[i] != IPX_OK) continue;
+        idx.push_back(i);
+        foff.push_back(fbytes);
+        slot.push_back(info[i].kind == IPX_PNG_PALETTED ? npal++ : -1);
+        fbytes += align256((size_t)info[i].w * info[i].h * png_kind_bpp(info[i].kind));
+    }
+    if (idx.empty()) return IPX_OK;
+    OwnedBlocks<ipx_png_frames> o(ctx, s);
+    uint8_t *dframes = nullptr, *dpal = nullptr;
+    hipError_t e = o.alloc(&dframes, fbytes);
+    if (e == hipSuccess && npal) e = o.alloc(&dpal, (size_t)npal * 1024);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("ipx_png_decode_mixed: device allocation failed: %s", hipGetErrorString(e));
+        return IPX_ERR_NOMEM;
+    }
+    rc = png_decode_files(ctx, s, files, idx, slot, foff, info, dframes, dpal, status);
+    if (rc) return rc;
+    if (!any_ok(status, n)) return IPX_OK;
+    for (size_t g = 0; g < idx.size(); g++) {
+        const int i = idx[g];
+        if (status[i] != IPX_OK) continue;
+        const PngFileInfo &f = info[i];
+        frames[i] = ipx_png_frame{f.w, f.h, f.kind, dframes + foff[g], f.w * png_kind_bpp(f.kind), slot[g] >= 0 ? dpal + (size_t)slot[g] * 1024 : nullptr};
+    }
     *owner = o.release();
     return IPX_OK;
 }
@@ -893,13 +952,14 @@ static int run_png_png(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n,
         for (size_t g0 = 0; g0 < of_kind.size(); g0 += group) {
             const int m = (int)std::min<size_t>(group, of_kind.size() - g0);
             std::vector<int> idx(of_kind.begin() + g0, of_kind.begin() + g0 + m), slot(m);
-            for (int g = 0; g < m; g++) slot[g] = g;
+            std::vector<size_t> foff(m);
+            for (int g = 0; g < m; g++) { slot[g] = g; foff[g] = (size_t)g * fs; }
             StreamSync sync{s};
             AsyncFree mem{s, {}};
             uint8_t *dfr, *dpal = nullptr;
             IPX_HIP(mem.get(&dfr, fs * m));
             if (kind == IPX_PNG_PALETTED) IPX_HIP(mem.get(&dpal, (size_t)1024 * m));
-            rc = png_decode_files(ctx, s, files, idx, slot, info, dfr, fs, dpal, status);
+            rc = png_decode_files(ctx, s, files, idx, slot, foff, info, dfr, dpal, status);
             if (rc) return rc;
             for (int c0 = 0; c0 < m; c0 += chunk) {
                 const int cm = std::min(chunk, m - c0);
@@ -935,6 +995,186 @@ int ipx_plan_run_png_png_texts(ipx_ctx *ctx, const ipx_plan *pl, int n, const ip
     IPX_ENTER(ctx);
     if (const int rc = leg_entry_check("ipx_plan_run_png_png_texts", pl, n, files, status, result, true, texts)) return rc;
     return run_png_png("ipx_plan_run_png_png_texts", ctx, pl, n, files, texts, resize_out, thumb_out, wm_out, status, result);
+}
+IPX_CATCH_STATUS
+
+}  // extern "C"
+
+// ---- the mixed-size PNG leg ------------------------------------------------------------------------------------------------------
+
+namespace {
+// the plans of one call, one per frame size, from the context's cache; handed back on every way out
+struct SizePlans {
+    struct Held { ipx_plan *pl; int cached; };
+    ipx_ctx *ctx;
+    std::map<std::pair<int, int>, Held> held;
+    explicit SizePlans(ipx_ctx *c) : ctx(c) {}
+    SizePlans(const SizePlans &) = delete;
+    ~SizePlans()
+    {
+        for (auto &kv : held)
+            if (kv.second.pl) ipx_plan_release(ctx, kv.second.pl, kv.second.cached);
+    }
+};
+
+// what output k of a plan costs a chunk: the frame itself and the encoder's scratch for it -- the filtered stream, a word of match
+// scratch per filtered byte, and the frame's region
+size_t mixed_out_cost(const OutShape &sh)
+{
+    if (!sh.bytes || sh.w <= 0 || sh.h <= 0) return 0;
+    const size_t filt = (size_t)sh.h * (1 + 4 * (size_t)sh.w);
+    return align256(sh.bytes) + 5 * align256(filt) + align256(kPngSegBase + png_segs_bytes(sh.w, sh.h, 4) + kPngTailBytes);
+}
+}  // namespace
+
+extern "C" {
+
+// The PNG leg for uploads of any sizes and kinds: the host parse; a plan per size from the context's cache; the cut of
+// ipx_png_mixed_plan.h (order by size and kind, decode groups, chunks, runs); per group ONE png_decode_files call whatever it holds;
+// per chunk the operators once per run, into the run's slice of three arenas, its texts in one launch from a set clipped to its size;
+// then one mixed-size png.Encode per present output over every frame of the chunk.  The host does not wait for the stream between
+// runs beyond what those stages contain (the upload of a run's texts).
+int ipx_run_png_png_mixed(ipx_ctx *ctx, const ipx_pool_ops *ops, int n, const ipx_bytes *files, const ipx_text *texts,
+                          ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result) try
+{
+    static const char who[] = "ipx_run_png_png_mixed";
+    IPX_ENTER(ctx);
+    if (!ops || n < 0 || !result || (n && (!files || !status))) { set_error("%s: bad argument", who); return IPX_ERR_INVALID; }
+    *result = nullptr;
+    if (ops->sw != 0 || ops->sh != 0) { set_error("%s: ops->sw and ops->sh must be 0: every file's own size is used", who); return IPX_ERR_INVALID; }
+    if (ops->glyphs || ops->n_glyphs) {
+        set_error("%s: ops->glyphs must be NULL: a positioned glyph list is anchored for one frame size; pass a text per file", who);
+        return IPX_ERR_INVALID;
+    }
+    if (texts)
+        if (const int rc = texts_check(who, texts, n)) return rc;
+    ipx_bytes *const dst[kOuts] = {resize_out, thumb_out, wm_out};
+    for (int k = 0; k < kOuts; k++)
+        if (dst[k])
+            for (int i = 0; i < n; i++) dst[k][i] = ipx_bytes{nullptr, 0};
+    if (n == 0) return IPX_OK;
+    std::vector<PngFileInfo> info(n);
+    int rc = png_parse_all(files, n, info, status);
+    if (rc) return rc;
+    // a plan per size; files of a size no plan can be made for get ipx_plan_create's status, alone.  Every distinct size of the call
+    // holds its plan until the call returns: at most one per file (65535), of which the context's cache keeps IPX_PLAN_CACHE_MAX (256) and
+    // the rest live and die with this call -- a call with more sizes than that also turns the cache over once
+    SizePlans plans(ctx);
+    std::map<std::pair<int, int>, int> plan_rc;
+    std::vector<ipx_plan *> plan_of(n, nullptr);
+    for (int i = 0; i < n; i++) {
+        if (status[i] != IPX_OK) continue;
+        const std::pair<int, int> key(info[i].w, info[i].h);
+        auto it = plan_rc.find(key);
+        if (it == plan_rc.end()) {
+            ipx_pool_ops o = *ops;
+            o.sw = key.first;
+            o.sh = key.second;
+            SizePlans::Held hd{nullptr, 0};
+            const int prc = ipx_plan_acquire(ctx, &o, &hd.pl, &hd.cached);
+            // a size the operators cannot be planned for is that size's verdict; anything else (memory, the device) fails the call
+            if (prc != IPX_OK && prc != IPX_ERR_INVALID && prc != IPX_ERR_UNSUPPORTED) return prc;
+            if (prc == IPX_OK) plans.held[key] = hd;
+            it = plan_rc.emplace(key, prc).first;
+        }
+        if (it->second != IPX_OK) { status[i] = it->second; continue; }
+        plan_of[i] = plans.held[key].pl;
+    }
+    auto out_fs = [&](int i, int k) -> size_t { return dst[k] ? align256(out_shape(plan_of[i]->info, k).bytes) : 0; };
+    std::vector<MixItem> items(n);
+    for (int i = 0; i < n; i++) {
+        MixItem &it = items[i];
+        it = MixItem{status[i] == IPX_OK, info[i].w, info[i].h, info[i].kind, 0, 0};
+        if (!it.ok) continue;
+        it.frame_bytes = align256((size_t)it.w * it.h * png_kind_bpp(it.kind)) + 1024;
+        for (int k = 0; k < kOuts; k++)
+            if (dst[k]) it.chunk_bytes += mixed_out_cost(out_shape(plan_of[i]->info, k));
+    }
+    const int group_max = std::min(65535, std::max(1, env_int("IPX_HOST_CHUNK_PNG_DEC", 1024)));
+    const size_t chunk_bytes = (size_t)std::max(0, env_int("IPX_PNG_MIXED_CHUNK_MB", 1024)) << 20;
+    const MixCut cut = png_mixed_cut(items.data(), n, group_max, (size_t)4 << 30, chunk_bytes);
+    ResultOwner res(ctx);
+    LaneLease lane(ctx);
+    hipStream_t s = lane->stream;
+    for (const MixGroup &grp : cut.groups) {
+        const int m = grp.n;
+        std::vector<int> idx(cut.order.begin() + grp.first, cut.order.begin() + grp.first + m), slot(m);
+        std::vector<size_t> foff(m);
+        size_t fbytes = 0;
+        int npal = 0;
+        for (int g = 0; g < m; g++) {
+            const PngFileInfo &f = info[idx[g]];
+            foff[g] = fbytes;
+            slot[g] = f.kind == IPX_PNG_PALETTED ? npal++ : -1;
+            fbytes += align256((size_t)f.w * f.h * png_kind_bpp(f.kind));
+        }
+        StreamSync sync{s};
+        AsyncFree mem{s, {}};
+        uint8_t *dfr, *dpal = nullptr;
+        IPX_HIP(mem.get(&dfr, fbytes));
+        if (npal) IPX_HIP(mem.get(&dpal, (size_t)1024 * npal));
+        rc = png_decode_files(ctx, s, files, idx, slot, foff, info, dfr, dpal, status);     // every size and kind of the group at once
+        if (rc) return rc;
+        for (int c = grp.chunk0; c < grp.chunk0 + grp.nchunks; c++) {
+            const MixChunk &ch = cut.chunks[c];
+            const int *file = cut.order.data() + ch.first;          // the chunk's files, by the caller's index
+            bool any = false;
+            for (int p = 0; p < ch.n; p++) any |= status[file[p]] == IPX_OK;
+            if (!any) continue;
+            AsyncFree omem{s, {}};
+            // the chunk's three arenas: file p's frame of output k at arena[k] + off[k][p]
+            std::vector<size_t> off[kOuts];
+            uint8_t *arena[kOuts] = {nullptr, nullptr, nullptr};
+            for (int k = 0; k < kOuts; k++) {
+                off[k].resize(ch.n);
+                size_t total = 0;
+                for (int p = 0; p < ch.n; p++) { off[k][p] = total; total += out_fs(file[p], k); }
+                if (total) IPX_HIP(omem.get(&arena[k], total));
+            }
+            for (int r = ch.run0; r < ch.run0 + ch.nruns; r++) {
+                const MixRun &run = cut.runs[r];
+                const int g0 = run.first - grp.first, p0 = run.first - ch.first, i0 = cut.order[run.first];
+                const PngFileInfo &f = info[i0];
+                const ipx_plan *pl = plan_of[i0];
+                const int kb = png_kind_bpp(f.kind);
+                const BatchSrc d = packed_src(src_of_png(f.kind), dfr + foff[g0], f.w * kb, align256((size_t)f.w * f.h * kb),
+                                              slot[g0] >= 0 ? dpal + (size_t)slot[g0] * 1024 : nullptr);
+                BatchDst bd;
+                for (int k = 0; k < kOuts; k++)
+                    if (const size_t fs = out_fs(i0, k)) { bd.out[k] = arena[k] + off[k][p0]; bd.frame_stride[k] = fs; }
+                rc = run_dev_src(ctx, s, pl, run.n, d, bd);
+                if (rc) return rc;
+                if (texts && pl->p.do_watermark && bd.out[kOutWm]) {
+                    const OutShape sh = out_shape(pl->info, kOutWm);
+                    std::vector<ipx_text> own(run.n);
+                    for (int q = 0; q < run.n; q++) own[q] = texts[file[p0 + q]];
+                    ipx_textset ts;                             // (its memory goes back in stream order, behind the launch)
+                    if ((rc = textset_build(s, who, own.data(), run.n, sh.w, sh.h, &ts))) return rc;
+                    if ((rc = dev_composite_texts(s, &omem, bd.out[kOutWm], sh.w * 4, bd.frame_stride[kOutWm], run.n, ts, 0, nullptr))) return rc;
+                }
+            }
+            for (int k = 0; k < kOuts; k++) {
+                std::vector<ipx_rgba_frame> fr;
+                std::vector<int> owner_of;
+                for (int p = 0; p < ch.n; p++) {
+                    const OutShape sh = out_shape(plan_of[file[p]]->info, k);
+                    if (!out_fs(file[p], k) || sh.w <= 0 || sh.h <= 0) continue;
+                    fr.push_back(ipx_rgba_frame{arena[k] + off[k][p], sh.w, sh.h, sh.w * 4});
+                    owner_of.push_back(file[p]);
+                }
+                if (fr.empty()) continue;
+                std::vector<size_t> offs(fr.size()), lens(fr.size());
+                uint8_t *blob = nullptr;
+                rc = png_encode_mixed_core(ctx, s, fr.data(), (int)fr.size(), &blob, offs.data(), lens.data());
+                if (rc) return rc;
+                res.add(blob);
+                for (size_t j = 0; j < fr.size(); j++)
+                    if (status[owner_of[j]] == IPX_OK) dst[k][owner_of[j]] = ipx_bytes{blob + offs[j], lens[j]};
+            }
+        }
+    }
+    *result = res.release();
+    return IPX_OK;
 }
 IPX_CATCH_STATUS
 

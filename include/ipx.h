@@ -563,6 +563,14 @@ int ipx_png_encode_rgba8(ipx_ctx *ctx, const uint8_t *pix, int w, int h, int str
  * ipx_gif_encode_batch_dev: *blob is freed with ipx_host_free; stream i is blob[offs[i] .. offs[i] + lens[i]). */
 int ipx_png_encode_batch_dev(ipx_ctx *ctx, const uint8_t *src, int w, int h, int stride, size_t frame_stride, int n, uint8_t **blob,
                              size_t *offs, size_t *lens);
+/* The same for n frames of ANY sizes, each described on its own: RGBA8 in HBM, pix and stride multiples of 4.  One launch per stage
+ * for the whole call however many sizes it holds (the kernels read a per-frame table), and stream i is byte for byte what
+ * ipx_png_encode_batch_dev writes for frame i alone: nothing of it depends on its neighbours or its place.  The rules are that
+ * entry's: one pinned block (ipx_host_free), streams that start 16-byte aligned, a width or height below 1 IPX_ERR_INVALID, a frame
+ * beyond ipx_frame_supported IPX_ERR_UNSUPPORTED, more than 65535 frames IPX_ERR_UNSUPPORTED; one bad frame refuses the call before
+ * any launch.  DESIGN.md section 4.9. */
+typedef struct { const uint8_t *pix; int32_t w, h, stride; } ipx_rgba_frame;
+int ipx_png_encode_mixed_dev(ipx_ctx *ctx, const ipx_rgba_frame *frames, int n, uint8_t **blob, size_t *offs, size_t *lens);
 /* The PNG task's whole GPU leg (ipx_plan_run_host's inputs): upload, every requested operator, then png.Encode of all three outputs
  * (a PNG watermark stays PNG).  The streams land in pinned blocks owned by *result, released with ipx_jpeg_result_free. */
 int ipx_plan_run_host_png(ipx_ctx *ctx, const ipx_plan *plan, int n, const uint8_t *src, int sstride, size_t src_frame_stride,
@@ -691,6 +699,15 @@ typedef struct ipx_png_frames ipx_png_frames;
 int ipx_png_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *files, int n, int *w, int *h, int *kind, ipx_png_batch *frames,
                          int *status, ipx_png_frames **owner);
 void ipx_png_frames_free(ipx_ctx *ctx, ipx_png_frames *owner);
+/* n files of any sizes and kinds in ONE decode pass: every file that parses is decoded in the same launches (one CRC pass, one
+ * inflate, the unfilter) whatever its neighbours are.  frames[i] describes file i's frame in HBM: its size, its kind (IPX_PNG_*), pix
+ * (256-byte aligned, rows tight, stride = w * bytes per pixel) and, for IPX_PNG_PALETTED, its 1024-byte palette (else NULL).
+ * status[i] is what ipx_png_decode_batch gives the file in a batch of its own size and kind: no file is IPX_ERR_UNSUPPORTED because
+ * of a neighbour.  frames[i] of a non-OK file is all zero.  IPX_PNG_ADAM7 and IPX_PNG_PAR mean what they mean there.  *owner (NULL
+ * when nothing decoded) is freed with ipx_png_frames_free.  n == 0 is IPX_OK; more than 65535 files is IPX_ERR_UNSUPPORTED. */
+typedef struct { int32_t w, h, kind; uint8_t *pix; int32_t stride; uint8_t *palette; } ipx_png_frame;
+int ipx_png_decode_mixed(ipx_ctx *ctx, void *stream, const ipx_bytes *files, int n, ipx_png_frame *frames, int *status,
+                         ipx_png_frames **owner);
 /* The parallel inflate, with IPX_PNG_PAR=1 in the environment (read on every call that decodes PNG files; unset or anything else: the
  * serial inflate alone, as before).  In every entry that decodes PNG files -- this one, ipx_plan_run_png_png and its _texts twin, the
  * pool's IPX_JOB_PNG, the micro-batcher -- a Huffman block's body is then parsed by the 64 lanes of the file's wave side by side
@@ -772,6 +789,21 @@ typedef struct {
  * cache holds IPX_PLAN_CACHE_MAX (256) plans and replaces the least recently used one nobody holds. */
 int ipx_plan_acquire(ipx_ctx *ctx, const ipx_pool_ops *ops, ipx_plan **plan, int *cached);
 void ipx_plan_release(ipx_ctx *ctx, ipx_plan *plan, int cached);
+
+/* The PNG task compressed in, compressed out for uploads of ANY sizes and kinds in one call.  ops gives the operator parameters;
+ * ops->sw and ops->sh must be 0 (each file's own size is used) and ops->glyphs NULL (a positioned glyph list is anchored for one frame
+ * size, watermark.go:121-148), else IPX_ERR_INVALID with nothing written.  texts: NULL (the watermark output is the plain copy), or n
+ * texts, texts[i] positioned by the caller for file i's size (the rules of ipx_textset_create: more than 256 glyphs in any text refuses
+ * the call).  The files are ordered by (width, height, kind) and decoded in groups of IPX_HOST_CHUNK_PNG_DEC files and ~4 GiB of
+ * frames, each group in ONE decode pass; a group is cut into chunks of at most IPX_PNG_MIXED_CHUNK_MB (1024) of output frames and
+ * encoder scratch; within a chunk the operators run once per run of one size and kind, with a plan of that size from the context's
+ * cache (ipx_plan_acquire), and every present output is encoded by ONE mixed-size png.Encode over all frames of the chunk.
+ * status[i] and the three streams of file i are exactly what ipx_plan_run_png_png (or _texts) returns for that file in a call of its
+ * own with a plan of its size; files of a size for which no plan can be made get the status ipx_plan_create returned, alone.  A NULL
+ * output array skips that output; an operator ops does not ask for gives {NULL, 0}; n == 0 is IPX_OK.  Streams as for
+ * ipx_plan_run_png_png (ipx_jpeg_result_free).  DESIGN.md section 4.10. */
+int ipx_run_png_png_mixed(ipx_ctx *ctx, const ipx_pool_ops *ops, int n, const ipx_bytes *files, const ipx_text *texts,
+                          ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result);
 
 enum { IPX_JOB_RGBA8 = 0,       /* decoded frames in, the operators' RGBA8 outputs back (what ipx_plan_run_host does) */
        IPX_JOB_JPEG = 1,        /* uploaded JPEG files in, three JPEG streams per file back (what ipx_plan_run_jpeg_jpeg does) */
