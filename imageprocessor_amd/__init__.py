@@ -667,12 +667,11 @@ class Context:
         _check(lib().ipx_dev_jpeg_fdct_rgba8(self.handle, stream, src_ptr, w, h, stride or w * 4,
                                              frame_stride if frame_stride is not None else w * h * 4, n, int(quality), coefs_ptr))
 
-    def jpeg_encode_batch_dev(self, src_ptr, w, h, n, quality=85, stride=None, frame_stride=None, copy=True):
-        """n frames in HBM -> n streams.  copy=False returns (memoryviews into the pinned block, release()) instead of bytes."""
-        blob, offs, lens = C.c_void_p(), (C.c_size_t * n)(), (C.c_size_t * n)()
-        _check(lib().ipx_jpeg_encode_batch_dev(self.handle, src_ptr, w, h, stride or w * 4,
-                                               frame_stride if frame_stride is not None else w * h * 4, n, int(quality),
-                                               C.byref(blob), offs, lens))
+    def _stream_block(self, blob, offs, lens, n, copy):
+        """what an *_encode_*_dev entry hands back (n streams in one pinned block) -> n byte strings, the block freed; copy=False:
+        (memoryviews into the block, release()) instead"""
+        if n == 0:
+            return ([], (lambda: None)) if not copy else []
         if not copy:
             total = offs[n - 1] + lens[n - 1]
             buf = (C.c_uint8 * total).from_address(blob.value)
@@ -681,6 +680,14 @@ class Context:
         res = [C.string_at(blob.value + offs[i], lens[i]) for i in range(n)]
         lib().ipx_host_free(self.handle, blob)
         return res
+
+    def jpeg_encode_batch_dev(self, src_ptr, w, h, n, quality=85, stride=None, frame_stride=None, copy=True):
+        """n frames in HBM -> n streams.  copy=False returns (memoryviews into the pinned block, release()) instead of bytes."""
+        blob, offs, lens = C.c_void_p(), (C.c_size_t * n)(), (C.c_size_t * n)()
+        _check(lib().ipx_jpeg_encode_batch_dev(self.handle, src_ptr, w, h, stride or w * 4,
+                                               frame_stride if frame_stride is not None else w * h * 4, n, int(quality),
+                                               C.byref(blob), offs, lens))
+        return self._stream_block(blob, offs, lens, n, copy)
 
     def gif_encode(self, frame):
         """gif.Encode(w, *image.RGBA, nil) of one host frame (H x W x 4 uint8, premultiplied) -> bytes"""
@@ -702,16 +709,7 @@ class Context:
         blob, offs, lens = C.c_void_p(), (C.c_size_t * max(n, 1))(), (C.c_size_t * max(n, 1))()
         _check(lib().ipx_gif_encode_batch_dev(self.handle, src_ptr, w, h, stride or w * 4,
                                               frame_stride if frame_stride is not None else w * h * 4, n, C.byref(blob), offs, lens))
-        if n == 0:
-            return ([], (lambda: None)) if not copy else []
-        if not copy:
-            total = offs[n - 1] + lens[n - 1]
-            buf = (C.c_uint8 * total).from_address(blob.value)
-            mv = memoryview(buf)
-            return [mv[offs[i]:offs[i] + lens[i]] for i in range(n)], (lambda: lib().ipx_host_free(self.handle, blob))
-        res = [C.string_at(blob.value + offs[i], lens[i]) for i in range(n)]
-        lib().ipx_host_free(self.handle, blob)
-        return res
+        return self._stream_block(blob, offs, lens, n, copy)
 
     def png_encode(self, frame):
         """png.Encode(w, *image.RGBA) of one host frame (H x W x 4 uint8, premultiplied) -> bytes (the zlib stream is this project's own)"""
@@ -728,47 +726,52 @@ class Context:
         blob, offs, lens = C.c_void_p(), (C.c_size_t * max(n, 1))(), (C.c_size_t * max(n, 1))()
         _check(lib().ipx_png_encode_batch_dev(self.handle, src_ptr, w, h, stride or w * 4,
                                               frame_stride if frame_stride is not None else w * h * 4, n, C.byref(blob), offs, lens))
-        if n == 0:
-            return ([], (lambda: None)) if not copy else []
-        if not copy:
-            total = offs[n - 1] + lens[n - 1]
-            buf = (C.c_uint8 * total).from_address(blob.value)
-            mv = memoryview(buf)
-            return [mv[offs[i]:offs[i] + lens[i]] for i in range(n)], (lambda: lib().ipx_host_free(self.handle, blob))
-        res = [C.string_at(blob.value + offs[i], lens[i]) for i in range(n)]
-        lib().ipx_host_free(self.handle, blob)
-        return res
+        return self._stream_block(blob, offs, lens, n, copy)
+
+    def _decode_batch(self, entry, free, files, dims, batch, download):
+        """What the *_decode_batch methods share: the call of `entry` (dims: the size, and the kind, asked for; batch: the entry's
+        batch struct, filled here) -> (dims as the entry set them, status list, done).  done is None when no file was decodable;
+        else done(info) ends the method: the device blocks are released (download) or go into info as `batch` and `free`."""
+        n = len(files)
+        cdims = [C.c_int(v) for v in dims]
+        status = (C.c_int * max(n, 1))()
+        owner = C.c_void_p()
+        _check(getattr(lib(), entry)(self.handle, None, _bytes_array(files), n, *[C.byref(d) for d in cdims], C.byref(batch), status,
+                                     C.byref(owner)))
+        release = lambda: getattr(lib(), free)(self.handle, owner)
+
+        def done(info):
+            if download:
+                release()
+            else:
+                info.update(batch=batch, free=release)
+            return info
+        # (every batch struct starts with the pointer that is null when there are no frames)
+        return [d.value for d in cdims], list(status)[:n], (done if getattr(batch, batch._fields_[0][0]) else None)
+
+    def _grab(self, ptr, n, frame_stride):
+        """n frames frame_stride bytes apart in HBM -> an n x frame_stride uint8 array"""
+        out = np.empty((n, frame_stride), np.uint8)
+        _check(lib().ipx_memcpy_d2h(self.handle, out.ctypes.data, ptr, out.nbytes))
+        return out
 
     def jpeg_decode_batch(self, files, w=0, h=0, download=True):
         """image.Decode of a batch of JPEG byte strings on the GPU.  -> (info, status list); info = dict(w, h, ratio, ystride,
         cstride, y, cb, cr) with the planes as n x rows x stride arrays (download=True) or device pointers + `free()`."""
-        n = len(files)
-        arr = _bytes_array(files)
-        cw, chh = C.c_int(w), C.c_int(h)
-        b = _lib.YCbCrBatch()
-        status = (C.c_int * n)()
-        owner = C.c_void_p()
-        _check(lib().ipx_jpeg_decode_batch(self.handle, None, arr, n, C.byref(cw), C.byref(chh), C.byref(b), status, C.byref(owner)))
-        st = list(status)
-        if not b.y:
+        n, b = len(files), _lib.YCbCrBatch()
+        (w, h), st, done = self._decode_batch("ipx_jpeg_decode_batch", "ipx_jpeg_planes_free", files, (w, h), b, download)
+        if done is None:
             return None, st
-        info = {"w": cw.value, "h": chh.value, "ratio": b.ratio, "ystride": b.ystride, "cstride": b.cstride}
+        info = {"w": w, "h": h, "ratio": b.ratio, "ystride": b.ystride, "cstride": b.cstride}
         v0 = 2 if b.ratio in (2, 3, YCBCR_410) else 1   # 4:2:0, 4:4:0 and 4:1:0 halve the chroma rows (Gray: 8 x 8 MCUs)
-        myy = (chh.value + 8 * v0 - 1) // (8 * v0)
+        myy = (h + 8 * v0 - 1) // (8 * v0)
         yrows, crows = 8 * v0 * myy, 8 * myy            # image.NewYCbCr(Rect(0, 0, 8*h0*mxx, 8*v0*myy), ratio)
         if download:
-            def grab(ptr, fs, rows, stride):
-                out = np.empty((n, fs), np.uint8)
-                _check(lib().ipx_memcpy_d2h(self.handle, out.ctypes.data, ptr, out.nbytes))
-                return out[:, :rows * stride].reshape(n, rows, stride)
-            info["y"] = grab(b.y, b.y_frame_stride, yrows, b.ystride)
+            info["y"] = self._grab(b.y, n, b.y_frame_stride)[:, :yrows * b.ystride].reshape(n, yrows, b.ystride)
             if b.cb:   # *image.Gray has no chroma planes
-                info["cb"] = grab(b.cb, b.c_frame_stride, crows, b.cstride)
-                info["cr"] = grab(b.cr, b.c_frame_stride, crows, b.cstride)
-            lib().ipx_jpeg_planes_free(self.handle, owner)
-        else:
-            info.update(batch=b, free=lambda: lib().ipx_jpeg_planes_free(self.handle, owner))
-        return info, st
+                info["cb"] = self._grab(b.cb, n, b.c_frame_stride)[:, :crows * b.cstride].reshape(n, crows, b.cstride)
+                info["cr"] = self._grab(b.cr, n, b.c_frame_stride)[:, :crows * b.cstride].reshape(n, crows, b.cstride)
+        return done(info), st
 
     JPEG_ROUTE_PAR, JPEG_ROUTE_HOST_SCANS, JPEG_ROUTE_GPU_SCANS = 0, 1, 2
 
@@ -808,25 +811,14 @@ class Context:
         """image.Decode of a batch of four-component JPEG byte strings (Adobe CMYK / YCCK) on the GPU, under IPX_JPEG_CMYK=1.
         -> (info, status list); info = dict(w, h, stride, pix) with pix as an n x h x w x 4 uint8 array of *image.CMYK pixels
         (download=True), or the device batch (CmykBatch) + `free()`; None when no file was decodable."""
-        n = len(files)
-        arr = _bytes_array(files)
-        cw, chh = C.c_int(w), C.c_int(h)
-        b = _lib.CmykBatch()
-        status = (C.c_int * max(n, 1))()
-        owner = C.c_void_p()
-        _check(lib().ipx_jpeg_decode_batch_cmyk(self.handle, None, arr, n, C.byref(cw), C.byref(chh), C.byref(b), status, C.byref(owner)))
-        st = list(status)[:n]
-        if not b.pix:
+        n, b = len(files), _lib.CmykBatch()
+        (w, h), st, done = self._decode_batch("ipx_jpeg_decode_batch_cmyk", "ipx_jpeg_planes_free", files, (w, h), b, download)
+        if done is None:
             return None, st
-        info = {"w": cw.value, "h": chh.value, "stride": b.stride}
+        info = {"w": w, "h": h, "stride": b.stride}
         if download:
-            out = np.empty((n, b.frame_stride), np.uint8)
-            _check(lib().ipx_memcpy_d2h(self.handle, out.ctypes.data, b.pix, out.nbytes))
-            info["pix"] = out[:, :chh.value * b.stride].reshape(n, chh.value, cw.value, 4)
-            lib().ipx_jpeg_planes_free(self.handle, owner)
-        else:
-            info.update(batch=b, free=lambda: lib().ipx_jpeg_planes_free(self.handle, owner))
-        return info, st
+            info["pix"] = self._grab(b.pix, n, b.frame_stride)[:, :h * b.stride].reshape(n, h, w, 4)
+        return done(info), st
 
     def jpeg_cmyk_files(self):
         """Since the context was made: files that reached the four-component JPEG decoder."""
@@ -838,28 +830,15 @@ class Context:
         """image.Decode of a batch of GIF byte strings on the GPU (the first image of each).  -> (info, status list); info = dict(w, h,
         stride, index, palettes) with index as n x h x w and palettes as n x 256 x 4 uint8 arrays (download=True), or the device
         batch (PalettedBatch) + `free()`; None when no file was decodable."""
-        n = len(files)
-        arr = _bytes_array(files)
-        cw, chh = C.c_int(w), C.c_int(h)
-        b = _lib.PalettedBatch()
-        status = (C.c_int * max(n, 1))()
-        owner = C.c_void_p()
-        _check(lib().ipx_gif_decode_batch(self.handle, None, arr, n, C.byref(cw), C.byref(chh), C.byref(b), status, C.byref(owner)))
-        st = list(status)[:n]
-        if not b.index:
+        n, b = len(files), _lib.PalettedBatch()
+        (w, h), st, done = self._decode_batch("ipx_gif_decode_batch", "ipx_gif_frames_free", files, (w, h), b, download)
+        if done is None:
             return None, st
-        info = {"w": cw.value, "h": chh.value, "stride": b.stride}
+        info = {"w": w, "h": h, "stride": b.stride}
         if download:
-            fr = np.empty((n, b.frame_stride), np.uint8)
-            _check(lib().ipx_memcpy_d2h(self.handle, fr.ctypes.data, b.index, fr.nbytes))
-            pal = np.empty((n, 256, 4), np.uint8)
-            _check(lib().ipx_memcpy_d2h(self.handle, pal.ctypes.data, b.palettes, pal.nbytes))
-            info["index"] = fr[:, :cw.value * chh.value].reshape(n, chh.value, cw.value)
-            info["palettes"] = pal
-            lib().ipx_gif_frames_free(self.handle, owner)
-        else:
-            info.update(batch=b, free=lambda: lib().ipx_gif_frames_free(self.handle, owner))
-        return info, st
+            info["index"] = self._grab(b.index, n, b.frame_stride)[:, :w * h].reshape(n, h, w)
+            info["palettes"] = self._grab(b.palettes, n, 1024).reshape(n, 256, 4)
+        return done(info), st
 
     PNG_BPP = (1, 4, 4, 1, 2, 8, 8)     # bytes per pixel of the PNG_* frame layouts
 
@@ -867,31 +846,15 @@ class Context:
         """image.Decode of a batch of PNG byte strings on the GPU.  -> (info, status list); info = dict(w, h, kind, stride, pix, palettes)
         with pix as n x h x (w * bytes per pixel) uint8 (Go's Pix rows) and palettes as n x 256 x 4 uint8 (PNG_PALETTED) or None
         (download=True), or the device batch (PngBatch) + `free()`; None when no file was decodable."""
-        n = len(files)
-        arr = _bytes_array(files)
-        cw, chh, ck = C.c_int(w), C.c_int(h), C.c_int(kind)
-        b = _lib.PngBatch()
-        status = (C.c_int * max(n, 1))()
-        owner = C.c_void_p()
-        _check(lib().ipx_png_decode_batch(self.handle, None, arr, n, C.byref(cw), C.byref(chh), C.byref(ck), C.byref(b), status,
-                                          C.byref(owner)))
-        st = list(status)[:n]
-        if not b.pix:
+        n, b = len(files), _lib.PngBatch()
+        (w, h, kind), st, done = self._decode_batch("ipx_png_decode_batch", "ipx_png_frames_free", files, (w, h, kind), b, download)
+        if done is None:
             return None, st
-        info = {"w": cw.value, "h": chh.value, "kind": ck.value, "stride": b.stride}
+        info = {"w": w, "h": h, "kind": kind, "stride": b.stride}
         if download:
-            fr = np.empty((n, b.frame_stride), np.uint8)
-            _check(lib().ipx_memcpy_d2h(self.handle, fr.ctypes.data, b.pix, fr.nbytes))
-            info["pix"] = fr[:, :b.stride * chh.value].reshape(n, chh.value, b.stride)
-            info["palettes"] = None
-            if b.palettes:
-                pal = np.empty((n, 256, 4), np.uint8)
-                _check(lib().ipx_memcpy_d2h(self.handle, pal.ctypes.data, b.palettes, pal.nbytes))
-                info["palettes"] = pal
-            lib().ipx_png_frames_free(self.handle, owner)
-        else:
-            info.update(batch=b, free=lambda: lib().ipx_png_frames_free(self.handle, owner))
-        return info, st
+            info["pix"] = self._grab(b.pix, n, b.frame_stride)[:, :b.stride * h].reshape(n, h, b.stride)
+            info["palettes"] = self._grab(b.palettes, n, 1024).reshape(n, 256, 4) if b.palettes else None
+        return done(info), st
 
     def png_decode_mixed(self, files, download=True):
         """image.Decode of PNG byte strings of ANY sizes and kinds in one decode pass (ipx_png_decode_mixed).  -> (frames, status
@@ -939,16 +902,7 @@ class Context:
             arr[i] = _lib.RgbaFrame(ptr, int(w), int(h), int(stride))
         blob, offs, lens = C.c_void_p(), (C.c_size_t * max(n, 1))(), (C.c_size_t * max(n, 1))()
         _check(lib().ipx_png_encode_mixed_dev(self.handle, arr, n, C.byref(blob), offs, lens))
-        if n == 0:
-            return ([], (lambda: None)) if not copy else []
-        if not copy:
-            total = offs[n - 1] + lens[n - 1]
-            buf = (C.c_uint8 * total).from_address(blob.value)
-            mv = memoryview(buf)
-            return [mv[offs[i]:offs[i] + lens[i]] for i in range(n)], (lambda: lib().ipx_host_free(self.handle, blob))
-        res = [C.string_at(blob.value + offs[i], lens[i]) for i in range(n)]
-        lib().ipx_host_free(self.handle, blob)
-        return res
+        return self._stream_block(blob, offs, lens, n, copy)
 
     def run_png_png_mixed(self, ops, files, want=("resize", "thumbnail", "watermark"), copy=True, texts=None):
         """PNG byte strings of ANY sizes and kinds in -> ({operator: [png bytes | None] * n}, status list): one decode pass per group,

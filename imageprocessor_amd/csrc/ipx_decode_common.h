@@ -1,5 +1,5 @@
 // ipx_decode_common.h -- the host scaffolding the three decode drivers share (jpeg_decode_files in ipx_jpeg_dec_runtime.hip,
-// gif_decode_files in ipx_gif_dec.hip, png_decode_files in ipx_png_dec.hip).  What a driver schedules, and the
+// gif_decode_files in ipx_gif_dec.hip, png_decode_files in ipx_png_dec_runtime.hip).  What a driver schedules, and the
 // JPEG driver's lane arena, stay with the driver.  Not part of the ABI.
 #pragma once
 

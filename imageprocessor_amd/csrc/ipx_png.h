@@ -172,10 +172,10 @@ hipError_t launch_png_mixed_frame(const PngMixFrame *frames, int n, const uint32
 struct ipx_ctx;
 namespace ipx {
 // png.Encode of n RGBA8 frames in HBM -> streams in one pinned block (ipx_host_alloc), everything on stream s; returns once the block
-// is filled (ipx_png.hip; the PNG legs of ipx_png.hip and ipx_png_dec.hip)
+// is filled (ipx_png.hip; the PNG legs of ipx_png.hip and ipx_png_legs.hip)
 int png_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w, int h, int stride, size_t frame_stride, int n,
                     uint8_t **blob, size_t *offs, size_t *lens);
-// the same for n frames of any sizes, one launch per stage (ipx_png_mixed.hip; the mixed PNG leg of ipx_png_dec.hip).  The frames are
+// the same for n frames of any sizes, one launch per stage (ipx_png_mixed.hip; the mixed PNG leg of ipx_png_legs.hip).  The frames are
 // taken as checked (ipx_png_encode_mixed_dev checks them).
 int png_encode_mixed_core(ipx_ctx *ctx, hipStream_t s, const ipx_rgba_frame *frames, int n, uint8_t **blob, size_t *offs, size_t *lens);
 

@@ -1,6 +1,6 @@
-// ipx_png_dec.h -- png.Decode (non-interlaced files, and Adam7 ones under IPX_PNG_ADAM7=1) on the GPU: what the kernels (ipx_png_dec.hip) and the host half
-// (ipx_png_dec_host.cpp) share.  Not part of the ABI.  The restatement of Go's reader is in DESIGN.md section 4.10;
-// tests/png_decode_model.py is the model it is held to.
+// ipx_png_dec.h -- png.Decode (non-interlaced files, and Adam7 ones under IPX_PNG_ADAM7=1) on the GPU: what the kernels
+// (ipx_png_dec.hip), the driver (ipx_png_dec_runtime.hip), the legs (ipx_png_legs.hip) and the host half (ipx_png_dec_host.cpp) share.
+// Not part of the ABI.  The restatement of Go's reader is in DESIGN.md section 4.10; tests/png_decode_model.py is the model it is held to.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "ipx_internal.h"
+#include "ipx_png_layout.h"
 
 namespace ipx {
 
@@ -97,4 +98,14 @@ hipError_t launch_png_inflate_redo(const uint8_t *zlib, const PngDecDesc *desc, 
 hipError_t launch_png_unfilter(const PngDecDesc *desc, int n, uint8_t *raw, uint8_t *frames, uint32_t *status, hipStream_t s);
 hipError_t launch_png_unfilter_adam7(const PngDecDesc *desc, int n, uint8_t *raw, uint8_t *frames, uint32_t *status, hipStream_t s);
 
+// a file's frame as the packed layout (ipx_png_layout.h) takes it
+inline PngFrameNeed png_frame_need(const PngFileInfo &f) { return PngFrameNeed{(size_t)f.w * f.h * png_kind_bpp(f.kind), f.kind == IPX_PNG_PALETTED}; }
+
 }  // namespace ipx
+
+// ---- the decode driver (ipx_png_dec_runtime.hip), as the entries and the legs (ipx_png_legs.hip) call it -------------------------
+// parse n files on the host pool: status[i] and info[i] from the container (png_parse; IPX_PNG_ADAM7 is read here)
+int png_parse_all(const ipx_bytes *files, int n, std::vector<ipx::PngFileInfo> &info, int *status);
+// decodes files[at.idx[g]] into frames + at.off[g], its palette into slot at.pal_slot[g] of palettes (when set); verdicts in status
+int png_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files, const ipx::PngFrameLayout &at, const std::vector<ipx::PngFileInfo> &info,
+                     uint8_t *frames, uint8_t *palettes, int *status);

@@ -1,19 +1,13 @@
-// ipx_png_dec.hip -- png.Decode (image/png reader.go, compress/zlib, compress/flate) of a batch of files on the GPU, and
-// the ABI entries built on it.  Kernels: the CRC of every chunk in pieces (combined with crc_shift) that also gathers the IDAT payloads
+// ipx_png_dec.hip -- png.Decode (image/png reader.go, compress/zlib, compress/flate) of a batch of files on the GPU: the kernels and
+// their launchers.  Kernels: the CRC of every chunk in pieces (combined with crc_shift) that also gathers the IDAT payloads
 // into one zlib stream per file, the per-chunk check, the inflate (one wave per file: input, Huffman tables and the 32 KiB window in
 // LDS, match copies spread over the lanes, coalesced flushes with the Adler-32) and the unfilter (a diagonal wavefront of 64 rows that
 // writes the frame layout of the type Go returns; for Adam7 files, taken under IPX_PNG_ADAM7=1, one such wave per pass that scatters
 // its pixels to where the pass puts them).  Every kernel takes a workgroup per file and reads the file's own descriptor, so one pass
-// decodes files of any sizes and kinds (ipx_png_decode_mixed; the mixed-size leg ipx_run_png_png_mixed at the end of this file).
-// Host half: ipx_png_dec_host.cpp.  DESIGN.md section 4.10.
-#include <map>
-#include <numeric>
-#include <vector>
-
+// decodes files of any sizes and kinds.  The driver and the decode entries: ipx_png_dec_runtime.hip; the PNG-in, PNG-out legs:
+// ipx_png_legs.hip; the host parse: ipx_png_dec_host.cpp.  DESIGN.md section 4.10.
 #include "ipx_png.h"
 #include "ipx_png_dec.h"
-#include "ipx_png_mixed_plan.h"
-#include "ipx_decode_common.h"
 
 namespace ipx {
 
@@ -612,570 +606,3 @@ hipError_t launch_png_unfilter_adam7(const PngDecDesc *desc, int n, uint8_t *raw
 }
 
 }  // namespace ipx
-
-// ---- the decode core -------------------------------------------------------------------------------------------------------------
-
-namespace {
-constexpr uint32_t kCrcPiece = 16384;
-
-// parse n files (a thread per eight of them); status[i] from the container.  IPX_PNG_ADAM7=1 in the environment, read on every call,
-// lets Adam7 files through to the GPU; anything else keeps them UNSUPPORTED.
-int png_parse_all(const ipx_bytes *files, int n, std::vector<PngFileInfo> &info, int *status)
-{
-    const bool adam7 = env_int("IPX_PNG_ADAM7", 0) == 1;
-    return parallel_light(n, [&](int i) { status[i] = png_parse(files[i].data, files[i].data ? files[i].len : 0, adam7, &info[i]); }, "png decode: host parse failed");
-}
-
-// the batch's size and kind: *w x *h (or the first parsed file's when *w == 0) and *kind (or the first's when -1); others UNSUPPORTED
-void png_select(const std::vector<PngFileInfo> &info, int n, int *w, int *h, int *kind, int *status)
-{
-    for (int i = 0; i < n; i++) {
-        if (status[i] != IPX_OK) continue;
-        if (*w <= 0) { *w = info[i].w; *h = info[i].h; }
-        if (*kind < 0 && info[i].w == *w && info[i].h == *h) *kind = info[i].kind;
-        if (info[i].w != *w || info[i].h != *h || info[i].kind != *kind) status[i] = IPX_ERR_UNSUPPORTED;
-    }
-}
-
-size_t png_group_bytes(const PngFileInfo &f) { return align256(f.file_len) + align256(f.idat_len + 32) + align256(f.raw_len); }
-}  // namespace
-
-// Decodes files[idx[g]] (status IPX_OK, of any sizes and kinds: the kernels read everything from the file's descriptor) into
-// frames + frame_off[g] and, when palettes is set, the palette of a file with slot[g] >= 0 to palettes + slot[g] * 1024, on stream s; the
-// verdicts land in status[idx[g]].  All of them go through the same launches.  The scratch (the files' pinned upload
-// block and, in HBM, the files, zlib streams, filtered rows and tables) is cut into groups of at most IPX_PNG_DEC_SCRATCH_MB, and each
-// group's scratch is released before the next group takes its own; one read-back of the per-file words at the end.
-static int png_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files, const std::vector<int> &idx, const std::vector<int> &slot,
-                            const std::vector<size_t> &frame_off, const std::vector<PngFileInfo> &info, uint8_t *frames, uint8_t *palettes,
-                            int *status)
-{
-    const int n = (int)idx.size();
-    if (n == 0) return IPX_OK;
-    PinnedBlocks pinned(ctx, s);
-    AsyncFree mem{s, {}};
-    // IPX_PNG_PAR=1 in the environment, read on every call: the inflate is png_inflate_par_kernel with the serial decoder behind it for
-    // the files it leaves; anything else keeps the serial kernel alone.  IPX_PNG_PAR_SUB: its sub-sequence size in bits (tests).
-    const bool par = env_int("IPX_PNG_PAR", 0) == 1;
-    const uint32_t par_sub = (uint32_t)std::min(kPngParSubMax, std::max(kPngParSubMin, env_int("IPX_PNG_PAR_SUB", kPngParSub)));
-    const size_t words = par ? (size_t)n * 3 : (size_t)n;        // the status words, then the parallel kernel's word pairs
-    uint32_t *dstate;
-    IPX_HIP(mem.get(&dstate, words * 4));
-    IPX_HIP(hipMemsetAsync(dstate, 0, words * 4, s));
-    uint32_t *dpar = dstate + n;
-    const int nslot = *std::max_element(slot.begin(), slot.end()) + 1;
-    if (palettes && nslot > 0) {     // one upload of every slot up to the last (zero for slots not decoded here)
-        uint8_t *hpal = pinned.get((size_t)nslot * 1024);
-        if (!hpal) return IPX_ERR_NOMEM;
-        memset(hpal, 0, (size_t)nslot * 1024);
-        for (int g = 0; g < n; g++)
-            if (slot[g] >= 0) memcpy(hpal + (size_t)slot[g] * 1024, info[idx[g]].pal, 1024);
-        IPX_HIP(hipMemcpyAsync(palettes, hpal, (size_t)nslot * 1024, hipMemcpyHostToDevice, s));
-    }
-    const size_t budget = (size_t)env_int("IPX_PNG_DEC_SCRATCH_MB", 8192) << 20;
-    auto run_group = [&](const std::vector<int> &group) -> int {     // positions in idx
-        const int m = (int)group.size();
-        // this group's scratch: the device blocks go back (stream-ordered) first, then the pinned block once the stream is past its copy
-        PinnedBlocks gpinned(ctx, s);
-        AsyncFree gmem{s, {}};
-        std::vector<PngDecDesc> desc(m);
-        std::vector<PngCrcPiece> pieces;
-        std::vector<PngChunk> chunks;
-        std::vector<size_t> foff(m);
-        size_t fbytes = 0, zbytes = 0, rbytes = 0;
-        for (int g = 0; g < m; g++) {
-            const PngFileInfo &f = info[idx[group[g]]];
-            PngDecDesc &d = desc[g];
-            memset(&d, 0, sizeof d);
-            foff[g] = fbytes;
-            d.zoff = zbytes;
-            d.roff = rbytes;
-            d.foff = (uint64_t)frame_off[group[g]];
-            d.zlen = f.idat_len;
-            d.zlast = f.idat_last;
-            d.raw_len = (uint32_t)f.raw_len;
-            d.w = (uint32_t)f.w;
-            d.h = (uint32_t)f.h;
-            d.rowbytes = f.rowbytes;
-            d.slot = (uint32_t)group[g];
-            d.ctype = (uint16_t)f.ctype;
-            d.depth = (uint16_t)f.depth;
-            d.kind = (uint16_t)f.kind;
-            d.trns = f.trns ? 1 : 0;
-            for (int k = 0; k < 3; k++) d.tv[k] = f.trns_v[k];
-            d.bpp = (uint16_t)f.bpp;
-            d.interlace = f.interlace ? 1 : 0;
-            // the chunks' CRC pieces; IDAT payloads land back to back at zoff
-            size_t zat = zbytes;
-            uint32_t ii = 0;
-            for (const PngSpan &c : f.crc) {
-                const uint32_t k = (uint32_t)chunks.size();
-                chunks.push_back(PngChunk{foff[g] + c.off, c.len, (uint32_t)group[g]});
-                const bool is_idat = ii < f.idat.size() && f.idat[ii].off == c.off + 4;
-                for (uint32_t p0 = 0; p0 < c.len; p0 += kCrcPiece) {
-                    const uint32_t p1 = std::min(c.len, p0 + kCrcPiece);
-                    PngCrcPiece pc;
-                    pc.src = foff[g] + c.off + p0;
-                    pc.len = p1 - p0;
-                    pc.chunk = k;
-                    pc.after = c.len - p1;
-                    pc.skip = p0 < 4 ? 4 - p0 : 0;
-                    pc.dst = is_idat && pc.len > pc.skip ? zat + (p0 + pc.skip - 4) : ~0ull;
-                    pieces.push_back(pc);
-                }
-                if (is_idat) { zat += f.idat[ii].len; ii++; }
-            }
-            fbytes += align256(f.file_len);
-            zbytes += align256((size_t)f.idat_len + 32);
-            rbytes += align256(f.raw_len);
-        }
-        uint8_t *hblob = gpinned.get(fbytes);
-        if (!hblob) return IPX_ERR_NOMEM;
-        const int rc = parallel_light(m, [&](int g) {
-            const int i = idx[group[g]];
-            memcpy(hblob + foff[g], files[i].data, info[i].file_len);
-        }, "png decode: host gather failed");
-        if (rc) return rc;
-        // the Adam7 files' descriptors go behind the others: each unfilter kernel takes its own run of the table
-        const int m0 = (int)(std::stable_partition(desc.begin(), desc.end(), [](const PngDecDesc &d) { return !d.interlace; }) - desc.begin());
-        uint8_t *dblob, *dz, *draw;
-        uint32_t *dacc;
-        PngCrcPiece *dpieces;
-        PngChunk *dchunks;
-        PngDecDesc *ddesc;
-        IPX_HIP(gmem.get(&dblob, fbytes));
-        IPX_HIP(gmem.get(&dz, zbytes));
-        IPX_HIP(gmem.get(&draw, rbytes));
-        IPX_HIP(gmem.get(&dacc, chunks.size() * 4));
-        IPX_HIP(gmem.get(&dpieces, pieces.size() * sizeof(PngCrcPiece)));
-        IPX_HIP(gmem.get(&dchunks, chunks.size() * sizeof(PngChunk)));
-        IPX_HIP(gmem.get(&ddesc, (size_t)m * sizeof(PngDecDesc)));
-        IPX_HIP(hipMemcpyAsync(dblob, hblob, fbytes, hipMemcpyHostToDevice, s));
-        IPX_HIP(hipMemcpyAsync(dpieces, pieces.data(), pieces.size() * sizeof(PngCrcPiece), hipMemcpyHostToDevice, s));
-        IPX_HIP(hipMemcpyAsync(dchunks, chunks.data(), chunks.size() * sizeof(PngChunk), hipMemcpyHostToDevice, s));
-        IPX_HIP(hipMemcpyAsync(ddesc, desc.data(), (size_t)m * sizeof(PngDecDesc), hipMemcpyHostToDevice, s));
-        IPX_HIP(hipMemsetAsync(dacc, 0, chunks.size() * 4, s));
-        IPX_HIP(launch_png_crc(dblob, dpieces, (int)pieces.size(), dacc, dz, s));
-        IPX_HIP(launch_png_crc_check(dblob, dchunks, (int)chunks.size(), dacc, dstate, s));
-        if (par) {
-            IPX_HIP(launch_png_inflate_par(dz, ddesc, m, draw, dstate, dpar, par_sub, s));
-            IPX_HIP(launch_png_inflate_redo(dz, ddesc, m, draw, dstate, dpar, s));
-        } else {
-            IPX_HIP(launch_png_inflate(dz, ddesc, m, draw, dstate, s));
-        }
-        IPX_HIP(launch_png_unfilter(ddesc, m0, draw, frames, dstate, s));
-        IPX_HIP(launch_png_unfilter_adam7(ddesc + m0, m - m0, draw, frames, dstate, s));
-        // the host vectors must outlive the copies: wait before they go
-        IPX_HIP(hipStreamSynchronize(s));
-        return IPX_OK;
-    };
-    std::vector<int> all(n);
-    std::iota(all.begin(), all.end(), 0);
-    const int rc = for_groups_under(all, budget, [&](int g) { return png_group_bytes(info[idx[g]]); }, run_group);
-    if (rc) return rc;
-    std::vector<uint32_t> st(words);
-    IPX_HIP(hipMemcpyAsync(st.data(), dstate, words * 4, hipMemcpyDeviceToHost, s));
-    IPX_HIP(hipStreamSynchronize(s));
-    if (par) {                                                   // ipx_png_decode_counts
-        long long c[5] = {n, 0, 0, 0, 0};
-        for (int g = 0; g < n; g++) {
-            const uint32_t a = st[n + 2 * g], b = st[n + 2 * g + 1];
-            if (b & kPngParRedo) { c[2]++; continue; }
-            c[1]++;
-            c[3] += a;
-            c[4] += b;
-        }
-        for (int k = 0; k < 5; k++) ctx->png_counts[k] += c[k];
-    }
-    for (int g = 0; g < n; g++) {
-        const uint32_t v = st[g];
-        status[idx[g]] = v == 0 ? IPX_OK : (v & ~kPngTrailing) ? IPX_ERR_INVALID : IPX_ERR_UNSUPPORTED;
-    }
-    return IPX_OK;
-}
-
-// ---- the entries -----------------------------------------------------------------------------------------------------------------
-extern "C" {
-
-int ipx_png_decode_counts(ipx_ctx *ctx, long long counts[5])
-{
-    clear_error();
-    if (!ctx || !counts) { set_error("ipx_png_decode_counts: bad argument"); return IPX_ERR_INVALID; }
-    for (int k = 0; k < 5; k++) counts[k] = ctx->png_counts[k].load();
-    return IPX_OK;
-}
-
-void ipx_png_frames_free(ipx_ctx *ctx, ipx_png_frames *o) { dev_blocks_free(ctx, o); }
-
-int ipx_png_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *files, int n, int *w, int *h, int *kind, ipx_png_batch *frames,
-                         int *status, ipx_png_frames **owner) try
-{
-    IPX_ENTER(ctx);
-    if (!files || n < 0 || !w || !h || !kind || !frames || !status || !owner || *w < 0 || *h < 0 || (*w == 0) != (*h == 0) ||
-        *kind < -1 || *kind >= kPngKinds) {
-        set_error("ipx_png_decode_batch: bad argument");
-        return IPX_ERR_INVALID;
-    }
-    *owner = nullptr;
-    memset(frames, 0, sizeof *frames);
-    if (n == 0) return IPX_OK;
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    std::vector<PngFileInfo> info(n);
-    int rc = png_parse_all(files, n, info, status);
-    if (rc) return rc;
-    int bw = *w, bh = *h, bk = *kind;
-    png_select(info, n, &bw, &bh, &bk, status);
-    std::vector<int> idx;
-    for (int i = 0; i < n; i++)
-        if (status[i] == IPX_OK) idx.push_back(i);
-    if (idx.empty()) return IPX_OK;
-    OwnedBlocks<ipx_png_frames> o(ctx, s);
-    const int kb = png_kind_bpp(bk);
-    const size_t fs = align256((size_t)bw * bh * kb);
-    uint8_t *dframes = nullptr, *dpal = nullptr;
-    hipError_t e = o.alloc(&dframes, fs * n);
-    if (e == hipSuccess && bk == IPX_PNG_PALETTED) e = o.alloc(&dpal, (size_t)n * 1024);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("ipx_png_decode_batch: device allocation failed: %s", hipGetErrorString(e));
-        return IPX_ERR_NOMEM;
-    }
-    if (dpal) IPX_HIP(hipMemsetAsync(dpal, 0, (size_t)n * 1024, s));
-    std::vector<size_t> foff(idx.size());
-    for (size_t g = 0; g < idx.size(); g++) foff[g] = (size_t)idx[g] * fs;
-    rc = png_decode_files(ctx, s, files, idx, idx, foff, info, dframes, dpal, status);     // frame i of file i
-    if (rc) return rc;
-    *w = bw;
-    *h = bh;
-    *kind = bk;
-    if (!any_ok(status, n)) return IPX_OK;
-    frames->pix = dframes;
-    frames->stride = bw * kb;
-    frames->frame_stride = fs;
-    frames->palettes = dpal;
-    *owner = o.release();
-    return IPX_OK;
-}
-IPX_CATCH_STATUS
-
-// n files of any sizes and kinds: every file that parses goes through ONE png_decode_files call, its frame at an offset of its own in
-// one block (256-byte aligned, rows tight) and, for a paletted file, its palette in the next free slot of a second block
-int ipx_png_decode_mixed(ipx_ctx *ctx, void *stream, const ipx_bytes *files, int n, ipx_png_frame *frames, int *status,
-                         ipx_png_frames **owner) try
-{
-    IPX_ENTER(ctx);
-    if (n < 0 || !owner || (n && (!files || !frames || !status))) { set_error("ipx_png_decode_mixed: bad argument"); return IPX_ERR_INVALID; }
-    *owner = nullptr;
-    if (n == 0) return IPX_OK;
-    if (n > 65535) { set_error("ipx_png_decode_mixed: at most 65535 files per call"); return IPX_ERR_UNSUPPORTED; }
-    memset(frames, 0, (size_t)n * sizeof *frames);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    std::vector<PngFileInfo> info(n);
-    int rc = png_parse_all(files, n, info, status);
-    if (rc) return rc;
-    std::vector<int> idx, slot;
-    std::vector<size_t> foff;
-    size_t fbytes = 0;
-    int npal = 0;
-    for (int i = 0; i < n; i++) {
-        if (status[i] != IPX_OK) continue;
-        idx.push_back(i);
-        foff.push_back(fbytes);
-        slot.push_back(info[i].kind == IPX_PNG_PALETTED ? npal++ : -1);
-        fbytes += align256((size_t)info[i].w * info[i].h * png_kind_bpp(info[i].kind));
-    }
-    if (idx.empty()) return IPX_OK;
-    OwnedBlocks<ipx_png_frames> o(ctx, s);
-    uint8_t *dframes = nullptr, *dpal = nullptr;
-    hipError_t e = o.alloc(&dframes, fbytes);
-    if (e == hipSuccess && npal) e = o.alloc(&dpal, (size_t)npal * 1024);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("ipx_png_decode_mixed: device allocation failed: %s", hipGetErrorString(e));
-        return IPX_ERR_NOMEM;
-    }
-    rc = png_decode_files(ctx, s, files, idx, slot, foff, info, dframes, dpal, status);
-    if (rc) return rc;
-    if (!any_ok(status, n)) return IPX_OK;
-    for (size_t g = 0; g < idx.size(); g++) {
-        const int i = idx[g];
-        if (status[i] != IPX_OK) continue;
-        const PngFileInfo &f = info[i];
-        frames[i] = ipx_png_frame{f.w, f.h, f.kind, dframes + foff[g], f.w * png_kind_bpp(f.kind), slot[g] >= 0 ? dpal + (size_t)slot[g] * 1024 : nullptr};
-    }
-    *owner = o.release();
-    return IPX_OK;
-}
-IPX_CATCH_STATUS
-
-}  // extern "C"
-
-// ---- the PNG leg -----------------------------------------------------------------------------------------------------------------
-
-extern "C" {
-
-// The PNG task's GPU leg from the uploads on: the host parse of every file, then per kind, per decode group (IPX_HOST_CHUNK_PNG_DEC
-// files, at most ~4 GiB of frames): upload, CRC, inflate and unfilter into HBM; then per chunk of IPX_HOST_CHUNK_PNG frames the
-// operators on frames of that kind and png.Encode of all three outputs (run_chunk).  The operators run on every slot of a chunk (a failed file's slot
-// holds whatever its frame holds); only OK files' streams are handed out.
-// (the body of ipx_plan_run_png_png -- texts == NULL: no text launch -- and of ipx_plan_run_png_png_texts, where texts[i] is drawn on
-// file i's watermark frame between the operators and the encoder: one text set per call, indexed by the caller's index; the files are
-// sorted by kind here, so a group is a selection through its idx and run_chunk takes texts, statuses and output slots through it)
-static int run_png_png(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, const ipx_text *texts,
-                       ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result)
-{
-    *result = nullptr;
-    const int sw = pl->p.sw, sh = pl->p.sh;
-    const PlanOutputs outs(pl, resize_out, thumb_out, wm_out, Codec::Png, Codec::Png, Codec::Png);
-    outs.clear(n);
-    if (n == 0) return IPX_OK;
-    std::vector<PngFileInfo> info(n);
-    int rc = png_parse_all(files, n, info, status);
-    if (rc) return rc;
-    for (int i = 0; i < n; i++)
-        if (status[i] == IPX_OK && (info[i].w != sw || info[i].h != sh)) status[i] = IPX_ERR_UNSUPPORTED;
-    const size_t per_out = outs.frame_bytes();
-    const int chunk_max = std::max(1, env_int("IPX_HOST_CHUNK_PNG", 64)), group_max = std::max(1, env_int("IPX_HOST_CHUNK_PNG_DEC", 1024));
-    ResultOwner res(ctx);
-    LaneLease lane(ctx);
-    hipStream_t s = lane->stream;
-    LegTexts lt;                        // one set per call, indexed by the caller's index: a group's chunks select through its idx
-    if ((rc = lt.build(s, who, pl, outs, texts, all_files(n), false))) return rc;
-    for (int kind = 0; kind < kPngKinds; kind++) {
-        std::vector<int> of_kind;
-        for (int i = 0; i < n; i++)
-            if (status[i] == IPX_OK && info[i].kind == kind) of_kind.push_back(i);
-        if (of_kind.empty()) continue;
-        const int kb = png_kind_bpp(kind);
-        const size_t fs = align256((size_t)sw * sh * kb);
-        const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)group_max, ((size_t)4 << 30) / (fs + 1024)));
-        const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)chunk_max, per_out ? ((size_t)1 << 30) / per_out : (size_t)chunk_max));
-        for (size_t g0 = 0; g0 < of_kind.size(); g0 += group) {
-            const int m = (int)std::min<size_t>(group, of_kind.size() - g0);
-            std::vector<int> idx(of_kind.begin() + g0, of_kind.begin() + g0 + m), slot(m);
-            std::vector<size_t> foff(m);
-            for (int g = 0; g < m; g++) { slot[g] = g; foff[g] = (size_t)g * fs; }
-            StreamSync sync{s};
-            AsyncFree mem{s, {}};
-            uint8_t *dfr, *dpal = nullptr;
-            IPX_HIP(mem.get(&dfr, fs * m));
-            if (kind == IPX_PNG_PALETTED) IPX_HIP(mem.get(&dpal, (size_t)1024 * m));
-            rc = png_decode_files(ctx, s, files, idx, slot, foff, info, dfr, dpal, status);
-            if (rc) return rc;
-            for (int c0 = 0; c0 < m; c0 += chunk) {
-                const int cm = std::min(chunk, m - c0);
-                bool any = false;
-                for (int g = c0; g < c0 + cm; g++) any |= status[idx[g]] == IPX_OK;
-                if (!any) continue;
-                AsyncFree omem{s, {}};
-                uint8_t *dout = nullptr;
-                if (per_out) IPX_HIP(omem.get(&dout, per_out * cm));
-                const BatchSrc d = packed_src(src_of_png(kind), dfr, sw * kb, fs, dpal).from(c0);
-                // (idx outlives the group's wait for the stream, and with it the copy of this chunk's slice in omem)
-                rc = run_chunk(ctx, s, pl, outs, dout, cm, d, FileSel{idx.data(), 0, m}, c0, cm, &lt, &omem, 0, status, res);
-                if (rc) return rc;
-            }
-        }
-    }
-    *result = res.release();
-    return IPX_OK;
-}
-
-int ipx_plan_run_png_png(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, ipx_bytes *resize_out, ipx_bytes *thumb_out,
-                         ipx_bytes *wm_out, int *status, ipx_jpeg_result **result) try
-{
-    IPX_ENTER(ctx);
-    if (const int rc = leg_entry_check("ipx_plan_run_png_png", pl, n, files, status, result, false, nullptr)) return rc;
-    return run_png_png("ipx_plan_run_png_png", ctx, pl, n, files, nullptr, resize_out, thumb_out, wm_out, status, result);
-}
-IPX_CATCH_STATUS
-
-int ipx_plan_run_png_png_texts(ipx_ctx *ctx, const ipx_plan *pl, int n, const ipx_bytes *files, const ipx_text *texts, ipx_bytes *resize_out,
-                               ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result) try
-{
-    IPX_ENTER(ctx);
-    if (const int rc = leg_entry_check("ipx_plan_run_png_png_texts", pl, n, files, status, result, true, texts)) return rc;
-    return run_png_png("ipx_plan_run_png_png_texts", ctx, pl, n, files, texts, resize_out, thumb_out, wm_out, status, result);
-}
-IPX_CATCH_STATUS
-
-}  // extern "C"
-
-// ---- the mixed-size PNG leg ------------------------------------------------------------------------------------------------------
-
-namespace {
-// the plans of one call, one per frame size, from the context's cache; handed back on every way out
-struct SizePlans {
-    struct Held { ipx_plan *pl; int cached; };
-    ipx_ctx *ctx;
-    std::map<std::pair<int, int>, Held> held;
-    explicit SizePlans(ipx_ctx *c) : ctx(c) {}
-    SizePlans(const SizePlans &) = delete;
-    ~SizePlans()
-    {
-        for (auto &kv : held)
-            if (kv.second.pl) ipx_plan_release(ctx, kv.second.pl, kv.second.cached);
-    }
-};
-
-// what output k of a plan costs a chunk: the frame itself and the encoder's scratch for it -- the filtered stream, a word of match
-// scratch per filtered byte, and the frame's region
-size_t mixed_out_cost(const OutShape &sh)
-{
-    if (!sh.bytes || sh.w <= 0 || sh.h <= 0) return 0;
-    const size_t filt = (size_t)sh.h * (1 + 4 * (size_t)sh.w);
-    return align256(sh.bytes) + 5 * align256(filt) + align256(kPngSegBase + png_segs_bytes(sh.w, sh.h, 4) + kPngTailBytes);
-}
-}  // namespace
-
-extern "C" {
-
-// The PNG leg for uploads of any sizes and kinds: the host parse; a plan per size from the context's cache; the cut of
-// ipx_png_mixed_plan.h (order by size and kind, decode groups, chunks, runs); per group ONE png_decode_files call whatever it holds;
-// per chunk the operators once per run, into the run's slice of three arenas, its texts in one launch from a set clipped to its size;
-// then one mixed-size png.Encode per present output over every frame of the chunk.  The host does not wait for the stream between
-// runs beyond what those stages contain (the upload of a run's texts).
-int ipx_run_png_png_mixed(ipx_ctx *ctx, const ipx_pool_ops *ops, int n, const ipx_bytes *files, const ipx_text *texts,
-                          ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result) try
-{
-    static const char who[] = "ipx_run_png_png_mixed";
-    IPX_ENTER(ctx);
-    if (!ops || n < 0 || !result || (n && (!files || !status))) { set_error("%s: bad argument", who); return IPX_ERR_INVALID; }
-    *result = nullptr;
-    if (ops->sw != 0 || ops->sh != 0) { set_error("%s: ops->sw and ops->sh must be 0: every file's own size is used", who); return IPX_ERR_INVALID; }
-    if (ops->glyphs || ops->n_glyphs) {
-        set_error("%s: ops->glyphs must be NULL: a positioned glyph list is anchored for one frame size; pass a text per file", who);
-        return IPX_ERR_INVALID;
-    }
-    if (texts)
-        if (const int rc = texts_check(who, texts, n)) return rc;
-    ipx_bytes *const dst[kOuts] = {resize_out, thumb_out, wm_out};
-    for (int k = 0; k < kOuts; k++)
-        if (dst[k])
-            for (int i = 0; i < n; i++) dst[k][i] = ipx_bytes{nullptr, 0};
-    if (n == 0) return IPX_OK;
-    std::vector<PngFileInfo> info(n);
-    int rc = png_parse_all(files, n, info, status);
-    if (rc) return rc;
-    // a plan per size; files of a size no plan can be made for get ipx_plan_create's status, alone.  Every distinct size of the call
-    // holds its plan until the call returns: at most one per file (65535), of which the context's cache keeps IPX_PLAN_CACHE_MAX (256) and
-    // the rest live and die with this call -- a call with more sizes than that also turns the cache over once
-    SizePlans plans(ctx);
-    std::map<std::pair<int, int>, int> plan_rc;
-    std::vector<ipx_plan *> plan_of(n, nullptr);
-    for (int i = 0; i < n; i++) {
-        if (status[i] != IPX_OK) continue;
-        const std::pair<int, int> key(info[i].w, info[i].h);
-        auto it = plan_rc.find(key);
-        if (it == plan_rc.end()) {
-            ipx_pool_ops o = *ops;
-            o.sw = key.first;
-            o.sh = key.second;
-            SizePlans::Held hd{nullptr, 0};
-            const int prc = ipx_plan_acquire(ctx, &o, &hd.pl, &hd.cached);
-            // a size the operators cannot be planned for is that size's verdict; anything else (memory, the device) fails the call
-            if (prc != IPX_OK && prc != IPX_ERR_INVALID && prc != IPX_ERR_UNSUPPORTED) return prc;
-            if (prc == IPX_OK) plans.held[key] = hd;
-            it = plan_rc.emplace(key, prc).first;
-        }
-        if (it->second != IPX_OK) { status[i] = it->second; continue; }
-        plan_of[i] = plans.held[key].pl;
-    }
-    auto out_fs = [&](int i, int k) -> size_t { return dst[k] ? align256(out_shape(plan_of[i]->info, k).bytes) : 0; };
-    std::vector<MixItem> items(n);
-    for (int i = 0; i < n; i++) {
-        MixItem &it = items[i];
-        it = MixItem{status[i] == IPX_OK, info[i].w, info[i].h, info[i].kind, 0, 0};
-        if (!it.ok) continue;
-        it.frame_bytes = align256((size_t)it.w * it.h * png_kind_bpp(it.kind)) + 1024;
-        for (int k = 0; k < kOuts; k++)
-            if (dst[k]) it.chunk_bytes += mixed_out_cost(out_shape(plan_of[i]->info, k));
-    }
-    const int group_max = std::min(65535, std::max(1, env_int("IPX_HOST_CHUNK_PNG_DEC", 1024)));
-    const size_t chunk_bytes = (size_t)std::max(0, env_int("IPX_PNG_MIXED_CHUNK_MB", 1024)) << 20;
-    const MixCut cut = png_mixed_cut(items.data(), n, group_max, (size_t)4 << 30, chunk_bytes);
-    ResultOwner res(ctx);
-    LaneLease lane(ctx);
-    hipStream_t s = lane->stream;
-    for (const MixGroup &grp : cut.groups) {
-        const int m = grp.n;
-        std::vector<int> idx(cut.order.begin() + grp.first, cut.order.begin() + grp.first + m), slot(m);
-        std::vector<size_t> foff(m);
-        size_t fbytes = 0;
-        int npal = 0;
-        for (int g = 0; g < m; g++) {
-            const PngFileInfo &f = info[idx[g]];
-            foff[g] = fbytes;
-            slot[g] = f.kind == IPX_PNG_PALETTED ? npal++ : -1;
-            fbytes += align256((size_t)f.w * f.h * png_kind_bpp(f.kind));
-        }
-        StreamSync sync{s};
-        AsyncFree mem{s, {}};
-        uint8_t *dfr, *dpal = nullptr;
-        IPX_HIP(mem.get(&dfr, fbytes));
-        if (npal) IPX_HIP(mem.get(&dpal, (size_t)1024 * npal));
-        rc = png_decode_files(ctx, s, files, idx, slot, foff, info, dfr, dpal, status);     // every size and kind of the group at once
-        if (rc) return rc;
-        for (int c = grp.chunk0; c < grp.chunk0 + grp.nchunks; c++) {
-            const MixChunk &ch = cut.chunks[c];
-            const int *file = cut.order.data() + ch.first;          // the chunk's files, by the caller's index
-            bool any = false;
-            for (int p = 0; p < ch.n; p++) any |= status[file[p]] == IPX_OK;
-            if (!any) continue;
-            AsyncFree omem{s, {}};
-            // the chunk's three arenas: file p's frame of output k at arena[k] + off[k][p]
-            std::vector<size_t> off[kOuts];
-            uint8_t *arena[kOuts] = {nullptr, nullptr, nullptr};
-            for (int k = 0; k < kOuts; k++) {
-                off[k].resize(ch.n);
-                size_t total = 0;
-                for (int p = 0; p < ch.n; p++) { off[k][p] = total; total += out_fs(file[p], k); }
-                if (total) IPX_HIP(omem.get(&arena[k], total));
-            }
-            for (int r = ch.run0; r < ch.run0 + ch.nruns; r++) {
-                const MixRun &run = cut.runs[r];
-                const int g0 = run.first - grp.first, p0 = run.first - ch.first, i0 = cut.order[run.first];
-                const PngFileInfo &f = info[i0];
-                const ipx_plan *pl = plan_of[i0];
-                const int kb = png_kind_bpp(f.kind);
-                const BatchSrc d = packed_src(src_of_png(f.kind), dfr + foff[g0], f.w * kb, align256((size_t)f.w * f.h * kb),
-                                              slot[g0] >= 0 ? dpal + (size_t)slot[g0] * 1024 : nullptr);
-                BatchDst bd;
-                for (int k = 0; k < kOuts; k++)
-                    if (const size_t fs = out_fs(i0, k)) { bd.out[k] = arena[k] + off[k][p0]; bd.frame_stride[k] = fs; }
-                rc = run_dev_src(ctx, s, pl, run.n, d, bd);
-                if (rc) return rc;
-                if (texts && pl->p.do_watermark && bd.out[kOutWm]) {
-                    const OutShape sh = out_shape(pl->info, kOutWm);
-                    std::vector<ipx_text> own(run.n);
-                    for (int q = 0; q < run.n; q++) own[q] = texts[file[p0 + q]];
-                    ipx_textset ts;                             // (its memory goes back in stream order, behind the launch)
-                    if ((rc = textset_build(s, who, own.data(), run.n, sh.w, sh.h, &ts))) return rc;
-                    if ((rc = dev_composite_texts(s, &omem, bd.out[kOutWm], sh.w * 4, bd.frame_stride[kOutWm], run.n, ts, 0, nullptr))) return rc;
-                }
-            }
-            for (int k = 0; k < kOuts; k++) {
-                std::vector<ipx_rgba_frame> fr;
-                std::vector<int> owner_of;
-                for (int p = 0; p < ch.n; p++) {
-                    const OutShape sh = out_shape(plan_of[file[p]]->info, k);
-                    if (!out_fs(file[p], k) || sh.w <= 0 || sh.h <= 0) continue;
-                    fr.push_back(ipx_rgba_frame{arena[k] + off[k][p], sh.w, sh.h, sh.w * 4});
-                    owner_of.push_back(file[p]);
-                }
-                if (fr.empty()) continue;
-                std::vector<size_t> offs(fr.size()), lens(fr.size());
-                uint8_t *blob = nullptr;
-                rc = png_encode_mixed_core(ctx, s, fr.data(), (int)fr.size(), &blob, offs.data(), lens.data());
-                if (rc) return rc;
-                res.add(blob);
-                for (size_t j = 0; j < fr.size(); j++)
-                    if (status[owner_of[j]] == IPX_OK) dst[k][owner_of[j]] = ipx_bytes{blob + offs[j], lens[j]};
-            }
-        }
-    }
-    *result = res.release();
-    return IPX_OK;
-}
-IPX_CATCH_STATUS
-
-}  // extern "C"

@@ -1,7 +1,7 @@
 // ipx_png_dec_host.cpp -- the host half of png.Decode: image/png's reader.go over the chunk headers only (signature, IHDR, PLTE, tRNS,
 // the IDAT run, IEND; unknown ancillary chunks skipped), never the image data.  It decides the rules that need no inflate, the file's
-// frame layout and raw length, the palette with tRNS applied, and the chunk spans the CRC kernel checks.  Kernels and entries:
-// ipx_png_dec.hip.  DESIGN.md section 4.10.
+// frame layout and raw length, the palette with tRNS applied, and the chunk spans the CRC kernel checks.  Kernels: ipx_png_dec.hip;
+// driver and entries: ipx_png_dec_runtime.hip.  DESIGN.md section 4.10.
 #include <cstring>
 
 #include "ipx_internal.h"

@@ -1,4 +1,4 @@
-// ipx_png_dec_par.hip -- the two inflate kernels taken under IPX_PNG_PAR=1 (ipx_png_dec.hip reads the switch).  png_inflate_par_kernel: the
+// ipx_png_dec_par.hip -- the two inflate kernels taken under IPX_PNG_PAR=1 (ipx_png_dec_runtime.hip reads the switch).  png_inflate_par_kernel: the
 // inflate of ipx_png_inflate.h with a Huffman block's body parsed by the 64 lanes side by side.  One workgroup of one wave per file; the
 // zlib header, the block headers, stored blocks, the tables, the staging, the flushes and the end of the stream are that header's
 // wave-uniform code, the serial kernel's steps.  png_inflate_redo_kernel, at the end: the serial walk for the files the first one leaves.

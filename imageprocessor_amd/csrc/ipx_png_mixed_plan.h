@@ -1,4 +1,4 @@
-// ipx_png_mixed_plan.h -- how the mixed-size PNG leg (ipx_run_png_png_mixed, ipx_png_dec.hip) orders its files and cuts them: files ->
+// ipx_png_mixed_plan.h -- how the mixed-size PNG leg (ipx_run_png_png_mixed, ipx_png_legs.hip) orders its files and cuts them: files ->
 // decode groups -> output chunks -> runs of one size and kind.  Plain host C++ with no dependency on the runtime, so that
 // tools/png_mixed_plan_test.cpp can hold it to its rules as a program of its own.  DESIGN.md section 4.10.
 #pragma once

@@ -1,4 +1,4 @@
-"""PNG uploads of mixed sizes in one GPU batch (csrc/ipx_png_mixed.hip, the mixed entries of csrc/ipx_png_dec.hip):
+"""PNG uploads of mixed sizes in one GPU batch (csrc/ipx_png_mixed.hip, the mixed entries of csrc/ipx_png_dec_runtime.hip and csrc/ipx_png_legs.hip):
 ipx_png_decode_mixed against tests/png_decode_model.py, ipx_png_encode_mixed_dev byte for byte against tests/png_model.py and the uniform
 entries, and ipx_run_png_png_mixed against the uniform leg run per size group with a plan of that size (the uniform leg is itself pinned
 to the models by tests/test_png_decode_gpu.py and tests/test_texts_gpu.py)."""

@@ -1,5 +1,6 @@
 // png_mixed_plan_test.cpp -- the mixed-size PNG leg's ordering and cutting (imageprocessor_amd/csrc/ipx_png_mixed_plan.h: files ->
-// decode groups -> chunks -> runs) held to its rules as a program of its own: plain g++, no GPU, no runtime.
+// decode groups -> chunks -> runs) and the two layouts of decoded frames and palettes (ipx_png_layout.h: strided, packed), compared
+// with the four loops they replaced, held to their rules as a program of its own: plain g++, no GPU, no runtime.
 //   g++ -std=c++17 -fsanitize=address,undefined -o png_mixed_plan_test tools/png_mixed_plan_test.cpp && ./png_mixed_plan_test
 // Prints "png mixed plan ok" and exits 0, or says what broke and exits 1.  tests/test_png_mixed_host.py runs it.
 #include <cstdio>
@@ -7,6 +8,7 @@
 #include <random>
 #include <vector>
 
+#include "../imageprocessor_amd/csrc/ipx_png_layout.h"
 #include "../imageprocessor_amd/csrc/ipx_png_mixed_plan.h"
 
 using namespace ipx;
@@ -82,8 +84,188 @@ static void check_cut(const char *name, const std::vector<MixItem> &items, int g
     for (int i = 0; i < n; i++) CHECK(in_run[i] == (items[i].ok ? 1 : 0), "%s: file %d is in %d runs", name, i, in_run[i]);
 }
 
+// ---- where decoded frames and palettes go (ipx_png_layout.h) ------------------------------------------------------------------------
+static size_t a256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// the rules every layout keeps; packed: also that the frames lie back to back from 0 and the slots are dense over the paletted files
+static void check_layout(const char *name, const PngFrameLayout &at, const std::vector<int> &idx, const std::vector<size_t> &frame_bytes, bool packed,
+                         const std::vector<bool> *paletted)
+{
+    const size_t m = idx.size();
+    CHECK(at.idx == idx && at.pal_slot.size() == m && at.off.size() == m, "%s: the vectors do not cover the selection", name);
+    if (at.pal_slot.size() != m || at.off.size() != m) return;
+    int next_slot = 0;
+    for (size_t g = 0; g < m; g++) {
+        CHECK(at.off[g] % 256 == 0, "%s: offset %zu of position %zu is not aligned", name, at.off[g], g);
+        const size_t end = at.off[g] + frame_bytes[g];
+        CHECK(end <= (g + 1 < m ? at.off[g + 1] : at.bytes), "%s: frame %zu runs into the next", name, g);
+        if (packed) {
+            CHECK(at.off[g] == (g ? at.off[g - 1] + a256(frame_bytes[g - 1]) : 0), "%s: frame %zu is not packed", name, g);
+            CHECK(at.pal_slot[g] == ((*paletted)[g] ? next_slot : -1), "%s: slot %d at position %zu", name, at.pal_slot[g], g);
+            if ((*paletted)[g]) next_slot++;
+        }
+    }
+    if (m) CHECK(at.bytes == at.off[m - 1] + a256(frame_bytes[m - 1]), "%s: the last frame does not end at bytes", name);
+    else CHECK(at.bytes == 0 && at.pal_slots == 0, "%s: an empty selection takes room", name);
+    if (packed) CHECK(at.pal_slots == next_slot, "%s: %d palette slots for %d paletted files", name, at.pal_slots, next_slot);
+}
+
+static void check_strided(const char *name, const std::vector<int> &idx, size_t fs, bool by_index)
+{
+    const PngFrameLayout at = png_layout_strided(idx, fs, by_index);
+    check_layout(name, at, idx, std::vector<size_t>(idx.size(), fs), false, nullptr);
+    for (size_t g = 0; g < idx.size() && g < at.off.size(); g++) {
+        const int k = by_index ? idx[g] : (int)g;
+        CHECK(at.off[g] == (size_t)k * fs && at.pal_slot[g] == k, "%s: position %zu at offset %zu, slot %d", name, g, at.off[g], at.pal_slot[g]);
+    }
+    if (!idx.empty()) CHECK(at.pal_slots == (by_index ? idx.back() : (int)idx.size() - 1) + 1, "%s: %d palette slots", name, at.pal_slots);
+}
+
+// The four loops the builders replaced, as their callers had them.  What each handed to the decode driver: idx, slot, frame_off; the
+// driver uploaded max(slot) + 1 palette slots; the packed callers allocated fbytes and npal slots, run_png_png fs * m and m.
+struct OldLayout { std::vector<int> idx, slot; std::vector<size_t> foff; };
+static int old_nslot(const OldLayout &o) { return o.idx.empty() ? 0 : *std::max_element(o.slot.begin(), o.slot.end()) + 1; }
+static OldLayout old_decode_batch(const std::vector<int> &status, size_t fs)
+{
+    std::vector<int> idx;
+    for (int i = 0; i < (int)status.size(); i++)
+        if (status[i] == 0) idx.push_back(i);
+    std::vector<size_t> foff(idx.size());
+    for (size_t g = 0; g < idx.size(); g++) foff[g] = (size_t)idx[g] * fs;
+    return OldLayout{idx, idx, foff};
+}
+static OldLayout old_run_png_png(const std::vector<int> &of_kind, size_t g0, int m, size_t fs)
+{
+    std::vector<int> idx(of_kind.begin() + g0, of_kind.begin() + g0 + m), slot(m);
+    std::vector<size_t> foff(m);
+    for (int g = 0; g < m; g++) { slot[g] = g; foff[g] = (size_t)g * fs; }
+    return OldLayout{idx, slot, foff};
+}
+struct OldFile { int status, w, h, bpp; bool paletted; };
+static OldLayout old_decode_mixed(const std::vector<OldFile> &info, size_t *fbytes_out, int *npal_out)
+{
+    std::vector<int> idx, slot;
+    std::vector<size_t> foff;
+    size_t fbytes = 0;
+    int npal = 0;
+    for (int i = 0; i < (int)info.size(); i++) {
+        if (info[i].status != 0) continue;
+        idx.push_back(i);
+        foff.push_back(fbytes);
+        slot.push_back(info[i].paletted ? npal++ : -1);
+        fbytes += a256((size_t)info[i].w * info[i].h * info[i].bpp);
+    }
+    *fbytes_out = fbytes;
+    *npal_out = npal;
+    return OldLayout{idx, slot, foff};
+}
+static OldLayout old_run_mixed(const std::vector<OldFile> &info, const std::vector<int> &order, int first, int m, size_t *fbytes_out, int *npal_out)
+{
+    std::vector<int> idx(order.begin() + first, order.begin() + first + m), slot(m);
+    std::vector<size_t> foff(m);
+    size_t fbytes = 0;
+    int npal = 0;
+    for (int g = 0; g < m; g++) {
+        const OldFile &f = info[idx[g]];
+        foff[g] = fbytes;
+        slot[g] = f.paletted ? npal++ : -1;
+        fbytes += a256((size_t)f.w * f.h * f.bpp);
+    }
+    *fbytes_out = fbytes;
+    *npal_out = npal;
+    return OldLayout{idx, slot, foff};
+}
+static void same_layout(const char *name, const PngFrameLayout &at, const OldLayout &o)
+{
+    CHECK(at.idx == o.idx && at.pal_slot == o.slot && at.off == o.foff, "%s: not what the old loop made", name);
+    CHECK(at.pal_slots == old_nslot(o), "%s: %d palette slots, the old loop's upload covered %d", name, at.pal_slots, old_nslot(o));
+}
+
+static void layout_cases()
+{
+    // the empty selection, one file, a zero-byte frame size
+    for (int by_index = 0; by_index < 2; by_index++) {
+        check_strided("strided, empty", {}, 512, by_index);
+        check_strided("strided, one file", {3}, 256, by_index);
+        check_strided("strided, zero-byte frames", {0, 2, 5}, 0, by_index);
+        check_strided("strided, gaps", {1, 2, 7, 9}, 1024, by_index);
+    }
+    {
+        const PngFrameLayout at = png_layout_strided({1, 2, 7, 9}, 1024, true);
+        CHECK(at.off[2] == 7 * 1024 && at.pal_slot[3] == 9 && at.pal_slots == 10 && at.bytes == 10 * 1024, "strided by index: a known case");
+        const PngFrameLayout bt = png_layout_strided({1, 2, 7, 9}, 1024, false);
+        CHECK(bt.off[2] == 2 * 1024 && bt.pal_slot[3] == 3 && bt.pal_slots == 4 && bt.bytes == 4 * 1024, "strided by position: a known case");
+    }
+    {
+        // files 4, 0, 6, 2 of 24, 0, 300 and 256 bytes; 4 and 6 paletted
+        const std::vector<int> idx = {4, 0, 6, 2};
+        const size_t bytes_of[7] = {0, 0, 256, 0, 24, 0, 300};
+        const bool pal_of[7] = {false, false, false, false, true, false, true};
+        const PngFrameLayout at = png_layout_packed(idx, [&](int i) { return PngFrameNeed{bytes_of[i], pal_of[i]}; });
+        const std::vector<bool> pal = {true, false, true, false};
+        check_layout("packed, known", at, idx, {24, 0, 300, 256}, true, &pal);
+        CHECK(at.off == (std::vector<size_t>{0, 256, 256, 768}) && at.bytes == 1024, "packed: a known case");
+        CHECK(at.pal_slot == (std::vector<int>{0, -1, 1, -1}) && at.pal_slots == 2, "packed: the known case's slots");
+        const PngFrameLayout e = png_layout_packed({}, [&](int) { return PngFrameNeed{1, true}; });
+        check_layout("packed, empty", e, {}, {}, true, nullptr);
+        const PngFrameLayout one = png_layout_packed({5}, [&](int) { return PngFrameNeed{1, false}; });
+        CHECK(one.off == std::vector<size_t>{0} && one.bytes == 256 && one.pal_slot == std::vector<int>{-1} && one.pal_slots == 0, "packed: one file");
+    }
+    // seeded random batches against the old loops
+    std::mt19937 rng(20241021);
+    for (int round = 0; round < 400; round++) {
+        const int n = (int)(rng() % 40);
+        std::vector<OldFile> info(n);
+        std::vector<int> status(n);
+        for (int i = 0; i < n; i++) {
+            const int bpps[4] = {1, 2, 4, 8};
+            info[i] = OldFile{rng() % 4 == 0 ? -1 : 0, 1 + (int)(rng() % 40), 1 + (int)(rng() % 30), bpps[rng() % 4], rng() % 3 == 0};
+            if (info[i].paletted) info[i].bpp = 1;
+            status[i] = info[i].status;
+        }
+        auto need = [&](int i) { return PngFrameNeed{(size_t)info[i].w * info[i].h * info[i].bpp, info[i].paletted}; };
+        const size_t fs = 256 * (size_t)(rng() % 20);
+        // ipx_png_decode_batch
+        const OldLayout ob = old_decode_batch(status, fs);
+        same_layout("decode batch", png_layout_strided(ob.idx, fs, true), ob);
+        check_strided("decode batch", ob.idx, fs, true);
+        // run_png_png: a group of the OK files
+        if (!ob.idx.empty()) {
+            const size_t g0 = rng() % ob.idx.size();
+            const int m = 1 + (int)(rng() % (ob.idx.size() - g0));
+            const OldLayout og = old_run_png_png(ob.idx, g0, m, fs);
+            const PngFrameLayout at = png_layout_strided(og.idx, fs, false);
+            same_layout("run_png_png", at, og);
+            CHECK(at.bytes == fs * m && at.pal_slots == m, "run_png_png: %zu bytes and %d slots for %d files", at.bytes, at.pal_slots, m);
+            check_strided("run_png_png", og.idx, fs, false);
+        }
+        // ipx_png_decode_mixed
+        size_t fbytes;
+        int npal;
+        const OldLayout om = old_decode_mixed(info, &fbytes, &npal);
+        const PngFrameLayout am = png_layout_packed(om.idx, need);
+        same_layout("decode mixed", am, om);
+        CHECK(am.bytes == fbytes && am.pal_slots == npal, "decode mixed: %zu bytes, %d slots", am.bytes, am.pal_slots);
+        std::vector<size_t> fb;
+        std::vector<bool> pal;
+        for (int i : om.idx) { fb.push_back(need(i).bytes); pal.push_back(info[i].paletted); }
+        check_layout("decode mixed", am, om.idx, fb, true, &pal);
+        // ipx_run_png_png_mixed: a group of a shuffled order of the OK files
+        std::vector<int> order = om.idx;
+        std::shuffle(order.begin(), order.end(), rng);
+        if (!order.empty()) {
+            const int first = (int)(rng() % order.size()), m = 1 + (int)(rng() % (order.size() - first));
+            const OldLayout ox = old_run_mixed(info, order, first, m, &fbytes, &npal);
+            const PngFrameLayout ax = png_layout_packed(ox.idx, need);
+            same_layout("run mixed", ax, ox);
+            CHECK(ax.bytes == fbytes && ax.pal_slots == npal, "run mixed: %zu bytes, %d slots", ax.bytes, ax.pal_slots);
+        }
+    }
+}
+
 int main()
 {
+    layout_cases();
     // n = 0, and nothing but failed files
     {
         const MixCut c = png_mixed_cut(nullptr, 0, 1024, 1u << 30, 1u << 30);
