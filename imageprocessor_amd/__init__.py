@@ -773,6 +773,47 @@ class Context:
                 info["cr"] = self._grab(b.cr, n, b.c_frame_stride)[:, :crows * b.cstride].reshape(n, crows, b.cstride)
         return done(info), st
 
+    def jpeg_decode_mixed(self, files, download=True):
+        """image.Decode of JPEG byte strings of ANY sizes and samplings, one decode pass per sampling class (ipx_jpeg_decode_mixed).
+        A file given as None goes in as a NULL entry.  -> (frames, status list); frames[i] is None for a non-OK file, else dict(w, h,
+        ratio, ystride, cstride, y, cb, cr) with the
+        planes over the image's MCU-padded extent as rows x stride uint8 arrays, cb and cr None for a Gray file (download=True), or the
+        device pointers.  With download=False a third value, free(), releases the planes."""
+        n = len(files)
+        fr = (_lib.JpegFrame * max(n, 1))()
+        status = (C.c_int * max(n, 1))()
+        owner = C.c_void_p()
+        arr = _bytes_array([f if f is not None else b"" for f in files])
+        for i, f in enumerate(files):
+            if f is None:                       # an entry with data == NULL: IPX_ERR_INVALID for that file alone
+                arr[i].data = None
+        _check(lib().ipx_jpeg_decode_mixed(self.handle, None, arr, n, fr, status, C.byref(owner)))
+        free = lambda: lib().ipx_jpeg_planes_free(self.handle, owner)
+
+        def grab(ptr, rows, stride):
+            a = np.empty((rows, stride), np.uint8)
+            _check(lib().ipx_memcpy_d2h(self.handle, a.ctypes.data, ptr, a.nbytes))
+            return a
+        out = []
+        try:
+            for i in range(n):
+                f = fr[i]
+                if not f.y:
+                    out.append(None)
+                    continue
+                d = {"w": f.w, "h": f.h, "ratio": f.ratio, "ystride": f.ystride, "cstride": f.cstride, "y": f.y, "cb": f.cb, "cr": f.cr}
+                if download:
+                    v0 = 2 if f.ratio in (2, 3) else 1          # 4:2:0 and 4:4:0 halve the chroma rows (Gray: 8 x 8 MCUs)
+                    myy = (f.h + 8 * v0 - 1) // (8 * v0)
+                    d["y"] = grab(f.y, 8 * v0 * myy, f.ystride)
+                    d["cb"] = grab(f.cb, 8 * myy, f.cstride) if f.cb else None
+                    d["cr"] = grab(f.cr, 8 * myy, f.cstride) if f.cr else None
+                out.append(d)
+        finally:
+            if download:
+                free()
+        return (out, list(status)[:n]) if download else (out, list(status)[:n], free)
+
     JPEG_ROUTE_PAR, JPEG_ROUTE_HOST_SCANS, JPEG_ROUTE_GPU_SCANS = 0, 1, 2
 
     @staticmethod
@@ -929,6 +970,47 @@ class Context:
         res = C.c_void_p()
         _check(lib().ipx_run_png_png_mixed(self.handle, C.byref(ops), n, _bytes_array(files), tarr, arrs.get("resize"),
                                            arrs.get("thumbnail"), arrs.get("watermark"), status, C.byref(res)))
+        out = {k: [(C.string_at(a[j].data, a[j].len) if copy else a[j].len) if a[j].data else None for j in range(n)]
+               for k, a in arrs.items()}
+        lib().ipx_jpeg_result_free(self.handle, res)
+        return out, list(status)[:n]
+
+    def run_jpeg_jpeg_mixed(self, ops, files, quality=85, want=("resize", "thumbnail", "watermark"), copy=True, texts=None):
+        """JPEG byte strings of ANY sizes and samplings in -> ({operator: [jpeg bytes | None] * n}, status list): one decode pass per
+        group and sampling class, the operators per run of one size, jpeg.Encode per chunk or per run (ipx_run_jpeg_jpeg_mixed).  ops:
+        a PoolOps, or dict(resize=(w, h, keep_aspect) | None, thumbnail=(size, crop_to_fit) | None, watermark=bool | (glyphs, col): a
+        glyph list every size's plan clips against its own frame).  texts: None, or one (glyphs, col) per file, positioned for that
+        file's size (then no glyph list in ops).  copy=False: lengths instead of bytes."""
+        keep = []
+        if isinstance(ops, dict):
+            o = _lib.PoolOps()
+            if ops.get("resize"):
+                o.do_resize, o.resize_w, o.resize_h, o.keep_aspect = 1, ops["resize"][0], ops["resize"][1], int(bool(ops["resize"][2]))
+            if ops.get("thumbnail"):
+                o.do_thumbnail, o.thumb_size, o.crop_to_fit = 1, ops["thumbnail"][0], int(bool(ops["thumbnail"][1]))
+            wm = ops.get("watermark")
+            o.do_watermark = int(bool(wm))
+            if isinstance(wm, (tuple, list)):
+                glyphs, col = list(wm[0]), wm[1]
+                ga, gk = _glyph_array(glyphs)
+                keep.append((ga, gk))
+                o.glyphs, o.n_glyphs = ga, len(glyphs)
+                for c in range(4):
+                    o.col[c] = int(col[c])
+            ops = o
+        n = len(files)
+        tarr = None
+        if texts is not None:
+            texts = list(texts)
+            if len(texts) != n:
+                raise ValueError("one text per file")
+            tarr, tkeep = _text_array(texts)
+            keep.append(tkeep)
+        arrs = {k: (_lib.Bytes * max(n, 1))() for k in ("resize", "thumbnail", "watermark") if k in want}
+        status = (C.c_int * max(n, 1))()
+        res = C.c_void_p()
+        _check(lib().ipx_run_jpeg_jpeg_mixed(self.handle, C.byref(ops), n, _bytes_array(files), tarr, int(quality), arrs.get("resize"),
+                                             arrs.get("thumbnail"), arrs.get("watermark"), status, C.byref(res)))
         out = {k: [(C.string_at(a[j].data, a[j].len) if copy else a[j].len) if a[j].data else None for j in range(n)]
                for k, a in arrs.items()}
         lib().ipx_jpeg_result_free(self.handle, res)

@@ -69,6 +69,11 @@ class PngFrame(C.Structure):
                 ("palette", C.c_void_p)]
 
 
+class JpegFrame(C.Structure):
+    _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("ratio", C.c_int32), ("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p),
+                ("ystride", C.c_int32), ("cstride", C.c_int32)]
+
+
 class RgbaFrame(C.Structure):
     _fields_ = [("pix", C.c_void_p), ("w", C.c_int32), ("h", C.c_int32), ("stride", C.c_int32)]
 
@@ -226,6 +231,7 @@ SIGNATURES = {
     "ipx_jpeg_decode_batch": (_I, [_P, _P, C.POINTER(Bytes), _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(YCbCrBatch), C.POINTER(_I),
                                    C.POINTER(_P)]),
     "ipx_jpeg_planes_free": (None, [_P, _P]),
+    "ipx_jpeg_decode_mixed": (_I, [_P, _P, C.POINTER(Bytes), _I, C.POINTER(JpegFrame), C.POINTER(_I), C.POINTER(_P)]),
     "ipx_jpeg_scan_route": (_I, [_P, _Z, C.POINTER(_I)]),
     "ipx_jpeg_decode_counts": (_I, [_P, C.POINTER(C.c_longlong)]),
     "ipx_png_decode_counts": (_I, [_P, C.POINTER(C.c_longlong)]),
@@ -259,6 +265,8 @@ SIGNATURES = {
     "ipx_png_encode_mixed_dev": (_I, [_P, C.POINTER(RgbaFrame), _I, C.POINTER(_P), C.POINTER(_Z), C.POINTER(_Z)]),
     "ipx_run_png_png_mixed": (_I, [_P, C.POINTER(PoolOps), _I, C.POINTER(Bytes), C.POINTER(Text), C.POINTER(Bytes), C.POINTER(Bytes),
                                    C.POINTER(Bytes), C.POINTER(_I), C.POINTER(_P)]),
+    "ipx_run_jpeg_jpeg_mixed": (_I, [_P, C.POINTER(PoolOps), _I, C.POINTER(Bytes), C.POINTER(Text), _I, C.POINTER(Bytes), C.POINTER(Bytes),
+                                     C.POINTER(Bytes), C.POINTER(_I), C.POINTER(_P)]),
     "ipx_plan_run_png_png": (_I, [_P, _P, _I, C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(Bytes), C.POINTER(_I),
                                   C.POINTER(_P)]),
     "ipx_plan_run_jpeg_jpeg_texts": (_I, [_P, _P, _I, C.POINTER(Bytes), C.POINTER(Text), _I, C.POINTER(Bytes), C.POINTER(Bytes),

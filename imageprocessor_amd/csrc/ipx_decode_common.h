@@ -42,6 +42,16 @@ template <class T> struct OwnedBlocks {
     T *release() { return o.release(); }
 };
 
+// ---- a mixed-size JPEG decode in its two halves (ipx_jpeg_dec_runtime.hip), for ipx_jpeg_decode_mixed and the mixed-size leg ------------
+// Every file parsed once: status[i] the parser's verdict, *all what the decode needs of the files.
+int jpeg_mixed_parse(const ipx_bytes *jpegs, int n, int *status, ipx::JpegBatchPlan *all);
+// The m files idx[0 .. m) of that call whose status is IPX_OK, of any sizes and samplings: one run of the decode stages per sampling
+// class, each class's files in idx's order, so files of one size and class that are neighbours in idx have planes one frame stride apart
+// (256-byte aligned plane sizes).  frames and status by the caller's index; a file is decoded once (its parse is used up).  The planes
+// are blocks of `own`; lane != NULL: scratch is bumped out of the lane's decode buffer.
+int jpeg_mixed_decode(ipx_ctx *ctx, hipStream_t s, Lane *lane, const ipx_bytes *jpegs, ipx::JpegBatchPlan &all, const int *idx, int m,
+                      OwnedBlocks<ipx_jpeg_planes> &own, ipx_jpeg_frame *frames, int *status);
+
 // ---- the pinned blocks of one call (ipx_host_alloc): they go back once the stream is past the copies that read them --------------------
 // Like StreamSync, declare it AFTER the host buffers the stream still reads or writes.
 struct PinnedBlocks {

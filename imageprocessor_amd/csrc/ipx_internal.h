@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/ipx.h"
+#include "ipx_jpeg_mixed_plan.h"
 
 namespace ipx {
 
@@ -236,6 +237,9 @@ struct JpegDecArgs {
     int bpm, ybl;                    // blocks per MCU and how many of them are luma (Gray: 1, 1; 4:1:1: 6, 4 in one row; 4:1:0: 10, 8 as 2 rows of 4)
     int nitems;                      // pieces to decode (>= images)
     int shared_tables, first_valid;   // every valid image carries the Huffman tables of image first_valid
+    const JpegMixGeom *geom;          // a mixed-size class (ipx_jpeg_mixed_plan.h): one record per image replaces mxx, myy, nblk, w, h and the
+                                      // planes' strides, which are then unset; NULL: the uniform kernels, which never read it
+    unsigned mix_wgs;                 // geom != NULL: workgroups of the one-dimensional IDCT launch
 };
 // the per-image status word of the decoder kernels: 0, or a negative key whose low three bits are -IPX_ERR_* and whose upper bits order
 // the reporting pieces so that atomicMin keeps the verdict of the piece a sequential decoder would have reached first
@@ -264,6 +268,7 @@ struct JpegParArgs {
     uint32_t *changed;
     int16_t *coefs; int *status;
     int16_t *dcs;                          // [image][nblk]: DC differences from the write pass, DC values after par_dc_kernel
+    const JpegMixGeom *geom;               // as JpegDecArgs::geom, indexed by JpegParImage::img: the block count and the slot base per image
 };
 int jpeg_par_sub_bytes();
 int jpeg_par_checkpoints();
@@ -332,6 +337,8 @@ struct JpegPlanOptions {
     int forced_sub, max_sub;   // IPX_JPEG_PAR_SUB: 128 .. 1024 fixes the sub-sequence size, else the batch chooses; jpeg_par_sub_bytes()
     bool prog_gpu = false;     // IPX_JPEG_PROG_GPU=1: progressive files with a clean pre-pass are walked on the GPU
     bool s411 = false;         // IPX_JPEG_411=1: 4:1:1 and 4:1:0 files are taken (never by the GPU scan walk)
+    bool mixed = false;        // every parsed file of the call is taken whatever its size (want_w, want_h unused); the caller passes files
+                               // of ONE sampling class (jpeg_plan_place)
 };
 struct JpegBatchPlan {
     std::vector<JpegDecInfo> info;
@@ -344,12 +351,17 @@ struct JpegBatchPlan {
     std::vector<uint8_t> route;       // per file: the IPX_JPEG_ROUTE_* its decoder is reached by; 0xff: refused before (ipx_jpeg_decode_counts)
     std::vector<JpegDecImage> items;  // pieces by table class, every class but the last padded to whole groups of 64 (padding: valid == 0)
     std::vector<JpegParImage> par;
+    std::vector<std::vector<uint32_t>> marks;   // per file: the RSTn markers of a baseline scan, as offsets into it (jpeg_plan_parse)
     int ref = -1, par_sub = 0, nhost = 0;   // ref: the file that sets the batch's geometry; -1: nothing decodable
     size_t blob_bytes = 0, piece_ubytes = 0;
     double parse_ms = 0;              // for the IPX_DEBUG timing line
 };
 // status[i]: the parser's verdict, UNSUPPORTED outside the batch's geometry.  Returns the status of an exception on a preparation thread.
 int jpeg_plan_batch(const ipx_bytes *files, int n, const JpegPlanOptions &opt, int *status, JpegBatchPlan *plan);
+// its two halves: every file parsed (info, tabs, marks, prog; status[i] the parser's verdict), then the geometry chosen and the scans
+// placed.  A mixed-size call parses once and places once per sampling class, on that class's files moved into a plan of their own.
+int jpeg_plan_parse(const ipx_bytes *files, int n, const JpegPlanOptions &opt, int *status, JpegBatchPlan *plan);
+void jpeg_plan_place(const ipx_bytes *files, int n, const JpegPlanOptions &opt, int *status, JpegBatchPlan *plan);
 bool jpeg_same_tables(const JpegDecTables &x, const JpegDecTables &y);     // the Huffman tables (not the quantisers)
 hipError_t launch_jpeg_huff(const JpegDecArgs &a, hipStream_t s);
 // the same pieces through the word-wise reader of the parallel decoder: unstuff each piece into ublob (+ its length into ulen), then one

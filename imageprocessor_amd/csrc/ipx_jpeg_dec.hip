@@ -142,7 +142,8 @@ __device__ __forceinline__ int decode_symbol(BitReader &br, const uint16_t *lut,
 // SHARED: every image of the batch carries the same Huffman tables (the usual case: Annex K tables, or one encoder's
 // output), so one 3.7 KiB copy per (single-wave) workgroup serves all lanes and many waves fit on a CU; otherwise each lane
 // keeps its own first-level tables (128 KiB per wave, one wave per CU).
-template <bool SHARED>
+// MIXED: the images of the launch differ in size; a lane reads its image's slot base from the image's record (ipx_jpeg_mixed_plan.h).
+template <bool SHARED, bool MIXED>
 __global__ __launch_bounds__(64) void jpeg_huff_kernel(JpegDecArgs a)
 {
     extern __shared__ uint4 lds_raw[];
@@ -181,7 +182,8 @@ __global__ __launch_bounds__(64) void jpeg_huff_kernel(JpegDecArgs a)
     br.base = (const uint4 *)(a.blob + im.scan_off);
     br.len = im.scan_len;
     for (int k = 0; k < (int)im.pad; k++) br.advance();   // the piece starts inside its first 16-byte chunk
-    int16_t *coefs = a.coefs + (size_t)img * a.nblk * 64;
+    const size_t blk0 = MIXED ? (size_t)a.geom[img].blk0 : (size_t)img * a.nblk;
+    int16_t *coefs = a.coefs + blk0 * 64;
     const int ybl = a.ybl, bpm = a.bpm;
     // table slots and DC predictions as scalars selected by the component: arrays indexed by c would live in scratch memory
     // (a global-memory round trip per block)
@@ -200,7 +202,7 @@ __global__ __launch_bounds__(64) void jpeg_huff_kernel(JpegDecArgs a)
             const int dcv = (c == 0 ? dc0 : (c == 1 ? dc1 : dc2)) + diff;
             if (c == 0) dc0 = dcv; else if (c == 1) dc1 = dcv; else dc2 = dcv;
             if (dcv < -32768 || dcv > 32767) wide = true;   // Go keeps int32 and decodes on: not representable here (kJpegStatusLast)
-            a.dcs[(size_t)img * a.nblk + (size_t)m * bpm + bi] = (int16_t)dcv;
+            a.dcs[blk0 + (size_t)m * bpm + bi] = (int16_t)dcv;
             const uint16_t *aclut = lut + ta * 256;
             for (int zig = 1; zig < 64; zig++) {
                 const int v = decode_symbol(br, aclut, st, ta);
@@ -305,17 +307,52 @@ __device__ __forceinline__ void idct_col(uint32_t (&s)[8])   // vertical pass (i
 // 1024 1080p files; the kernel ran at 2.8 TB/s of its 9.5 GB.)  Index arithmetic: one division by the blocks-per-MCU count, a
 // constant per branch (1, 3, 4, 6 or 10); per-image bases in scalar registers plus 32-bit offsets.
 constexpr int kIdctMcus = 8, kIdctMaxBlocks = 48, kIdctThreads = kIdctMaxBlocks * 8;
-__global__ __launch_bounds__(kIdctThreads) void jpeg_idct_kernel(JpegDecArgs a, JpegPlanes pl, int wgs_per_row, int mcus_per_wg)
+
+// What a workgroup knows of its image, every value uniform over the workgroup.  The uniform launch (one size per batch, grid y = image)
+// takes them from the launch arguments where the body asks for them; the mixed launch (a one-dimensional grid over the workgroups of
+// all images of a class) from the image's record, read once as scalars.
+struct IdctUniform {
+    const JpegDecArgs &a; const JpegPlanes &pl; int img, wgs_per_row, mcus_per_wg;
+    __device__ __forceinline__ int my() const { return (int)blockIdx.x / wgs_per_row; }
+    __device__ __forceinline__ int mx0(int my) const { return ((int)blockIdx.x - my * wgs_per_row) * mcus_per_wg; }
+    __device__ __forceinline__ int mxx() const { return a.mxx; }
+    __device__ __forceinline__ int w() const { return a.w; }
+    __device__ __forceinline__ int h() const { return a.h; }
+    __device__ __forceinline__ const int16_t *coefs() const { return a.coefs + (size_t)img * a.nblk * 64; }
+    __device__ __forceinline__ const int16_t *dcs() const { return a.dcs + (size_t)img * a.nblk; }
+    __device__ __forceinline__ uint8_t *py() const { return pl.y + (size_t)img * pl.y_fs; }
+    __device__ __forceinline__ uint8_t *pcb() const { return pl.cb + (size_t)img * pl.c_fs; }
+    __device__ __forceinline__ uint8_t *pcr() const { return pl.cr + (size_t)img * pl.c_fs; }
+    __device__ __forceinline__ uint32_t ystride() const { return (uint32_t)pl.ystride; }
+    __device__ __forceinline__ uint32_t cstride() const { return (uint32_t)pl.cstride; }
+};
+struct IdctMixed {
+    const JpegDecArgs &a; const JpegPlanes &pl; int img; JpegMixGeom g; int wg, mcus_per_wg;     // wg: the workgroup within the image
+    __device__ __forceinline__ int my() const { return wg / g.wgs_per_row; }
+    __device__ __forceinline__ int mx0(int my) const { return (wg - my * g.wgs_per_row) * mcus_per_wg; }
+    __device__ __forceinline__ int mxx() const { return g.mxx; }
+    __device__ __forceinline__ int w() const { return g.w; }
+    __device__ __forceinline__ int h() const { return g.h; }
+    __device__ __forceinline__ const int16_t *coefs() const { return a.coefs + (size_t)g.blk0 * 64; }
+    __device__ __forceinline__ const int16_t *dcs() const { return a.dcs + (size_t)g.blk0; }
+    __device__ __forceinline__ uint8_t *py() const { return pl.y + (size_t)g.yoff; }
+    __device__ __forceinline__ uint8_t *pcb() const { return pl.cb + (size_t)g.coff; }
+    __device__ __forceinline__ uint8_t *pcr() const { return pl.cr + (size_t)g.coff; }
+    __device__ __forceinline__ uint32_t ystride() const { return (uint32_t)g.ystride; }
+    __device__ __forceinline__ uint32_t cstride() const { return (uint32_t)g.cstride; }
+};
+
+// one workgroup of the reconstruction; vflags != 0 is the image's JpegPlanes::valid byte
+template <class Image>
+__device__ __forceinline__ void idct_workgroup(const JpegDecArgs &a, const Image &im, const int img, const int vflags, const int mcus_per_wg)
 {
     __shared__ uint32_t ws[kIdctMaxBlocks * 72];
     __shared__ __attribute__((aligned(8))) uint8_t ob[kIdctMaxBlocks * 64];     // the strips: Y (8 * v0 rows), then Cb, then Cr (8 rows each)
     const int t = threadIdx.x, blk = t >> 3, r = t & 7;
-    const int img = blockIdx.y;
-    const int vflags = pl.valid[img];
-    if (!vflags) return;                                  // uniform over the workgroup
     const bool prog = (vflags & 2) != 0;                  // reconstructProgressiveImage: blocks that hold no image pixel stay zero
     const int ybl = a.ybl, bpm = a.bpm;
-    const int my = (int)blockIdx.x / wgs_per_row, mx0 = ((int)blockIdx.x - my * wgs_per_row) * mcus_per_wg;      // scalar
+    const int my = im.my(), mx0 = im.mx0(my);             // scalar
+    const int mxx = im.mxx(), w = im.w(), h = im.h();
     int mxl, bi;                                          // MCU within the workgroup, block within the MCU
     switch (bpm) {                                        // uniform
     case 1: mxl = blk; bi = 0; break;
@@ -325,11 +362,11 @@ __global__ __launch_bounds__(kIdctThreads) void jpeg_idct_kernel(JpegDecArgs a, 
     default: mxl = blk / 6; bi = blk - mxl * 6; break;    // 6 (4:2:0: Y 2 x 2; 4:1:1: Y 4 x 1)
     }
     const int mx = mx0 + mxl;
-    const bool live = mxl < mcus_per_wg && mx < a.mxx;
+    const bool live = mxl < mcus_per_wg && mx < mxx;
     const int c = bi < ybl ? 0 : bi - ybl + 1;
-    const uint32_t gb = (uint32_t)((my * a.mxx + mx) * bpm + bi);
-    const int16_t *coefs = a.coefs + (size_t)img * a.nblk * 64;       // per image: scalar
-    const int16_t *dcs = a.dcs + (size_t)img * a.nblk;
+    const uint32_t gb = (uint32_t)((my * mxx + mx) * bpm + bi);
+    const int16_t *coefs = im.coefs();                                // per image: scalar
+    const int16_t *dcs = im.dcs();
     const uint16_t *qnat = &a.tab[img].qnat[0][0];
     const int ypitch = 8 * a.h0 * mcus_per_wg, cpitch = 8 * mcus_per_wg;   // bytes per strip row
     const int ybytes = 8 * a.v0 * ypitch, cbytes = 8 * cpitch;
@@ -363,9 +400,9 @@ __global__ __launch_bounds__(kIdctThreads) void jpeg_idct_kernel(JpegDecArgs a, 
     }
     __syncthreads();
     // the strips, 8 bytes (one block row) per thread and step
-    const int mcus = min(mcus_per_wg, a.mxx - mx0);                    // MCUs of this workgroup that exist
+    const int mcus = min(mcus_per_wg, mxx - mx0);                    // MCUs of this workgroup that exist
     const int ypieces = ybytes >> 3, cpieces = cbytes >> 3, npieces = a.bpm == 1 ? ypieces : ypieces + 2 * cpieces;
-    uint8_t *const py = pl.y + (size_t)img * pl.y_fs, *const pcb = pl.cb + (size_t)img * pl.c_fs, *const pcr = pl.cr + (size_t)img * pl.c_fs;
+    uint8_t *const py = im.py(), *const pcb = im.pcb(), *const pcr = im.pcr();
     for (int p = t; p < npieces; p += kIdctThreads) {
         int q = p, plane_i = 0;
         if (q >= ypieces) { q -= ypieces; plane_i = 1; if (q >= cpieces) { q -= cpieces; plane_i = 2; } }
@@ -373,30 +410,57 @@ __global__ __launch_bounds__(kIdctThreads) void jpeg_idct_kernel(JpegDecArgs a, 
         const int row = q >> (31 - __builtin_clz((unsigned)ppr)), col = q & (ppr - 1);
         if (col >= mcus * (plane_i == 0 ? a.h0 : 1)) continue;          // beyond the last MCU of the row
         const int bx = (plane_i == 0 ? mx0 * a.h0 : mx0) + col, y = (plane_i == 0 ? my * 8 * a.v0 : my * 8) + row;
-        const bool inside = plane_i == 0 ? bx * 8 < a.w && (y & ~7) < a.h : bx * 8 * a.h0 < a.w && my * 8 * a.v0 < a.h;   // the block's test (scan.go)
+        const bool inside = plane_i == 0 ? bx * 8 < w && (y & ~7) < h : bx * 8 * a.h0 < w && my * 8 * a.v0 < h;   // the block's test (scan.go)
         uint2 v = *(const uint2 *)(ob + (p << 3));
         if (prog && !inside) v = make_uint2(0u, 0u);      // image.NewYCbCr's zeros: Go never writes these blocks of a progressive image
         // nor the blocks a non-interleaved sequential scan carries no data for: outside the image by the component's OWN block grid
-        if (((vflags >> (2 + plane_i)) & 1) && (bx * 8 >= a.w || (y & ~7) >= a.h)) v = make_uint2(0u, 0u);
+        if (((vflags >> (2 + plane_i)) & 1) && (bx * 8 >= w || (y & ~7) >= h)) v = make_uint2(0u, 0u);
         uint8_t *plane = plane_i == 0 ? py : (plane_i == 1 ? pcb : pcr);
-        const uint32_t stride = (uint32_t)(plane_i == 0 ? pl.ystride : pl.cstride);
+        const uint32_t stride = plane_i == 0 ? im.ystride() : im.cstride();
         *(uint2 *)(plane + ((uint32_t)y * stride + (uint32_t)bx * 8u)) = v;
     }
+}
+
+__global__ __launch_bounds__(kIdctThreads) void jpeg_idct_kernel(JpegDecArgs a, JpegPlanes pl, int wgs_per_row, int mcus_per_wg)
+{
+    const int img = blockIdx.y;
+    const int vflags = pl.valid[img];
+    if (!vflags) return;                                  // uniform over the workgroup
+    idct_workgroup(a, IdctUniform{a, pl, img, wgs_per_row, mcus_per_wg}, img, vflags, mcus_per_wg);
+}
+
+// The images of a class in one launch: workgroup blockIdx.x belongs to the last image whose first workgroup is not behind it -- a
+// search by a value the whole workgroup shares, so its probes and the record are scalar loads.  A workgroup beyond the last image, or
+// of an image that is not decodable, returns before any other load.
+__global__ __launch_bounds__(kIdctThreads) void jpeg_idct_mixed_kernel(JpegDecArgs a, JpegPlanes pl, int mcus_per_wg)
+{
+    const uint32_t wg = blockIdx.x;
+    if (wg >= a.mix_wgs) return;
+    const int img = jpeg_mix_find(a.geom, a.n, wg);
+    const int vflags = pl.valid[img];
+    if (!vflags) return;
+    const JpegMixGeom g = a.geom[img];
+    idct_workgroup(a, IdctMixed{a, pl, img, g, (int)(wg - g.wg0), mcus_per_wg}, img, vflags, mcus_per_wg);
 }
 
 }  // namespace
 
 hipError_t launch_jpeg_huff(const JpegDecArgs &a, hipStream_t s)
 {
+    const dim3 grid((a.nitems + 63) / 64);
     if (a.shared_tables) {
-        hipLaunchKernelGGL(jpeg_huff_kernel<true>, dim3((a.nitems + 63) / 64), dim3(64), 2048 + 64 + 2 * 72 * 4 + 1024, s, a);
+        const size_t lds = 2048 + 64 + 2 * 72 * 4 + 1024;
+        if (a.geom) hipLaunchKernelGGL((jpeg_huff_kernel<true, true>), grid, dim3(64), lds, s, a);
+        else hipLaunchKernelGGL((jpeg_huff_kernel<true, false>), grid, dim3(64), lds, s, a);
         return hipGetLastError();
     }
     const size_t lds = (size_t)64 * kLutStride + 64;
-    static KernelLaunchCache cache;
-    hipError_t e = cache.prepare((const void *)jpeg_huff_kernel<false>, 64, lds, nullptr);
+    static KernelLaunchCache cache, cache_mixed;
+    hipError_t e = a.geom ? cache_mixed.prepare((const void *)jpeg_huff_kernel<false, true>, 64, lds, nullptr)
+                          : cache.prepare((const void *)jpeg_huff_kernel<false, false>, 64, lds, nullptr);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(jpeg_huff_kernel<false>, dim3((a.nitems + 63) / 64), dim3(64), lds, s, a);
+    if (a.geom) hipLaunchKernelGGL((jpeg_huff_kernel<false, true>), grid, dim3(64), lds, s, a);
+    else hipLaunchKernelGGL((jpeg_huff_kernel<false, false>), grid, dim3(64), lds, s, a);
     return hipGetLastError();
 }
 
@@ -406,6 +470,11 @@ hipError_t launch_jpeg_idct(const JpegDecArgs &a, const JpegPlanes &pl, hipStrea
     const bool known = a.bpm == 1 ? a.ybl == 1 : (a.bpm == a.ybl + 2 && a.ybl == a.h0 * a.v0 && (a.h0 == 1 || a.h0 == 2 || a.h0 == 4) && (a.v0 == 1 || a.v0 == 2));
     if (!known) return hipErrorInvalidValue;
     const int mcus_per_wg = a.bpm == 1 ? 32 : a.bpm == 10 ? 4 : kIdctMcus;   // 32, 24, 32, 48 or 40 blocks: the strips fill ob exactly at 48
+    if (a.geom) {                                                            // (JpegMixClass::mcus_per_wg is the same rule: the records count workgroups by it)
+        if (a.mix_wgs == 0 || a.mix_wgs > 0x7fffffffu || mcus_per_wg != JpegMixClass{a.h0, a.v0, a.bpm == 1}.mcus_per_wg()) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(jpeg_idct_mixed_kernel, dim3(a.mix_wgs), dim3(kIdctThreads), 0, s, a, pl, mcus_per_wg);
+        return hipGetLastError();
+    }
     const int wgs_per_row = (a.mxx + mcus_per_wg - 1) / mcus_per_wg;
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)(wgs_per_row * a.myy), a.n), dim3(kIdctThreads), 0, s, a, pl, wgs_per_row, mcus_per_wg);
     return hipGetLastError();

@@ -310,13 +310,21 @@ void group_by_class(std::vector<JpegDecImage> &items)
 
 int jpeg_plan_batch(const ipx_bytes *files, int n, const JpegPlanOptions &opt, int *status, JpegBatchPlan *plan)
 {
+    const int rc = jpeg_plan_parse(files, n, opt, status, plan);
+    if (rc) return rc;
+    jpeg_plan_place(files, n, opt, status, plan);
+    return IPX_OK;
+}
+
+int jpeg_plan_parse(const ipx_bytes *files, int n, const JpegPlanOptions &opt, int *status, JpegBatchPlan *plan)
+{
     JpegBatchPlan &P = *plan;
     P.info.resize(n); P.tabs.resize(n);
-    P.valid.assign(n, 0); P.blob_off.assign(n, 0); P.hslot.assign(n, -1);
-    P.prog.resize(n); P.route.assign(n, 0xff);
+    P.prog.resize(n);
     const auto t0 = std::chrono::steady_clock::now();
     // pieces of a scan: the whole scan, or one per restart interval
-    std::vector<std::vector<uint32_t>> marks(n);
+    P.marks.assign(n, {});
+    std::vector<std::vector<uint32_t>> &marks = P.marks;
     // host preparation runs on a few threads: parsing is trivial, but finding the RSTn markers walks every compressed byte (0.3 GB for
     // a thousand 1080p files).  Files whose scans are walked on the host (progressive, several scans) only have their frame header
     // read here; their scans wait for the batch's geometry.
@@ -330,7 +338,15 @@ int jpeg_plan_batch(const ipx_bytes *files, int n, const JpegPlanOptions &opt, i
             P.info[i].gpu_scans = jpeg_prog_prepass(files[i].data, files[i].len, P.info[i], &P.prog[i], P.tabs[i].qnat) ? 1 : 0;
     }, "jpeg decode: host preparation failed");
     P.parse_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (rc) return rc;
+    return rc;
+}
+
+void jpeg_plan_place(const ipx_bytes *files, int n, const JpegPlanOptions &opt, int *status, JpegBatchPlan *plan)
+{
+    JpegBatchPlan &P = *plan;
+    P.valid.assign(n, 0); P.blob_off.assign(n, 0); P.hslot.assign(n, -1);
+    P.route.assign(n, 0xff);
+    const std::vector<std::vector<uint32_t>> &marks = P.marks;
     const std::vector<int> tab_of = table_classes(P, status);
     // Sub-sequences of the scans that are decoded in parallel (ipx_jpeg_dec_par.hip): 1 KiB each for a large batch.  A lane walks its
     // sub-sequence symbol by symbol, so a pass over a small batch takes as long as ONE sub-sequence takes while the chip idles (8
@@ -345,8 +361,9 @@ int jpeg_plan_batch(const ipx_bytes *files, int n, const JpegPlanOptions &opt, i
     const std::vector<JpegDecInfo> &info = P.info;
     for (int i = 0; i < n; i++) {
         if (status[i] == IPX_OK) {
-            if (P.ref < 0 && (opt.want_w <= 0 || (info[i].w == opt.want_w && info[i].h == opt.want_h))) P.ref = i;
-            if (P.ref >= 0 && (info[i].w != info[P.ref].w || info[i].h != info[P.ref].h || info[i].h0 != info[P.ref].h0 || info[i].v0 != info[P.ref].v0 ||
+            if (P.ref < 0 && (opt.mixed || opt.want_w <= 0 || (info[i].w == opt.want_w && info[i].h == opt.want_h))) P.ref = i;
+            // (mixed: the sizes are free; the class still is the reference file's)
+            if (P.ref >= 0 && ((!opt.mixed && (info[i].w != info[P.ref].w || info[i].h != info[P.ref].h)) || info[i].h0 != info[P.ref].h0 || info[i].v0 != info[P.ref].v0 ||
                                info[i].ncomp != info[P.ref].ncomp))
                 status[i] = IPX_ERR_UNSUPPORTED;
             else if (P.ref < 0) status[i] = IPX_ERR_UNSUPPORTED;   // a size other than the one asked for
@@ -397,7 +414,6 @@ int jpeg_plan_batch(const ipx_bytes *files, int n, const JpegPlanOptions &opt, i
         P.blob_bytes += (I.scan_len + 15 + 16) & ~(size_t)15;
     }
     if (P.ref >= 0) group_by_class(P.items);
-    return IPX_OK;
 }
 
 }  // namespace ipx

@@ -37,6 +37,17 @@ constexpr int kSub = 1024;            // bytes of scan per sub-sequence at most 
 constexpr int kRowPad = 4;            // a staged sub-sequence takes sub + 4 LDS bytes: lanes at the same depth of their rows hit different banks
 constexpr uint32_t kEnd = 0xffffffffu;
 
+// An image's slot in the coefficient and DC arrays.  Uniform batches: img * nblk blocks in, nblk blocks long, from the launch arguments.
+// MIXED (a class of several sizes, ipx_jpeg_mixed_plan.h): both from the image's record -- one read per workgroup where the image is
+// the workgroup's (the parallel passes: a scalar load), one per lane where every lane has a piece of its own.
+struct Slot { size_t blk0; uint32_t nblk; };
+template <bool MIXED, class Args>
+__device__ __forceinline__ Slot slot_of(const Args &a, uint32_t img)
+{
+    if (MIXED) { const JpegMixGeom *g = a.geom + img; return Slot{(size_t)g->blk0, (uint32_t)g->nblk}; }
+    return Slot{(size_t)img * a.nblk, (uint32_t)a.nblk};
+}
+
 __constant__ uint8_t c_unzig_par[64] = {
     0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
     35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
@@ -425,6 +436,7 @@ struct CoefSink {
 };
 
 // step 3: a.ends holds the exclusive scan of the block ends = the block each lane starts in
+template <bool MIXED>
 __global__ __launch_bounds__(64) void par_write_kernel(JpegParArgs a)
 {
     extern __shared__ uint4 lds_raw[];
@@ -439,7 +451,8 @@ __global__ __launch_bounds__(64) void par_write_kernel(JpegParArgs a)
     const uint32_t p = (uint32_t)entry;
     const uint32_t uend = min(((uint32_t)t + 1) * (uint32_t)a.sub * 8u, r.ubits);
     if (p == kEnd || p >= uend) return;
-    CoefSink sink{a.coefs + (size_t)im.img * a.nblk * 64, a.dcs + (size_t)im.img * a.nblk, T.unz, a.ends[(size_t)blockIdx.y * a.max_nsub + t], (uint32_t)a.nblk, a.status + im.img};
+    const Slot sl = slot_of<MIXED>(a, im.img);
+    CoefSink sink{a.coefs + sl.blk0 * 64, a.dcs + sl.blk0, T.unz, a.ends[(size_t)blockIdx.y * a.max_nsub + t], sl.nblk, a.status + im.img};
     sink.drop = a.stage_rows == 2;
     if (sink.g >= sink.nblk) return;
     r.seek(p);
@@ -453,13 +466,15 @@ __global__ __launch_bounds__(64) void par_write_kernel(JpegParArgs a)
 // 2-byte load after the other: 79 us for ONE 1080p file, 0.94 ms per 1024 files with 256 threads per image.)
 constexpr int kDcThreads = 1024;
 constexpr int kDcBlocks = 10;         // blocks per MCU at most (B.2.3: the sampling factors of a scan's components sum to <= 10)
+template <bool MIXED>
 __global__ __launch_bounds__(kDcThreads) void par_dc_kernel(JpegParArgs a)
 {
     __shared__ int wsum[2][16][3];
     const JpegParImage im = a.img[blockIdx.x];
-    int16_t *dcs = a.dcs + (size_t)im.img * a.nblk;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, bpm = a.bpm, ybl = a.ybl, nmcu = a.nblk / bpm;
-    if (t == 0 && a.total_ends[blockIdx.x] < (uint32_t)a.nblk) atomicMin(a.status + im.img, jpeg_status_key(0, IPX_ERR_INVALID));   // "short Huffman data"
+    const Slot sl = slot_of<MIXED>(a, im.img);
+    int16_t *dcs = a.dcs + sl.blk0;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, bpm = a.bpm, ybl = a.ybl, nmcu = (int)sl.nblk / bpm;
+    if (t == 0 && a.total_ends[blockIdx.x] < sl.nblk) atomicMin(a.status + im.img, jpeg_status_key(0, IPX_ERR_INVALID));   // "short Huffman data"
     auto load = [&](int m, int (&x)[kDcBlocks]) {
 #pragma unroll
         for (int bi = 0; bi < kDcBlocks; bi++) x[bi] = bi < bpm && m < nmcu ? (int)dcs[(size_t)m * bpm + bi] : 0;
@@ -591,6 +606,7 @@ struct PieceSink {
     __device__ __forceinline__ void bad() { err = true; }   // "bad Huffman code" / "excessive DC component": nothing speculative here
 };
 
+template <bool MIXED>
 __global__ __launch_bounds__(64) void piece_decode_kernel(JpegDecArgs a, const uint8_t *ublob, const uint32_t *ulen)
 {
     __shared__ __attribute__((aligned(16))) uint8_t tb[4096];
@@ -618,7 +634,8 @@ __global__ __launch_bounds__(64) void piece_decode_kernel(JpegDecArgs a, const u
     r.lds = nullptr; r.g = ublob + ip->uoff; r.wg_base = 0; r.wg_bytes = 0; r.ubits = ulen[item] * 8u;
     r.seek(0);
     const uint32_t g0 = first_mcu * (uint32_t)a.bpm;
-    PieceSink sink{a.coefs + (size_t)img * a.nblk * 64, a.dcs + (size_t)img * a.nblk, unz, g0, g0 + n_mcu * (uint32_t)a.bpm,
+    const Slot sl = slot_of<MIXED>(a, img);
+    PieceSink sink{a.coefs + sl.blk0 * 64, a.dcs + sl.blk0, unz, g0, g0 + n_mcu * (uint32_t)a.bpm,
                    0, a.bpm, a.ybl, 0, 0, 0, false, false};
     uint32_t ends;
     (void)run(r, T, slots, a.bpm, a.ybl, 0, 0, r.ubits, sink, &ends);
@@ -640,7 +657,8 @@ hipError_t launch_jpeg_pieces(const JpegDecArgs &a, uint8_t *ublob, uint32_t *ul
 {
     if (a.nitems <= 0) return hipSuccess;
     hipLaunchKernelGGL(piece_unstuff_kernel, dim3((a.nitems + 255) / 256), dim3(256), 0, s, a, ublob, ulen);
-    hipLaunchKernelGGL(piece_decode_kernel, dim3((a.nitems + 63) / 64), dim3(64), 0, s, a, (const uint8_t *)ublob, (const uint32_t *)ulen);
+    if (a.geom) hipLaunchKernelGGL(piece_decode_kernel<true>, dim3((a.nitems + 63) / 64), dim3(64), 0, s, a, (const uint8_t *)ublob, (const uint32_t *)ulen);
+    else hipLaunchKernelGGL(piece_decode_kernel<false>, dim3((a.nitems + 63) / 64), dim3(64), 0, s, a, (const uint8_t *)ublob, (const uint32_t *)ulen);
     return hipGetLastError();
 }
 
@@ -656,9 +674,10 @@ hipError_t launch_par_unstuff(const JpegParArgs &a, hipStream_t s)
 }
 hipError_t launch_par_sync(const JpegParArgs &a, int round, hipStream_t s)
 {
-    static KernelLaunchCache sync_cache, write_cache;
+    static KernelLaunchCache sync_cache, write_cache, write_cache_mixed;
     hipError_t e = sync_cache.prepare((const void *)par_sync_kernel, 64, kParLds, nullptr);
-    if (e == hipSuccess) e = write_cache.prepare((const void *)par_write_kernel, 64, kParLds, nullptr);
+    if (e == hipSuccess) e = a.geom ? write_cache_mixed.prepare((const void *)par_write_kernel<true>, 64, kParLds, nullptr)
+                                    : write_cache.prepare((const void *)par_write_kernel<false>, 64, kParLds, nullptr);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(par_sync_kernel, dim3((a.max_nsub + 63) / 64, a.nimg), dim3(64), a.stage_rows == 1 ? par_lds(a.sub) : 4096, s, a, round);
     return hipGetLastError();
@@ -669,12 +688,15 @@ hipError_t launch_par_write(const JpegParArgs &a, hipStream_t s)
     // 128-byte line each in flight, and with 2048 lanes per CU those lines do not fit the XCD's 4 MiB L2 -- every line is then written
     // back (and read for the merge) several times
     static const int write_lds = [] { const char *e = getenv("IPX_JPEG_WRITE_LDS"); return e ? atoi(e) : 16384; }();   // measured per 1024 x 1080p files: 4 KiB 8.7 ms, 10 KiB 8.4, 16 KiB 7.9, 20 KiB 8.1, 40 KiB 11.7
-    hipLaunchKernelGGL(par_write_kernel, dim3((a.max_nsub + 63) / 64, a.nimg), dim3(64), a.stage_rows == 1 ? std::max(par_lds(a.sub), (size_t)write_lds) : (size_t)std::max(4096, write_lds), s, a);
+    const size_t lds = a.stage_rows == 1 ? std::max(par_lds(a.sub), (size_t)write_lds) : (size_t)std::max(4096, write_lds);
+    if (a.geom) hipLaunchKernelGGL(par_write_kernel<true>, dim3((a.max_nsub + 63) / 64, a.nimg), dim3(64), lds, s, a);
+    else hipLaunchKernelGGL(par_write_kernel<false>, dim3((a.max_nsub + 63) / 64, a.nimg), dim3(64), lds, s, a);
     return hipGetLastError();
 }
 hipError_t launch_par_dc(const JpegParArgs &a, hipStream_t s)
 {
-    hipLaunchKernelGGL(par_dc_kernel, dim3(a.nimg), dim3(kDcThreads), 0, s, a);
+    if (a.geom) hipLaunchKernelGGL(par_dc_kernel<true>, dim3(a.nimg), dim3(kDcThreads), 0, s, a);
+    else hipLaunchKernelGGL(par_dc_kernel<false>, dim3(a.nimg), dim3(kDcThreads), 0, s, a);
     return hipGetLastError();
 }
 

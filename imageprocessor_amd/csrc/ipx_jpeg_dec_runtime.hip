@@ -26,6 +26,17 @@ struct DecRun {
     double t_alloc = 0, t_pin = 0, t_pack = 0, t_launch = 0;
     JpegBatchPlan plan;
     bool s411 = false;                 // IPX_JPEG_411=1 as this call read it
+    // A mixed-size call: the run is one sampling class, of any sizes.  geom holds a record per file (ipx_jpeg_mixed_plan.h; a file
+    // that is not decodable counts as 1 x 1), tot their sums; the launch arguments mxx, myy, nblk, w, h and the strides stay 0.
+    bool mixed = false;
+    std::vector<JpegMixGeom> geom;
+    JpegMixTotals tot;
+    JpegMixGeom *d_geom = nullptr;
+    size_t blocks = 0;                 // of all images: n * nblk, or the sum over the records
+    int max_nsub = 0;
+    size_t plane_bytes = 0, scratch_bytes = 0;   // of this run: the planes; the estimate of everything else in HBM (the timing line)
+    size_t blk0(int i) const { return mixed ? (size_t)geom[i].blk0 : (size_t)i * a.nblk; }
+    size_t nblk(int i) const { return mixed ? (size_t)geom[i].nblk : (size_t)a.nblk; }
     std::vector<int> dev_status;
     std::vector<uint8_t> prog_block;   // the scan programs of the GPU-walked files as uploaded (dec_scans)
     JpegDecArgs a{};
@@ -48,24 +59,42 @@ int dec_blocks(DecRun &r, Lane *lane, bool planes_in_lane, OwnedBlocks<ipx_jpeg_
     const int n = r.n;
     JpegDecArgs &a = r.a;
     JpegPlanes &pl = r.pl;
-    a.n = n; a.h0 = R.h0; a.v0 = R.v0; a.w = R.w; a.h = R.h;
-    a.mxx = (R.w + 8 * R.h0 - 1) / (8 * R.h0); a.myy = (R.h + 8 * R.v0 - 1) / (8 * R.v0);
+    a.n = n; a.h0 = R.h0; a.v0 = R.v0;
     const bool gray = R.ncomp == 1;                        // *image.Gray: one block per MCU, no chroma planes
     a.ybl = R.h0 * R.v0; a.bpm = gray ? 1 : a.ybl + 2;
-    a.nblk = a.mxx * a.myy * a.bpm;
     a.nitems = (int)P.items.size();
-    pl.ystride = 8 * R.h0 * a.mxx; pl.cstride = 8 * a.mxx;
-    pl.y_fs = align256((size_t)pl.ystride * 8 * R.v0 * a.myy); pl.c_fs = gray ? 0 : align256((size_t)pl.cstride * 8 * a.myy);
-    if (lane) {
+    size_t ybytes, cbytes;                                 // the Y block; each chroma block
+    if (r.mixed) {
+        std::vector<int> ws(n), hs(n);
+        for (int i = 0; i < n; i++) { const bool ok = r.status[i] == IPX_OK; ws[i] = ok ? P.info[i].w : 1; hs[i] = ok ? P.info[i].h : 1; }
+        if (!jpeg_mix_build(JpegMixClass{R.h0, R.v0, gray ? 1 : 0}, ws.data(), hs.data(), n, &r.geom, &r.tot)) {
+            set_error("jpeg decode: the files of one sampling class are too large for one decode pass");
+            return IPX_ERR_UNSUPPORTED;
+        }
+        r.blocks = (size_t)r.tot.blocks; a.mix_wgs = (unsigned)r.tot.wgs;
+        ybytes = (size_t)r.tot.ybytes; cbytes = (size_t)r.tot.cbytes;
+    } else {
+        a.w = R.w; a.h = R.h;
+        a.mxx = (R.w + 8 * R.h0 - 1) / (8 * R.h0); a.myy = (R.h + 8 * R.v0 - 1) / (8 * R.v0);
+        a.nblk = a.mxx * a.myy * a.bpm;
+        pl.ystride = 8 * R.h0 * a.mxx; pl.cstride = 8 * a.mxx;
+        pl.y_fs = align256((size_t)pl.ystride * 8 * R.v0 * a.myy); pl.c_fs = gray ? 0 : align256((size_t)pl.cstride * 8 * a.myy);
+        r.blocks = (size_t)n * a.nblk;
+        ybytes = pl.y_fs * n; cbytes = pl.c_fs * n;
+    }
+    r.plane_bytes = ybytes + 2 * cbytes;
+    {
         size_t subs = 0;
         for (auto &pi : P.par) subs = std::max(subs, (size_t)pi.nsub);
         subs *= P.par.size();
         size_t prog_bytes = 0;                   // the scan programs as dec_scans uploads them
         for (int i : P.gfiles) prog_bytes += sizeof(JpegProgFile) + P.prog[i].scans.size() * sizeof(JpegProgScan) + P.prog[i].defs.size() * sizeof(JpegProgHuff) + 64;
-        const size_t est = (pl.y_fs + 2 * pl.c_fs) * n + (size_t)n * a.nblk * 130 + 3 * (P.blob_bytes + 1024) + P.piece_ubytes +
-                           P.items.size() * (sizeof(JpegDecImage) + 8) + (size_t)n * (sizeof(JpegDecTables) + 64) + P.par.size() * (sizeof(JpegParImage) + 64) +
-                           subs * 96 + ((size_t)4 << 20) + prog_bytes;
-        const int rr = lane_reserve_dec(*lane, est);
+        r.scratch_bytes = r.blocks * 130 + 3 * (P.blob_bytes + 1024) + P.piece_ubytes +
+                           P.items.size() * (sizeof(JpegDecImage) + 8) + (size_t)n * (sizeof(JpegDecTables) + sizeof(JpegMixGeom) + 64) + P.par.size() * (sizeof(JpegParImage) + 64) +
+                           subs * (32 + 12 * (size_t)jpeg_par_checkpoints()) + ((size_t)4 << 20) + prog_bytes;   // (par_setup: images x max_nsub entries)
+    }
+    if (lane) {
+        const int rr = lane_reserve_dec(*lane, r.plane_bytes + r.scratch_bytes);
         if (rr) return rr;
         r.mem.arena = lane->dec; r.mem.cap = lane->dec_bytes;
     }
@@ -73,16 +102,17 @@ int dec_blocks(DecRun &r, Lane *lane, bool planes_in_lane, OwnedBlocks<ipx_jpeg_
         if (lane && planes_in_lane) return r.mem.get(p, bytes);   // first requests of the call and counted in est: they always fit
         return own.alloc(p, bytes);
     };
-    DEC_HIP("plane allocation", plane(&pl.y, pl.y_fs * n));
-    if (!gray) DEC_HIP("plane allocation", plane(&pl.cb, pl.c_fs * n));
-    if (!gray) DEC_HIP("plane allocation", plane(&pl.cr, pl.c_fs * n));
+    DEC_HIP("plane allocation", plane(&pl.y, ybytes));
+    if (!gray) DEC_HIP("plane allocation", plane(&pl.cb, cbytes));
+    if (!gray) DEC_HIP("plane allocation", plane(&pl.cr, cbytes));
     DEC_HIP("scratch allocation", r.mem.get(&r.d_blob, P.blob_bytes + 16));
     DEC_HIP("scratch allocation", r.mem.get(&r.d_img, sizeof(JpegDecImage) * P.items.size()));
     DEC_HIP("scratch allocation", r.mem.get(&r.d_valid, (size_t)n));
     DEC_HIP("scratch allocation", r.mem.get(&r.d_tab, sizeof(JpegDecTables) * n));
-    DEC_HIP("scratch allocation", r.mem.get(&a.coefs, (size_t)n * a.nblk * 128));
+    DEC_HIP("scratch allocation", r.mem.get(&a.coefs, r.blocks * 128));
     DEC_HIP("scratch allocation", r.mem.get(&a.status, sizeof(int) * n));
-    DEC_HIP("scratch allocation", r.mem.get(&a.dcs, (size_t)n * a.nblk * 2 + 16));
+    DEC_HIP("scratch allocation", r.mem.get(&a.dcs, r.blocks * 2 + 16));
+    if (r.mixed) { DEC_HIP("scratch allocation", r.mem.get(&r.d_geom, sizeof(JpegMixGeom) * n)); a.geom = r.d_geom; }
     a.blob = r.d_blob; a.img = r.d_img; a.tab = r.d_tab; pl.valid = r.d_valid;
     r.t_alloc = r.ms();
     return IPX_OK;
@@ -102,13 +132,21 @@ int dec_upload(DecRun &r)
     static const char *const kPrep = "jpeg decode: host preparation failed";
     uint8_t *hblob = r.pinned.get(P.blob_bytes + 16);
     if (!hblob) return IPX_ERR_NOMEM;
-    const size_t hcoef_words = (size_t)a.nblk * 64, hslot_words = hcoef_words + a.nblk;
     const int group = std::max(1, env_int("IPX_JPEG_HOST_GROUP", 16));
     std::vector<int> hfiles;
     for (int i = 0; i < n; i++) if (P.hslot[i] >= 0) hfiles.push_back(i);
+    // a host-decoded file's slot in its half of the pinned block: its coefficients (64 per block), then its DC values -- sized by the
+    // file; a half holds the largest group (uniform batches: min(nhost, group) slots of one size)
+    std::vector<size_t> hoff(hfiles.size());
+    size_t half_words = 0;
+    for (size_t g0 = 0; g0 < hfiles.size(); g0 += group) {
+        size_t words = 0;
+        for (size_t k = g0; k < std::min(hfiles.size(), g0 + group); k++) { hoff[k] = words; words += r.nblk(hfiles[k]) * 65; }
+        half_words = std::max(half_words, words);
+    }
     int16_t *hpin = nullptr;
     if (P.nhost) {
-        hpin = (int16_t *)r.pinned.get((size_t)2 * std::min(P.nhost, group) * hslot_words * sizeof(int16_t));
+        hpin = (int16_t *)r.pinned.get((size_t)2 * half_words * sizeof(int16_t));
         if (!hpin) {   // no pinned memory for them: these files stay on the caller's CPU path, the rest of the batch goes on
             for (int i : hfiles) { r.status[i] = IPX_ERR_UNSUPPORTED; P.valid[i] = 0; }
             hfiles.clear();
@@ -125,21 +163,22 @@ int dec_upload(DecRun &r)
     r.t_pack = r.ms();
     DEC_HIP("jpeg decode", hipMemcpyAsync(r.d_blob, hblob, P.blob_bytes, hipMemcpyHostToDevice, s));
     DEC_HIP("jpeg decode", hipMemcpyAsync(r.d_img, P.items.data(), sizeof(JpegDecImage) * P.items.size(), hipMemcpyHostToDevice, s));
-    DEC_HIP("jpeg decode", hipMemsetAsync(a.coefs, 0, (size_t)n * a.nblk * 128, s));
+    if (r.mixed) DEC_HIP("jpeg decode", hipMemcpyAsync(r.d_geom, r.geom.data(), sizeof(JpegMixGeom) * n, hipMemcpyHostToDevice, s));
+    DEC_HIP("jpeg decode", hipMemsetAsync(a.coefs, 0, r.blocks * 128, s));
     DEC_HIP("jpeg decode", hipMemsetAsync(a.status, 0, sizeof(int) * n, s));
-    DEC_HIP("jpeg decode", hipMemsetAsync(a.dcs, 0, (size_t)n * a.nblk * 2, s));
+    DEC_HIP("jpeg decode", hipMemsetAsync(a.dcs, 0, r.blocks * 2, s));
     Events ev;
     for (int g0 = 0, gi = 0; g0 < (int)hfiles.size(); g0 += group, gi++) {
         const int half = gi & 1, cnt = std::min(group, (int)hfiles.size() - g0);
-        int16_t *base = hpin + (size_t)half * std::min(P.nhost, group) * hslot_words;
+        int16_t *base = hpin + (size_t)half * half_words;
         if (gi >= 2) DEC_HIP("jpeg decode", hipEventSynchronize(ev.ev[half]));          // the copies of two groups ago have left this half
         rc = parallel_heavy(cnt, [&](int j) {
             const int i = hfiles[g0 + j];
             bool prog = false;
             int alone = 0;
             JpegDecInfo full;
-            const int st = jpeg_host_decode(r.jpegs[i].data, r.jpegs[i].len, &full, base + (size_t)j * hslot_words, base + (size_t)j * hslot_words + hcoef_words,
-                                            (size_t)a.nblk, P.tabs[i].qnat, &prog, r.s411, &alone);
+            int16_t *slot = base + hoff[g0 + j];
+            const int st = jpeg_host_decode(r.jpegs[i].data, r.jpegs[i].len, &full, slot, slot + r.nblk(i) * 64, r.nblk(i), P.tabs[i].qnat, &prog, r.s411, &alone);
             if (st != IPX_OK) { r.status[i] = st; P.valid[i] = 0; }
             else P.valid[i] |= (uint8_t)(alone << 2);     // the blocks a non-interleaved sequential scan skips stay zero (jpeg_idct_kernel)
         }, kPrep);
@@ -147,8 +186,9 @@ int dec_upload(DecRun &r)
         for (int j = 0; j < cnt; j++) {
             const int i = hfiles[g0 + j];
             if (!P.valid[i]) continue;
-            DEC_HIP("jpeg decode", hipMemcpyAsync(a.coefs + (size_t)i * hcoef_words, base + (size_t)j * hslot_words, hcoef_words * 2, hipMemcpyHostToDevice, s));
-            DEC_HIP("jpeg decode", hipMemcpyAsync(a.dcs + (size_t)i * a.nblk, base + (size_t)j * hslot_words + hcoef_words, (size_t)a.nblk * 2, hipMemcpyHostToDevice, s));
+            const int16_t *slot = base + hoff[g0 + j];
+            DEC_HIP("jpeg decode", hipMemcpyAsync(a.coefs + r.blk0(i) * 64, slot, r.nblk(i) * 128, hipMemcpyHostToDevice, s));
+            DEC_HIP("jpeg decode", hipMemcpyAsync(a.dcs + r.blk0(i), slot + r.nblk(i) * 64, r.nblk(i) * 2, hipMemcpyHostToDevice, s));
         }
         if (!ev.ev[half]) DEC_HIP("jpeg decode", hipEventCreateWithFlags(&ev.ev[half], hipEventDisableTiming));
         DEC_HIP("jpeg decode", hipEventRecord(ev.ev[half], s));
@@ -204,9 +244,11 @@ int par_setup(DecRun &r, JpegParArgs &P, uint32_t **d_tot)
     hipStream_t s = r.s;
     const size_t blob_bytes = r.plan.blob_bytes;
     P.blob = r.d_blob; P.tab = r.d_tab; P.nimg = (int)par.size(); P.bpm = a.bpm; P.ybl = a.ybl; P.nblk = a.nblk;
+    P.geom = a.geom;
     P.coefs = a.coefs; P.status = a.status; P.dcs = a.dcs;
     P.sub = r.plan.par_sub;
     for (auto &pi : par) P.max_nsub = std::max(P.max_nsub, (int)pi.nsub);
+    r.max_nsub = P.max_nsub;
     for (size_t k = 0; k < par.size(); k++) par[k].sub_off = k * (size_t)P.max_nsub;
     const size_t nsubs = par.size() * (size_t)P.max_nsub, cks = (size_t)jpeg_par_checkpoints();
     // The scan bytes of a wave's 64 sub-sequences staged in LDS (small batches: a SIMD has one wave, which would wait for a global load
@@ -249,7 +291,7 @@ int par_fallback(DecRun &r)
     for (auto &pi : r.plan.par) {
         JpegDecImage it;
         memset(&it, 0, sizeof it);
-        it.scan_off = pi.scan_off; it.scan_len = pi.scan_len; it.img = pi.img; it.first_mcu = 0; it.n_mcu = (uint32_t)(a.mxx * a.myy);
+        it.scan_off = pi.scan_off; it.scan_len = pi.scan_len; it.img = pi.img; it.first_mcu = 0; it.n_mcu = (uint32_t)(r.nblk((int)pi.img) / (size_t)a.bpm);
         memcpy(it.td, pi.td, 3); memcpy(it.ta, pi.ta, 3);
         it.valid = 1;
         serial.push_back(it);
@@ -329,7 +371,8 @@ int dec_finish(DecRun &r, ipx_ycbcr_batch *planes)
     DEC_HIP("jpeg decode", hipMemcpyAsync(r.dev_status.data(), r.a.status, sizeof(int) * r.n, hipMemcpyDeviceToHost, r.s));
     DEC_HIP("jpeg decode", hipStreamSynchronize(r.s));
     if ((getenv("IPX_DEBUG") && r.ms() > 200.0) || env_int("IPX_DEBUG_J2J", 0))
-        fprintf(stderr, "[ipx] decode of %d files: parsed at %.1f ms, device scratch at %.1f, pinned block at %.1f, packed at %.1f, launched at %.1f, finished at %.1f\n", r.n, r.plan.parse_ms, r.t_alloc, r.t_pin, r.t_pack, r.t_launch, r.ms());
+        fprintf(stderr, "[ipx] decode of %d files%s: parsed at %.1f ms, device scratch at %.1f, pinned block at %.1f, packed at %.1f, launched at %.1f, finished at %.1f; planes %.1f MB, scratch %.1f MB, %d sub-sequences at most\n",
+                r.n, r.mixed ? " of mixed sizes" : "", r.plan.parse_ms, r.t_alloc, r.t_pin, r.t_pack, r.t_launch, r.ms(), r.plane_bytes / 1e6, r.scratch_bytes / 1e6, r.max_nsub);
     const JpegBatchPlan &P = r.plan;
     for (int i = 0; i < r.n; i++) {
         const bool walked = P.route[i] == IPX_JPEG_ROUTE_GPU_SCANS;
@@ -348,6 +391,7 @@ int dec_finish(DecRun &r, ipx_ycbcr_batch *planes)
         if (P.route[i] <= IPX_JPEG_ROUTE_GPU_SCANS) r.ctx->jpeg_counts[P.route[i]]++;
         if (walked && r.status[i] != IPX_OK) r.ctx->jpeg_counts[3]++;
     }
+    if (!planes) return IPX_OK;         // a mixed-size class: its caller describes every file's planes (decode_class)
     planes->y = r.pl.y; planes->cb = r.pl.cb; planes->cr = r.pl.cr;
     planes->ystride = r.pl.ystride; planes->cstride = r.pl.cstride;
     planes->y_frame_stride = r.pl.y_fs; planes->c_frame_stride = r.pl.c_fs;
@@ -355,7 +399,74 @@ int dec_finish(DecRun &r, ipx_ycbcr_batch *planes)
     return IPX_OK;
 }
 
+// One sampling class of a mixed-size call: files [0, n) -- parsed already, `parsed` holds what jpeg_plan_parse left for them -- of any
+// sizes through ONE run of the stages above.  The planes are blocks of `own`; frames[i] describes file i's, all zero unless it decoded.
+int decode_class(ipx_ctx *ctx, hipStream_t s, Lane *lane, const ipx_bytes *jpegs, int n, JpegBatchPlan &&parsed, const JpegPlanOptions &opt,
+                 OwnedBlocks<ipx_jpeg_planes> &own, ipx_jpeg_frame *frames, int *status)
+{
+    DecRun r(ctx, s, jpegs, n, status);
+    r.mixed = true;
+    r.plan = std::move(parsed);
+    jpeg_plan_place(jpegs, n, opt, status, &r.plan);
+    if (r.plan.ref < 0) return IPX_OK;
+    int rc = dec_blocks(r, lane, false, own);
+    if (!rc) rc = dec_upload(r);
+    if (!rc) rc = dec_huffman(r);
+    if (!rc) rc = dec_finish(r, nullptr);
+    if (rc) return rc;
+    const bool gray = r.a.bpm == 1;
+    for (int i = 0; i < n; i++) {
+        if (status[i] != IPX_OK) continue;
+        const JpegMixGeom &g = r.geom[i];
+        frames[i] = ipx_jpeg_frame{g.w, g.h, r.plan.info[i].ratio, r.pl.y + g.yoff, gray ? nullptr : r.pl.cb + g.coff, gray ? nullptr : r.pl.cr + g.coff,
+                                   g.ystride, gray ? 0 : g.cstride};
+    }
+    return IPX_OK;
+}
+
 }  // namespace
+
+// The two halves of a mixed-size decode (ipx_decode_common.h).  The GPU scan walk and 4:1:1 / 4:1:0 are off in both whatever their
+// switches say.
+static JpegPlanOptions mixed_options()
+{
+    return JpegPlanOptions{0, 0, env_int("IPX_JPEG_PAR", 1) != 0, env_int("IPX_JPEG_PAR_SUB", 0), jpeg_par_sub_bytes(), false, false, true};
+}
+
+int jpeg_mixed_parse(const ipx_bytes *jpegs, int n, int *status, JpegBatchPlan *all) { return jpeg_plan_parse(jpegs, n, mixed_options(), status, all); }
+
+// one decode_class per sampling class -- (h0, v0, components) -- of the m files idx[0 .. m), each class's files in idx's order
+int jpeg_mixed_decode(ipx_ctx *ctx, hipStream_t s, Lane *lane, const ipx_bytes *jpegs, JpegBatchPlan &all, const int *idx, int m,
+                      OwnedBlocks<ipx_jpeg_planes> &own, ipx_jpeg_frame *frames, int *status)
+{
+    const JpegPlanOptions opt = mixed_options();
+    std::vector<uint8_t> taken(m, 0);
+    for (int first = 0; first < m; first++) {
+        if (taken[first] || status[idx[first]] != IPX_OK) continue;
+        const JpegDecInfo F = all.info[idx[first]];
+        std::vector<int> of;                                  // the class's files, by the caller's index
+        for (int g = first; g < m; g++) {
+            const JpegDecInfo &I = all.info[idx[g]];
+            if (!taken[g] && status[idx[g]] == IPX_OK && I.h0 == F.h0 && I.v0 == F.v0 && I.ncomp == F.ncomp) { of.push_back(idx[g]); taken[g] = 1; }
+        }
+        const int c = (int)of.size();
+        std::vector<ipx_bytes> files(c);
+        std::vector<ipx_jpeg_frame> fr(c, ipx_jpeg_frame{});
+        std::vector<int> st(c, IPX_OK);
+        JpegBatchPlan P;
+        P.info.resize(c); P.tabs.resize(c); P.prog.resize(c); P.marks.resize(c);
+        P.parse_ms = all.parse_ms;
+        for (int k = 0; k < c; k++) {
+            const int i = of[k];
+            files[k] = jpegs[i];
+            P.info[k] = all.info[i]; P.tabs[k] = all.tabs[i]; P.marks[k] = std::move(all.marks[i]);
+        }
+        const int rc = decode_class(ctx, s, lane, files.data(), c, std::move(P), opt, own, fr.data(), st.data());
+        if (rc) return rc;
+        for (int k = 0; k < c; k++) { status[of[k]] = st[k]; if (st[k] == IPX_OK) frames[of[k]] = fr[k]; }
+    }
+    return IPX_OK;
+}
 
 // lane != NULL: scratch is bumped out of the lane's decode buffer (no allocation in the steady state); planes_in_lane: the planes too --
 // the caller then holds the lane for as long as it uses them and *owner has nothing to free
@@ -399,6 +510,31 @@ int ipx_jpeg_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *jpegs, in
     LaneLease lane(ctx);
     return jpeg_decode_files(ctx, stream ? (hipStream_t)stream : ctx->stream, env_int("IPX_JPEG_LANE_ARENA", 1) ? &lane.get() : nullptr, false, jpegs, n, w, h,
                              planes, status, owner);
+}
+IPX_CATCH_STATUS
+
+int ipx_jpeg_decode_mixed(ipx_ctx *ctx, void *stream, const ipx_bytes *files, int n, ipx_jpeg_frame *frames, int *status,
+                          ipx_jpeg_planes **owner) try
+{
+    IPX_ENTER(ctx);
+    if (n < 0 || !owner || (n && (!files || !frames || !status))) { set_error("ipx_jpeg_decode_mixed: bad argument"); return IPX_ERR_INVALID; }
+    *owner = nullptr;
+    if (n == 0) return IPX_OK;
+    if (n > 65535) { set_error("ipx_jpeg_decode_mixed: at most 65535 files per call"); return IPX_ERR_UNSUPPORTED; }
+    memset(frames, 0, sizeof(ipx_jpeg_frame) * (size_t)n);
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    OwnedBlocks<ipx_jpeg_planes> own(ctx, s);
+    JpegBatchPlan all;
+    int rc = jpeg_mixed_parse(files, n, status, &all);
+    if (rc) return rc;
+    std::vector<int> idx(n);
+    for (int i = 0; i < n; i++) idx[i] = i;
+    // the scratch comes out of a lane's decode buffer for the duration of the call; the planes are the caller's (stream-ordered allocations)
+    LaneLease lane(ctx);
+    rc = jpeg_mixed_decode(ctx, s, env_int("IPX_JPEG_LANE_ARENA", 1) ? &lane.get() : nullptr, files, all, idx.data(), n, own, frames, status);
+    if (rc) return rc;
+    if (any_ok(status, n)) *owner = own.release();
+    return IPX_OK;
 }
 IPX_CATCH_STATUS
 

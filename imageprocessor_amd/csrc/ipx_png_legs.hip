@@ -7,6 +7,7 @@
 #include "ipx_png.h"
 #include "ipx_png_dec.h"
 #include "ipx_png_mixed_plan.h"
+#include "ipx_size_plans.h"
 #include "ipx_decode_common.h"
 
 // ---- the PNG leg -----------------------------------------------------------------------------------------------------------------
@@ -102,20 +103,6 @@ IPX_CATCH_STATUS
 // ---- the mixed-size PNG leg ------------------------------------------------------------------------------------------------------
 
 namespace {
-// the plans of one call, one per frame size, from the context's cache; handed back on every way out
-struct SizePlans {
-    struct Held { ipx_plan *pl; int cached; };
-    ipx_ctx *ctx;
-    std::map<std::pair<int, int>, Held> held;
-    explicit SizePlans(ipx_ctx *c) : ctx(c) {}
-    SizePlans(const SizePlans &) = delete;
-    ~SizePlans()
-    {
-        for (auto &kv : held)
-            if (kv.second.pl) ipx_plan_release(ctx, kv.second.pl, kv.second.cached);
-    }
-};
-
 // what output k of a plan costs a chunk: the frame itself and the encoder's scratch for it -- the filtered stream, a word of match
 // scratch per filtered byte, and the frame's region
 size_t mixed_out_cost(const OutShape &sh)
@@ -139,32 +126,12 @@ struct MixedCall {
     size_t out_fs(int i, int k) const { return dst[k] ? align256(out_shape(plan_of[i]->info, k).bytes) : 0; }
 };
 
-// a plan per size; files of a size no plan can be made for get ipx_plan_create's status, alone.  Every distinct size of the call
-// holds its plan until the call returns: at most one per file (65535), of which the context's cache keeps IPX_PLAN_CACHE_MAX (256) and
-// the rest live and die with this call -- a call with more sizes than that also turns the cache over once
+// a plan per size (ipx_size_plans.h); files of a size no plan can be made for get ipx_plan_create's status, alone
 int mixed_plans(MixedCall &c, const ipx_pool_ops *ops, int n, SizePlans &plans)
 {
-    std::map<std::pair<int, int>, int> plan_rc;
-    c.plan_of.assign(n, nullptr);
-    for (int i = 0; i < n; i++) {
-        if (c.status[i] != IPX_OK) continue;
-        const std::pair<int, int> key(c.info[i].w, c.info[i].h);
-        auto it = plan_rc.find(key);
-        if (it == plan_rc.end()) {
-            ipx_pool_ops o = *ops;
-            o.sw = key.first;
-            o.sh = key.second;
-            SizePlans::Held hd{nullptr, 0};
-            const int prc = ipx_plan_acquire(c.ctx, &o, &hd.pl, &hd.cached);
-            // a size the operators cannot be planned for is that size's verdict; anything else (memory, the device) fails the call
-            if (prc != IPX_OK && prc != IPX_ERR_INVALID && prc != IPX_ERR_UNSUPPORTED) return prc;
-            if (prc == IPX_OK) plans.held[key] = hd;
-            it = plan_rc.emplace(key, prc).first;
-        }
-        if (it->second != IPX_OK) { c.status[i] = it->second; continue; }
-        c.plan_of[i] = plans.held[key].pl;
-    }
-    return IPX_OK;
+    std::vector<int> w(n), h(n);
+    for (int i = 0; i < n; i++) { w[i] = c.info[i].w; h[i] = c.info[i].h; }
+    return size_plans_acquire(c.ctx, ops, n, w.data(), h.data(), c.status, plans, &c.plan_of);
 }
 
 // a chunk's three arenas: file p's frame of output k at arena[k] + off[k][p]

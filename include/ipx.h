@@ -619,6 +619,21 @@ int ipx_jpeg_scan_route(const uint8_t *file, size_t len, int *route);
  * with; files refused by the marker parser or for their geometry reach none), and [3] the files the GPU scan walk ended with a status
  * other than IPX_OK */
 int ipx_jpeg_decode_counts(ipx_ctx *ctx, long long counts[4]);
+/* n JPEG files of any sizes and samplings in ONE decode pass per sampling class.  The files are grouped by class -- one (h0, v0,
+ * components): 4:4:4, 4:2:2, 4:2:0, 4:4:0 or Gray -- and every class is decoded by one set of launches whatever sizes it holds: the
+ * kernels read each image's geometry from a per-image record in HBM instead of the launch arguments.  One
+ * baseline scan goes to the parallel Huffman passes, restart intervals to the piece kernels, progressive and multi-scan files to the
+ * host threads.  frames[i] describes file i's own *image.YCbCr or *image.Gray in HBM: its size, its ratio (IPX_YCBCR_*, IPX_GRAY),
+ * the planes (256-byte aligned) and the MCU-padded strides of image.NewYCbCr; cb and cr are NULL and cstride 0 for IPX_GRAY; every
+ * field is zero for a non-OK file.  status[i] is exactly what ipx_jpeg_decode_batch gives that file in a call of its own with
+ * *w = *h = 0: no file is IPX_ERR_UNSUPPORTED because of a neighbour's size or sampling.  Whatever the switches say, in this entry
+ * the GPU scan walk (IPX_JPEG_PROG_GPU=1) is not used -- such files take the host route, with the same planes and statuses -- and
+ * 4:1:1, 4:1:0 (IPX_JPEG_411=1) and four-component files (IPX_JPEG_CMYK=1) are IPX_ERR_UNSUPPORTED.  The three route counters of
+ * ipx_jpeg_decode_counts count these files too.  *owner (NULL when nothing decoded) is freed with ipx_jpeg_planes_free.  n == 0 is
+ * IPX_OK; more than 65535 files is IPX_ERR_UNSUPPORTED. */
+typedef struct { int32_t w, h, ratio; uint8_t *y, *cb, *cr; int32_t ystride, cstride; } ipx_jpeg_frame;
+int ipx_jpeg_decode_mixed(ipx_ctx *ctx, void *stream, const ipx_bytes *files, int n, ipx_jpeg_frame *frames, int *status,
+                          ipx_jpeg_planes **owner);
 /* Four-component JPEGs (Adobe CMYK and YCCK: print-workflow and Photoshop files), with IPX_JPEG_CMYK=1 in the environment (read on every
  * call; unset or anything else: every such file is IPX_ERR_UNSUPPORTED in every entry, as before).  Go takes two sampling vectors,
  * (h, v) = 11 11 11 11 and 22 11 11 22, and needs a valid Adobe APP14 segment; a file of the call's size (*w, *h: 0, or the size the
@@ -804,6 +819,26 @@ void ipx_plan_release(ipx_ctx *ctx, ipx_plan *plan, int cached);
  * ipx_plan_run_png_png (ipx_jpeg_result_free).  DESIGN.md section 4.10. */
 int ipx_run_png_png_mixed(ipx_ctx *ctx, const ipx_pool_ops *ops, int n, const ipx_bytes *files, const ipx_text *texts,
                           ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result);
+
+/* The JPEG task compressed in, compressed out for uploads of ANY sizes and samplings in one call; the contract is
+ * ipx_run_png_png_mixed's.  ops gives the operator parameters; ops->sw and ops->sh are ignored (each file's own size is used).
+ * texts: NULL, or n texts, texts[i] positioned by the caller for file i's size and drawn as ipx_plan_run_jpeg_jpeg_texts draws it
+ * (then ops->glyphs must be NULL, else IPX_ERR_INVALID with nothing written; the rules of ipx_textset_create: more than 256 glyphs in
+ * any text refuses the call); without texts, a glyph list in ops is clipped against every size's frame as a plan of that size clips it.
+ * The files are parsed once and decoded as ipx_jpeg_decode_mixed decodes them -- so here too the GPU scan walk (IPX_JPEG_PROG_GPU=1) is
+ * not used, and 4:1:1, 4:1:0 and four-component files are IPX_ERR_UNSUPPORTED whatever IPX_JPEG_411 and IPX_JPEG_CMYK say.  The OK
+ * files are ordered by (width, height, sampling class) and cut into decode groups of IPX_JPEG_MIXED_GROUP (256) files and ~4 GiB of
+ * planes and coefficient scratch, each group ONE decode pass per sampling class; a group is cut into chunks of at most
+ * IPX_JPEG_MIXED_CHUNK_MB (8192: the 256 files of a 1080p group in one chunk) of output frames and encoder scratch; within a chunk the operators run once per run of one size and
+ * class, with a plan of that size from the context's cache (ipx_plan_acquire).  An output that has one size for every file of the chunk
+ * (a resize without keep_aspect, a cropped thumbnail) is encoded once per chunk, every other output once per run; there is no
+ * mixed-size jpeg.Encode.  status[i] and the three streams of file i are byte for byte what ipx_plan_run_jpeg_jpeg (or _texts) returns
+ * for that file in a call of its own with a plan of its size and the same quality -- outside the three switches named above; files of a
+ * size for which no plan can be made get the status ipx_plan_create returned, alone.  A NULL output array skips that output; an
+ * operator ops does not ask for gives {NULL, 0}; n == 0 is IPX_OK; more than 65535 files is IPX_ERR_UNSUPPORTED.  Streams as for
+ * ipx_plan_run_jpeg_jpeg (ipx_jpeg_result_free).  DESIGN.md sections 4.6 and 7. */
+int ipx_run_jpeg_jpeg_mixed(ipx_ctx *ctx, const ipx_pool_ops *ops, int n, const ipx_bytes *files, const ipx_text *texts, int quality,
+                            ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result);
 
 enum { IPX_JOB_RGBA8 = 0,       /* decoded frames in, the operators' RGBA8 outputs back (what ipx_plan_run_host does) */
        IPX_JOB_JPEG = 1,        /* uploaded JPEG files in, three JPEG streams per file back (what ipx_plan_run_jpeg_jpeg does) */
