@@ -140,6 +140,44 @@ def _text_array(texts):
     return arr, keep
 
 
+def _texts_for(texts, n):
+    """texts: None, or one (glyphs, col) per file -> (ipx_text array | None, what it points into)"""
+    if texts is None:
+        return None, None
+    texts = list(texts)
+    if len(texts) != n:
+        raise ValueError("one text per file")
+    return _text_array(texts)
+
+
+def _pool_ops(ops, glyph_list=False):
+    """ops: a PoolOps, taken as it is, or dict(resize=(w, h, keep_aspect) | None, thumbnail=(size, crop_to_fit) | None, watermark=bool)
+    -> (PoolOps with sw = sh = 0, what it points into).  glyph_list: watermark=(glyphs, col) puts that glyph list into the PoolOps;
+    where it is False such a pair means no more than True."""
+    if not isinstance(ops, dict):
+        return ops, None
+    o, keep = _lib.PoolOps(), None
+    if ops.get("resize"):
+        o.do_resize, o.resize_w, o.resize_h, o.keep_aspect = 1, ops["resize"][0], ops["resize"][1], int(bool(ops["resize"][2]))
+    if ops.get("thumbnail"):
+        o.do_thumbnail, o.thumb_size, o.crop_to_fit = 1, ops["thumbnail"][0], int(bool(ops["thumbnail"][1]))
+    wm = ops.get("watermark")
+    o.do_watermark = int(bool(wm))
+    if glyph_list and isinstance(wm, (tuple, list)):
+        glyphs, col = list(wm[0]), wm[1]
+        keep = _glyph_array(glyphs)
+        o.glyphs, o.n_glyphs = keep[0], len(glyphs)
+        for c in range(4):
+            o.col[c] = int(col[c])
+    return o, keep
+
+
+def _streams(arrs, n, copy):
+    """{operator: the ipx_bytes array a compressed-out entry filled} -> {operator: [bytes | None] * n}: None for a slot the entry left
+    unpublished; copy=False: the stream's length instead of its bytes"""
+    return {k: [(C.string_at(a[j].data, a[j].len) if copy else a[j].len) if a[j].data else None for j in range(n)] for k, a in arrs.items()}
+
+
 # ---- GPU objects -------------------------------------------------------------------------------------
 
 class DevBuffer:
@@ -314,8 +352,7 @@ class Plan:
         extra = () if status is None else (status,)
         _check(entry(self.ctx.handle, self.handle, n, *args, arrs.get("resize"), arrs.get("thumbnail"), arrs.get("watermark"), *extra,
                      C.byref(res)))
-        out = {k: [(C.string_at(a[j].data, a[j].len) if copy else a[j].len) if a[j].data else None for j in range(n)]
-               for k, a in arrs.items()}
+        out = _streams(arrs, n, copy)
         lib().ipx_jpeg_result_free(self.ctx.handle, res)
         return out
 
@@ -361,11 +398,8 @@ class Plan:
 
     def _run_files_texts(self, entry, files, texts, want, copy, args=()):
         """A file-in entry with texts[i] = (glyphs, col) drawn on file i's watermark (the plan must be copy-only: watermark=True)."""
-        texts = list(texts)
-        if len(texts) != len(files):
-            raise ValueError("one text per file")
-        arr, keep = _text_array(texts)
         n = len(files)
+        arr, keep = _texts_for(texts, n)
         status = (C.c_int * max(n, 1))()
         out = self._run_streams(entry, n, want, copy, (_bytes_array(files), arr) + args, status)
         return out, list(status)[:n]
@@ -779,40 +813,39 @@ class Context:
         ratio, ystride, cstride, y, cb, cr) with the
         planes over the image's MCU-padded extent as rows x stride uint8 arrays, cb and cr None for a Gray file (download=True), or the
         device pointers.  With download=False a third value, free(), releases the planes."""
+        def frame(f):
+            if not f.y:
+                return None
+            d = {"w": f.w, "h": f.h, "ratio": f.ratio, "ystride": f.ystride, "cstride": f.cstride, "y": f.y, "cb": f.cb, "cr": f.cr}
+            if download:
+                v0 = 2 if f.ratio in (2, 3) else 1          # 4:2:0 and 4:4:0 halve the chroma rows (Gray: 8 x 8 MCUs)
+                myy = (f.h + 8 * v0 - 1) // (8 * v0)
+                d["y"] = self._grab(f.y, 8 * v0 * myy, f.ystride)
+                d["cb"] = self._grab(f.cb, 8 * myy, f.cstride) if f.cb else None
+                d["cr"] = self._grab(f.cr, 8 * myy, f.cstride) if f.cr else None
+            return d
+        return self._decode_mixed("ipx_jpeg_decode_mixed", "ipx_jpeg_planes_free", files, _lib.JpegFrame, frame, download)
+
+    def _decode_mixed(self, entry, free, files, frame_type, frame, download):
+        """What the *_decode_mixed methods share: the arrays (a file given as None goes in as a NULL entry: IPX_ERR_INVALID for that file
+        alone), the call of `entry`, then frame(record) for every file -- the dict of a decoded frame, downloading what it downloads,
+        or None -- and the release of the device blocks: here (download), or left to the caller as a third value."""
         n = len(files)
-        fr = (_lib.JpegFrame * max(n, 1))()
-        status = (C.c_int * max(n, 1))()
-        owner = C.c_void_p()
         arr = _bytes_array([f if f is not None else b"" for f in files])
         for i, f in enumerate(files):
-            if f is None:                       # an entry with data == NULL: IPX_ERR_INVALID for that file alone
+            if f is None:
                 arr[i].data = None
-        _check(lib().ipx_jpeg_decode_mixed(self.handle, None, arr, n, fr, status, C.byref(owner)))
-        free = lambda: lib().ipx_jpeg_planes_free(self.handle, owner)
-
-        def grab(ptr, rows, stride):
-            a = np.empty((rows, stride), np.uint8)
-            _check(lib().ipx_memcpy_d2h(self.handle, a.ctypes.data, ptr, a.nbytes))
-            return a
-        out = []
+        fr = (frame_type * max(n, 1))()
+        status = (C.c_int * max(n, 1))()
+        owner = C.c_void_p()
+        _check(getattr(lib(), entry)(self.handle, None, arr, n, fr, status, C.byref(owner)))
+        release = lambda: getattr(lib(), free)(self.handle, owner)
         try:
-            for i in range(n):
-                f = fr[i]
-                if not f.y:
-                    out.append(None)
-                    continue
-                d = {"w": f.w, "h": f.h, "ratio": f.ratio, "ystride": f.ystride, "cstride": f.cstride, "y": f.y, "cb": f.cb, "cr": f.cr}
-                if download:
-                    v0 = 2 if f.ratio in (2, 3) else 1          # 4:2:0 and 4:4:0 halve the chroma rows (Gray: 8 x 8 MCUs)
-                    myy = (f.h + 8 * v0 - 1) // (8 * v0)
-                    d["y"] = grab(f.y, 8 * v0 * myy, f.ystride)
-                    d["cb"] = grab(f.cb, 8 * myy, f.cstride) if f.cb else None
-                    d["cr"] = grab(f.cr, 8 * myy, f.cstride) if f.cr else None
-                out.append(d)
+            out = [frame(fr[i]) for i in range(n)]
         finally:
             if download:
-                free()
-        return (out, list(status)[:n]) if download else (out, list(status)[:n], free)
+                release()
+        return (out, list(status)[:n]) if download else (out, list(status)[:n], release)
 
     JPEG_ROUTE_PAR, JPEG_ROUTE_HOST_SCANS, JPEG_ROUTE_GPU_SCANS = 0, 1, 2
 
@@ -902,36 +935,15 @@ class Context:
         list); frames[i] is None for a non-OK file, else dict(w, h, kind, stride, pix, palette) with pix as h x (w * bytes per pixel)
         uint8 (Go's Pix rows) and palette as 256 x 4 uint8 (PNG_PALETTED) or None (download=True), or the device pointers.  With
         download=False a third value, free(), releases the frames."""
-        n = len(files)
-        arr = _bytes_array(files)
-        fr = (_lib.PngFrame * max(n, 1))()
-        status = (C.c_int * max(n, 1))()
-        owner = C.c_void_p()
-        _check(lib().ipx_png_decode_mixed(self.handle, None, arr, n, fr, status, C.byref(owner)))
-        st = list(status)[:n]
-        out = []
-        try:
-            for i in range(n):
-                f = fr[i]
-                if not f.pix:
-                    out.append(None)
-                    continue
-                d = {"w": f.w, "h": f.h, "kind": f.kind, "stride": f.stride, "pix": f.pix, "palette": f.palette}
-                if download:
-                    pix = np.empty((f.h, f.stride), np.uint8)
-                    _check(lib().ipx_memcpy_d2h(self.handle, pix.ctypes.data, f.pix, pix.nbytes))
-                    d["pix"], d["palette"] = pix, None
-                    if f.palette:
-                        pal = np.empty((256, 4), np.uint8)
-                        _check(lib().ipx_memcpy_d2h(self.handle, pal.ctypes.data, f.palette, pal.nbytes))
-                        d["palette"] = pal
-                out.append(d)
-        finally:
+        def frame(f):
+            if not f.pix:
+                return None
+            d = {"w": f.w, "h": f.h, "kind": f.kind, "stride": f.stride, "pix": f.pix, "palette": f.palette}
             if download:
-                lib().ipx_png_frames_free(self.handle, owner)
-        if download:
-            return out, st
-        return out, st, (lambda: lib().ipx_png_frames_free(self.handle, owner))
+                d["pix"] = self._grab(f.pix, f.h, f.stride)
+                d["palette"] = self._grab(f.palette, 256, 4) if f.palette else None
+            return d
+        return self._decode_mixed("ipx_png_decode_mixed", "ipx_png_frames_free", files, _lib.PngFrame, frame, download)
 
     def png_encode_mixed_dev(self, frames, copy=True):
         """frames: (device pointer, w, h, stride) per RGBA8 frame in HBM, of any sizes -> one PNG stream each (ipx_png_encode_mixed_dev).
@@ -950,30 +962,8 @@ class Context:
         the operators per run of one size, one mixed-size png.Encode per output (ipx_run_png_png_mixed).  ops: a PoolOps with sw = sh
         = 0 and no glyphs, or dict(resize=(w, h, keep_aspect) | None, thumbnail=(size, crop_to_fit) | None, watermark=bool).
         texts: None, or one (glyphs, col) per file, positioned for that file's size.  copy=False: lengths instead of bytes."""
-        if isinstance(ops, dict):
-            o = _lib.PoolOps()
-            if ops.get("resize"):
-                o.do_resize, o.resize_w, o.resize_h, o.keep_aspect = 1, ops["resize"][0], ops["resize"][1], int(bool(ops["resize"][2]))
-            if ops.get("thumbnail"):
-                o.do_thumbnail, o.thumb_size, o.crop_to_fit = 1, ops["thumbnail"][0], int(bool(ops["thumbnail"][1]))
-            o.do_watermark = int(bool(ops.get("watermark")))
-            ops = o
-        n = len(files)
-        tarr, keep = (None, None)
-        if texts is not None:
-            texts = list(texts)
-            if len(texts) != n:
-                raise ValueError("one text per file")
-            tarr, keep = _text_array(texts)
-        arrs = {k: (_lib.Bytes * max(n, 1))() for k in ("resize", "thumbnail", "watermark") if k in want}
-        status = (C.c_int * max(n, 1))()
-        res = C.c_void_p()
-        _check(lib().ipx_run_png_png_mixed(self.handle, C.byref(ops), n, _bytes_array(files), tarr, arrs.get("resize"),
-                                           arrs.get("thumbnail"), arrs.get("watermark"), status, C.byref(res)))
-        out = {k: [(C.string_at(a[j].data, a[j].len) if copy else a[j].len) if a[j].data else None for j in range(n)]
-               for k, a in arrs.items()}
-        lib().ipx_jpeg_result_free(self.handle, res)
-        return out, list(status)[:n]
+        ops, keep = _pool_ops(ops)
+        return self._run_mixed(lib().ipx_run_png_png_mixed, ops, files, texts, want, copy)
 
     def run_jpeg_jpeg_mixed(self, ops, files, quality=85, want=("resize", "thumbnail", "watermark"), copy=True, texts=None):
         """JPEG byte strings of ANY sizes and samplings in -> ({operator: [jpeg bytes | None] * n}, status list): one decode pass per
@@ -981,38 +971,20 @@ class Context:
         a PoolOps, or dict(resize=(w, h, keep_aspect) | None, thumbnail=(size, crop_to_fit) | None, watermark=bool | (glyphs, col): a
         glyph list every size's plan clips against its own frame).  texts: None, or one (glyphs, col) per file, positioned for that
         file's size (then no glyph list in ops).  copy=False: lengths instead of bytes."""
-        keep = []
-        if isinstance(ops, dict):
-            o = _lib.PoolOps()
-            if ops.get("resize"):
-                o.do_resize, o.resize_w, o.resize_h, o.keep_aspect = 1, ops["resize"][0], ops["resize"][1], int(bool(ops["resize"][2]))
-            if ops.get("thumbnail"):
-                o.do_thumbnail, o.thumb_size, o.crop_to_fit = 1, ops["thumbnail"][0], int(bool(ops["thumbnail"][1]))
-            wm = ops.get("watermark")
-            o.do_watermark = int(bool(wm))
-            if isinstance(wm, (tuple, list)):
-                glyphs, col = list(wm[0]), wm[1]
-                ga, gk = _glyph_array(glyphs)
-                keep.append((ga, gk))
-                o.glyphs, o.n_glyphs = ga, len(glyphs)
-                for c in range(4):
-                    o.col[c] = int(col[c])
-            ops = o
+        ops, keep = _pool_ops(ops, glyph_list=True)
+        return self._run_mixed(lib().ipx_run_jpeg_jpeg_mixed, ops, files, texts, want, copy, (int(quality),))
+
+    def _run_mixed(self, entry, ops, files, texts, want, copy, args=()):
+        """A mixed-size leg: the texts, an output array per wanted operator, the call (args go between the texts and the arrays), then
+        ({operator: [bytes | length | None] * n}, status list); the result is freed."""
         n = len(files)
-        tarr = None
-        if texts is not None:
-            texts = list(texts)
-            if len(texts) != n:
-                raise ValueError("one text per file")
-            tarr, tkeep = _text_array(texts)
-            keep.append(tkeep)
+        tarr, keep = _texts_for(texts, n)
         arrs = {k: (_lib.Bytes * max(n, 1))() for k in ("resize", "thumbnail", "watermark") if k in want}
         status = (C.c_int * max(n, 1))()
         res = C.c_void_p()
-        _check(lib().ipx_run_jpeg_jpeg_mixed(self.handle, C.byref(ops), n, _bytes_array(files), tarr, int(quality), arrs.get("resize"),
-                                             arrs.get("thumbnail"), arrs.get("watermark"), status, C.byref(res)))
-        out = {k: [(C.string_at(a[j].data, a[j].len) if copy else a[j].len) if a[j].data else None for j in range(n)]
-               for k, a in arrs.items()}
+        _check(entry(self.handle, C.byref(ops), n, _bytes_array(files), tarr, *args, arrs.get("resize"), arrs.get("thumbnail"),
+                     arrs.get("watermark"), status, C.byref(res)))
+        out = _streams(arrs, n, copy)
         lib().ipx_jpeg_result_free(self.handle, res)
         return out, list(status)[:n]
 
@@ -1049,8 +1021,7 @@ class PoolJob:
             _check(lib().ipx_job_wait(self.pool.handle, self.ticket, C.byref(fd)))
             if self.job.kind not in Pool.FILE_KINDS.values():      # every kind but the file jobs hands pixels back
                 return self.outs
-            out = {k: [C.string_at(a[j].data, a[j].len) if a[j].data else None for j in range(self.n)] for k, a in self.outs.items()}
-            return out, list(self.keep["status"])[:self.n]
+            return _streams(self.outs, self.n, True), list(self.keep["status"])[:self.n]
         finally:
             self.release()
 

@@ -9,6 +9,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "ipx_align.h"
+
 #if defined(__HIPCC__)
 #define IPX_MIX_HD __host__ __device__
 #else
@@ -45,8 +47,6 @@ struct JpegMixTotals {
     int max_nblk = 0;
 };
 
-inline size_t jpeg_mix_align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // The records of n images of class c, in the order given.  Every prefix sum is kept in 64 bits; false when the class cannot be one
 // launch set: a negative size, or more IDCT workgroups than a grid's x dimension holds (2^31 - 1).
 inline bool jpeg_mix_build(const JpegMixClass &c, const int *w, const int *h, int n, std::vector<JpegMixGeom> *out, JpegMixTotals *tot)
@@ -68,8 +68,8 @@ inline bool jpeg_mix_build(const JpegMixClass &c, const int *w, const int *h, in
         g.blk0 = tot->blocks; g.yoff = tot->ybytes; g.coff = tot->cbytes; g.wg0 = (uint32_t)tot->wgs;
         tot->blocks += nblk;
         tot->wgs += (unsigned long long)g.wgs_per_row * (unsigned long long)g.myy;
-        tot->ybytes += jpeg_mix_align256((size_t)g.ystride * 8 * c.v0 * g.myy);
-        if (!c.gray) tot->cbytes += jpeg_mix_align256((size_t)g.cstride * 8 * g.myy);
+        tot->ybytes += align256((size_t)g.ystride * 8 * c.v0 * g.myy);
+        if (!c.gray) tot->cbytes += align256((size_t)g.cstride * 8 * g.myy);
         if (g.nblk > tot->max_nblk) tot->max_nblk = g.nblk;
     }
     return tot->wgs <= 0x7fffffffull;

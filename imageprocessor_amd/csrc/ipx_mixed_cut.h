@@ -1,6 +1,8 @@
-// ipx_png_mixed_plan.h -- how the mixed-size PNG leg (ipx_run_png_png_mixed, ipx_png_legs.hip) orders its files and cuts them: files ->
-// decode groups -> output chunks -> runs of one size and kind.  Plain host C++ with no dependency on the runtime, so that
-// tools/png_mixed_plan_test.cpp can hold it to its rules as a program of its own.  DESIGN.md section 4.10.
+// ipx_mixed_cut.h -- how a mixed-size leg orders its files and cuts them: files -> decode groups -> output chunks -> runs of one size
+// and kind.  Its one caller is the walk both legs share (mixed_leg in ipx_mixed_leg.h); `kind` is whatever keeps two files of one size
+// out of one operator launch: the frame layout (IPX_PNG_*) for ipx_run_png_png_mixed, the sampling class (0 for Gray, else h0 * 4 + v0)
+// for ipx_run_jpeg_jpeg_mixed.  Plain host C++ with no dependency on the runtime, so that tools/png_mixed_plan_test.cpp and
+// tools/jpeg_mixed_plan_test.cpp can hold it to its rules as programs of their own.  DESIGN.md sections 4.10 and 7.
 #pragma once
 
 #include <algorithm>
@@ -29,7 +31,7 @@ struct MixCut {
 };
 
 // A file beyond a byte budget still gets a group, or a chunk, of its own; a count limit below 1 counts as 1.
-inline MixCut png_mixed_cut(const MixItem *items, int n, int group_files, size_t group_bytes, size_t chunk_bytes)
+inline MixCut mixed_cut(const MixItem *items, int n, int group_files, size_t group_bytes, size_t chunk_bytes)
 {
     MixCut c;
     for (int i = 0; i < n; i++)

@@ -20,6 +20,7 @@
 #include <utility>
 #include <vector>
 
+#include "ipx_align.h"
 #include "ipx_internal.h"
 #include "ipx_ks.h"
 
@@ -277,8 +278,6 @@ inline uint8_t *pinned_device_view(uint8_t *host, size_t span)
     if (hipPointerGetAttributes(&last, host + span - 1) != hipSuccess || last.type != hipMemoryTypeHost) { (void)hipGetLastError(); return nullptr; }   // a registered range may end before the batch does
     return (uint8_t *)at.devicePointer;
 }
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // stream-ordered scratch of one call: freed (in stream order) when the call returns
 struct AsyncFree {

@@ -1,6 +1,6 @@
 """PNG uploads of mixed sizes in one batch, the part that needs no GPU: the three new entries and the two structs are declared in the
 header, bound in the ctypes table, wrapped in Python and called from the Go source; and the mixed leg's ordering and cutting (files ->
-decode groups -> chunks -> runs, csrc/ipx_png_mixed_plan.h) and the layouts of decoded frames and palettes (csrc/ipx_png_layout.h) hold their rules in tools/png_mixed_plan_test.cpp, built with the address and
+decode groups -> chunks -> runs, csrc/ipx_mixed_cut.h) and the layouts of decoded frames and palettes (csrc/ipx_png_layout.h) hold their rules in tools/png_mixed_plan_test.cpp, built with the address and
 undefined-behaviour sanitizers and run as a program of its own."""
 import ctypes as C
 import os

@@ -1,6 +1,6 @@
 // jpeg_mixed_plan_test.cpp -- the host side of a mixed-size JPEG decode's per-image records (imageprocessor_amd/csrc/
 // ipx_jpeg_mixed_plan.h: jpeg_mix_build, jpeg_mix_find) and the cut the mixed-size JPEG leg makes with the sampling class as the kind
-// (ipx_png_mixed_plan.h), held to their rules as a program of its own: plain g++, no GPU, no runtime.
+// (ipx_mixed_cut.h), held to their rules as a program of its own: plain g++, no GPU, no runtime.
 //   g++ -std=c++17 -fsanitize=address,undefined -o jpeg_mixed_plan_test tools/jpeg_mixed_plan_test.cpp && ./jpeg_mixed_plan_test
 // Prints "jpeg mixed plan ok" and exits 0, or says what broke and exits 1.  tests/test_jpeg_mixed_host.py runs it.
 #include <cstdio>
@@ -9,7 +9,7 @@
 #include <vector>
 
 #include "../imageprocessor_amd/csrc/ipx_jpeg_mixed_plan.h"
-#include "../imageprocessor_amd/csrc/ipx_png_mixed_plan.h"
+#include "../imageprocessor_amd/csrc/ipx_mixed_cut.h"
 
 using namespace ipx;
 
@@ -131,7 +131,7 @@ int main()
                 const int s = (int)(rng() % 4), k = (int)(rng() % 5);
                 it = MixItem{rng() % 7 != 0, sizes[s][0], sizes[s][1], kClasses[k].gray ? 0 : kClasses[k].h0 * 4 + kClasses[k].v0, 1000 + rng() % 5000, 500 + rng() % 3000};
             }
-            const MixCut c = png_mixed_cut(items.data(), n, 1 + (int)(rng() % 8), 2000 + rng() % 20000, rng() % 10000);
+            const MixCut c = mixed_cut(items.data(), n, 1 + (int)(rng() % 8), 2000 + rng() % 20000, rng() % 10000);
             std::vector<int> in_run(n, 0);
             size_t at = 0;
             for (const MixGroup &grp : c.groups)

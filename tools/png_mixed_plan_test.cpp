@@ -1,4 +1,4 @@
-// png_mixed_plan_test.cpp -- the mixed-size PNG leg's ordering and cutting (imageprocessor_amd/csrc/ipx_png_mixed_plan.h: files ->
+// png_mixed_plan_test.cpp -- the mixed-size PNG leg's ordering and cutting (imageprocessor_amd/csrc/ipx_mixed_cut.h: files ->
 // decode groups -> chunks -> runs) and the two layouts of decoded frames and palettes (ipx_png_layout.h: strided, packed), compared
 // with the four loops they replaced, held to their rules as a program of its own: plain g++, no GPU, no runtime.
 //   g++ -std=c++17 -fsanitize=address,undefined -o png_mixed_plan_test tools/png_mixed_plan_test.cpp && ./png_mixed_plan_test
@@ -9,7 +9,7 @@
 #include <vector>
 
 #include "../imageprocessor_amd/csrc/ipx_png_layout.h"
-#include "../imageprocessor_amd/csrc/ipx_png_mixed_plan.h"
+#include "../imageprocessor_amd/csrc/ipx_mixed_cut.h"
 
 using namespace ipx;
 
@@ -20,7 +20,7 @@ static int failures = 0;
 static void check_cut(const char *name, const std::vector<MixItem> &items, int group_files, size_t group_bytes, size_t chunk_bytes)
 {
     const int n = (int)items.size();
-    const MixCut c = png_mixed_cut(items.data(), n, group_files, group_bytes, chunk_bytes);
+    const MixCut c = mixed_cut(items.data(), n, group_files, group_bytes, chunk_bytes);
     const int gf = group_files < 1 ? 1 : group_files;
     // the order: every OK file once, no other, sorted by (w, h, kind) with ties by index
     std::vector<int> seen(n, 0);
@@ -268,10 +268,10 @@ int main()
     layout_cases();
     // n = 0, and nothing but failed files
     {
-        const MixCut c = png_mixed_cut(nullptr, 0, 1024, 1u << 30, 1u << 30);
+        const MixCut c = mixed_cut(nullptr, 0, 1024, 1u << 30, 1u << 30);
         CHECK(c.order.empty() && c.groups.empty() && c.chunks.empty() && c.runs.empty(), "n = 0 makes something");
         std::vector<MixItem> bad(5, MixItem{false, 4, 4, 0, 100, 100});
-        const MixCut d = png_mixed_cut(bad.data(), 5, 1024, 1u << 30, 1u << 30);
+        const MixCut d = mixed_cut(bad.data(), 5, 1024, 1u << 30, 1u << 30);
         CHECK(d.order.empty() && d.groups.empty() && d.chunks.empty() && d.runs.empty(), "failed files make something");
         check_cut("all failed", bad, 1024, 1u << 30, 1u << 30);
     }
@@ -281,21 +281,21 @@ int main()
         const int sizes[4][2] = {{64, 48}, {48, 64}, {200, 150}, {5, 1}};
         for (int i = 0; i < 24; i++) it.push_back(MixItem{true, sizes[i % 4][0], sizes[i % 4][1], (i / 4) % 3, 1000, 5000});
         it[7].ok = false;
-        const MixCut c = png_mixed_cut(it.data(), (int)it.size(), 1024, 1u << 30, 1u << 30);
+        const MixCut c = mixed_cut(it.data(), (int)it.size(), 1024, 1u << 30, 1u << 30);
         CHECK(c.order.size() == 23 && c.groups.size() == 1 && c.chunks.size() == 1 && c.runs.size() == 12, "known case: %zu files, %zu groups, %zu chunks, %zu runs",
               c.order.size(), c.groups.size(), c.chunks.size(), c.runs.size());
         CHECK(it[c.order[0]].w == 5 && it[c.order.back()].w == 200, "known case: the order does not start at the narrowest size");
         check_cut("known", it, 1024, 1u << 30, 1u << 30);
         // the same with budgets that split inside a size run: two files per chunk, five per group
         check_cut("known, split", it, 5, 1u << 30, 10000);
-        const MixCut s = png_mixed_cut(it.data(), (int)it.size(), 5, 1u << 30, 10000);
+        const MixCut s = mixed_cut(it.data(), (int)it.size(), 5, 1u << 30, 10000);
         CHECK(s.groups.size() == 5 && s.chunks.size() == 14, "known case, split: %zu groups, %zu chunks", s.groups.size(), s.chunks.size());
     }
     // a single file larger than both budgets still gets a group and a chunk of its own
     {
         std::vector<MixItem> it = {MixItem{true, 10, 10, 2, 100, 100}, MixItem{true, 9000, 9000, 2, (size_t)5 << 30, (size_t)9 << 30},
                                    MixItem{true, 10, 10, 2, 100, 100}};
-        const MixCut c = png_mixed_cut(it.data(), 3, 1024, (size_t)4 << 30, (size_t)1 << 30);
+        const MixCut c = mixed_cut(it.data(), 3, 1024, (size_t)4 << 30, (size_t)1 << 30);
         CHECK(c.groups.size() == 2 && c.chunks.size() == 2 && c.runs.size() == 2, "big file: %zu groups, %zu chunks, %zu runs", c.groups.size(),
               c.chunks.size(), c.runs.size());
         CHECK(c.groups[1].n == 1 && c.order[c.groups[1].first] == 1 && c.chunks[1].n == 1, "big file: not alone");
