@@ -1,6 +1,7 @@
 package ipx
 
 /*
+#include <stdlib.h>
 #include "ipx.h"
 */
 import "C"
@@ -61,7 +62,7 @@ func (x *Context) DecodeJPEGMixed(files [][]byte) (*JPEGFrames, error) {
 
 // RunJPEGJPEGMixed is the JPEG task compressed in, compressed out for uploads of ANY sizes and samplings in one call: one decode pass per
 // group of files and sampling class, the operators once per run of one size (plans by content from the context's cache), jpeg.Encode
-// once per chunk for an output that has one size for every file and once per run otherwise.  o describes the operators; o.Glyphs, if
+// once per chunk, whatever sizes the chunk's outputs have.  o describes the operators; o.Glyphs, if
 // any, is clipped against every size's frame, and must be empty when texts is given.  texts is nil or one Text per file, positioned by
 // the caller for that file's size.  Status[i] and the three streams of files[i] are what RunJPEGJPEG (or RunJPEGJPEGTexts) returns for
 // that file in a call of its own with a plan of its size and the same quality.
@@ -111,4 +112,59 @@ func (x *Context) RunJPEGJPEGMixed(o Ops, files [][]byte, texts []Text, quality 
 		s.Status[i] = Status(st[i])
 	}
 	return s, nil
+}
+
+// RGBAFrame describes one RGBA8 frame resident in HBM: Pix is its first byte, rows lie Stride bytes apart.
+type RGBAFrame struct {
+	Pix          unsafe.Pointer
+	W, H, Stride int
+}
+
+// JPEGBatch holds the streams of EncodeJPEGMixed: views into one pinned block owned by the library, valid until Release.
+type JPEGBatch struct {
+	x       *Context
+	blob    *C.uint8_t
+	Streams [][]byte
+}
+
+func (b *JPEGBatch) Release() {
+	if b.blob != nil {
+		C.ipx_host_free(b.x.c, unsafe.Pointer(b.blob))
+		b.blob = nil
+		b.Streams = nil
+	}
+}
+
+// EncodeJPEGMixed: jpeg.Encode at quality of RGBA frames of ANY sizes and strides resident in HBM, one launch per stage for the whole
+// call and three waits for the device in all.  Streams[i] is byte for byte what jpeg.Encode writes for frame i.  One bad frame (a nil
+// Pix, a side below 1 or of 65536 or more, a stride below 4 * W) refuses the call.
+func (x *Context) EncodeJPEGMixed(frames []RGBAFrame, quality int) (*JPEGBatch, error) {
+	b := &JPEGBatch{x: x}
+	n := len(frames)
+	if n == 0 {
+		return b, nil
+	}
+	// (the array goes to C, and a Go pointer to memory holding pointers may not: the records live in C memory for the call)
+	cf := (*C.ipx_rgba_frame)(C.malloc(C.size_t(n) * C.size_t(unsafe.Sizeof(C.ipx_rgba_frame{}))))
+	if cf == nil {
+		return nil, &Error{Status: NoMem, Text: "out of memory"}
+	}
+	defer C.free(unsafe.Pointer(cf))
+	fr := unsafe.Slice(cf, n)
+	for i, f := range frames {
+		fr[i] = C.ipx_rgba_frame{pix: (*C.uint8_t)(f.Pix), w: C.int32_t(f.W), h: C.int32_t(f.H), stride: C.int32_t(f.Stride)}
+	}
+	offs := make([]C.size_t, n)
+	lens := make([]C.size_t, n)
+	err := call(func() C.int {
+		return C.ipx_jpeg_encode_mixed_dev(x.c, cf, C.int(n), C.int(quality), &b.blob, &offs[0], &lens[0])
+	})
+	if err != nil {
+		return nil, err
+	}
+	b.Streams = make([][]byte, n)
+	for i := range b.Streams {
+		b.Streams[i] = unsafe.Slice((*byte)(unsafe.Add(unsafe.Pointer(b.blob), int(offs[i]))), int(lens[i]))
+	}
+	return b, nil
 }

@@ -957,6 +957,19 @@ class Context:
         _check(lib().ipx_png_encode_mixed_dev(self.handle, arr, n, C.byref(blob), offs, lens))
         return self._stream_block(blob, offs, lens, n, copy)
 
+    def jpeg_encode_mixed_dev(self, frames, quality=85, copy=True):
+        """frames: (device pointer, w, h, stride) per RGBA8 frame in HBM, of any sizes -> one JPEG stream each, byte for byte
+        jpeg_encode_batch_dev's for that frame alone (ipx_jpeg_encode_mixed_dev).  copy=False returns (memoryviews into the pinned
+        block, release()) instead of bytes."""
+        frames = list(frames)
+        n = len(frames)
+        arr = (_lib.RgbaFrame * max(n, 1))()
+        for i, (ptr, w, h, stride) in enumerate(frames):
+            arr[i] = _lib.RgbaFrame(ptr, int(w), int(h), int(stride))
+        blob, offs, lens = C.c_void_p(), (C.c_size_t * max(n, 1))(), (C.c_size_t * max(n, 1))()
+        _check(lib().ipx_jpeg_encode_mixed_dev(self.handle, arr, n, int(quality), C.byref(blob), offs, lens))
+        return self._stream_block(blob, offs, lens, n, copy)
+
     def run_png_png_mixed(self, ops, files, want=("resize", "thumbnail", "watermark"), copy=True, texts=None):
         """PNG byte strings of ANY sizes and kinds in -> ({operator: [png bytes | None] * n}, status list): one decode pass per group,
         the operators per run of one size, one mixed-size png.Encode per output (ipx_run_png_png_mixed).  ops: a PoolOps with sw = sh
@@ -967,7 +980,7 @@ class Context:
 
     def run_jpeg_jpeg_mixed(self, ops, files, quality=85, want=("resize", "thumbnail", "watermark"), copy=True, texts=None):
         """JPEG byte strings of ANY sizes and samplings in -> ({operator: [jpeg bytes | None] * n}, status list): one decode pass per
-        group and sampling class, the operators per run of one size, jpeg.Encode per chunk or per run (ipx_run_jpeg_jpeg_mixed).  ops:
+        group and sampling class, the operators per run of one size, one jpeg.Encode per chunk (ipx_run_jpeg_jpeg_mixed).  ops:
         a PoolOps, or dict(resize=(w, h, keep_aspect) | None, thumbnail=(size, crop_to_fit) | None, watermark=bool | (glyphs, col): a
         glyph list every size's plan clips against its own frame).  texts: None, or one (glyphs, col) per file, positioned for that
         file's size (then no glyph list in ops).  copy=False: lengths instead of bytes."""

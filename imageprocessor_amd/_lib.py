@@ -263,6 +263,7 @@ SIGNATURES = {
     "ipx_png_frames_free": (None, [_P, _P]),
     "ipx_png_decode_mixed": (_I, [_P, _P, C.POINTER(Bytes), _I, C.POINTER(PngFrame), C.POINTER(_I), C.POINTER(_P)]),
     "ipx_png_encode_mixed_dev": (_I, [_P, C.POINTER(RgbaFrame), _I, C.POINTER(_P), C.POINTER(_Z), C.POINTER(_Z)]),
+    "ipx_jpeg_encode_mixed_dev": (_I, [_P, C.POINTER(RgbaFrame), _I, _I, C.POINTER(_P), C.POINTER(_Z), C.POINTER(_Z)]),
     "ipx_run_png_png_mixed": (_I, [_P, C.POINTER(PoolOps), _I, C.POINTER(Bytes), C.POINTER(Text), C.POINTER(Bytes), C.POINTER(Bytes),
                                    C.POINTER(Bytes), C.POINTER(_I), C.POINTER(_P)]),
     "ipx_run_jpeg_jpeg_mixed": (_I, [_P, C.POINTER(PoolOps), _I, C.POINTER(Bytes), C.POINTER(Text), _I, C.POINTER(Bytes), C.POINTER(Bytes),

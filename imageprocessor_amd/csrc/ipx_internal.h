@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/ipx.h"
+#include "ipx_jpeg_enc_mixed_plan.h"
 #include "ipx_jpeg_mixed_plan.h"
 
 namespace ipx {
@@ -198,6 +199,9 @@ struct JpegArgs {
     uint16_t div8[2][64];
 };
 hipError_t launch_jpeg_fdct(const JpegArgs &a, int n, hipStream_t s);
+// the transform of n frames of any sizes in one launch (ipx_jpeg_enc_mixed_plan.h): of `a` the tables and the three dense arrays are read
+// (huff, aclen, dcq: required), the frame's own fields come from its record; wgs = JpegEncTotals::fdct_wgs
+hipError_t launch_jpeg_fdct_mixed(const JpegArgs &a, const JpegEncFrame *frames, int n, unsigned long long wgs, hipStream_t s);
 
 
 // ---- image.Decode for baseline JPEGs (ipx_jpeg_dec_host.cpp parses, ipx_jpeg_dec.hip decodes) ------------
@@ -388,4 +392,17 @@ hipError_t launch_jpeg_ffcount(const uint8_t *ustream, const unsigned long long 
 hipError_t launch_jpeg_stuff(const uint8_t *ustream, const unsigned long long *ubase, const uint32_t *ubytes, int max_chunks, int n,
                              const uint32_t *ffoff, const uint8_t *header, int hdr_len, const unsigned long long *obase, uint8_t *ostream,
                              hipStream_t s);
+// The same stages for n frames of any sizes, one launch each (ipx_jpeg_enc_mixed_plan.h): a frame's geometry, bases and first workgroups
+// come from its record, len / dcq / ffcount are the dense arrays the records index, total_bits and fftotal are [n].  header: one
+// jpeg_write_header output for the call; the stuffing pass writes each frame's own height and width over its bytes at kJpegSofDims.
+hipError_t launch_jpeg_dclen_mixed(const JpegEncFrame *frames, int n, unsigned long long wgs, const int16_t *dcq, const uint32_t *tables,
+                                   uint32_t *len, hipStream_t s);
+hipError_t launch_jpeg_bits_mixed(const JpegEncFrame *frames, int n, unsigned long long wgs, const uint32_t *tables, const uint32_t *off,
+                                  const unsigned long long *total_bits, uint8_t *ustream, hipStream_t s);
+hipError_t launch_scan_mixed_len(const JpegEncFrame *frames, int n, uint32_t *len, unsigned long long *total_bits, hipStream_t s);
+hipError_t launch_scan_mixed_ff(const JpegEncFrame *frames, int n, uint32_t *ffcount, uint32_t *fftotal, hipStream_t s);
+hipError_t launch_jpeg_ffcount_mixed(const JpegEncFrame *frames, int n, unsigned long long wgs, const uint8_t *ustream, uint32_t *ffcount,
+                                     hipStream_t s);
+hipError_t launch_jpeg_stuff_mixed(const JpegEncFrame *frames, int n, unsigned long long wgs, const uint8_t *ustream, const uint32_t *ffoff,
+                                   const uint8_t *header, int hdr_len, uint8_t *ostream, hipStream_t s);
 }  // namespace ipx

@@ -75,7 +75,40 @@ __device__ __forceinline__ void rgb_to_ycc(uint32_t px, int &yy, int &cb, int &c
     cr = min(max((32768 * r - 27440 * g - 5328 * b + (257 << 15)) >> 16, 0), 255);
 }
 
-__global__ __launch_bounds__(256) void jpeg_fdct_kernel(JpegArgs a)
+// What a workgroup knows of its frame, every value uniform over the workgroup.  The uniform launch (one size per call, grid = workgroups
+// of a row x MCU rows x frames) takes them from the launch arguments where the body asks for them; the mixed launch (a one-dimensional
+// grid over the workgroups of all frames) from the frame's record, read once as scalars.  mcu(): the workgroup's first MCU, counted from
+// the start of coefs() and, six entries per MCU, of the dense block-length and DC arrays.
+struct FdctUniform {
+    const JpegArgs &a;
+    __device__ __forceinline__ int mcu0() const { return blockIdx.x * kMcuPerWg; }
+    __device__ __forceinline__ int row() const { return blockIdx.y; }
+    __device__ __forceinline__ int w() const { return a.w; }
+    __device__ __forceinline__ int h() const { return a.h; }
+    __device__ __forceinline__ int stride() const { return a.stride; }
+    __device__ __forceinline__ int aligned16() const { return a.aligned16; }
+    __device__ __forceinline__ const uint8_t *src() const { return a.src + (size_t)blockIdx.z * a.frame_stride; }
+    __device__ __forceinline__ int16_t *coefs() const { return a.coefs; }
+    __device__ __forceinline__ size_t mcu(int mw) const { return (size_t)blockIdx.z * a.mcus_per_frame + (size_t)blockIdx.y * mw + mcu0(); }
+    __device__ __forceinline__ size_t dense_mcu(int mw) const { return mcu(mw); }
+};
+struct FdctMixed {
+    const JpegEncFrame &g; int wg;                       // wg: the workgroup within the frame
+    __device__ __forceinline__ int mcu0() const { return (wg - row() * g.wgs_per_row) * kMcuPerWg; }
+    __device__ __forceinline__ int row() const { return wg / g.wgs_per_row; }
+    __device__ __forceinline__ int w() const { return g.w; }
+    __device__ __forceinline__ int h() const { return g.h; }
+    __device__ __forceinline__ int stride() const { return g.stride; }
+    __device__ __forceinline__ int aligned16() const { return g.aligned16; }
+    __device__ __forceinline__ const uint8_t *src() const { return g.src; }
+    __device__ __forceinline__ int16_t *coefs() const { return g.coefs; }
+    __device__ __forceinline__ size_t mcu(int mw) const { return (size_t)row() * mw + mcu0(); }
+    __device__ __forceinline__ size_t dense_mcu(int mw) const { return (size_t)g.mcu_base + mcu(mw); }
+};
+
+// one workgroup of the transform
+template <class Frame>
+__device__ __forceinline__ void fdct_workgroup(const JpegArgs &a, const Frame &fr)
 {
     __shared__ int ws[48 * kBlkStride];
     __shared__ __attribute__((aligned(16))) int16_t so[48 * 64];
@@ -84,23 +117,24 @@ __global__ __launch_bounds__(256) void jpeg_fdct_kernel(JpegArgs a)
     if (a.aclen)
         for (int i = t; i < 512; i += 256) aclen[i >> 8][i & 255] = (uint8_t)(a.huff[(2 * (i >> 8) + 1) * 256 + (i & 255)] >> 16);
     const int r = t >> 4, xb = t & 15;
-    const int mcu0 = blockIdx.x * kMcuPerWg;
-    const int x0 = mcu0 * 16 + xb * 8, y = blockIdx.y * 16 + r;
-    const uint8_t *frame = a.src + (size_t)blockIdx.z * a.frame_stride;
+    const int mcu0 = fr.mcu0(), row = fr.row();
+    const int fw = fr.w(), fh = fr.h(), stride = fr.stride();
+    const int x0 = mcu0 * 16 + xb * 8, y = row * 16 + r;
+    const uint8_t *frame = fr.src();
 
     // ---- 1. load + colour conversion -------------------------------------------------------------------
     uint32_t px[8];
-    const bool inside = mcu0 * 16 + 128 <= a.w && blockIdx.y * 16 + 16 <= a.h;   // uniform over the workgroup
-    if (inside && a.aligned16) {
-        const uint4 *p = (const uint4 *)(frame + (size_t)y * a.stride + (size_t)x0 * 4);
+    const bool inside = mcu0 * 16 + 128 <= fw && row * 16 + 16 <= fh;   // uniform over the workgroup
+    if (inside && fr.aligned16()) {
+        const uint4 *p = (const uint4 *)(frame + (size_t)y * stride + (size_t)x0 * 4);
         const uint4 v0 = p[0], v1 = p[1];
         px[0] = v0.x; px[1] = v0.y; px[2] = v0.z; px[3] = v0.w; px[4] = v1.x; px[5] = v1.y; px[6] = v1.z; px[7] = v1.w;
     } else {
-        const int sy = min(y, a.h - 1);   // rgbaToYCbCr: edge pixels replicated
+        const int sy = min(y, fh - 1);   // rgbaToYCbCr: edge pixels replicated
 #pragma unroll
         for (int i = 0; i < 8; i++) {
-            const int sx = min(x0 + i, a.w - 1);
-            px[i] = *(const uint32_t *)(frame + (size_t)sy * a.stride + (size_t)sx * 4);
+            const int sx = min(x0 + i, fw - 1);
+            px[i] = *(const uint32_t *)(frame + (size_t)sy * stride + (size_t)sx * 4);
         }
     }
     int yy[8], cb[8], cr[8];
@@ -166,7 +200,7 @@ __global__ __launch_bounds__(256) void jpeg_fdct_kernel(JpegArgs a)
     // 48 lanes of the first wave: spreading them over the four waves was measured slower (1.9 against 1.45 ms per 256 frames) ----
     if (a.aclen && t < 48) {
         const int m = t / 6, j = t - m * 6;
-        const int mw2 = (a.w + 15) >> 4;
+        const int mw2 = (fw + 15) >> 4;
         if (mcu0 + m < mw2) {
             const int blk = j < 4 ? m * 4 + j : (j == 4 ? 32 + m : 40 + m);
             const int q = j < 4 ? 0 : 1;
@@ -191,15 +225,15 @@ __global__ __launch_bounds__(256) void jpeg_fdct_kernel(JpegArgs a)
                 bits += (uint32_t)(run >> 4) * aclen[q][0xf0] + aclen[q][((run & 15) << 4 | nb) & 255] + (uint32_t)nb;
             }
             if (prev != 63) bits += aclen[q][0];
-            const size_t gb = ((size_t)blockIdx.z * a.mcus_per_frame + (size_t)blockIdx.y * mw2 + mcu0) * 6 + t;
+            const size_t gb = fr.dense_mcu(mw2) * 6 + t;
             a.aclen[gb] = bits;
             a.dcq[gb] = so[blk * 64];
         }
     }
 
     // ---- 3. coalesced store: MCU m of this workgroup = Y blocks 4m..4m+3, Cb block 32+m, Cr block 40+m ----
-    const int mw = (a.w + 15) >> 4;
-    int16_t *out = a.coefs + ((size_t)blockIdx.z * a.mcus_per_frame + (size_t)blockIdx.y * mw + mcu0) * 384;
+    const int mw = (fw + 15) >> 4;
+    int16_t *out = fr.coefs() + fr.mcu(mw) * 384;
     for (int c = t; c < 48 * 8; c += 256) {               // 16-byte chunks: 8 per block
         const int ob = c >> 3, part = c & 7;                // ob = output block index within the workgroup: m * 6 + j
         const int m = ob / 6, j = ob - m * 6;
@@ -209,6 +243,21 @@ __global__ __launch_bounds__(256) void jpeg_fdct_kernel(JpegArgs a)
     }
 }
 
+__global__ __launch_bounds__(256) void jpeg_fdct_kernel(JpegArgs a)
+{
+    fdct_workgroup(a, FdctUniform{a});
+}
+
+// The frames of a call in one launch: workgroup blockIdx.x belongs to the last frame whose first workgroup is not behind it -- a search
+// by a value the whole workgroup shares, so its probes and the record are scalar loads.  a: the tables and the dense arrays; the
+// frame's own fields of JpegArgs are not read.
+__global__ __launch_bounds__(256) void jpeg_fdct_mixed_kernel(JpegArgs a, const JpegEncFrame *__restrict__ frames, int n)
+{
+    const uint32_t wg = blockIdx.x;
+    const JpegEncFrame g = frames[jpeg_enc_find(frames, n, wg, &JpegEncFrame::wg_fdct)];
+    fdct_workgroup(a, FdctMixed{g, (int)(wg - g.wg_fdct)});
+}
+
 }  // namespace
 
 hipError_t launch_jpeg_fdct(const JpegArgs &a, int n, hipStream_t s)
@@ -216,6 +265,14 @@ hipError_t launch_jpeg_fdct(const JpegArgs &a, int n, hipStream_t s)
     const int mw = (a.w + 15) >> 4, mh = (a.h + 15) >> 4;
     dim3 grid((mw + kMcuPerWg - 1) / kMcuPerWg, mh, n);
     hipLaunchKernelGGL(jpeg_fdct_kernel, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_jpeg_fdct_mixed(const JpegArgs &a, const JpegEncFrame *frames, int n, unsigned long long wgs, hipStream_t s)
+{
+    static_assert(kMcuPerWg == kJpegEncMcuPerWg, "the records count the transform's workgroups by this");
+    if (n <= 0 || wgs == 0 || wgs > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(jpeg_fdct_mixed_kernel, dim3((unsigned)wgs), dim3(256), 0, s, a, frames, n);
     return hipGetLastError();
 }
 

@@ -19,6 +19,9 @@
 // buffer with atomics: words shared by neighbouring blocks need no ownership rule.
 // The padding of writeSOS's final emit(0x7f, 7) -- ones up to the byte boundary -- is written by the frame's last
 // block.  Pass D also places the stream header (SOI .. SOS, built on the host) and EOI.
+// Every stage has two front ends over one body: the uniform kernel (one size per launch, frame = blockIdx.y, geometry in the launch
+// arguments) and the mixed kernel (frames of any sizes in one launch, a one-dimensional grid, geometry from the frame's record in HBM:
+// ipx_jpeg_enc_mixed_plan.h).
 #include "ipx_internal.h"
 
 namespace ipx {
@@ -120,11 +123,9 @@ __global__ __launch_bounds__(256) void jpeg_len_kernel(const int16_t *coefs, int
 }
 
 // pass A': the AC part of len[] comes from the transform kernel (ipx_jpeg.hip, step 2b); this adds the DC symbol
-__global__ __launch_bounds__(256) void jpeg_dclen_kernel(const int16_t *dcq, int nblk, const uint32_t *tables, uint32_t *len)
+// (fd, fl: the frame's DC terms and lengths; the uniform kernel finds them by f * nblk, the mixed one from the frame's record)
+__device__ __forceinline__ void dclen_block(const int16_t *fd, uint32_t *fl, int b, const uint32_t *tables)
 {
-    const int f = blockIdx.y, b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= nblk) return;
-    const int16_t *fd = dcq + (size_t)f * nblk;
     const int m = b / 6, j = b - m * 6;
     int p;                                                   // the previous block of the same component (prev_dc_of)
     if (j == 0) p = m > 0 ? (m - 1) * 6 + 3 : -1;
@@ -133,7 +134,27 @@ __global__ __launch_bounds__(256) void jpeg_dclen_kernel(const int16_t *dcq, int
     const int diff = (int)fd[b] - (p < 0 ? 0 : (int)fd[p]);
     const int a = diff < 0 ? -diff : diff;
     const int nb = a ? 32 - __clz(a) : 0;
-    len[(size_t)f * nblk + b] += (tables[(j < 4 ? 0 : 2) * 256 + nb] >> 16) + (uint32_t)nb;
+    fl[b] += (tables[(j < 4 ? 0 : 2) * 256 + nb] >> 16) + (uint32_t)nb;
+}
+
+__global__ __launch_bounds__(256) void jpeg_dclen_kernel(const int16_t *dcq, int nblk, const uint32_t *tables, uint32_t *len)
+{
+    const int f = blockIdx.y, b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= nblk) return;
+    dclen_block(dcq + (size_t)f * nblk, len + (size_t)f * nblk, b, tables);
+}
+
+// The mixed kernels of this file: a one-dimensional grid over the workgroups of all frames; workgroup blockIdx.x belongs to the last
+// frame whose first workgroup in that grid is not behind it (jpeg_enc_find), a search by a value the whole workgroup shares, so its
+// probes and the record are scalar loads.  A frame's last workgroup is partial; no workgroup spans two frames.
+__global__ __launch_bounds__(256) void jpeg_dclen_mixed_kernel(const JpegEncFrame *__restrict__ frames, int n, const int16_t *dcq,
+                                                               const uint32_t *tables, uint32_t *len)
+{
+    const uint32_t wg = blockIdx.x;
+    const JpegEncFrame g = frames[jpeg_enc_find(frames, n, wg, &JpegEncFrame::wg_blk)];
+    const int b = (int)(wg - g.wg_blk) * 256 + threadIdx.x;
+    if (b >= g.mcus * 6) return;
+    dclen_block(dcq + (size_t)g.mcu_base * 6, len + (size_t)g.mcu_base * 6, b, tables);
 }
 
 struct BitSink {
@@ -158,26 +179,40 @@ struct BitSink {
 };
 
 // pass B: every block's bits to their place (off = exclusive scan of len); the last block pads with ones
-__global__ __launch_bounds__(256) void jpeg_bits_kernel(const int16_t *coefs, int nblk, const uint32_t *tables, const uint32_t *off,
-                                                        const unsigned long long *total_bits, const unsigned long long *ubase, uint8_t *ustream)
+// (fc, foff, ftotal, fu: the frame's coefficients, block offsets, bit total and unstuffed stream; first: the workgroup's first block)
+__device__ __forceinline__ void bits_workgroup(const int16_t *fc, int nblk, int first, const uint32_t *tables, const uint32_t *foff,
+                                               const unsigned long long *ftotal, uint8_t *fu)
 {
     __shared__ HuffLds h;
     __shared__ uint32_t lds[256 * kBlkWords];
-    const int f = blockIdx.y;
-    const int16_t *fc = coefs + (size_t)f * nblk * 64;
-    const int first = blockIdx.x * 256;
     load_tables(h, tables);
     stage_blocks(lds, fc, first, nblk);
     __syncthreads();
     const int b = first + threadIdx.x;
     if (b >= nblk) return;
-    BitSink s((uint32_t *)(ustream + ubase[f]), off[(size_t)f * nblk + b]);
+    BitSink s((uint32_t *)fu, foff[b]);
     code_block(lds + threadIdx.x * kBlkWords, prev_dc_of(fc, b), (b % 6) < 4 ? 0 : 1, h, s);
     if (b == nblk - 1) {
-        const uint32_t pad = (8 - (uint32_t)(total_bits[f] & 7)) & 7;   // emit(0x7f, 7): only the bits that complete a byte get out
+        const uint32_t pad = (8 - (uint32_t)(*ftotal & 7)) & 7;   // emit(0x7f, 7): only the bits that complete a byte get out
         if (pad) s((1u << pad) - 1, pad);
     }
     s.flush();
+}
+
+__global__ __launch_bounds__(256) void jpeg_bits_kernel(const int16_t *coefs, int nblk, const uint32_t *tables, const uint32_t *off,
+                                                        const unsigned long long *total_bits, const unsigned long long *ubase, uint8_t *ustream)
+{
+    const int f = blockIdx.y;
+    bits_workgroup(coefs + (size_t)f * nblk * 64, nblk, blockIdx.x * 256, tables, off + (size_t)f * nblk, total_bits + f, ustream + ubase[f]);
+}
+
+__global__ __launch_bounds__(256) void jpeg_bits_mixed_kernel(const JpegEncFrame *__restrict__ frames, int n, const uint32_t *tables,
+                                                              const uint32_t *off, const unsigned long long *total_bits, uint8_t *ustream)
+{
+    const uint32_t wg = blockIdx.x;
+    const int f = jpeg_enc_find(frames, n, wg, &JpegEncFrame::wg_blk);
+    const JpegEncFrame g = frames[f];
+    bits_workgroup(g.coefs, g.mcus * 6, (int)(wg - g.wg_blk) * 256, tables, off + (size_t)g.mcu_base * 6, total_bits + f, ustream + g.ubase);
 }
 
 // exclusive scan of one frame's array per workgroup, in place; sum -> total[frame].
@@ -187,11 +222,11 @@ __global__ __launch_bounds__(256) void jpeg_bits_kernel(const int16_t *coefs, in
 // Total = unsigned long long for the encoder's bit lengths: the offsets stay 32-bit (and wrap past 2^32), the frame's sum does not, so
 // the host can refuse such a frame before anything uses its offsets.  A tile's own sum fits 32 bits (4096 values of at most a block's
 // ~2600 bits, or a chunk's 64 bytes).
+// (a, n: the frame's array; the uniform kernel finds it by blockIdx.x * n, the mixed ones from the frame's record)
 template <class Total>
-__global__ __launch_bounds__(1024) void scan_kernel(uint32_t *v, int n, Total *total)
+__device__ __forceinline__ void scan_frame(uint32_t *a, int n, Total *total)
 {
     __shared__ uint32_t wsum[2][16];
-    uint32_t *a = v + (size_t)blockIdx.x * n;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     auto load = [&](int i, uint32_t (&x)[4]) {
         for (int k = 0; k < 4; k++) x[k] = i + k < n ? a[i + k] : 0u;
@@ -225,53 +260,93 @@ __global__ __launch_bounds__(1024) void scan_kernel(uint32_t *v, int n, Total *t
     if (t == 0) total[blockIdx.x] = sum;
 }
 
+template <class Total>
+__global__ __launch_bounds__(1024) void scan_kernel(uint32_t *v, int n, Total *total)
+{
+    scan_frame(v + (size_t)blockIdx.x * n, n, total);
+}
+
+// one workgroup per frame: its block lengths (sum in 64 bits), or its chunks' 0xff counts
+__global__ __launch_bounds__(1024) void scan_mixed_len_kernel(const JpegEncFrame *__restrict__ frames, uint32_t *len, unsigned long long *total)
+{
+    const JpegEncFrame g = frames[blockIdx.x];
+    scan_frame(len + (size_t)g.mcu_base * 6, g.mcus * 6, total);
+}
+__global__ __launch_bounds__(1024) void scan_mixed_ff_kernel(const JpegEncFrame *__restrict__ frames, uint32_t *ffcount, uint32_t *total)
+{
+    const JpegEncFrame g = frames[blockIdx.x];
+    scan_frame(ffcount + (size_t)g.ff0, (int)g.nchunks, total);
+}
+
 constexpr int kChunk = 64;    // unstuffed bytes per thread in the stuffing passes
 
 // pass C: 0xff bytes per chunk of the unstuffed stream
-__global__ __launch_bounds__(256) void jpeg_ffcount_kernel(const uint8_t *ustream, const unsigned long long *ubase, const uint32_t *ubytes,
-                                                           int max_chunks, uint32_t *ffcount)
+// (fu, nb: the frame's unstuffed stream and its bytes) -> the 0xff bytes of chunk c
+__device__ __forceinline__ uint32_t ffcount_chunk(const uint8_t *fu, uint32_t nb, int c)
 {
-    const int f = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= max_chunks) return;
-    const uint32_t nb = ubytes[f];
     uint32_t cnt = 0;
     const uint32_t b0 = (uint32_t)c * kChunk;
     if (b0 < nb) {
-        const uint32_t *p = (const uint32_t *)(ustream + ubase[f] + b0);   // chunks are word aligned; the tail word is zero padded
+        const uint32_t *p = (const uint32_t *)(fu + b0);   // chunks are word aligned; the tail word is zero padded
         const uint32_t words = (min(nb - b0, (uint32_t)kChunk) + 3) >> 2;
         for (uint32_t i = 0; i < words; i++) {
             const uint32_t wv = p[i];
             cnt += ((wv & 0xffu) == 0xffu) + (((wv >> 8) & 0xffu) == 0xffu) + (((wv >> 16) & 0xffu) == 0xffu) + ((wv >> 24) == 0xffu);
         }
     }
-    ffcount[(size_t)f * max_chunks + c] = cnt;
+    return cnt;
+}
+
+__global__ __launch_bounds__(256) void jpeg_ffcount_kernel(const uint8_t *ustream, const unsigned long long *ubase, const uint32_t *ubytes,
+                                                           int max_chunks, uint32_t *ffcount)
+{
+    const int f = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= max_chunks) return;
+    ffcount[(size_t)f * max_chunks + c] = ffcount_chunk(ustream + ubase[f], ubytes[f], c);
+}
+
+// (a frame's chunks are its own count, not the largest frame's: no workgroup idles through a small frame)
+__global__ __launch_bounds__(256) void jpeg_ffcount_mixed_kernel(const JpegEncFrame *__restrict__ frames, int n, const uint8_t *ustream,
+                                                                 uint32_t *ffcount)
+{
+    const uint32_t wg = blockIdx.x;
+    const JpegEncFrame g = frames[jpeg_enc_find(frames, n, wg, &JpegEncFrame::wg_chunk)];
+    const int c = (int)(wg - g.wg_chunk) * 256 + threadIdx.x;
+    if (c >= (int)g.nchunks) return;
+    ffcount[(size_t)g.ff0 + c] = ffcount_chunk(ustream + g.ubase, g.ubytes, c);
 }
 
 // pass D: header, stuffed scan, EOI.  A thread stuffs its 64-byte chunk into LDS, at the place its output has inside the workgroup's
 // (contiguous) piece of the stream, shifted so that 16-byte boundaries of the LDS buffer are 16-byte boundaries of the stream; the
 // piece then goes out in whole 16-byte stores, byte stores only for its two ragged ends (the neighbouring workgroups write the bytes
 // next to them).  The first version stored every byte from the chunk loop: 470 M one-byte stores per 1024 x 3 streams, 1.9 ms.
-__global__ __launch_bounds__(256) void jpeg_stuff_kernel(const uint8_t *ustream, const unsigned long long *ubase, const uint32_t *ubytes,
-                                                         int max_chunks, const uint32_t *ffoff, const uint8_t *header, int hdr_len,
-                                                         const unsigned long long *obase, uint8_t *ostream)
+// (fu, nb, ffo, o: the frame's unstuffed stream, its bytes, its chunks' 0xff offsets and its finished stream; wgx: the workgroup
+// within the frame.  DIMS: the header is the call's, and the frame's own SOF0 height and width -- dims = h << 16 | w, the four bytes
+// big-endian at kJpegSofDims -- replace the ones it carries.)
+template <bool DIMS>
+__device__ __forceinline__ void stuff_workgroup(const uint8_t *fu, const uint32_t nb, const int max_chunks, const uint32_t *ffo,
+                                                const uint8_t *header, const int hdr_len, uint8_t *o, const uint32_t wgx, const uint32_t dims)
 {
     __shared__ __attribute__((aligned(16))) uint8_t buf[256 * 2 * kChunk + 32];
     __shared__ uint32_t piece_end;
-    const int f = blockIdx.y, t = threadIdx.x, c = blockIdx.x * 256 + t;
-    uint8_t *o = ostream + obase[f];
-    if (blockIdx.x == 0)
-        for (int i = t; i < hdr_len; i += 256) o[i] = header[i];
-    const uint32_t nb = ubytes[f], w0 = (uint32_t)blockIdx.x * 256u * kChunk;          // first input byte of the workgroup
-    if (w0 >= nb || (int)(blockIdx.x * 256) >= max_chunks) return;                     // uniform
-    const size_t out0 = (size_t)hdr_len + w0 + ffoff[(size_t)f * max_chunks + blockIdx.x * 256];   // where the workgroup's piece starts in the frame's stream
+    const int t = threadIdx.x, c = wgx * 256 + t;
+    if (wgx == 0)
+        for (int i = t; i < hdr_len; i += 256) {
+            uint8_t v = header[i];
+            if (DIMS && (uint32_t)(i - kJpegSofDims) < 4u) v = (uint8_t)(dims >> (8 * (3 - (i - kJpegSofDims))));
+            o[i] = v;
+        }
+    const uint32_t w0 = (uint32_t)wgx * 256u * kChunk;                                 // first input byte of the workgroup
+    if (w0 >= nb || (int)(wgx * 256) >= max_chunks) return;                            // uniform
+    const size_t out0 = (size_t)hdr_len + w0 + ffo[wgx * 256];                         // where the workgroup's piece starts in the frame's stream
     const uint32_t phase = (uint32_t)((uintptr_t)(o + out0) & 15u);
     if (t == 0) piece_end = 0;
     __syncthreads();
     const uint32_t b0 = (uint32_t)c * kChunk;
     if (c < max_chunks && b0 < nb) {
-        const uint32_t *p = (const uint32_t *)(ustream + ubase[f] + b0);   // word aligned; the tail word is zero padded
+        const uint32_t *p = (const uint32_t *)(fu + b0);   // word aligned; the tail word is zero padded
         const uint32_t n = min(nb - b0, (uint32_t)kChunk);
-        uint32_t at = phase + (b0 - w0) + (ffoff[(size_t)f * max_chunks + c] - ffoff[(size_t)f * max_chunks + blockIdx.x * 256]);
+        uint32_t at = phase + (b0 - w0) + (ffo[c] - ffo[wgx * 256]);
         uint32_t wv[kChunk / 4];
 #pragma unroll
         for (int i = 0; i < kChunk / 4; i++) wv[i] = (uint32_t)i * 4 < n ? p[i] : 0u;
@@ -297,6 +372,24 @@ __global__ __launch_bounds__(256) void jpeg_stuff_kernel(const uint8_t *ustream,
         else
             for (uint32_t i = max(k, phase); i < min(k + 16, end); i++) g[i] = buf[i];
     }
+}
+
+__global__ __launch_bounds__(256) void jpeg_stuff_kernel(const uint8_t *ustream, const unsigned long long *ubase, const uint32_t *ubytes,
+                                                         int max_chunks, const uint32_t *ffoff, const uint8_t *header, int hdr_len,
+                                                         const unsigned long long *obase, uint8_t *ostream)
+{
+    const int f = blockIdx.y;
+    stuff_workgroup<false>(ustream + ubase[f], ubytes[f], max_chunks, ffoff + (size_t)f * max_chunks, header, hdr_len, ostream + obase[f],
+                           blockIdx.x, 0u);
+}
+
+__global__ __launch_bounds__(256) void jpeg_stuff_mixed_kernel(const JpegEncFrame *__restrict__ frames, int n, const uint8_t *ustream,
+                                                               const uint32_t *ffoff, const uint8_t *header, int hdr_len, uint8_t *ostream)
+{
+    const uint32_t wg = blockIdx.x;
+    const JpegEncFrame g = frames[jpeg_enc_find(frames, n, wg, &JpegEncFrame::wg_chunk)];
+    stuff_workgroup<true>(ustream + g.ubase, g.ubytes, (int)g.nchunks, ffoff + (size_t)g.ff0, header, hdr_len, ostream + g.obase,
+                          wg - g.wg_chunk, (uint32_t)g.h << 16 | (uint32_t)g.w);
 }
 
 }  // namespace
@@ -341,6 +434,51 @@ hipError_t launch_jpeg_stuff(const uint8_t *ustream, const unsigned long long *u
 {
     hipLaunchKernelGGL(jpeg_stuff_kernel, dim3((max_chunks + 255) / 256, n), dim3(256), 0, s, ustream, ubase, ubytes, max_chunks, ffoff, header,
                        hdr_len, obase, ostream);
+    return hipGetLastError();
+}
+
+// ---- the mixed launches: wgs is the grid's total from the records' builder (JpegEncTotals) ----
+static_assert(kChunk == kJpegEncChunk && kJpegEncBlkPerWg == 256, "the records count chunks and workgroups by these");
+static bool mixed_grid_ok(int n, unsigned long long wgs) { return n > 0 && wgs > 0 && wgs <= 0x7fffffffull; }
+
+hipError_t launch_jpeg_dclen_mixed(const JpegEncFrame *frames, int n, unsigned long long wgs, const int16_t *dcq, const uint32_t *tables,
+                                   uint32_t *len, hipStream_t s)
+{
+    if (!mixed_grid_ok(n, wgs)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(jpeg_dclen_mixed_kernel, dim3((unsigned)wgs), dim3(256), 0, s, frames, n, dcq, tables, len);
+    return hipGetLastError();
+}
+hipError_t launch_jpeg_bits_mixed(const JpegEncFrame *frames, int n, unsigned long long wgs, const uint32_t *tables, const uint32_t *off,
+                                  const unsigned long long *total_bits, uint8_t *ustream, hipStream_t s)
+{
+    if (!mixed_grid_ok(n, wgs)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(jpeg_bits_mixed_kernel, dim3((unsigned)wgs), dim3(256), 0, s, frames, n, tables, off, total_bits, ustream);
+    return hipGetLastError();
+}
+hipError_t launch_scan_mixed_len(const JpegEncFrame *frames, int n, uint32_t *len, unsigned long long *total_bits, hipStream_t s)
+{
+    if (n <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(scan_mixed_len_kernel, dim3(n), dim3(1024), 0, s, frames, len, total_bits);
+    return hipGetLastError();
+}
+hipError_t launch_scan_mixed_ff(const JpegEncFrame *frames, int n, uint32_t *ffcount, uint32_t *fftotal, hipStream_t s)
+{
+    if (n <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(scan_mixed_ff_kernel, dim3(n), dim3(1024), 0, s, frames, ffcount, fftotal);
+    return hipGetLastError();
+}
+hipError_t launch_jpeg_ffcount_mixed(const JpegEncFrame *frames, int n, unsigned long long wgs, const uint8_t *ustream, uint32_t *ffcount,
+                                     hipStream_t s)
+{
+    if (!mixed_grid_ok(n, wgs)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(jpeg_ffcount_mixed_kernel, dim3((unsigned)wgs), dim3(256), 0, s, frames, n, ustream, ffcount);
+    return hipGetLastError();
+}
+hipError_t launch_jpeg_stuff_mixed(const JpegEncFrame *frames, int n, unsigned long long wgs, const uint8_t *ustream, const uint32_t *ffoff,
+                                   const uint8_t *header, int hdr_len, uint8_t *ostream, hipStream_t s)
+{
+    if (!mixed_grid_ok(n, wgs)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(jpeg_stuff_mixed_kernel, dim3((unsigned)wgs), dim3(256), 0, s, frames, n, ustream, ffoff, header, hdr_len, ostream);
     return hipGetLastError();
 }
 

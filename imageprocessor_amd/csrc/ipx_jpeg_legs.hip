@@ -1,6 +1,7 @@
 // ipx_jpeg_legs.hip -- what JPEG supplies to the mixed-size JPEG-in, JPEG-out leg (ipx_run_jpeg_jpeg_mixed; the walk is mixed_leg in
 // ipx_mixed_leg.h): the sampling class as the cut's kind, one decode pass per group (jpeg_mixed_decode in ipx_jpeg_dec_runtime.hip), a
-// chunk's block out of the lane's scratch, jpeg.Encode through jpeg_encode_sets.  The uniform leg is in ipx_jpeg_runtime.hip.
+// chunk's block out of the lane's scratch, one jpeg.Encode per chunk: jpeg_encode_sets where every output has one size, else
+// jpeg_encode_mixed_core over every frame of the chunk.  The uniform leg is in ipx_jpeg_runtime.hip.
 // DESIGN.md sections 4.6 and 7.
 #include <vector>
 
@@ -119,18 +120,43 @@ struct JpegMixed {
             for (int q = 0; q < n; q++) c.publish(file[p0 + q], ks[j], blob + sets[j].offs[q], sets[j].lens[q]);
         return IPX_OK;
     }
-    // the outputs every file of the chunk has in one size are encoded once per chunk, the others once per run
-    int encode_run(const MixedCall &c, hipStream_t s, const int *file, int p0, int n, const Chunk &b, ResultOwner &res) const
-    {
-        std::vector<int> ks;
-        for (int k = 0; k < kOuts; k++) if (c.has(file[p0], k) && !b.same_size[k]) ks.push_back(k);
-        return encode(c, s, file, p0, n, b, ks, res);
-    }
+    // nothing per run: the chunk's frames are encoded together once its runs have all been through the operators
+    int encode_run(const MixedCall &, hipStream_t, const int *, int, int, const Chunk &, ResultOwner &) const { return IPX_OK; }
+    // A chunk whose every present output has one size for every file: one jpeg_encode_sets call, the one-size cost.  Any other chunk:
+    // every present output of its files that are still IPX_OK in ONE jpeg_encode_mixed_core call, the records pointing at the frames
+    // and coefficient scratch where the block already holds them.  Three waits for the device per chunk either way.
     int encode_chunk(const MixedCall &c, hipStream_t s, const int *file, int n, const Chunk &b, ResultOwner &res) const
     {
-        std::vector<int> ks;
-        for (int k = 0; k < kOuts; k++) if (b.same_size[k]) ks.push_back(k);
-        if (const int rc = encode(c, s, file, 0, n, b, ks, res)) return rc;
+        bool uniform = true;
+        for (int k = 0; k < kOuts && uniform; k++)
+            if (!b.same_size[k])
+                for (int p = 0; p < n && uniform; p++) uniform = !c.has(file[p], k);
+        int rc = IPX_OK;
+        if (uniform) {
+            std::vector<int> ks;
+            for (int k = 0; k < kOuts; k++) if (b.same_size[k]) ks.push_back(k);
+            rc = encode(c, s, file, 0, n, b, ks, res);
+        } else {
+            std::vector<JpegEncSrc> fr;
+            std::vector<std::pair<int, int>> owner_of;      // (file, output) of a frame
+            for (int k = 0; k < kOuts; k++)
+                for (int p = 0; p < n; p++) {
+                    if (c.status[file[p]] != IPX_OK || !decoded(file[p]) || !c.has(file[p], k)) continue;
+                    const OutShape sh = c.shape(file[p], k);
+                    fr.push_back(JpegEncSrc{b.at(k, p), (int16_t *)(b.base[k] + b.coef_off[k][p]), sh.w, sh.h, sh.w * 4});
+                    owner_of.emplace_back(file[p], k);
+                }
+            if (!fr.empty()) {
+                std::vector<size_t> offs(fr.size()), lens(fr.size());
+                uint8_t *blob = nullptr;
+                rc = jpeg_encode_mixed_core(c.ctx, s, fr.data(), (int)fr.size(), quality, &blob, offs.data(), lens.data());
+                if (!rc) {
+                    res.add(blob);
+                    for (size_t j = 0; j < fr.size(); j++) c.publish(owner_of[j].first, owner_of[j].second, blob + offs[j], lens[j]);
+                }
+            }
+        }
+        if (rc) return rc;
         (void)hipStreamSynchronize(s);                      // the next chunk takes the block over
         return IPX_OK;
     }

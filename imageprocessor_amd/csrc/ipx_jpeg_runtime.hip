@@ -267,6 +267,147 @@ static int jpeg_encode_core(ipx_ctx *ctx, hipStream_t s, int16_t *dcoefs, const 
     return jpeg_encode_sets(ctx, s, &one, 1, n, quality, blob);
 }
 
+// jpeg.Encode of n frames of ANY sizes with the same three waits for the device as jpeg_encode_sets -- sizes back, 0xff counts back,
+// streams down -- for the whole list: every stage is one launch over all frames, which read their geometry, bases and first workgroups
+// from a per-frame record in HBM (ipx_jpeg_enc_mixed_plan.h).  The records go up three times, each time with what the host has learnt
+// since.  The same single pinned block, the same 16-byte-aligned stream starts; stream i is byte for byte what jpeg_encode_sets writes
+// for frame i alone.  Scratch and grids are sums over the frames, not n x the largest.  A scan of 2^32 - 1 bits or more (lowered by
+// IPX_JPEG_MAX_SCAN_BITS) refuses the call with IPX_ERR_UNSUPPORTED before anything reads the offsets, and names the frame.  It always
+// sizes the blocks in the transform kernel: IPX_JPEG_FUSED_LEN and IPX_JPEG_HOST_ENTROPY do not apply to it.  Frames are taken as checked
+// (ipx_jpeg_encode_mixed_dev checks them; the leg's come from plans).
+int jpeg_encode_mixed_core(ipx_ctx *ctx, hipStream_t s, const JpegEncSrc *frames, int n, int quality, uint8_t **blob, size_t *offs, size_t *lens)
+{
+    *blob = nullptr;
+    if (n <= 0) return IPX_OK;
+    JpegTables t;
+    jpeg_tables(quality, &t);
+    uint32_t packed[1024];
+    jpeg_huff_packed(packed);
+    std::vector<uint8_t> hdr;
+    jpeg_write_header(frames[0].w, frames[0].h, t, &hdr);     // one header for the call: a frame's differs in the SOF0 height and width alone
+    if (hdr.size() < (size_t)kJpegSofDims + 4 || hdr[kJpegSofDims] != (uint8_t)(frames[0].h >> 8) || hdr[kJpegSofDims + 1] != (uint8_t)frames[0].h ||
+        hdr[kJpegSofDims + 2] != (uint8_t)(frames[0].w >> 8) || hdr[kJpegSofDims + 3] != (uint8_t)frames[0].w) {
+        set_error("jpeg: the header's SOF0 is not where the mixed-size encoder writes a frame's size");
+        return IPX_ERR_INVALID;
+    }
+    std::vector<JpegEncFrame> recs;
+    JpegEncTotals tot;
+    if (!jpeg_enc_build(frames, n, &recs, &tot)) {
+        set_error("jpeg: %d frames are more than one mixed-size encode takes (a grid of 2^31 - 1 workgroups)", n);
+        return IPX_ERR_UNSUPPORTED;
+    }
+    std::vector<unsigned long long> bits((size_t)n);
+    std::vector<uint32_t> ff((size_t)n);
+    StreamSync sync{s};                           // after the host buffers above: the queued copies read and write them
+    AsyncFree mem{s, {}};
+    const size_t nblk = (size_t)tot.mcus * 6, rec_bytes = (size_t)n * sizeof(JpegEncFrame);
+    uint32_t *d_tab, *d_len, *d_fftot;
+    int16_t *d_dcq;
+    uint8_t *d_hdr;
+    JpegEncFrame *d_recs;
+    unsigned long long *d_bits;
+    IPX_HIP(mem.get(&d_tab, sizeof packed));
+    IPX_HIP(mem.get(&d_hdr, hdr.size()));
+    IPX_HIP(mem.get(&d_recs, rec_bytes));
+    IPX_HIP(mem.get(&d_bits, (size_t)n * 8));
+    IPX_HIP(mem.get(&d_fftot, (size_t)n * 4));
+    IPX_HIP(mem.get(&d_len, nblk * 4));
+    IPX_HIP(mem.get(&d_dcq, nblk * 2));
+    IPX_HIP(hipMemcpyAsync(d_tab, packed, sizeof packed, hipMemcpyHostToDevice, s));
+    IPX_HIP(hipMemcpyAsync(d_hdr, hdr.data(), hdr.size(), hipMemcpyHostToDevice, s));
+    IPX_HIP(hipMemcpyAsync(d_recs, recs.data(), rec_bytes, hipMemcpyHostToDevice, s));
+    // ---- transform and symbol sizing; the sizes come back ----
+    JpegArgs a{};
+    a.huff = d_tab; a.aclen = d_len; a.dcq = d_dcq;
+    memcpy(a.recip, t.recip, sizeof a.recip);
+    memcpy(a.div8, t.div8, sizeof a.div8);
+    IPX_HIP(launch_jpeg_fdct_mixed(a, d_recs, n, tot.fdct_wgs, s));
+    IPX_HIP(launch_jpeg_dclen_mixed(d_recs, n, tot.blk_wgs, d_dcq, d_tab, d_len, s));
+    IPX_HIP(launch_scan_mixed_len(d_recs, n, d_len, d_bits, s));
+    IPX_HIP(hipMemcpyAsync(bits.data(), d_bits, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    IPX_HIP(hipStreamSynchronize(s));
+    {
+        const unsigned long long top = 0xffffffffull;
+        const int knob = env_int("IPX_JPEG_MAX_SCAN_BITS", 0);
+        const unsigned long long limit = knob > 0 ? std::min<unsigned long long>((unsigned long long)knob, top) : top;
+        for (int i = 0; i < n; i++)
+            if (bits[(size_t)i] >= limit) {
+                set_error("jpeg: scan too long for the GPU entropy coder (%llu bits in frame %d, %dx%d; the limit is %llu)", bits[(size_t)i], i,
+                          frames[i].w, frames[i].h, limit);
+                return IPX_ERR_UNSUPPORTED;        // (AsyncFree and StreamSync release and wait on the way out)
+            }
+    }
+    // ---- bit packing and the 0xff counts; the counts come back ----
+    if (!jpeg_enc_place_scans(bits.data(), n, &recs, &tot)) {
+        set_error("jpeg: %d frames are more than one mixed-size encode takes (a grid of 2^31 - 1 workgroups)", n);
+        return IPX_ERR_UNSUPPORTED;
+    }
+    uint8_t *d_ustream, *d_ostream;
+    uint32_t *d_ff;
+    IPX_HIP(mem.get(&d_ustream, (size_t)tot.ubytes));
+    IPX_HIP(mem.get(&d_ff, std::max<size_t>((size_t)tot.chunks, 1) * 4));
+    IPX_HIP(hipMemsetAsync(d_ustream, 0, (size_t)tot.ubytes, s));
+    IPX_HIP(hipMemcpyAsync(d_recs, recs.data(), rec_bytes, hipMemcpyHostToDevice, s));
+    IPX_HIP(launch_jpeg_bits_mixed(d_recs, n, tot.blk_wgs, d_tab, d_len, d_bits, d_ustream, s));
+    IPX_HIP(launch_jpeg_ffcount_mixed(d_recs, n, tot.chunk_wgs, d_ustream, d_ff, s));
+    IPX_HIP(launch_scan_mixed_ff(d_recs, n, d_ff, d_fftot, s));
+    IPX_HIP(hipMemcpyAsync(ff.data(), d_fftot, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    IPX_HIP(hipStreamSynchronize(s));
+    // ---- byte stuffing into one block; the streams come down ----
+    const size_t ototal = (size_t)jpeg_enc_place_streams(ff.data(), n, hdr.size(), &recs, offs, lens);
+    IPX_HIP(mem.get(&d_ostream, ototal));
+    IPX_HIP(hipMemcpyAsync(d_recs, recs.data(), rec_bytes, hipMemcpyHostToDevice, s));
+    IPX_HIP(launch_jpeg_stuff_mixed(d_recs, n, tot.chunk_wgs, d_ustream, d_ff, d_hdr, (int)hdr.size(), d_ostream, s));
+    uint8_t *host = (uint8_t *)ipx_host_alloc(ctx, ototal ? ototal : 1);   // pinned: the download runs at link speed
+    if (!host) return IPX_ERR_NOMEM;
+    hipError_t e = hipMemcpyAsync(host, d_ostream, ototal, hipMemcpyDeviceToHost, s);
+    { const hipError_t e2 = hipStreamSynchronize(s); if (e == hipSuccess) e = e2; }          // (the records are read by the queued copy until here)
+    if (e != hipSuccess) { (void)ipx_host_free(ctx, host); set_error("stream download failed: %s", hipGetErrorString(e)); return IPX_ERR_HIP; }
+    *blob = host;
+    return IPX_OK;
+}
+
+extern "C" {
+
+int ipx_jpeg_encode_mixed_dev(ipx_ctx *ctx, const ipx_rgba_frame *frames, int n, int quality, uint8_t **blob, size_t *offs, size_t *lens) try
+{
+    IPX_ENTER(ctx);
+    if (!blob || !offs || !lens || n < 0 || (n && !frames)) { set_error("ipx_jpeg_encode_mixed_dev: bad argument"); return IPX_ERR_INVALID; }
+    *blob = nullptr;
+    if (n == 0) return IPX_OK;
+    if (n > 65535) { set_error("ipx_jpeg_encode_mixed_dev: at most 65535 frames per call"); return IPX_ERR_UNSUPPORTED; }
+    // every frame before any launch: a malformed one first (IPX_ERR_INVALID), then one beyond the span the kernels address
+    for (int f = 0; f < n; f++) {
+        const ipx_rgba_frame &fr = frames[f];
+        if (!fr.pix || fr.w <= 0 || fr.h <= 0 || (long long)fr.stride < (long long)fr.w * 4) {
+            set_error("ipx_jpeg_encode_mixed_dev: frame %d: bad argument", f);
+            return IPX_ERR_INVALID;
+        }
+        if (fr.w >= 1 << 16 || fr.h >= 1 << 16) { set_error("ipx_jpeg_encode_mixed_dev: frame %d: jpeg: image is too large to encode", f); return IPX_ERR_INVALID; }
+    }
+    size_t coef_bytes = 0;
+    for (int f = 0; f < n; f++) {
+        if (!frame_span_ok(frames[f].w, frames[f].h, frames[f].stride, 4)) {
+            set_error("ipx_jpeg_encode_mixed_dev: frame %d: %dx%d is beyond the frames the encoder addresses", f, frames[f].w, frames[f].h);
+            return IPX_ERR_UNSUPPORTED;
+        }
+        coef_bytes += align256(ipx_jpeg_coef_count(frames[f].w, frames[f].h) * sizeof(int16_t));
+    }
+    LaneLease lane(ctx);
+    const int rc = lane_reserve(lane.get(), coef_bytes + 256);
+    if (rc) return rc;
+    std::vector<JpegEncSrc> src((size_t)n);
+    uint8_t *at = (uint8_t *)(((uintptr_t)lane->dev + 255) & ~(uintptr_t)255);
+    for (int f = 0; f < n; f++) {
+        src[(size_t)f] = JpegEncSrc{frames[f].pix, (int16_t *)at, frames[f].w, frames[f].h, frames[f].stride};
+        at += align256(ipx_jpeg_coef_count(frames[f].w, frames[f].h) * sizeof(int16_t));
+    }
+    return jpeg_encode_mixed_core(ctx, lane->stream, src.data(), n, quality, blob, offs, lens);
+}
+IPX_CATCH_STATUS
+
+}  // extern "C"
+
 // ---- host frames in, JPEG streams out: the worker's whole GPU leg ----------------------------------------
 
 extern "C" {

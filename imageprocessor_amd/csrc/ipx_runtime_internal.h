@@ -510,6 +510,10 @@ int run_dev_src(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, int m, const Ba
 // int16 of scratch per set.
 struct JpegEncSet { int16_t *dcoefs; const uint8_t *src; int w, h, stride; size_t frame_stride; size_t *offs, *lens; };   // offs / lens: [n], into *blob
 int jpeg_encode_sets(ipx_ctx *ctx, hipStream_t s, const JpegEncSet *sets, int K, int n, int quality, uint8_t **blob);
+// jpeg.Encode of n frames of any sizes in HBM into one pinned block *blob, three waits for the device for the whole list
+// (ipx_jpeg_runtime.hip; the records: ipx_jpeg_enc_mixed_plan.h).  offs / lens: [n], into *blob.  Always the fused length pass:
+// IPX_JPEG_FUSED_LEN and IPX_JPEG_HOST_ENTROPY do not apply.
+int jpeg_encode_mixed_core(ipx_ctx *ctx, hipStream_t s, const ipx::JpegEncSrc *frames, int n, int quality, uint8_t **blob, size_t *offs, size_t *lens);
 
 // gif.Encode of n frames in HBM into one pinned block *blob (ipx_gif.hip)
 int gif_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w, int h, int stride, size_t frame_stride, int n,

@@ -571,6 +571,16 @@ int ipx_png_encode_batch_dev(ipx_ctx *ctx, const uint8_t *src, int w, int h, int
  * any launch.  DESIGN.md section 4.9. */
 typedef struct { const uint8_t *pix; int32_t w, h, stride; } ipx_rgba_frame;
 int ipx_png_encode_mixed_dev(ipx_ctx *ctx, const ipx_rgba_frame *frames, int n, uint8_t **blob, size_t *offs, size_t *lens);
+/* jpeg.Encode of n frames of ANY sizes and strides, each described on its own: RGBA8 in HBM.  One launch per stage for the whole call
+ * however many sizes it holds (the kernels read a per-frame record) and three waits for the device in all, as
+ * ipx_jpeg_encode_batch_dev has for one size; stream i is byte for byte what that entry writes for frame i in a call of its own at the
+ * same quality.  One pinned block (ipx_host_free), streams that start 16-byte aligned; n == 0 is IPX_OK with *blob = NULL.  One bad
+ * frame refuses the call before any launch: a NULL pix, a width or height below 1, a stride below 4 * w or a side of 65536 or more
+ * IPX_ERR_INVALID, a frame beyond ipx_frame_supported IPX_ERR_UNSUPPORTED; more than 65535 frames IPX_ERR_UNSUPPORTED.  A frame whose
+ * scan reaches the GPU entropy coder's limit (above) refuses the call with IPX_ERR_UNSUPPORTED and is named in the message.  The
+ * blocks are always sized in the transform kernel: IPX_JPEG_FUSED_LEN and IPX_JPEG_HOST_ENTROPY do not apply.  Thread-safe like
+ * ipx_jpeg_encode_batch_dev.  DESIGN.md section 4.6. */
+int ipx_jpeg_encode_mixed_dev(ipx_ctx *ctx, const ipx_rgba_frame *frames, int n, int quality, uint8_t **blob, size_t *offs, size_t *lens);
 /* The PNG task's whole GPU leg (ipx_plan_run_host's inputs): upload, every requested operator, then png.Encode of all three outputs
  * (a PNG watermark stays PNG).  The streams land in pinned blocks owned by *result, released with ipx_jpeg_result_free. */
 int ipx_plan_run_host_png(ipx_ctx *ctx, const ipx_plan *plan, int n, const uint8_t *src, int sstride, size_t src_frame_stride,
@@ -830,9 +840,10 @@ int ipx_run_png_png_mixed(ipx_ctx *ctx, const ipx_pool_ops *ops, int n, const ip
  * files are ordered by (width, height, sampling class) and cut into decode groups of IPX_JPEG_MIXED_GROUP (256) files and ~4 GiB of
  * planes and coefficient scratch, each group ONE decode pass per sampling class; a group is cut into chunks of at most
  * IPX_JPEG_MIXED_CHUNK_MB (8192: the 256 files of a 1080p group in one chunk) of output frames and encoder scratch; within a chunk the operators run once per run of one size and
- * class, with a plan of that size from the context's cache (ipx_plan_acquire).  An output that has one size for every file of the chunk
- * (a resize without keep_aspect, a cropped thumbnail) is encoded once per chunk, every other output once per run; there is no
- * mixed-size jpeg.Encode.  status[i] and the three streams of file i are byte for byte what ipx_plan_run_jpeg_jpeg (or _texts) returns
+ * class, with a plan of that size from the context's cache (ipx_plan_acquire).  Every chunk is encoded once, with three waits for the
+ * device: a chunk whose every present output has one size for every file (a resize without keep_aspect, a cropped thumbnail) as
+ * ipx_jpeg_encode_batch_dev encodes one size, any other chunk by one mixed-size jpeg.Encode over every present output of its files
+ * that are still IPX_OK (what ipx_jpeg_encode_mixed_dev runs).  status[i] and the three streams of file i are byte for byte what ipx_plan_run_jpeg_jpeg (or _texts) returns
  * for that file in a call of its own with a plan of its size and the same quality -- outside the three switches named above; files of a
  * size for which no plan can be made get the status ipx_plan_create returned, alone.  A NULL output array skips that output; an
  * operator ops does not ask for gives {NULL, 0}; n == 0 is IPX_OK; more than 65535 files is IPX_ERR_UNSUPPORTED.  Streams as for
