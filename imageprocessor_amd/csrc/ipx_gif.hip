@@ -290,20 +290,14 @@ int gif_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w, int 
         offs[i] = total;
         lens[i] = hl[i];
         ob[i] = total;
-        total += (hl[i] + 15) & ~(size_t)15;
+        total += align16(hl[i]);
         max_len = std::max<size_t>(max_len, hl[i]);
     }
     uint8_t *dpack;
     IPX_HIP(mem.get(&dpack, total));
     IPX_HIP(hipMemcpyAsync(dob, ob.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
     IPX_HIP(launch_gif_pack(dout, region, dlens, dob, n, max_len, dpack, s));
-    uint8_t *host = (uint8_t *)ipx_host_alloc(ctx, total);
-    if (!host) return IPX_ERR_NOMEM;
-    hipError_t e = hipMemcpyAsync(host, dpack, total, hipMemcpyDeviceToHost, s);
-    { const hipError_t e2 = hipStreamSynchronize(s); if (e == hipSuccess) e = e2; }
-    if (e != hipSuccess) { (void)ipx_host_free(ctx, host); set_error("gif stream download failed: %s", hipGetErrorString(e)); return IPX_ERR_HIP; }
-    *blob = host;
-    return IPX_OK;
+    return download_streams(ctx, s, dpack, total, "gif ", blob);
 }
 
 extern "C" {
@@ -337,31 +331,7 @@ IPX_CATCH_STATUS
 int ipx_gif_encode_rgba8(ipx_ctx *ctx, const uint8_t *pix, int w, int h, int stride, uint8_t **out, size_t *len) try
 {
     IPX_ENTER(ctx);
-    if (!out || !len) { set_error("ipx_gif_encode_rgba8: bad argument"); return IPX_ERR_INVALID; }
-    *out = nullptr;
-    *len = 0;
-    int rc = gif_check("ipx_gif_encode_rgba8", pix, w, h, stride, 1);
-    if (rc) return rc;
-    LaneLease lane(ctx);
-    hipStream_t s = lane->stream;
-    const size_t fbytes = (size_t)w * h * 4;
-    uint8_t *blob = nullptr;
-    size_t off = 0, n = 0;
-    {
-        AsyncFree mem{s, {}};
-        uint8_t *dsrc;
-        IPX_HIP(mem.get(&dsrc, fbytes));
-        IPX_HIP(hipMemcpy2DAsync(dsrc, (size_t)w * 4, pix, stride, (size_t)w * 4, h, hipMemcpyHostToDevice, s));
-        rc = gif_encode_core(ctx, s, dsrc, w, h, w * 4, fbytes, 1, &blob, &off, &n);
-        if (rc) return rc;
-    }
-    uint8_t *m = (uint8_t *)malloc(n);
-    if (!m) { (void)ipx_host_free(ctx, blob); set_error("ipx_gif_encode_rgba8: out of memory"); return IPX_ERR_NOMEM; }
-    memcpy(m, blob + off, n);
-    (void)ipx_host_free(ctx, blob);
-    *out = m;
-    *len = n;
-    return IPX_OK;
+    return encode_one_rgba8("ipx_gif_encode_rgba8", ctx, gif_check, gif_encode_core, pix, w, h, stride, out, len);
 }
 IPX_CATCH_STATUS
 
@@ -373,36 +343,8 @@ int ipx_plan_run_host_paletted_gif(ipx_ctx *ctx, const ipx_plan *pl, int n, cons
                                    ipx_jpeg_result **result) try
 {
     IPX_ENTER(ctx);
-    if (!result) { set_error("ipx_plan_run_host_paletted_gif: bad argument"); return IPX_ERR_INVALID; }
-    *result = nullptr;
-    const BatchSrc host = packed_src(kSrcPaletted, index, stride, frame_stride, palettes);
-    int rc0 = src_check("ipx_plan_run_host_paletted_gif", pl, host, n, false);
-    if (rc0) return rc0;
-    const PlanOutputs outs(pl, resize_out, thumb_out, wm_out, Codec::Gif, Codec::Gif, Codec::Jpeg);
-    rc0 = outs.check_gif();                       // every frame handed to gif.Encode must fit its limits: checked before anything runs
-    if (rc0) return rc0;
-    if (n == 0) return IPX_OK;
-    const SrcLayout L = src_layout(pl, host);
-    const size_t per_frame = L.frame_bytes() + outs.frame_bytes();
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n, (size_t)env_int("IPX_HOST_CHUNK_GIF", 64),
-                                                                 ((size_t)1 << 30) / per_frame}));
-    ResultOwner res(ctx);                         // the blocks of finished chunks go back to the cache on every way out but success
-    LaneLease lane(ctx);
-    hipStream_t s = lane->stream;
-    for (int i0 = 0; i0 < n; i0 += chunk) {
-        const int m = std::min(chunk, n - i0);
-        StreamSync sync{s};
-        AsyncFree mem{s, {}};
-        uint8_t *dsrc, *dout = nullptr;
-        IPX_HIP(mem.get(&dsrc, L.frame_bytes() * m));        // [m x index plane][m x palette]
-        if (outs.frame_bytes()) IPX_HIP(mem.get(&dout, outs.frame_bytes() * m));
-        BatchSrc d;
-        IPX_HIP(src_upload(host, L, i0, m, dsrc, m, s, kCopyFrameRows, &d));
-        const int rc = run_chunk(ctx, s, pl, outs, dout, m, d, all_files(n), i0, m, nullptr, nullptr, quality, nullptr, res);
-        if (rc) return rc;
-    }
-    *result = res.release();
-    return IPX_OK;
+    return run_host_streams("ipx_plan_run_host_paletted_gif", ctx, pl, n, packed_src(kSrcPaletted, index, stride, frame_stride, palettes), Codec::Gif,
+                            Codec::Gif, Codec::Jpeg, "IPX_HOST_CHUNK_GIF", 64, quality, resize_out, thumb_out, wm_out, result);
 }
 IPX_CATCH_STATUS
 

@@ -241,7 +241,7 @@ static int gif_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
             d.slot = (uint32_t)group[g];
             d.lit = (uint16_t)f.lit;
             d.flags = (uint8_t)((f.terminated ? kGifTerminated : 0) | (f.last_is_one ? kGifLastIsOne : 0) | (f.interlaced ? kGifInterlaced : 0));
-            data_bytes += (f.data_len + 15) & ~(size_t)15;
+            data_bytes += align16(f.data_len);
             codes += d.code_cap;
             max_cap = std::max(max_cap, d.code_cap);
         }

@@ -23,7 +23,7 @@
 // words of a large batch are read through L1 / L2 (a lane walks its own sub-sequence sequentially): staging 64 KiB-rows in LDS
 // (IPX_JPEG_PAR_STAGE=1, row stride sub + 4 bytes against bank aliasing) leaves two waves per CU and is 2.2x slower than the occupancy
 // it costs.  A small batch (every wave resident at once, 256-byte rows) is staged: its waves sit alone on their SIMDs and would wait
-// for a global load almost every symbol (ipx_jpeg_runtime.hip, where stage_rows is set).
+// for a global load almost every symbol (ipx_jpeg_dec_runtime.hip, where stage_rows is set).
 #include <algorithm>
 #include <cstdlib>
 

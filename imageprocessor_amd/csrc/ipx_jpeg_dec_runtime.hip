@@ -211,7 +211,7 @@ int dec_scans(DecRun &r)
     size_t nscans = 0, ndefs = 0;
     for (int i : P.gfiles) { nscans += P.prog[i].scans.size(); ndefs += P.prog[i].defs.size(); }
     const size_t nf = P.gfiles.size();
-    const size_t off_scans = (nf * sizeof(JpegProgFile) + 15) & ~(size_t)15, off_defs = (off_scans + nscans * sizeof(JpegProgScan) + 15) & ~(size_t)15;
+    const size_t off_scans = align16(nf * sizeof(JpegProgFile)), off_defs = align16(off_scans + nscans * sizeof(JpegProgScan));
     r.prog_block.assign(off_defs + ndefs * sizeof(JpegProgHuff) + 16, 0);
     JpegProgFile *hf = (JpegProgFile *)r.prog_block.data();
     JpegProgScan *hs = (JpegProgScan *)(r.prog_block.data() + off_scans);

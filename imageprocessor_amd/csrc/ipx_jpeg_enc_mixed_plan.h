@@ -3,8 +3,8 @@
 // max_chunks, blockIdx.y * nblk) a mixed kernel reads from its frame's record.  The records are built in three steps, one before each of
 // the encoder's waits for the device: the geometry (jpeg_enc_build), the unstuffed streams once the scans' bit counts are back
 // (jpeg_enc_place_scans), the finished streams once the 0xff counts are back (jpeg_enc_place_streams).  Plain C++ with no dependency
-// on the runtime, shared by the kernels, the driver and tools/jpeg_enc_mixed_plan_test.cpp, which holds the builder and the search to
-// their rules as a program of its own.  DESIGN.md section 4.6.
+// on the runtime, shared by the kernels, the driver and tools/jpeg_enc_mixed_plan_test.cpp, which holds the builder, the search and the
+// scan-length rule (jpeg_scan_limit: the uniform core's too) to their rules as a program of its own.  DESIGN.md section 4.6.
 #pragma once
 
 #include <cstddef>
@@ -82,6 +82,23 @@ inline bool jpeg_enc_build(const JpegEncSrc *in, int n, std::vector<JpegEncFrame
     return tot->fdct_wgs <= 0x7fffffffull && tot->blk_wgs <= 0x7fffffffull;
 }
 
+// The scan-length rule of both encode cores.  The block offsets (the block lengths after the scan) and a frame's unstuffed bytes are
+// 32-bit: a frame whose scan reaches 2^32 - 1 bits (some 200 M pixels of binary noise at quality 100) would wrap them, and the bit
+// packer would then write beyond the unstuffed scratch.  The cores refuse such a call once the sizes are back, before anything reads
+// the offsets or is sized from them.  knob: IPX_JPEG_MAX_SCAN_BITS, which can only lower the limit (for the tests); 0 or less: unset.
+constexpr unsigned long long kJpegScanBitsTop = 0xffffffffull;
+inline unsigned long long jpeg_scan_limit(int knob)
+{
+    return knob > 0 && (unsigned long long)knob < kJpegScanBitsTop ? (unsigned long long)knob : kJpegScanBitsTop;
+}
+// the first of n scans that is at the limit or beyond it, or -1
+inline long long jpeg_scan_too_long(const unsigned long long *bits, size_t n, unsigned long long limit)
+{
+    for (size_t j = 0; j < n; j++)
+        if (bits[j] >= limit) return (long long)j;
+    return -1;
+}
+
 // Once every frame's scan length is known (bits[i] < 2^32 - 1, the caller's refusal): its unstuffed bytes, their place in the scratch
 // (256-byte aligned, eight bytes of slack for the bit packer's last word), its chunks and its first workgroup in the chunk grids.  A
 // frame has at least one chunk workgroup -- the one that writes its header -- so first workgroups are strictly increasing.
@@ -90,7 +107,7 @@ inline bool jpeg_enc_place_scans(const unsigned long long *bits, int n, std::vec
     tot->chunks = tot->chunk_wgs = tot->ubytes = 0;
     for (int i = 0; i < n; i++) {
         JpegEncFrame &g = (*recs)[(size_t)i];
-        if (bits[i] >= 0xffffffffull || tot->chunk_wgs > 0x7fffffffull) return false;
+        if (bits[i] >= kJpegScanBitsTop || tot->chunk_wgs > 0x7fffffffull) return false;
         g.ubytes = (uint32_t)((bits[i] + 7) / 8);
         g.nchunks = (g.ubytes + kJpegEncChunk - 1) / kJpegEncChunk;
         g.ubase = tot->ubytes;
@@ -114,7 +131,7 @@ inline unsigned long long jpeg_enc_place_streams(const uint32_t *ff, int n, size
         lens[i] = hdr_len + g.ubytes + ff[i] + 2;
         g.obase = total;
         offs[i] = (size_t)total;
-        total += (lens[i] + 15) & ~(size_t)15;
+        total += align16(lens[i]);
     }
     return total;
 }

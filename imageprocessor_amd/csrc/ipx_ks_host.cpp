@@ -67,11 +67,9 @@ bool ks_build_axis(int dw, int sw, KsAxis *out)
     return true;
 }
 
-static size_t al16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 size_t ks_axis_bytes(const KsAxis &a)
 {
-    return 2 * al16((size_t)a.dw * sizeof(int32_t)) + al16(a.w.size() * sizeof(double)) + 3 * al16((size_t)a.dw * sizeof(double));
+    return 2 * align16((size_t)a.dw * sizeof(int32_t)) + align16(a.w.size() * sizeof(double)) + 3 * align16((size_t)a.dw * sizeof(double));
 }
 
 void ks_axis_pack(const KsAxis &a, uint8_t *h, const uint8_t *d, KsAxisDev *out)
@@ -80,7 +78,7 @@ void ks_axis_pack(const KsAxis &a, uint8_t *h, const uint8_t *d, KsAxisDev *out)
     auto put = [&](const void *p, size_t bytes) {
         memcpy(h + off, p, bytes);
         const uint8_t *dev = d + off;
-        off += al16(bytes);
+        off += align16(bytes);
         return dev;
     };
     out->lo = (const int32_t *)put(a.lo.data(), (size_t)a.dw * sizeof(int32_t));
@@ -121,7 +119,7 @@ namespace {
 
 size_t blob_put(std::vector<uint8_t> *blob, const void *src, size_t bytes)
 {
-    const size_t off = (blob->size() + 15) & ~(size_t)15;
+    const size_t off = align16(blob->size());
     blob->resize(off + bytes);
     if (bytes) memcpy(blob->data() + off, src, bytes);
     return off;
@@ -332,7 +330,7 @@ bool ks_fused_plan(int sw, int sh, const KsFusedIn *sc0, const KsFusedIn *sc1, i
         KsFusedPlan::Lds F;
         {
             size_t wf = 0;
-            for (int k = 0; k < 2; k++) if (sc[k]) wf += ((size_t)(sc[k]->hx->ntap + 1) * wcols[k] * sizeof(float) + 15) & ~(size_t)15;   // (+ 1: a split output's padded tap row)
+            for (int k = 0; k < 2; k++) if (sc[k]) wf += align16((size_t)(sc[k]->hx->ntap + 1) * wcols[k] * sizeof(float));   // (+ 1: a split output's padded tap row)
             const size_t rows_b = 2 * 2 * (size_t)B * row_bytes + 64, cu = ((size_t)160 << 10) - 512;
             F.dbuf = 0; F.open_per_wave = kKsOpenPerWave;
             for (int per : {kKsOpenPerWave, 64})                   // (never under 64: one ballot may add an entry per lane)
@@ -340,11 +338,11 @@ bool ks_fused_plan(int sw, int sh, const KsFusedIn *sc0, const KsFusedIn *sc1, i
             size_t at = (size_t)(F.dbuf + 1) * B * pitch;
             for (int k = 0; k < 2; k++) {
                 F.lds_w[k] = (int)at;
-                if (sc[k]) at += ((size_t)(sc[k]->hx->ntap + 1) * wcols[k] * sizeof(float) + 15) & ~(size_t)15;
+                if (sc[k]) at += align16((size_t)(sc[k]->hx->ntap + 1) * wcols[k] * sizeof(float));
             }
             F.lds_rows = (int)at;
             at += rows_b;
-            at = (at + 15) & ~(size_t)15;
+            at = align16(at);
             F.lds_open = (int)at;
             at += (size_t)kKsMaxWaves * F.open_per_wave * sizeof(uint2);
             F.lds_bytes = (int)at;

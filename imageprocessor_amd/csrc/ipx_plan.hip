@@ -63,7 +63,7 @@ int ipx_plan_create(ipx_ctx *ctx, const ipx_plan_params *p, ipx_plan **out) try
     // newDistrib of both axes of every scaled output (an output with a zero dimension -- resize.go:70-72 has no guard -- is simply empty)
     std::vector<uint8_t> blob;
     auto put = [&](size_t bytes) {
-        const size_t off = (blob.size() + 15) & ~(size_t)15;
+        const size_t off = align16(blob.size());
         blob.resize(off + bytes);
         return off;
     };

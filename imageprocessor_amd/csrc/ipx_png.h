@@ -7,8 +7,9 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
-#include "../../include/ipx.h"
+#include "ipx_internal.h"
 
 namespace ipx {
 
@@ -62,6 +63,45 @@ struct PngPiece {
     unsigned long long src, dst;
     uint32_t len, pad;
 };
+
+// ---- the host arithmetic of both encode cores (png_encode_core, png_encode_mixed_core) ----
+// Appends the segments of frame `frame`, w x h of bpp 3 or 4 (its colour type), whose region of the output scratch starts at `region`:
+// each segment's IDAT chunk gets the slot of its stored bound, from kPngSegBase on.
+inline void png_append_segs(std::vector<PngSeg> *segs, uint32_t frame, int w, int h, int bpp, size_t region)
+{
+    const PngSegs g(w, h, bpp);
+    size_t at = region + kPngSegBase;
+    for (int k = 0; k < g.nseg; k++) {
+        PngSeg sg;
+        sg.frame = frame;
+        sg.s0 = (uint32_t)((size_t)g.row0(k, h) * g.stride);
+        sg.s1 = (uint32_t)((size_t)g.row0(k + 1, h) * g.stride);
+        sg.flags = (k == 0 ? 1u : 0u) | (k == g.nseg - 1 ? 2u : 0u);
+        sg.out = at;
+        at += png_slot_bytes(sg.s1 - sg.s0, k == 0);
+        segs->push_back(sg);
+    }
+}
+// Appends the pieces of one frame's stream, which starts at *total of the packed block: the head at `region`, the chunks of its
+// segments [seg0, seg1) at the lengths the deflate reported (sl), the tail at region + tail.  -> the stream's length, with *total moved
+// to where the next stream starts (16-byte aligned); 0, with the error text set, when a segment overran its slot.
+inline size_t png_place_pieces(std::vector<PngPiece> *pieces, const std::vector<PngSeg> &segs, const std::vector<uint32_t> &sl, uint32_t seg0,
+                               uint32_t seg1, size_t region, size_t tail, size_t *total)
+{
+    size_t at = *total;
+    pieces->push_back({region, at, (uint32_t)kPngHeadBytes, 0});
+    at += kPngHeadBytes;
+    for (uint32_t k = seg0; k < seg1; k++) {
+        if (sl[k] > png_slot_bytes(segs[k].s1 - segs[k].s0, k == seg0)) { set_error("png: segment %u overran its bound", k); return 0; }
+        pieces->push_back({segs[k].out, at, sl[k], 0});
+        at += sl[k];
+    }
+    pieces->push_back({region + tail, at, (uint32_t)kPngTailBytes, 0});
+    at += kPngTailBytes;
+    const size_t len = at - *total;
+    *total = align16(at);
+    return len;
+}
 
 // ---- CRC-32 of chunks and the Paeth predictor: shared by the encoder (ipx_png.hip) and the decoder (ipx_png_dec.hip) ----------------
 // crc: the byte table of the reflected polynomial 0xEDB88320; x2n[k]: x^(2^k) mod P (zlib's x2n_table).  Each translation unit that
@@ -172,7 +212,7 @@ hipError_t launch_png_mixed_frame(const PngMixFrame *frames, int n, const uint32
 struct ipx_ctx;
 namespace ipx {
 // png.Encode of n RGBA8 frames in HBM -> streams in one pinned block (ipx_host_alloc), everything on stream s; returns once the block
-// is filled (ipx_png.hip; the PNG legs of ipx_png.hip and ipx_png_legs.hip)
+// is filled (ipx_png.hip; the chunk step of ipx_out_stage.hip calls it for every PNG leg)
 int png_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w, int h, int stride, size_t frame_stride, int n,
                     uint8_t **blob, size_t *offs, size_t *lens);
 // the same for n frames of any sizes, one launch per stage (ipx_png_mixed.hip; the mixed PNG leg of ipx_png_legs.hip).  The frames are

@@ -151,18 +151,7 @@ int ipx::png_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w,
     // the segments of every frame, by its colour type
     for (int f = 0; f < n; f++) {
         item0[f] = (uint32_t)segs.size();
-        const PngSegs g(w, h, alpha[f] ? 4 : 3);
-        size_t at = (size_t)f * region + kPngSegBase;
-        for (int k = 0; k < g.nseg; k++) {
-            PngSeg sg;
-            sg.frame = (uint32_t)f;
-            sg.s0 = (uint32_t)((size_t)g.row0(k, h) * g.stride);
-            sg.s1 = (uint32_t)((size_t)g.row0(k + 1, h) * g.stride);
-            sg.flags = (k == 0 ? 1u : 0u) | (k == g.nseg - 1 ? 2u : 0u);
-            sg.out = at;
-            at += png_slot_bytes(sg.s1 - sg.s0, k == 0);
-            segs.push_back(sg);
-        }
+        png_append_segs(&segs, (uint32_t)f, w, h, alpha[f] ? 4 : 3, (size_t)f * region);
     }
     item0[n] = (uint32_t)segs.size();
     const int nseg = (int)segs.size();
@@ -192,18 +181,7 @@ int ipx::png_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w,
     size_t total = 0;
     for (int f = 0; f < n; f++) {
         offs[f] = total;
-        size_t at = total;
-        pieces.push_back({(unsigned long long)f * region, at, (uint32_t)kPngHeadBytes, 0});
-        at += kPngHeadBytes;
-        for (uint32_t k = item0[f]; k < item0[f + 1]; k++) {
-            if (sl[k] > png_slot_bytes(segs[k].s1 - segs[k].s0, k == item0[f])) { set_error("png: segment %u overran its bound", k); return IPX_ERR_INVALID; }
-            pieces.push_back({segs[k].out, at, sl[k], 0});
-            at += sl[k];
-        }
-        pieces.push_back({(unsigned long long)f * region + tail, at, (uint32_t)kPngTailBytes, 0});
-        at += kPngTailBytes;
-        lens[f] = at - total;
-        total = (at + 15) & ~(size_t)15;
+        if (!(lens[f] = png_place_pieces(&pieces, segs, sl, item0[f], item0[f + 1], (size_t)f * region, tail, &total))) return IPX_ERR_INVALID;
     }
     uint8_t *dpack;
     PngPiece *dpieces;
@@ -211,13 +189,7 @@ int ipx::png_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w,
     IPX_HIP(mem.get(&dpieces, pieces.size() * sizeof(PngPiece)));
     IPX_HIP(hipMemcpyAsync(dpieces, pieces.data(), pieces.size() * sizeof(PngPiece), hipMemcpyHostToDevice, s));
     IPX_HIP(launch_png_pack(dout, dpieces, (int)pieces.size(), dpack, s));
-    uint8_t *host = (uint8_t *)ipx_host_alloc(ctx, total);
-    if (!host) return IPX_ERR_NOMEM;
-    hipError_t e = hipMemcpyAsync(host, dpack, total, hipMemcpyDeviceToHost, s);
-    { const hipError_t e2 = hipStreamSynchronize(s); if (e == hipSuccess) e = e2; }
-    if (e != hipSuccess) { (void)ipx_host_free(ctx, host); set_error("png stream download failed: %s", hipGetErrorString(e)); return IPX_ERR_HIP; }
-    *blob = host;
-    return IPX_OK;
+    return download_streams(ctx, s, dpack, total, "png ", blob);
 }
 
 extern "C" {
@@ -240,31 +212,7 @@ IPX_CATCH_STATUS
 int ipx_png_encode_rgba8(ipx_ctx *ctx, const uint8_t *pix, int w, int h, int stride, uint8_t **out, size_t *len) try
 {
     IPX_ENTER(ctx);
-    if (!out || !len) { set_error("ipx_png_encode_rgba8: bad argument"); return IPX_ERR_INVALID; }
-    *out = nullptr;
-    *len = 0;
-    int rc = png_check("ipx_png_encode_rgba8", pix, w, h, stride, 1);
-    if (rc) return rc;
-    LaneLease lane(ctx);
-    hipStream_t s = lane->stream;
-    const size_t fbytes = (size_t)w * h * 4;
-    uint8_t *blob = nullptr;
-    size_t off = 0, n = 0;
-    {
-        AsyncFree mem{s, {}};
-        uint8_t *dsrc;
-        IPX_HIP(mem.get(&dsrc, fbytes));
-        IPX_HIP(hipMemcpy2DAsync(dsrc, (size_t)w * 4, pix, stride, (size_t)w * 4, h, hipMemcpyHostToDevice, s));
-        rc = png_encode_core(ctx, s, dsrc, w, h, w * 4, fbytes, 1, &blob, &off, &n);
-        if (rc) return rc;
-    }
-    uint8_t *m = (uint8_t *)malloc(n);
-    if (!m) { (void)ipx_host_free(ctx, blob); set_error("ipx_png_encode_rgba8: out of memory"); return IPX_ERR_NOMEM; }
-    memcpy(m, blob + off, n);
-    (void)ipx_host_free(ctx, blob);
-    *out = m;
-    *len = n;
-    return IPX_OK;
+    return encode_one_rgba8("ipx_png_encode_rgba8", ctx, png_check, png_encode_core, pix, w, h, stride, out, len);
 }
 IPX_CATCH_STATUS
 
@@ -274,34 +222,8 @@ int ipx_plan_run_host_png(ipx_ctx *ctx, const ipx_plan *pl, int n, const uint8_t
                           ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, ipx_jpeg_result **result) try
 {
     IPX_ENTER(ctx);
-    if (!result) { set_error("ipx_plan_run_host_png: bad argument"); return IPX_ERR_INVALID; }
-    *result = nullptr;
-    const BatchSrc host = packed_src(kSrcRGBA, src, sstride, src_frame_stride);
-    const int rc0 = src_check("ipx_plan_run_host_png", pl, host, n, false);
-    if (rc0 || n == 0) return rc0;
-    const SrcLayout L = src_layout(pl, host);
-    const size_t fsrc = L.frame_bytes();
-    const PlanOutputs outs(pl, resize_out, thumb_out, wm_out, Codec::Png, Codec::Png, Codec::Png);
-    const size_t per_frame = fsrc + outs.frame_bytes();
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n, (size_t)env_int("IPX_HOST_CHUNK_PNG", 64),
-                                                                 ((size_t)1 << 30) / per_frame}));
-    ResultOwner res(ctx);
-    LaneLease lane(ctx);
-    hipStream_t s = lane->stream;
-    for (int i0 = 0; i0 < n; i0 += chunk) {
-        const int m = std::min(chunk, n - i0);
-        StreamSync sync{s};
-        AsyncFree mem{s, {}};
-        uint8_t *dsrc, *dout = nullptr;
-        IPX_HIP(mem.get(&dsrc, fsrc * m));
-        if (outs.frame_bytes()) IPX_HIP(mem.get(&dout, outs.frame_bytes() * m));
-        BatchSrc d;
-        IPX_HIP(src_upload(host, L, i0, m, dsrc, m, s, kCopyFrameRows, &d));
-        const int rc = run_chunk(ctx, s, pl, outs, dout, m, d, all_files(n), i0, m, nullptr, nullptr, 0, nullptr, res);
-        if (rc) return rc;
-    }
-    *result = res.release();
-    return IPX_OK;
+    return run_host_streams("ipx_plan_run_host_png", ctx, pl, n, packed_src(kSrcRGBA, src, sstride, src_frame_stride), Codec::Png, Codec::Png,
+                            Codec::Png, "IPX_HOST_CHUNK_PNG", 64, 0, resize_out, thumb_out, wm_out, result);
 }
 IPX_CATCH_STATUS
 

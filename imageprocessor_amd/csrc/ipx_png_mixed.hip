@@ -175,27 +175,16 @@ int ipx::png_encode_mixed_core(ipx_ctx *ctx, hipStream_t s, const ipx_rgba_frame
     size_t rows = 0, fbytes = 0, obytes = 0;
     for (int f = 0; f < n; f++) {
         const int w = tab[f].w, h = tab[f].h, bpp = alpha[f] ? 4 : 3;
-        const PngSegs g(w, h, bpp);
         const size_t tail = kPngSegBase + png_segs_bytes(w, h, bpp);
         tab[f].row0 = (uint32_t)rows;
         tab[f].filt = fbytes;
         tab[f].region = obytes;
         tab[f].tail = (uint32_t)tail;
         tab[f].seg0 = (uint32_t)segs.size();
-        size_t at = obytes + kPngSegBase;
-        for (int k = 0; k < g.nseg; k++) {
-            PngSeg sg;
-            sg.frame = (uint32_t)f;
-            sg.s0 = (uint32_t)((size_t)g.row0(k, h) * g.stride);
-            sg.s1 = (uint32_t)((size_t)g.row0(k + 1, h) * g.stride);
-            sg.flags = (k == 0 ? 1u : 0u) | (k == g.nseg - 1 ? 2u : 0u);
-            sg.out = at;
-            at += png_slot_bytes(sg.s1 - sg.s0, k == 0);
-            segs.push_back(sg);
-        }
+        png_append_segs(&segs, (uint32_t)f, w, h, bpp, obytes);
         tab[f].seg1 = (uint32_t)segs.size();
         rows += (size_t)h;
-        fbytes += align256((size_t)h * g.stride);
+        fbytes += align256((size_t)h * PngSegs(w, h, bpp).stride);
         obytes += align256(tail + kPngTailBytes);
     }
     if (segs.size() > (size_t)INT_MAX) { set_error("png: too many segments in one call"); return IPX_ERR_UNSUPPORTED; }
@@ -223,18 +212,7 @@ int ipx::png_encode_mixed_core(ipx_ctx *ctx, hipStream_t s, const ipx_rgba_frame
     size_t total = 0;
     for (int f = 0; f < n; f++) {
         offs[f] = total;
-        size_t at = total;
-        pieces.push_back({tab[f].region, at, (uint32_t)kPngHeadBytes, 0});
-        at += kPngHeadBytes;
-        for (uint32_t k = tab[f].seg0; k < tab[f].seg1; k++) {
-            if (sl[k] > png_slot_bytes(segs[k].s1 - segs[k].s0, k == tab[f].seg0)) { set_error("png: segment %u overran its bound", k); return IPX_ERR_INVALID; }
-            pieces.push_back({segs[k].out, at, sl[k], 0});
-            at += sl[k];
-        }
-        pieces.push_back({tab[f].region + tab[f].tail, at, (uint32_t)kPngTailBytes, 0});
-        at += kPngTailBytes;
-        lens[f] = at - total;
-        total = (at + 15) & ~(size_t)15;
+        if (!(lens[f] = png_place_pieces(&pieces, segs, sl, tab[f].seg0, tab[f].seg1, tab[f].region, tab[f].tail, &total))) return IPX_ERR_INVALID;
     }
     if (pieces.size() > (size_t)INT_MAX) { set_error("png: too many pieces in one call"); return IPX_ERR_UNSUPPORTED; }
     uint8_t *dpack;
@@ -243,13 +221,7 @@ int ipx::png_encode_mixed_core(ipx_ctx *ctx, hipStream_t s, const ipx_rgba_frame
     IPX_HIP(mem.get(&dpieces, pieces.size() * sizeof(PngPiece)));
     IPX_HIP(hipMemcpyAsync(dpieces, pieces.data(), pieces.size() * sizeof(PngPiece), hipMemcpyHostToDevice, s));
     IPX_HIP(launch_png_pack(dout, dpieces, (int)pieces.size(), dpack, s));
-    uint8_t *host = (uint8_t *)ipx_host_alloc(ctx, total);
-    if (!host) return IPX_ERR_NOMEM;
-    hipError_t e = hipMemcpyAsync(host, dpack, total, hipMemcpyDeviceToHost, s);
-    { const hipError_t e2 = hipStreamSynchronize(s); if (e == hipSuccess) e = e2; }
-    if (e != hipSuccess) { (void)ipx_host_free(ctx, host); set_error("png stream download failed: %s", hipGetErrorString(e)); return IPX_ERR_HIP; }
-    *blob = host;
-    return IPX_OK;
+    return download_streams(ctx, s, dpack, total, "png ", blob);
 }
 
 extern "C" {
@@ -257,27 +229,13 @@ extern "C" {
 int ipx_png_encode_mixed_dev(ipx_ctx *ctx, const ipx_rgba_frame *frames, int n, uint8_t **blob, size_t *offs, size_t *lens) try
 {
     IPX_ENTER(ctx);
-    if (!blob || !offs || !lens || n < 0 || (n && !frames)) { set_error("ipx_png_encode_mixed_dev: bad argument"); return IPX_ERR_INVALID; }
-    *blob = nullptr;
-    if (n == 0) return IPX_OK;
-    if (n > 65535) { set_error("ipx_png_encode_mixed_dev: at most 65535 frames per call"); return IPX_ERR_UNSUPPORTED; }
-    // every frame before any launch: a malformed one first (IPX_ERR_INVALID), then one beyond the span the kernels address
-    for (int f = 0; f < n; f++) {
-        const ipx_rgba_frame &fr = frames[f];
-        if (!fr.pix || fr.w <= 0 || fr.h <= 0 || (long long)fr.stride < (long long)fr.w * 4) {
-            set_error("ipx_png_encode_mixed_dev: frame %d: bad argument", f);
-            return IPX_ERR_INVALID;
-        }
-        if (((uintptr_t)fr.pix | (unsigned)fr.stride) & 3) {
-            set_error("ipx_png_encode_mixed_dev: frame %d: the address and the stride must be multiples of 4", f);
-            return IPX_ERR_INVALID;
-        }
-    }
-    for (int f = 0; f < n; f++)
-        if (!frame_span_ok(frames[f].w, frames[f].h, (long long)frames[f].w * 4, 4)) {
-            set_error("ipx_png_encode_mixed_dev: frame %d: %dx%d is beyond the frames the encoder addresses", f, frames[f].w, frames[f].h);
-            return IPX_ERR_UNSUPPORTED;
-        }
+    const auto aligned = [](const char *who, int f, const ipx_rgba_frame &fr) -> int {
+        if (!(((uintptr_t)fr.pix | (unsigned)fr.stride) & 3)) return IPX_OK;
+        set_error("%s: frame %d: the address and the stride must be multiples of 4", who, f);
+        return IPX_ERR_INVALID;
+    };
+    const int rc = rgba_frames_check("ipx_png_encode_mixed_dev", frames, n, blob, offs, lens, aligned, false);
+    if (rc || n == 0) return rc;
     LaneLease lane(ctx);
     return png_encode_mixed_core(ctx, lane->stream, frames, n, blob, offs, lens);
 }

@@ -10,7 +10,7 @@
 #define IPX_DIAG 0
 #endif
 
-// what the compressed-in / compressed-out entries (ipx_jpeg_runtime.hip, the PNG and GIF legs) check before anything else
+// what the compressed-in / compressed-out entries (ipx_jpeg_legs.hip, the PNG and GIF legs) check before anything else
 int leg_entry_check(const char *who, const ipx_plan *pl, int n, const ipx_bytes *files, const int *status, ipx_jpeg_result **result,
                     bool texts_entry, const ipx_text *texts)
 {

@@ -1,7 +1,7 @@
 // ipx_runtime_internal.h -- the runtime's own types (context, lanes, glyph sets, plans) and the small helpers every
 // translation unit that implements ABI entries needs (ipx_context.hip, ipx_image_ops.hip, ipx_text.hip, ipx_plan.hip, ipx_runtime.hip,
-// ipx_jpeg_runtime.hip, ipx_jpeg_dec_runtime.hip, the GIF and PNG halves).  What only the decode drivers share sits on top of it in
-// ipx_decode_common.h.  Not part of the ABI.
+// ipx_out_stage.hip, ipx_jpeg_runtime.hip, ipx_jpeg_dec_runtime.hip, the legs, the GIF and PNG halves).  What only the decode drivers
+// share sits on top of it in ipx_decode_common.h.  Not part of the ABI.
 #pragma once
 
 #include <atomic>
@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <cctype>
+#include <chrono>
 #include <cstdio>
 #include <condition_variable>
 #include <cstdlib>
@@ -331,6 +332,88 @@ struct StreamSync {
     ~StreamSync() { (void)hipStreamSynchronize(s); }
 };
 
+// ---- what the five encode cores (jpeg_encode_sets, jpeg_encode_mixed_core, png_encode_core, png_encode_mixed_core, gif_encode_core)
+// ---- and the single-frame entries built on them share -----------------------------------------------------------------------------
+
+// The tail of every core: the `total` bytes of finished streams at `dev` come down into one pinned block (one byte for an empty total),
+// *blob.  Allocate, queue, wait, keep the first error; a failed download gives the block back and reports "<prefix>stream download
+// failed".  The wait is also what the core's host tables, read by copies queued before, are kept until.  queued: when the copy was queued.
+inline int download_streams(ipx_ctx *ctx, hipStream_t s, const uint8_t *dev, size_t total, const char *prefix, uint8_t **blob,
+                            std::chrono::steady_clock::time_point *queued = nullptr)
+{
+    uint8_t *host = (uint8_t *)ipx_host_alloc(ctx, total ? total : 1);   // pinned: the download runs at link speed
+    if (!host) return IPX_ERR_NOMEM;
+    hipError_t e = hipMemcpyAsync(host, dev, total, hipMemcpyDeviceToHost, s);
+    if (queued) *queued = std::chrono::steady_clock::now();
+    { const hipError_t e2 = hipStreamSynchronize(s); if (e == hipSuccess) e = e2; }
+    if (e != hipSuccess) { (void)ipx_host_free(ctx, host); set_error("%sstream download failed: %s", prefix, hipGetErrorString(e)); return IPX_ERR_HIP; }
+    *blob = host;
+    return IPX_OK;
+}
+
+// ipx_png_encode_rgba8 and ipx_gif_encode_rgba8: one frame in host memory is checked by the codec's rule, staged in stream-ordered
+// scratch of a leased lane, encoded by the codec's core and copied out of the pinned block into a malloc'ed buffer (ipx_buffer_free).
+using EncodeCheck = int (*)(const char *who, const void *src, int w, int h, long long stride, int n);
+using EncodeCore = int (*)(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w, int h, int stride, size_t frame_stride, int n, uint8_t **blob,
+                           size_t *offs, size_t *lens);
+inline int encode_one_rgba8(const char *who, ipx_ctx *ctx, EncodeCheck check, EncodeCore core, const uint8_t *pix, int w, int h, int stride,
+                            uint8_t **out, size_t *len)
+{
+    if (!out || !len) { set_error("%s: bad argument", who); return IPX_ERR_INVALID; }
+    *out = nullptr;
+    *len = 0;
+    int rc = check(who, pix, w, h, stride, 1);
+    if (rc) return rc;
+    LaneLease lane(ctx);
+    hipStream_t s = lane->stream;
+    const size_t fbytes = (size_t)w * h * 4;
+    uint8_t *blob = nullptr;
+    size_t off = 0, n = 0;
+    {
+        AsyncFree mem{s, {}};
+        uint8_t *dsrc;
+        IPX_HIP(mem.get(&dsrc, fbytes));
+        IPX_HIP(hipMemcpy2DAsync(dsrc, (size_t)w * 4, pix, stride, (size_t)w * 4, h, hipMemcpyHostToDevice, s));
+        rc = core(ctx, s, dsrc, w, h, w * 4, fbytes, 1, &blob, &off, &n);
+        if (rc) return rc;
+    }
+    uint8_t *m = (uint8_t *)malloc(n);
+    if (!m) { (void)ipx_host_free(ctx, blob); set_error("%s: out of memory", who); return IPX_ERR_NOMEM; }
+    memcpy(m, blob + off, n);
+    (void)ipx_host_free(ctx, blob);
+    *out = m;
+    *len = n;
+    return IPX_OK;
+}
+
+// The opening of ipx_png_encode_mixed_dev and ipx_jpeg_encode_mixed_dev: the arguments, then *blob = NULL (n == 0 is then done: the
+// caller returns), at most 65535 frames, and every frame before any launch -- a malformed one first (IPX_ERR_INVALID; `extra` is the
+// codec's own refusal of a well-formed frame, with its text set, or IPX_OK), then one beyond the span the kernels address
+// (IPX_ERR_UNSUPPORTED; span_of_stride: of rows `stride` apart as the caller has them, else of tight rows).
+using RgbaFrameCheck = int (*)(const char *who, int f, const ipx_rgba_frame &fr);
+inline int rgba_frames_check(const char *who, const ipx_rgba_frame *frames, int n, uint8_t **blob, const size_t *offs, const size_t *lens,
+                             RgbaFrameCheck extra, bool span_of_stride)
+{
+    if (!blob || !offs || !lens || n < 0 || (n && !frames)) { set_error("%s: bad argument", who); return IPX_ERR_INVALID; }
+    *blob = nullptr;
+    if (n == 0) return IPX_OK;
+    if (n > 65535) { set_error("%s: at most 65535 frames per call", who); return IPX_ERR_UNSUPPORTED; }
+    for (int f = 0; f < n; f++) {
+        const ipx_rgba_frame &fr = frames[f];
+        if (!fr.pix || fr.w <= 0 || fr.h <= 0 || (long long)fr.stride < (long long)fr.w * 4) {
+            set_error("%s: frame %d: bad argument", who, f);
+            return IPX_ERR_INVALID;
+        }
+        if (const int rc = extra(who, f, fr)) return rc;
+    }
+    for (int f = 0; f < n; f++)
+        if (!frame_span_ok(frames[f].w, frames[f].h, span_of_stride ? (long long)frames[f].stride : (long long)frames[f].w * 4, 4)) {
+            set_error("%s: frame %d: %dx%d is beyond the frames the encoder addresses", who, f, frames[f].w, frames[f].h);
+            return IPX_ERR_UNSUPPORTED;
+        }
+    return IPX_OK;
+}
+
 // ---- Scale and Draw on frames in HBM (ipx_image_ops.hip) -----------------------------------------------------------------------------
 
 // a source image resident in HBM: RGBA / NRGBA pixels, or the three planes of a YCbCr image
@@ -535,7 +618,7 @@ int jpeg_decode_cmyk_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *jpegs, 
 // the pinned blocks the streams of the compressed-out batch entries live in (ipx_jpeg_result_free)
 struct ipx_jpeg_result { std::vector<uint8_t *> blobs; };
 
-// ---- the output stage of the compressed-out batch entries (ipx_jpeg_runtime.hip) ----------------------------------------------------
+// ---- the output stage of the compressed-out batch entries (ipx_out_stage.hip) --------------------------------------------------------
 
 // An entry's result while it runs: freed on every way out but release(), which hands it to the caller.
 class ResultOwner {
@@ -597,3 +680,11 @@ struct LegTexts {
 // until `s` has been waited for.
 int run_chunk(ipx_ctx *ctx, hipStream_t s, const ipx_plan *pl, const PlanOutputs &outs, uint8_t *block, int slots, const BatchSrc &d,
               const FileSel &sel, int c0, int m, const LegTexts *texts, AsyncFree *mem, int quality, const int *status, ResultOwner &res);
+
+// The leg of ipx_plan_run_host_png and ipx_plan_run_host_paletted_gif: n frames in host memory go up in chunks on one lane, each chunk
+// through run_chunk; only the streams come back, into pinned blocks owned by *result.  chunk_env / chunk_default: the knob that caps a
+// chunk's frames (a chunk also stays within 1 GiB of scratch).  Refusals in this order: a null result, src_check, a GIF output beyond
+// gif.Encode's limits; then n == 0 is done.  (The host-frame JPEG leg drives every lane from a thread of its own: ipx_jpeg_legs.hip.)
+int run_host_streams(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n, const BatchSrc &host, Codec res, Codec thumb, Codec wm,
+                     const char *chunk_env, int chunk_default, int quality, ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out,
+                     ipx_jpeg_result **result);

@@ -1,7 +1,8 @@
 // jpeg_enc_mixed_plan_test.cpp -- the host side of a mixed-size jpeg.Encode's per-frame records (imageprocessor_amd/csrc/
 // ipx_jpeg_enc_mixed_plan.h: jpeg_enc_build, jpeg_enc_place_scans, jpeg_enc_place_streams, jpeg_enc_find) held to a transcription of the
-// uniform encoder's arithmetic (jpeg_encode_sets, launch_jpeg_fdct and the entropy launches) as a program of its own: plain g++, no
-// GPU, no runtime.
+// uniform encoder's arithmetic (jpeg_encode_sets, launch_jpeg_fdct and the entropy launches), and the scan-length rule of both encode
+// cores (jpeg_scan_limit, jpeg_scan_too_long) and the rounding rules (ipx_align.h) held to theirs, as a program of its own: plain g++,
+// no GPU, no runtime.
 //   g++ -std=c++17 -fsanitize=address,undefined -o jpeg_enc_mixed_plan_test tools/jpeg_enc_mixed_plan_test.cpp && ./jpeg_enc_mixed_plan_test
 // Prints "jpeg enc mixed plan ok" and exits 0, or says what broke and exits 1.  tests/test_jpeg_enc_mixed_host.py runs it.
 #include <cstdio>
@@ -88,6 +89,9 @@ static void check_records(const char *name, const std::vector<int> &w, const std
     unsigned long long at = 0;
     for (int i = 0; i < n; i++) {
         CHECK(lens[i] == 589 + (size_t)g[i].ubytes + ff[i] + 2 && offs[i] == at && g[i].obase == at && at % 16 == 0, "%s: frame %d stream placement", name, i);
+        // the next stream starts at the first multiple of 16 that is not inside this one: no overlap, and less than 16 bytes between them
+        const unsigned long long end = offs[i] + lens[i], next = i + 1 < n ? offs[i + 1] : total;
+        CHECK(next >= end && next - end < 16 && next % 16 == 0, "%s: stream %d ends at %llu, the next starts at %llu", name, i, end, next);
         at += (lens[i] + 15) & ~(size_t)15;
     }
     CHECK(total == at, "%s: block of %llu bytes, expected %llu", name, total, at);
@@ -174,6 +178,32 @@ int main()
         // the builder's refusals
         auto one = [&](int fw_, int fh_, int stride) { const JpegEncSrc f{(const uint8_t *)0x1000, nullptr, fw_, fh_, stride}; return jpeg_enc_build(&f, 1, &g, &t); };
         CHECK(!one(0, 1, 4) && !one(1, 0, 4) && !one(65536, 1, 4 * 65536) && !one(1, 65536, 4) && !one(2, 1, 7) && one(2, 1, 8) && one(65535, 1, 4 * 65535), "the builder's refusals");
+    }
+    // the two rounding rules
+    for (size_t v : {(size_t)0, (size_t)1, (size_t)15, (size_t)16, (size_t)17, (size_t)255, (size_t)256, (size_t)257, (size_t)0xfffffff1u}) {
+        CHECK(align16(v) % 16 == 0 && align16(v) >= v && align16(v) - v < 16, "align16(%zu) is %zu", v, align16(v));
+        CHECK(align256(v) % 256 == 0 && align256(v) >= v && align256(v) - v < 256, "align256(%zu) is %zu", v, align256(v));
+    }
+    // the scan-length rule of both cores: the limit is 2^32 - 1 bits, the knob can only lower it, a scan AT the limit is refused and one
+    // below it passes, and the first offender is the one named
+    {
+        const unsigned long long top = 0xffffffffull;
+        CHECK(kJpegScanBitsTop == top && jpeg_scan_limit(0) == top && jpeg_scan_limit(-1) == top && jpeg_scan_limit(-2147483647 - 1) == top, "no knob: the limit is 2^32 - 1");
+        CHECK(jpeg_scan_limit(1) == 1 && jpeg_scan_limit(4000) == 4000 && jpeg_scan_limit(2147483647) == 2147483647ull, "the knob lowers the limit");
+        for (int knob : {-5, 0, 1, 2, 4000, 65536, 2147483647}) CHECK(jpeg_scan_limit(knob) <= top && jpeg_scan_limit(knob) >= 1, "knob %d: limit %llu", knob, jpeg_scan_limit(knob));
+        for (unsigned long long limit : {1ull, 4000ull, 2147483647ull, top}) {
+            const unsigned long long below[] = {0, limit - 1, limit / 2}, at[] = {limit - 1, limit, 0}, over[] = {limit - 1, 0, limit + 1, limit};
+            CHECK(jpeg_scan_too_long(below, 3, limit) == -1, "limit %llu: a scan below it was refused", limit);
+            CHECK(jpeg_scan_too_long(at, 3, limit) == 1, "limit %llu: a scan at it passed, or another was named", limit);
+            CHECK(jpeg_scan_too_long(over, 4, limit) == 2, "limit %llu: the first offender is frame 2", limit);
+            CHECK(jpeg_scan_too_long(over, 2, limit) == -1 && jpeg_scan_too_long(over, 0, limit) == -1, "limit %llu: scans beyond n were read", limit);
+        }
+        // what passes the rule at its top is what jpeg_enc_place_scans takes
+        std::vector<JpegEncFrame> g(1);
+        JpegEncTotals t;
+        const unsigned long long last_ok = top - 1;
+        CHECK(jpeg_scan_too_long(&last_ok, 1, jpeg_scan_limit(0)) == -1 && jpeg_enc_place_scans(&last_ok, 1, &g, &t), "2^32 - 2 bits pass both");
+        CHECK(jpeg_scan_too_long(&top, 1, jpeg_scan_limit(0)) == 0 && !jpeg_enc_place_scans(&top, 1, &g, &t), "2^32 - 1 bits pass neither");
     }
     // the SOF0 dimensions lie where jpeg_write_header puts them: SOI, DQT with two tables, the SOF0 marker, length and precision
     CHECK(kJpegSofDims == 141, "SOF0 dimensions at %d", kJpegSofDims);
