@@ -970,6 +970,41 @@ class Context:
         _check(lib().ipx_jpeg_encode_mixed_dev(self.handle, arr, n, int(quality), C.byref(blob), offs, lens))
         return self._stream_block(blob, offs, lens, n, copy)
 
+    def gif_decode_mixed(self, files, download=True):
+        """image.Decode of GIF byte strings of ANY sizes in one decode pass (ipx_gif_decode_mixed; the first image of each).  A file
+        given as None goes in as a NULL entry.  -> (frames, status list); frames[i] is None for a non-OK file, else dict(w, h, stride,
+        index, palette) with index as h x w and palette as 256 x 4 uint8 (download=True), or the device pointers.  With download=False
+        a third value, free(), releases the frames."""
+        def frame(f):
+            if not f.index:
+                return None
+            d = {"w": f.w, "h": f.h, "stride": f.stride, "index": f.index, "palette": f.palette}
+            if download:
+                d["index"] = self._grab(f.index, f.h, f.stride)
+                d["palette"] = self._grab(f.palette, 256, 4)
+            return d
+        return self._decode_mixed("ipx_gif_decode_mixed", "ipx_gif_frames_free", files, _lib.GifFrame, frame, download)
+
+    def gif_encode_mixed_dev(self, frames, copy=True):
+        """frames: (device pointer, w, h, stride) per RGBA8 frame in HBM, of any sizes -> one GIF stream each, byte for byte
+        gif_encode_batch_dev's for that frame alone (ipx_gif_encode_mixed_dev).  copy=False returns (memoryviews into the pinned
+        block, release()) instead of bytes."""
+        frames = list(frames)
+        n = len(frames)
+        arr = (_lib.RgbaFrame * max(n, 1))()
+        for i, (ptr, w, h, stride) in enumerate(frames):
+            arr[i] = _lib.RgbaFrame(ptr, int(w), int(h), int(stride))
+        blob, offs, lens = C.c_void_p(), (C.c_size_t * max(n, 1))(), (C.c_size_t * max(n, 1))()
+        _check(lib().ipx_gif_encode_mixed_dev(self.handle, arr, n, C.byref(blob), offs, lens))
+        return self._stream_block(blob, offs, lens, n, copy)
+
+    def run_gif_gif_mixed(self, ops, files, quality=85, want=("resize", "thumbnail", "watermark"), copy=True, texts=None):
+        """GIF byte strings of ANY sizes in -> ({operator: [bytes | None] * n}, status list): one decode pass per group, the operators
+        per run of one size, one mixed-size gif.Encode of the resize and thumbnail outputs and one jpeg.Encode of the watermark
+        outputs per chunk (ipx_run_gif_gif_mixed).  ops, texts and copy as for run_jpeg_jpeg_mixed."""
+        ops, keep = _pool_ops(ops, glyph_list=True)
+        return self._run_mixed(lib().ipx_run_gif_gif_mixed, ops, files, texts, want, copy, (int(quality),))
+
     def run_png_png_mixed(self, ops, files, want=("resize", "thumbnail", "watermark"), copy=True, texts=None):
         """PNG byte strings of ANY sizes and kinds in -> ({operator: [png bytes | None] * n}, status list): one decode pass per group,
         the operators per run of one size, one mixed-size png.Encode per output (ipx_run_png_png_mixed).  ops: a PoolOps with sw = sh

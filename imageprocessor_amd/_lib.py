@@ -74,6 +74,10 @@ class JpegFrame(C.Structure):
                 ("ystride", C.c_int32), ("cstride", C.c_int32)]
 
 
+class GifFrame(C.Structure):
+    _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("index", C.c_void_p), ("stride", C.c_int32), ("palette", C.c_void_p)]
+
+
 class RgbaFrame(C.Structure):
     _fields_ = [("pix", C.c_void_p), ("w", C.c_int32), ("h", C.c_int32), ("stride", C.c_int32)]
 
@@ -264,6 +268,10 @@ SIGNATURES = {
     "ipx_png_decode_mixed": (_I, [_P, _P, C.POINTER(Bytes), _I, C.POINTER(PngFrame), C.POINTER(_I), C.POINTER(_P)]),
     "ipx_png_encode_mixed_dev": (_I, [_P, C.POINTER(RgbaFrame), _I, C.POINTER(_P), C.POINTER(_Z), C.POINTER(_Z)]),
     "ipx_jpeg_encode_mixed_dev": (_I, [_P, C.POINTER(RgbaFrame), _I, _I, C.POINTER(_P), C.POINTER(_Z), C.POINTER(_Z)]),
+    "ipx_gif_decode_mixed": (_I, [_P, _P, C.POINTER(Bytes), _I, C.POINTER(GifFrame), C.POINTER(_I), C.POINTER(_P)]),
+    "ipx_gif_encode_mixed_dev": (_I, [_P, C.POINTER(RgbaFrame), _I, C.POINTER(_P), C.POINTER(_Z), C.POINTER(_Z)]),
+    "ipx_run_gif_gif_mixed": (_I, [_P, C.POINTER(PoolOps), _I, C.POINTER(Bytes), C.POINTER(Text), _I, C.POINTER(Bytes), C.POINTER(Bytes),
+                                   C.POINTER(Bytes), C.POINTER(_I), C.POINTER(_P)]),
     "ipx_run_png_png_mixed": (_I, [_P, C.POINTER(PoolOps), _I, C.POINTER(Bytes), C.POINTER(Text), C.POINTER(Bytes), C.POINTER(Bytes),
                                    C.POINTER(Bytes), C.POINTER(_I), C.POINTER(_P)]),
     "ipx_run_jpeg_jpeg_mixed": (_I, [_P, C.POINTER(PoolOps), _I, C.POINTER(Bytes), C.POINTER(Text), _I, C.POINTER(Bytes), C.POINTER(Bytes),

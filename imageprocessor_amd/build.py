@@ -11,8 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libipx.so")
-SOURCES = ["ipx_kernels.hip", "ipx_ks_generic.hip", "ipx_ks_fused.hip", "ipx_ks_tail.hip", "ipx_jpeg.hip", "ipx_jpeg_entropy.hip", "ipx_jpeg_dec.hip", "ipx_jpeg_dec_par.hip", "ipx_jpeg_dec_scans.hip", "ipx_jpeg_dec_cmyk.hip", "ipx_context.hip", "ipx_image_ops.hip", "ipx_text.hip", "ipx_plan.hip", "ipx_runtime.hip", "ipx_out_stage.hip", "ipx_jpeg_runtime.hip", "ipx_jpeg_dec_runtime.hip", "ipx_pool.hip", "ipx_gif.hip", "ipx_gif_dec.hip", "ipx_gif_dec_par.hip", "ipx_png.hip", "ipx_png_mixed.hip", "ipx_png_dec.hip", "ipx_png_dec_par.hip", "ipx_png_dec_runtime.hip", "ipx_png_legs.hip", "ipx_jpeg_legs.hip", "ipx_host.cpp", "ipx_ks_host.cpp", "ipx_batcher.cpp", "ipx_ops.cpp", "ipx_font.cpp", "ipx_jpeg_host.cpp", "ipx_jpeg_dec_host.cpp", "ipx_jpeg_dec_prog.cpp", "ipx_gif_host.cpp", "ipx_gif_dec_host.cpp", "ipx_png_host.cpp", "ipx_png_dec_host.cpp"]
-HEADERS = ["ipx_internal.h", "ipx_runtime_internal.h", "ipx_decode_common.h", "ipx_device.h", "ipx_ks.h", "ipx_ks_exact.h", "ipx_threads.h", "ipx_batcher.h", "ipx_pool_core.h", "ipx_gif.h", "ipx_gif_dec.h", "ipx_png.h", "ipx_png_kernels.h", "ipx_png_deflate_body.inc", "ipx_align.h", "ipx_mixed_cut.h", "ipx_jpeg_mixed_plan.h", "ipx_jpeg_enc_mixed_plan.h", "ipx_mixed_leg.h", "ipx_png_layout.h", "ipx_png_dec.h", "ipx_png_inflate.h", os.path.join("..", "..", "include", "ipx.h")]
+SOURCES = ["ipx_kernels.hip", "ipx_ks_generic.hip", "ipx_ks_fused.hip", "ipx_ks_tail.hip", "ipx_jpeg.hip", "ipx_jpeg_entropy.hip", "ipx_jpeg_dec.hip", "ipx_jpeg_dec_par.hip", "ipx_jpeg_dec_scans.hip", "ipx_jpeg_dec_cmyk.hip", "ipx_context.hip", "ipx_image_ops.hip", "ipx_text.hip", "ipx_plan.hip", "ipx_runtime.hip", "ipx_out_stage.hip", "ipx_jpeg_runtime.hip", "ipx_jpeg_dec_runtime.hip", "ipx_pool.hip", "ipx_gif.hip", "ipx_gif_mixed.hip", "ipx_gif_dec.hip", "ipx_gif_dec_par.hip", "ipx_png.hip", "ipx_png_mixed.hip", "ipx_png_dec.hip", "ipx_png_dec_par.hip", "ipx_png_dec_runtime.hip", "ipx_png_legs.hip", "ipx_jpeg_legs.hip", "ipx_host.cpp", "ipx_ks_host.cpp", "ipx_batcher.cpp", "ipx_ops.cpp", "ipx_font.cpp", "ipx_jpeg_host.cpp", "ipx_jpeg_dec_host.cpp", "ipx_jpeg_dec_prog.cpp", "ipx_gif_host.cpp", "ipx_gif_dec_host.cpp", "ipx_png_host.cpp", "ipx_png_dec_host.cpp"]
+HEADERS = ["ipx_internal.h", "ipx_runtime_internal.h", "ipx_decode_common.h", "ipx_device.h", "ipx_ks.h", "ipx_ks_exact.h", "ipx_threads.h", "ipx_batcher.h", "ipx_pool_core.h", "ipx_gif.h", "ipx_gif_kernels.h", "ipx_gif_mixed_plan.h", "ipx_gif_dec.h", "ipx_png.h", "ipx_png_kernels.h", "ipx_png_deflate_body.inc", "ipx_align.h", "ipx_mixed_cut.h", "ipx_jpeg_mixed_plan.h", "ipx_jpeg_enc_mixed_plan.h", "ipx_mixed_leg.h", "ipx_png_layout.h", "ipx_png_dec.h", "ipx_png_inflate.h", os.path.join("..", "..", "include", "ipx.h")]
 # -ffp-contract=off: the kernel scaler must round every float64 product before the add, as the
 # reference's GOAMD64=v1 build does (no FMA); the kernels also carry `#pragma clang fp contract(off)`.
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off",

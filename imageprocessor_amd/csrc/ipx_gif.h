@@ -6,6 +6,9 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
+
+#include "ipx_gif_mixed_plan.h"
 
 namespace ipx {
 
@@ -38,12 +41,16 @@ struct Plan9 {
     }
 };
 
-// GIF89a, logical screen w x h with the 256-entry global table (flags 0x87, background 0, aspect 0), the Plan 9 table, the image
-// descriptor (0x2C, at 0,0, w x h, flags 0: the frame uses the global table) and the LZW minimum code size 8
-constexpr int kGifHeaderBytes = 13 + 768 + 10 + 1;
+// the kGifHeaderBytes of ipx_gif_mixed_plan.h, which also has the bound the regions are cut by (gif_stream_bound) and the rows a
+// frame's dither keeps in flight (gif_rows_in_flight)
 void gif_write_header(int w, int h, uint8_t out[kGifHeaderBytes]);
-// an upper bound of a whole stream's length for a w x h frame (header, sub-blocks of LZW data at <= 12 bits per code, trailer)
-size_t gif_stream_bound(int w, int h);
+// IPX_GIF_WAVES in the environment, read on every call (for measurements): -> whether it is set, *knob its value
+inline bool gif_waves_knob(int *knob)
+{
+    const char *v = getenv("IPX_GIF_WAVES");
+    *knob = v && *v ? atoi(v) : 0;
+    return v && *v;
+}
 
 // ---- kernel launchers (ipx_gif.hip) ----
 // rows_in_flight: a multiple of 64 up to 1024 (one wave per 64 rows); carry: n * w int4 of scratch (the last error row of a band)
@@ -56,5 +63,17 @@ hipError_t launch_gif_lzw(const uint8_t *index, size_t npix, int n, const uint8_
 // stream i (lens[i] bytes at out + i * region) to dst + obase[i]; obase 16-byte aligned, region a multiple of 16
 hipError_t launch_gif_pack(const uint8_t *out, size_t region, const uint32_t *lens, const unsigned long long *obase, int n, size_t max_len,
                            uint8_t *dst, hipStream_t s);
+
+// ---- the mixed-size launchers (ipx_gif_mixed.hip): every kernel finds its frame's record, rec[order[...]] or rec[blockIdx.y] ----
+// one launch per bucket of plan.buckets: blockDim = the bucket's rows in flight, one workgroup per frame of dorder[first .. first + n)
+hipError_t launch_gif_dither_mixed(const GifMixFrame *rec, const uint32_t *dorder, const GifMixBucket *buckets, int nbuckets, uint8_t *index,
+                                   int4 *carry, hipStream_t s);
+// one wave per frame, frame lorder[blockIdx.x]; header: the kGifHeaderBytes of gif_write_header(0, 0), each wave patches its sizes in;
+// lens[f] by the caller's index, as launch_gif_lzw writes them
+hipError_t launch_gif_lzw_mixed(const GifMixFrame *rec, const uint32_t *lorder, int n, const uint8_t *index, const uint8_t *header, uint8_t *out,
+                                uint32_t *lens, hipStream_t s);
+// stream f (lens[f] bytes at out + rec[f].region_off) to dst + obase[f]
+hipError_t launch_gif_pack_mixed(const GifMixFrame *rec, const uint8_t *out, const uint32_t *lens, const unsigned long long *obase, int n,
+                                 size_t max_len, uint8_t *dst, hipStream_t s);
 
 }  // namespace ipx

@@ -1,13 +1,15 @@
 // ipx_gif_dec.hip -- gif.Decode (image/gif reader.go, compress/lzw reader.go) of the first image of a batch of files on the GPU, and
-// the ABI entries built on it.  Kernels: the code walk (one lane per file reads the codes, keeps the live dictionary's lengths and
+// the ABI entries built on it: the decode entries for files of one size and of any sizes, the uniform GIF-in, GIF-out leg and what GIF
+// supplies to the mixed-size one (ipx_run_gif_gif_mixed: the walk is mixed_leg in ipx_mixed_leg.h).  Kernels: the code walk (one lane per file reads the codes, keeps the live dictionary's lengths and
 // first bytes in LDS and checks every rule of the reader, O(1) work per code) and the expansion (every lane of a grid takes one code and
 // writes its string backwards along the entry -> code-ordinal map of its segment, straight into the de-interlaced row).  Host half:
 // ipx_gif_dec_host.cpp.  Under IPX_GIF_PAR=1 the walk is gif_walk_par_kernel (ipx_gif_dec_par.hip: all 64 lanes read codes) with the walk
 // of this file behind it for the files it leaves.  DESIGN.md section 4.8 has the restatement and the numbers.
+#include <algorithm>
 #include <vector>
 
 #include "ipx_gif_dec.h"
-#include "ipx_decode_common.h"
+#include "ipx_mixed_leg.h"
 
 namespace ipx {
 
@@ -124,14 +126,13 @@ hipError_t launch_gif_walk(const uint8_t *blob, const GifDecDesc *desc, int n, G
 // string of L bytes costs L steps and nothing is shared between lanes.  Writes stay inside [off, next off) of the frame's own pixels
 // (checked against the frame size, whatever the records say); files whose walk failed are skipped.
 __global__ __launch_bounds__(256) void gif_expand_kernel(const GifDecDesc *__restrict__ desc, const GifCode *__restrict__ codes,
-                                                         const uint32_t *__restrict__ state, uint8_t *__restrict__ frames,
-                                                         size_t frame_stride)
+                                                         const uint32_t *__restrict__ state, uint8_t *__restrict__ frames)
 {
     const GifDecDesc d = desc[blockIdx.y];
     if (state[kGifStateWords * d.slot] != 0) return;
     const uint32_t nrec = min(state[kGifStateWords * d.slot + 1], d.code_cap - 1);
     const GifCode *rec = codes + d.code_off;
-    uint8_t *out = frames + (size_t)d.slot * frame_stride;
+    uint8_t *out = frames + d.frame_off;
     const uint32_t w = d.w, h = d.h, npix = w * h, clear = 1u << d.lit, eof = clear + 1;
     const bool il = (d.flags & kGifInterlaced) != 0;
     const uint32_t n0 = (h + 7) / 8, n1 = (h + 3) / 8, n2 = (h + 1) / 4;
@@ -174,10 +175,10 @@ __global__ __launch_bounds__(256) void gif_expand_kernel(const GifDecDesc *__res
 }
 
 hipError_t launch_gif_expand(const GifDecDesc *desc, int n, const GifCode *codes, const uint32_t *state, uint8_t *frames,
-                             size_t frame_stride, int blocks_per_file, hipStream_t s)
+                             int blocks_per_file, hipStream_t s)
 {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(gif_expand_kernel, dim3(blocks_per_file, n), dim3(256), 0, s, desc, codes, state, frames, frame_stride);
+    hipLaunchKernelGGL(gif_expand_kernel, dim3(blocks_per_file, n), dim3(256), 0, s, desc, codes, state, frames);
     return hipGetLastError();
 }
 
@@ -185,11 +186,16 @@ hipError_t launch_gif_expand(const GifDecDesc *desc, int n, const GifCode *codes
 
 // ---- the decode core -------------------------------------------------------------------------------------------------------------
 
-// parse n files (a thread per eight of them); status[i] from the container, then the batch's size: *w x *h, or the first parsed
-// file's when *w == 0 (files of another size: IPX_ERR_UNSUPPORTED)
+// parse n files (a thread per eight of them); status[i] from the container
+static int gif_parse_all(const ipx_bytes *files, int n, std::vector<GifFileInfo> &info, int *status)
+{
+    return parallel_light(n, [&](int i) { status[i] = gif_parse(files[i].data, files[i].data ? files[i].len : 0, &info[i]); }, "gif decode: host parse failed");
+}
+
+// gif_parse_all, then the batch's size: *w x *h, or the first parsed file's when *w == 0 (files of another size: IPX_ERR_UNSUPPORTED)
 static int gif_parse_batch(const ipx_bytes *files, int n, int *w, int *h, std::vector<GifFileInfo> &info, int *status)
 {
-    const int rc = parallel_light(n, [&](int i) { status[i] = gif_parse(files[i].data, files[i].data ? files[i].len : 0, &info[i]); }, "gif decode: host parse failed");
+    const int rc = gif_parse_all(files, n, info, status);
     if (rc) return rc;
     for (int i = 0; i < n; i++) {
         if (status[i] != IPX_OK) continue;
@@ -199,11 +205,14 @@ static int gif_parse_batch(const ipx_bytes *files, int n, int *w, int *h, std::v
     return IPX_OK;
 }
 
-// Decodes the files with status IPX_OK into frames + i * frame_stride (w x h, rows w bytes apart) and their palettes into
-// palettes + i * 1024 (every slot's palette is written; zero for the others), all on stream s; the walk's verdict lands in status[].
-// The code scratch is cut into groups of at most ~4 GiB (IPX_GIF_DEC_SCRATCH_MB); one read-back of the per-file words at the end.
+// Decodes the files with status IPX_OK, of any sizes, into frames + at.off[i] (w x h, rows w bytes apart) and their palettes into
+// palettes + at.pal_slot[i] * 1024 (every slot of the layout is written; zero for a file that is not decoded), all on stream s; the
+// walk's verdict lands in status[].  The code scratch is cut into groups of at most ~4 GiB (IPX_GIF_DEC_SCRATCH_MB); one read-back of
+// the per-file words at the end.  A launch's records are ordered longest data first when the layout asks for it (files of different
+// sizes): the walk is one wave per file and a launch ends with its longest file; what is written depends on nothing but a file's
+// own record.
 static int gif_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files, int n, const std::vector<GifFileInfo> &info,
-                            uint8_t *frames, size_t frame_stride, uint8_t *palettes, int *status)
+                            const GifFrameLayout &at, uint8_t *frames, uint8_t *palettes, int *status)
 {
     PinnedBlocks pinned(ctx, s);
     AsyncFree mem{s, {}};
@@ -213,16 +222,18 @@ static int gif_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
     uint32_t *dstate;
     IPX_HIP(mem.get(&dstate, (size_t)n * kGifStateWords * 4));
     // palettes: one upload of every slot
-    uint8_t *hpal = pinned.get((size_t)n * 1024);
+    uint8_t *hpal = pinned.get((size_t)std::max(at.pal_slots, 1) * 1024);
     if (!hpal) return IPX_ERR_NOMEM;
     for (int i = 0; i < n; i++) {
-        if (status[i] == IPX_OK) memcpy(hpal + (size_t)i * 1024, info[i].pal, 1024);
-        else memset(hpal + (size_t)i * 1024, 0, 1024);
+        if (at.pal_slot[i] < 0) continue;
+        if (status[i] == IPX_OK) memcpy(hpal + (size_t)at.pal_slot[i] * 1024, info[i].pal, 1024);
+        else memset(hpal + (size_t)at.pal_slot[i] * 1024, 0, 1024);
     }
-    IPX_HIP(hipMemcpyAsync(palettes, hpal, (size_t)n * 1024, hipMemcpyHostToDevice, s));
+    if (at.pal_slots) IPX_HIP(hipMemcpyAsync(palettes, hpal, (size_t)at.pal_slots * 1024, hipMemcpyHostToDevice, s));
     const size_t budget = (size_t)env_int("IPX_GIF_DEC_SCRATCH_MB", 4096) << 20;
-    auto run_group = [&](const std::vector<int> &group) -> int {
+    auto run_group = [&](std::vector<int> group) -> int {
         const int m = (int)group.size();
+        if (at.longest_first) std::stable_sort(group.begin(), group.end(), [&](int a, int b) { return info[a].data_len > info[b].data_len; });
         size_t data_bytes = 0, codes = 0;
         uint32_t max_cap = 0;
         std::vector<GifDecDesc> desc(m);
@@ -232,6 +243,7 @@ static int gif_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
             memset(&d, 0, sizeof d);
             d.data_off = data_bytes;
             d.code_off = codes;
+            d.frame_off = at.off[group[g]];
             d.data_len = f.data_len;
             d.last_start = f.last_start;
             d.code_cap = gif_code_cap(f);
@@ -267,7 +279,7 @@ static int gif_decode_files(ipx_ctx *ctx, hipStream_t s, const ipx_bytes *files,
             IPX_HIP(launch_gif_walk(dblob + desc_bytes, ddesc, m, dcodes, dstate, nullptr, s));
         }
         const int bpf = (int)std::max<uint32_t>(1, std::min<uint32_t>((max_cap + 255) / 256, (uint32_t)std::max(1, 16384 / m)));
-        IPX_HIP(launch_gif_expand(ddesc, m, dcodes, dstate, frames, frame_stride, bpf, s));
+        IPX_HIP(launch_gif_expand(ddesc, m, dcodes, dstate, frames, bpf, s));
         return IPX_OK;
     };
     std::vector<int> ok;
@@ -337,7 +349,7 @@ int ipx_gif_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *gifs, int 
         set_error("ipx_gif_decode_batch: device allocation failed: %s", hipGetErrorString(e));
         return IPX_ERR_NOMEM;
     }
-    rc = gif_decode_files(ctx, s, gifs, n, info, dframes, fs, dpal, status);
+    rc = gif_decode_files(ctx, s, gifs, n, info, gif_layout_strided(n, fs), dframes, dpal, status);
     if (rc) return rc;
     *w = bw;
     *h = bh;
@@ -346,6 +358,43 @@ int ipx_gif_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *gifs, int 
     frames->stride = bw;
     frames->frame_stride = fs;
     frames->palettes = dpal;
+    *owner = o.release();
+    return IPX_OK;
+}
+IPX_CATCH_STATUS
+
+// n files of any sizes: every file that parses goes through ONE gif_decode_files call -- one upload, one walk launch (two under
+// IPX_GIF_PAR=1) and one expand launch per scratch group -- its frame at an offset of its own in one block (256-byte aligned, rows
+// tight) and its palette in the next free slot of a second block
+int ipx_gif_decode_mixed(ipx_ctx *ctx, void *stream, const ipx_bytes *files, int n, ipx_gif_frame *frames, int *status,
+                         ipx_gif_frames **owner) try
+{
+    IPX_ENTER(ctx);
+    if (n < 0 || !owner || (n && (!files || !frames || !status))) { set_error("ipx_gif_decode_mixed: bad argument"); return IPX_ERR_INVALID; }
+    *owner = nullptr;
+    if (n == 0) return IPX_OK;
+    if (n > 65535) { set_error("ipx_gif_decode_mixed: at most 65535 files per call"); return IPX_ERR_UNSUPPORTED; }
+    memset(frames, 0, (size_t)n * sizeof *frames);
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    std::vector<GifFileInfo> info(n);
+    int rc = gif_parse_all(files, n, info, status);
+    if (rc) return rc;
+    if (!any_ok(status, n)) return IPX_OK;
+    const GifFrameLayout at = gif_layout_packed(n, [&](int i) { return status[i] == IPX_OK; }, [&](int i) { return (size_t)info[i].w * info[i].h; });
+    OwnedBlocks<ipx_gif_frames> o(ctx, s);
+    uint8_t *dframes = nullptr, *dpal = nullptr;
+    hipError_t e = o.alloc(&dframes, at.bytes);
+    if (e == hipSuccess) e = o.alloc(&dpal, (size_t)at.pal_slots * 1024);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("ipx_gif_decode_mixed: device allocation failed: %s", hipGetErrorString(e));
+        return IPX_ERR_NOMEM;
+    }
+    rc = gif_decode_files(ctx, s, files, n, info, at, dframes, dpal, status);
+    if (rc) return rc;
+    if (!any_ok(status, n)) return IPX_OK;     // every image failed in its data: no frames
+    for (int i = 0; i < n; i++)
+        if (status[i] == IPX_OK) frames[i] = ipx_gif_frame{info[i].w, info[i].h, dframes + at.off[i], info[i].w, dpal + (size_t)at.pal_slot[i] * 1024};
     *owner = o.release();
     return IPX_OK;
 }
@@ -394,7 +443,7 @@ static int run_gif_gif(const char *who, ipx_ctx *ctx, const ipx_plan *pl, int n,
         IPX_HIP(mem.get(&didx, fsrc * m));
         IPX_HIP(mem.get(&dpal, (size_t)1024 * m));
         if (outs.frame_bytes()) IPX_HIP(mem.get(&dout, outs.frame_bytes() * m));
-        rc = gif_decode_files(ctx, s, files + i0, m, info, didx, fsrc, dpal, status + i0);
+        rc = gif_decode_files(ctx, s, files + i0, m, info, gif_layout_strided(m, fsrc), didx, dpal, status + i0);
         if (rc) return rc;
         if (!any_ok(status + i0, m)) continue;
         rc = run_chunk(ctx, s, pl, outs, dout, m, packed_src(kSrcPaletted, didx, sw, fsrc, dpal), all_files(n), i0, m, &lt, nullptr, quality, status, res);
@@ -424,3 +473,172 @@ IPX_CATCH_STATUS
 
 }  // extern "C"
 
+// ---- the mixed-size GIF leg: what GIF supplies to the walk of ipx_mixed_leg.h ------------------------------------------------------
+
+namespace {
+struct GifMixed {
+    static constexpr const char *kWho = "ipx_run_gif_gif_mixed";
+    static constexpr const char *kGroupEnv = "IPX_GIF_MIXED_GROUP", *kChunkEnv = "IPX_GIF_MIXED_CHUNK_MB";
+    // the dither gives a frame one workgroup and the coder one wave, so a chunk wants some hundreds of frames; DESIGN.md section 4.8
+    // has what was measured beside these
+    static constexpr int kGroupFiles = 256, kChunkMB = 4096;
+    static constexpr bool kRunsWithoutOutputs = false;      // a run no output is made for is left out
+    // a file the walk failed is left out of its run and, with its status, out of every encode
+    bool decoded(int i) const { return status[i] == IPX_OK; }
+
+    int quality;
+    const int *status = nullptr;            // the caller's
+    std::vector<GifFileInfo> info;
+    // a group's frames and palettes: stream-ordered, they go back with the group
+    struct Group {
+        AsyncFree mem;
+        GifFrameLayout at;                  // by the file's place in the group
+        uint8_t *dfr = nullptr, *dpal = nullptr;
+        Group(ipx_ctx *, hipStream_t s) : mem{s, {}} {}
+    };
+    // three arenas of frames, and the watermark frames' coefficient scratch
+    struct Chunk : ChunkFrames {
+        uint8_t *coefs = nullptr;
+        std::vector<size_t> coef_off;       // file p's coefficients at coefs + coef_off[p]
+    };
+
+    int refuse(const ipx_pool_ops *ops, int n, const ipx_text *texts) const
+    {
+        if (texts && (ops->glyphs || ops->n_glyphs)) {
+            set_error("%s: a text per file needs ops->glyphs == NULL: the plan copies the frame and the texts are drawn behind it", kWho);
+            return IPX_ERR_INVALID;
+        }
+        if (n > 65535) { set_error("%s: at most 65535 files per call", kWho); return IPX_ERR_UNSUPPORTED; }
+        return IPX_OK;
+    }
+    int parse(const ipx_bytes *files, int n, int *st)
+    {
+        status = st;
+        info.resize(n);
+        return gif_parse_all(files, n, info, st);
+    }
+    std::pair<int, int> size(int i) const { return {info[i].w, info[i].h}; }
+    int kind(int) const { return 0; }       // every frame is *image.Paletted
+    // a GIF output of 65536 or more on a side is that file's refusal alone (the uniform leg's check_gif refuses the call)
+    int admit(const MixedCall &c, int i) const
+    {
+        for (int k : {kOutResize, kOutThumb})
+            if (c.has(i, k) && (c.shape(i, k).w >= 1 << 16 || c.shape(i, k).h >= 1 << 16)) return IPX_ERR_INVALID;
+        return IPX_OK;
+    }
+    // bytes a file costs its decode group: the frame, the palette, the LZW data and the code scratch
+    size_t decode_cost(int i) const
+    {
+        return align256((size_t)info[i].w * info[i].h) + 1024 + align16(info[i].data_len) + (size_t)gif_code_cap(info[i]) * sizeof(GifCode);
+    }
+    static size_t coef_bytes(const OutShape &sh) { return align256(ipx_jpeg_coef_count(sh.w, sh.h) * sizeof(int16_t)); }
+    // What output k costs a chunk: the frame and what the encoder allocates behind it.  A GIF output (resize, thumbnail): the index
+    // bytes, the region and the carry row.  The JPEG output (watermark): its coefficients, and the encoder's streams (about the
+    // coefficients again).
+    size_t out_cost(const OutShape &sh, int k) const
+    {
+        if (k == kOutWm) return align256(sh.bytes) + 2 * coef_bytes(sh);
+        return align256(sh.bytes) + align256((size_t)sh.w * sh.h) + align256(gif_stream_bound(sh.w, sh.h)) + (size_t)sh.w * sizeof(int4);
+    }
+    void trace(int n, const MixCut &cut) const
+    {
+        if (env_int("IPX_DEBUG_G2G", 0) != 0)
+            fprintf(stderr, "[ipx] %s: %d files, %zu groups, %zu chunks, %zu runs\n", kWho, n, cut.groups.size(), cut.chunks.size(), cut.runs.size());
+    }
+
+    // ONE gif_decode_files call for every size of the group: the group's files are gathered for it, their verdicts go back
+    int decode(const MixedCall &c, Lane &, hipStream_t s, const ipx_bytes *files, const int *idx, int m, Group &g)
+    {
+        std::vector<ipx_bytes> gfiles(m);
+        std::vector<GifFileInfo> ginfo(m);
+        std::vector<int> gstatus(m);
+        for (int q = 0; q < m; q++) { gfiles[q] = files[idx[q]]; ginfo[q] = info[idx[q]]; gstatus[q] = c.status[idx[q]]; }
+        g.at = gif_layout_packed(m, [&](int q) { return gstatus[q] == IPX_OK; }, [&](int q) { return (size_t)ginfo[q].w * ginfo[q].h; });
+        IPX_HIP(g.mem.get(&g.dfr, g.at.bytes));
+        IPX_HIP(g.mem.get(&g.dpal, (size_t)1024 * std::max(g.at.pal_slots, 1)));
+        const int rc = gif_decode_files(c.ctx, s, gfiles.data(), m, ginfo, g.at, g.dfr, g.dpal, gstatus.data());
+        for (int q = 0; q < m; q++) c.status[idx[q]] = gstatus[q];
+        return rc;
+    }
+    // the frames from file i, which sits in slot `slot` of the group's layout, on: the files of its size that follow it lie one frame
+    // stride apart, their palettes in the slots that follow
+    BatchSrc src(const Group &g, int i, int slot) const
+    {
+        const GifFileInfo &f = info[i];
+        return packed_src(kSrcPaletted, g.dfr + g.at.off[slot], f.w, align256((size_t)f.w * f.h), g.dpal + (size_t)g.at.pal_slot[slot] * 1024);
+    }
+    int chunk_memory(const MixedCall &c, Lane &, AsyncFree &omem, const int *file, int n, Chunk &b) const
+    {
+        size_t any = 0;
+        for (int k = 0; k < kOuts; k++)
+            if (const size_t total = b.lay(c, file, n, k, 0)) { IPX_HIP(omem.get(&b.base[k], total)); any += total; }
+        size_t bytes = 0;
+        b.coef_off.resize(n);
+        for (int p = 0; p < n; p++) { b.coef_off[p] = bytes; if (c.has(file[p], kOutWm)) bytes += coef_bytes(c.shape(file[p], kOutWm)); }
+        if (bytes) IPX_HIP(omem.get(&b.coefs, bytes));
+        b.empty = !any;
+        return IPX_OK;
+    }
+    // nothing per run: the chunk's frames are encoded together once its runs have all been through the operators
+    int encode_run(const MixedCall &, hipStream_t, const int *, int, int, const Chunk &, ResultOwner &) const { return IPX_OK; }
+    // ONE gif_encode_mixed_core over every present resize and thumbnail frame of the chunk's files that are still IPX_OK.  Then the
+    // watermark frames as JPEG (watermark.go:73): when every file of the chunk is IPX_OK and has that output at one size, one
+    // jpeg_encode_sets call over the chunk; else one jpeg_encode_mixed_core over the frames of the files that are IPX_OK.
+    int encode_chunk(const MixedCall &c, hipStream_t s, const int *file, int n, const Chunk &b, ResultOwner &res) const
+    {
+        std::vector<GifMixSrc> gf;
+        std::vector<std::pair<int, int>> owner_of;          // (file, output) of a frame
+        for (int k : {kOutResize, kOutThumb})
+            for (int p = 0; p < n; p++) {
+                if (c.status[file[p]] != IPX_OK || !c.has(file[p], k)) continue;
+                const OutShape sh = c.shape(file[p], k);
+                gf.push_back(GifMixSrc{b.at(k, p), sh.w, sh.h, sh.w * 4});
+                owner_of.emplace_back(file[p], k);
+            }
+        if (!gf.empty()) {
+            std::vector<size_t> offs(gf.size()), lens(gf.size());
+            uint8_t *blob = nullptr;
+            const int rc = gif_encode_mixed_core(c.ctx, s, gf.data(), (int)gf.size(), &blob, offs.data(), lens.data());
+            if (rc) return rc;
+            res.add(blob);
+            for (size_t j = 0; j < gf.size(); j++) c.publish(owner_of[j].first, owner_of[j].second, blob + offs[j], lens[j]);
+        }
+        bool uniform = true;
+        std::vector<JpegEncSrc> jf;
+        std::vector<int> jowner;
+        for (int p = 0; p < n; p++) {
+            const bool take = c.status[file[p]] == IPX_OK && c.has(file[p], kOutWm);
+            uniform = uniform && take && c.shape(file[p], kOutWm).w == c.shape(file[0], kOutWm).w && c.shape(file[p], kOutWm).h == c.shape(file[0], kOutWm).h;
+            if (!take) continue;
+            const OutShape sh = c.shape(file[p], kOutWm);
+            jf.push_back(JpegEncSrc{b.at(kOutWm, p), (int16_t *)(b.coefs + b.coef_off[p]), sh.w, sh.h, sh.w * 4});
+            jowner.push_back(file[p]);
+        }
+        if (jf.empty()) return IPX_OK;
+        std::vector<size_t> offs(jf.size()), lens(jf.size());
+        uint8_t *blob = nullptr;
+        int rc;
+        if (uniform) {
+            const OutShape sh = c.shape(file[0], kOutWm);
+            const JpegEncSet set{(int16_t *)b.coefs, b.at(kOutWm, 0), sh.w, sh.h, sh.w * 4, c.out_fs(file[0], kOutWm), offs.data(), lens.data()};
+            rc = jpeg_encode_sets(c.ctx, s, &set, 1, n, quality, &blob);
+        } else {
+            rc = jpeg_encode_mixed_core(c.ctx, s, jf.data(), (int)jf.size(), quality, &blob, offs.data(), lens.data());
+        }
+        if (rc) return rc;
+        res.add(blob);
+        for (size_t j = 0; j < jf.size(); j++) c.publish(jowner[j], kOutWm, blob + offs[j], lens[j]);
+        return IPX_OK;
+    }
+};
+}  // namespace
+
+extern "C" int ipx_run_gif_gif_mixed(ipx_ctx *ctx, const ipx_pool_ops *ops, int n, const ipx_bytes *files, const ipx_text *texts, int quality,
+                                     ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result) try
+{
+    IPX_ENTER(ctx);
+    GifMixed cx;
+    cx.quality = quality;
+    return mixed_leg(cx, ctx, ops, n, files, texts, resize_out, thumb_out, wm_out, status, result);
+}
+IPX_CATCH_STATUS

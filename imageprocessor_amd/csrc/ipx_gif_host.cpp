@@ -1,5 +1,6 @@
 // ipx_gif_host.cpp -- the host half of gif.Encode: the header bytes image/gif's writeHeader / writeImageBlock put before the LZW data of
-// a single-frame *image.Paletted with the Plan 9 palette, and the size bound the device regions are cut by.  Kernels: ipx_gif.hip.
+// a single-frame *image.Paletted with the Plan 9 palette.  (The size bound the device regions are cut by: ipx_gif_mixed_plan.h.)
+// Kernels: ipx_gif.hip, ipx_gif_mixed.hip.
 #include <cstring>
 
 #include "ipx_gif.h"
@@ -28,15 +29,6 @@ void gif_write_header(int w, int h, uint8_t out[kGifHeaderBytes])
     u16(h);
     *p++ = 0;          // the global table serves: no local one
     *p++ = 8;          // LZW minimum code size: log2(256) - 1 + 1
-}
-
-size_t gif_stream_bound(int w, int h)
-{
-    const size_t npix = (size_t)w * (size_t)h;
-    // a code per pixel at most, plus the first clear code, the code Close writes, EOF, and a clear code per 3838 codes (hi runs 257 .. 4095)
-    const size_t codes = npix + 3 + npix / 3838 + 1;
-    const size_t data = (codes * 12 + 7) / 8;
-    return kGifHeaderBytes + data + (data + 254) / 255 + 1 + 1;   // length bytes, terminator, trailer
 }
 
 }  // namespace ipx

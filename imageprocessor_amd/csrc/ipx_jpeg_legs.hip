@@ -56,6 +56,7 @@ struct JpegMixed {
     std::pair<int, int> size(int i) const { return {parsed.info[i].w, parsed.info[i].h}; }
     // the sampling class of a parsed file as one number
     int kind(int i) const { const JpegDecInfo &I = parsed.info[i]; return I.ncomp == 1 ? 0 : I.h0 * 4 + I.v0; }
+    int admit(const MixedCall &, int) const { return IPX_OK; }      // a file that has a plan is taken
     // bytes a file costs its decode group: the MCU-padded planes and the coefficient scratch (128 bytes per block and its DC value)
     size_t decode_cost(int i) const
     {
@@ -66,7 +67,7 @@ struct JpegMixed {
     }
     static size_t coef_bytes(const OutShape &sh) { return align256(ipx_jpeg_coef_count(sh.w, sh.h) * sizeof(int16_t)); }
     // what an output costs a chunk: the frame, its coefficients, and the encoder's streams (about the coefficients again)
-    size_t out_cost(const OutShape &sh) const { return align256(sh.bytes) + 2 * coef_bytes(sh); }
+    size_t out_cost(const OutShape &sh, int) const { return align256(sh.bytes) + 2 * coef_bytes(sh); }
     void trace(int n, const MixCut &cut) const
     {
         if (env_int("IPX_DEBUG_J2J", 0) != 0)

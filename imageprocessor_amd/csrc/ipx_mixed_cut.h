@@ -1,7 +1,7 @@
 // ipx_mixed_cut.h -- how a mixed-size leg orders its files and cuts them: files -> decode groups -> output chunks -> runs of one size
-// and kind.  Its one caller is the walk both legs share (mixed_leg in ipx_mixed_leg.h); `kind` is whatever keeps two files of one size
+// and kind.  Its one caller is the walk the three legs share (mixed_leg in ipx_mixed_leg.h); `kind` is whatever keeps two files of one size
 // out of one operator launch: the frame layout (IPX_PNG_*) for ipx_run_png_png_mixed, the sampling class (0 for Gray, else h0 * 4 + v0)
-// for ipx_run_jpeg_jpeg_mixed.  Plain host C++ with no dependency on the runtime, so that tools/png_mixed_plan_test.cpp and
+// for ipx_run_jpeg_jpeg_mixed, 0 for ipx_run_gif_gif_mixed (every frame is paletted).  Plain host C++ with no dependency on the runtime, so that tools/png_mixed_plan_test.cpp and
 // tools/jpeg_mixed_plan_test.cpp can hold it to its rules as programs of their own.  DESIGN.md sections 4.10 and 7.
 #pragma once
 

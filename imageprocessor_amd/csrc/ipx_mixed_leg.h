@@ -1,5 +1,5 @@
 // ipx_mixed_leg.h -- the walk the mixed-size legs share (ipx_run_png_png_mixed in ipx_png_legs.hip, ipx_run_jpeg_jpeg_mixed in
-// ipx_jpeg_legs.hip): the entry's checks, a plan per frame size from the context's cache, the cut (ipx_mixed_cut.h), then groups ->
+// ipx_jpeg_legs.hip, ipx_run_gif_gif_mixed in ipx_gif_dec.hip): the entry's checks, a plan per frame size from the context's cache, the cut (ipx_mixed_cut.h), then groups ->
 // chunks -> runs with the operators and the texts of a run.  What is a codec's -- parse, costs, decode, a run's source, the chunk's
 // memory, encode -- comes in as the struct mixed_leg is instantiated on; DESIGN.md section 7 lists it.  Not part of the ABI.
 #pragma once
@@ -65,7 +65,7 @@ struct MixedCall {
     std::vector<ipx_plan *> plan_of;        // null: the file is not OK
     OutShape shape(int i, int k) const { return out_shape(plan_of[i]->info, k); }
     // an output that is wanted and made for file i.  A plan's bytes are w * h * 4 of sizes that are never negative (ipx_plan_create), so
-    // bytes != 0 says that neither w nor h is 0: one test serves both legs.
+    // bytes != 0 says that neither w nor h is 0: one test serves every leg.
     bool has(int i, int k) const { return dst[k] && shape(i, k).bytes; }
     // how far apart the frames of file i's size lie in the chunk's memory for output k; 0: no such output
     size_t out_fs(int i, int k) const { return has(i, k) ? align256(shape(i, k).bytes) : 0; }
@@ -115,7 +115,8 @@ int mixed_run(Codec &cx, const MixedCall &c, hipStream_t s, const BatchSrc &d, c
 
 // The body of a mixed-size entry behind IPX_ENTER.  The order of the checks decides which error a bad call gets: the arguments, then the
 // codec's own refusals (cx.refuse), then the texts; the wanted outputs are cleared before anything is parsed.  Then the parse, a plan per
-// size, the cut, and per group ONE decode whatever sizes and kinds it holds; per chunk the operators once per run into the chunk's
+// size, the codec's verdict on a file with its plan (cx.admit: a status for that file alone), the cut, and per group ONE decode whatever
+// sizes and kinds it holds; per chunk the operators once per run into the chunk's
 // memory and the codec's encode.  The host does not wait for the stream between runs beyond what those stages contain.
 template <class Codec>
 int mixed_leg(Codec &cx, ipx_ctx *ctx, const ipx_pool_ops *ops, int n, const ipx_bytes *files, const ipx_text *texts, ipx_bytes *resize_out,
@@ -139,9 +140,10 @@ int mixed_leg(Codec &cx, ipx_ctx *ctx, const ipx_pool_ops *ops, int n, const ipx
     std::vector<MixItem> items(n, MixItem{false, 0, 0, 0, 0, 0});
     for (int i = 0; i < n; i++) {
         if (status[i] != IPX_OK) continue;
+        if ((status[i] = cx.admit(c, i)) != IPX_OK) { c.plan_of[i] = nullptr; continue; }
         items[i] = MixItem{true, cx.size(i).first, cx.size(i).second, cx.kind(i), cx.decode_cost(i), 0};
         for (int k = 0; k < kOuts; k++)
-            if (c.has(i, k)) items[i].chunk_bytes += cx.out_cost(c.shape(i, k));
+            if (c.has(i, k)) items[i].chunk_bytes += cx.out_cost(c.shape(i, k), k);
     }
     const int group_max = std::min(65535, std::max(1, env_int(Codec::kGroupEnv, Codec::kGroupFiles)));
     const size_t chunk_bytes = (size_t)std::max(0, env_int(Codec::kChunkEnv, Codec::kChunkMB)) << 20;

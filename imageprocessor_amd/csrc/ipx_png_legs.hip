@@ -131,10 +131,11 @@ struct PngMixed {
     int parse(const ipx_bytes *files, int n, int *status) { info.resize(n); return png_parse_all(files, n, info, status); }
     std::pair<int, int> size(int i) const { return {info[i].w, info[i].h}; }
     int kind(int i) const { return info[i].kind; }
+    int admit(const MixedCall &, int) const { return IPX_OK; }      // a file that has a plan is taken
     size_t decode_cost(int i) const { return align256((size_t)info[i].w * info[i].h * png_kind_bpp(info[i].kind)) + 1024; }
     // what an output costs a chunk: the frame itself and the encoder's scratch for it -- the filtered stream, a word of match scratch
     // per filtered byte, and the frame's region
-    size_t out_cost(const OutShape &sh) const
+    size_t out_cost(const OutShape &sh, int) const
     {
         const size_t filt = (size_t)sh.h * (1 + 4 * (size_t)sh.w);
         return align256(sh.bytes) + 5 * align256(filt) + align256(kPngSegBase + png_segs_bytes(sh.w, sh.h, 4) + kPngTailBytes);

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "ipx_align.h"
+#include "ipx_gif_mixed_plan.h"
 #include "ipx_internal.h"
 #include "ipx_ks.h"
 
@@ -332,7 +333,8 @@ struct StreamSync {
     ~StreamSync() { (void)hipStreamSynchronize(s); }
 };
 
-// ---- what the five encode cores (jpeg_encode_sets, jpeg_encode_mixed_core, png_encode_core, png_encode_mixed_core, gif_encode_core)
+// ---- what the six encode cores (jpeg_encode_sets, jpeg_encode_mixed_core, png_encode_core, png_encode_mixed_core, gif_encode_core,
+// ---- gif_encode_mixed_core)
 // ---- and the single-frame entries built on them share -----------------------------------------------------------------------------
 
 // The tail of every core: the `total` bytes of finished streams at `dev` come down into one pinned block (one byte for an empty total),
@@ -386,7 +388,7 @@ inline int encode_one_rgba8(const char *who, ipx_ctx *ctx, EncodeCheck check, En
     return IPX_OK;
 }
 
-// The opening of ipx_png_encode_mixed_dev and ipx_jpeg_encode_mixed_dev: the arguments, then *blob = NULL (n == 0 is then done: the
+// The opening of ipx_png_encode_mixed_dev, ipx_jpeg_encode_mixed_dev and ipx_gif_encode_mixed_dev: the arguments, then *blob = NULL (n == 0 is then done: the
 // caller returns), at most 65535 frames, and every frame before any launch -- a malformed one first (IPX_ERR_INVALID; `extra` is the
 // codec's own refusal of a well-formed frame, with its text set, or IPX_OK), then one beyond the span the kernels address
 // (IPX_ERR_UNSUPPORTED; span_of_stride: of rows `stride` apart as the caller has them, else of tight rows).
@@ -601,6 +603,9 @@ int jpeg_encode_mixed_core(ipx_ctx *ctx, hipStream_t s, const ipx::JpegEncSrc *f
 // gif.Encode of n frames in HBM into one pinned block *blob (ipx_gif.hip)
 int gif_encode_core(ipx_ctx *ctx, hipStream_t s, const uint8_t *src, int w, int h, int stride, size_t frame_stride, int n,
                     uint8_t **blob, size_t *offs, size_t *lens);
+// gif.Encode of n frames of any sizes in HBM into one pinned block *blob, two waits for the device for the whole list (ipx_gif_mixed.hip;
+// the records: ipx_gif_mixed_plan.h).  offs / lens: [n], into *blob.
+int gif_encode_mixed_core(ipx_ctx *ctx, hipStream_t s, const ipx::GifMixSrc *frames, int n, uint8_t **blob, size_t *offs, size_t *lens);
 
 // image.Decode of n JPEG files into planes in HBM (ipx_jpeg_dec_runtime.hip); *w x *h: the size asked for, or 0 for the first parsed file's
 int jpeg_decode_files(ipx_ctx *ctx, hipStream_t s, Lane *lane, bool planes_in_lane, const ipx_bytes *jpegs, int n, int *w, int *h,

@@ -581,6 +581,16 @@ int ipx_png_encode_mixed_dev(ipx_ctx *ctx, const ipx_rgba_frame *frames, int n, 
  * blocks are always sized in the transform kernel: IPX_JPEG_FUSED_LEN and IPX_JPEG_HOST_ENTROPY do not apply.  Thread-safe like
  * ipx_jpeg_encode_batch_dev.  DESIGN.md section 4.6. */
 int ipx_jpeg_encode_mixed_dev(ipx_ctx *ctx, const ipx_rgba_frame *frames, int n, int quality, uint8_t **blob, size_t *offs, size_t *lens);
+/* gif.Encode of n frames of ANY sizes and strides, each described on its own: RGBA8 in HBM.  Stream i is byte for byte what
+ * ipx_gif_encode_batch_dev writes for frame i in a call of its own: nothing in it depends on its neighbours, on its place in the call
+ * or on how many rows were in flight.  The kernels read a per-frame record: one dither launch per number of rows in flight (at most
+ * 16, one workgroup per frame, a frame's rows in flight from its own height), one LZW launch (one wave per frame, the longest first)
+ * and one packing launch, and the host waits for the device twice -- the lengths, the download -- as ipx_gif_encode_batch_dev does,
+ * whatever sizes the call holds.  One pinned block (ipx_host_free), streams that start 16-byte aligned; n == 0 is IPX_OK with *blob =
+ * NULL.  One bad frame refuses the call before any launch: a NULL pix, a width or height below 1 or a stride below 4 * w
+ * IPX_ERR_INVALID, a side of 65536 or more IPX_ERR_INVALID with gif.Encode's message, a frame beyond ipx_frame_supported
+ * IPX_ERR_UNSUPPORTED; more than 65535 frames IPX_ERR_UNSUPPORTED.  Thread-safe like ipx_gif_encode_batch_dev.  DESIGN.md section 4.7. */
+int ipx_gif_encode_mixed_dev(ipx_ctx *ctx, const ipx_rgba_frame *frames, int n, uint8_t **blob, size_t *offs, size_t *lens);
 /* The PNG task's whole GPU leg (ipx_plan_run_host's inputs): upload, every requested operator, then png.Encode of all three outputs
  * (a PNG watermark stays PNG).  The streams land in pinned blocks owned by *result, released with ipx_jpeg_result_free. */
 int ipx_plan_run_host_png(ipx_ctx *ctx, const ipx_plan *plan, int n, const uint8_t *src, int sstride, size_t src_frame_stride,
@@ -675,6 +685,15 @@ typedef struct ipx_gif_frames ipx_gif_frames;
 int ipx_gif_decode_batch(ipx_ctx *ctx, void *stream, const ipx_bytes *gifs, int n, int *w, int *h, ipx_paletted_batch *frames,
                          int *status, ipx_gif_frames **owner);
 void ipx_gif_frames_free(ipx_ctx *ctx, ipx_gif_frames *owner);
+/* The same for n files of ANY sizes in one decode pass: one upload, one walk launch (the parallel walk plus the redo walk under
+ * IPX_GIF_PAR=1) and one expand launch per scratch group (IPX_GIF_DEC_SCRATCH_MB), the files of a launch ordered longest data first.
+ * frames[i] describes file i's frame: index 256-byte aligned with tight rows (stride = w), palette its 1024 bytes; all zero for a
+ * non-OK file.  status[i] is exactly what ipx_gif_decode_batch gives that file in a call of its own with *w = *h = 0: no file is
+ * IPX_ERR_UNSUPPORTED because of a neighbour.  IPX_GIF_PAR and ipx_gif_decode_counts mean what they mean there and count these files.
+ * n == 0 is IPX_OK; more than 65535 files is IPX_ERR_UNSUPPORTED.  *owner is NULL when nothing decoded; it is freed with
+ * ipx_gif_frames_free.  DESIGN.md section 4.8. */
+typedef struct { int32_t w, h; uint8_t *index; int32_t stride; uint8_t *palette; } ipx_gif_frame;
+int ipx_gif_decode_mixed(ipx_ctx *ctx, void *stream, const ipx_bytes *files, int n, ipx_gif_frame *frames, int *status, ipx_gif_frames **owner);
 /* The parallel code walk, with IPX_GIF_PAR=1 in the environment (read on every call that decodes GIF files; unset or anything else: the
  * serial walk alone, as before).  In every entry that decodes GIF files -- this one, ipx_plan_run_gif_gif and its _texts twin, the
  * pool's IPX_JOB_GIF, the micro-batcher -- the 64 lanes of the file's wave then read 64 consecutive codes at once: between two clear
@@ -850,6 +869,25 @@ int ipx_run_png_png_mixed(ipx_ctx *ctx, const ipx_pool_ops *ops, int n, const ip
  * ipx_plan_run_jpeg_jpeg (ipx_jpeg_result_free).  DESIGN.md sections 4.6 and 7. */
 int ipx_run_jpeg_jpeg_mixed(ipx_ctx *ctx, const ipx_pool_ops *ops, int n, const ipx_bytes *files, const ipx_text *texts, int quality,
                             ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result);
+
+/* The GIF task compressed in, compressed out for uploads of ANY sizes in one call; the contract is ipx_run_jpeg_jpeg_mixed's.
+ * ops->sw and ops->sh are ignored (each file's own size is used).  texts: NULL, or n texts as for that entry; texts together with
+ * ops->glyphs is IPX_ERR_INVALID with nothing written.  The order of the refusals: a bad argument, more than 65535 files
+ * (IPX_ERR_UNSUPPORTED), then the texts' own rules.  The files are parsed once and decoded as ipx_gif_decode_mixed decodes them.  The OK
+ * files are ordered by size and cut into decode groups of IPX_GIF_MIXED_GROUP (256) files and ~4 GiB, each group ONE decode pass; a
+ * group is cut into chunks of at most IPX_GIF_MIXED_CHUNK_MB (4096) of output frames and encoder scratch; within a chunk the
+ * operators run once per run of one size with a plan of that size from the context's cache.  A file the walk failed is left out of
+ * its run and out of every encode.  Every chunk is encoded once: ONE mixed-size gif.Encode (what ipx_gif_encode_mixed_dev runs) over
+ * every resize and thumbnail frame of its files that are still IPX_OK, then jpeg.Encode at `quality` of the watermark frames
+ * (watermark.go:66-79: a GIF watermark becomes a JPEG) -- as ipx_jpeg_encode_batch_dev encodes one size when every file of the chunk
+ * is IPX_OK and has that output at one size, else by one mixed-size jpeg.Encode.  status[i] and the three streams of file i are byte for
+ * byte what ipx_plan_run_gif_gif (or _texts) returns for that file in a call of its own, with a plan of its size and the same quality,
+ * but for two cases, both per file: a size no plan can be made for gets ipx_plan_create's status, alone; a file whose resize or
+ * thumbnail output would be 65536 or more on a side gets IPX_ERR_INVALID, alone (the uniform leg refuses the whole call).  A NULL
+ * output array skips that output; an operator ops does not ask for gives {NULL, 0}; n == 0 is IPX_OK.  Streams as for
+ * ipx_plan_run_gif_gif (ipx_jpeg_result_free).  DESIGN.md sections 4.8 and 7. */
+int ipx_run_gif_gif_mixed(ipx_ctx *ctx, const ipx_pool_ops *ops, int n, const ipx_bytes *files, const ipx_text *texts, int quality,
+                          ipx_bytes *resize_out, ipx_bytes *thumb_out, ipx_bytes *wm_out, int *status, ipx_jpeg_result **result);
 
 enum { IPX_JOB_RGBA8 = 0,       /* decoded frames in, the operators' RGBA8 outputs back (what ipx_plan_run_host does) */
        IPX_JOB_JPEG = 1,        /* uploaded JPEG files in, three JPEG streams per file back (what ipx_plan_run_jpeg_jpeg does) */
